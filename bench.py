@@ -2,7 +2,8 @@
 """
 bench.py -- windows/sec of the MI355X wake-word hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: bench.py starts its own N ranks)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                           (N > 1 without a launcher: bench.py starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,8 +19,15 @@ The PCM of all W+K steps is resident in HBM before the timed region starts.
 Rank 0 prints ONE JSON line: metric/value (whole-job windows/s), ms_per_step, plus
   "roofline"       the launch of the timed region (network || MFCC || bookkeeping roles in one kernel) vs the dense
                    fp32 MFMA peak (HIP-event time on the launch stream); with --gru-precision bf16 (configs[4]) vs the
-                   HBM peak, which is what binds that configuration,
+                   HBM peak, which is what binds that configuration.  Taken from the run of back-to-back launches that
+                   brings the GPU out of idle before the warm-up, which a plain run needs anyway.
+--dump-outputs DIR writes the probabilities of the timed region's last step (what a caller of the update receives, one
+float32 per global stream) to DIR/probabilities.npy; the inputs are seeded, so two runs with the same arguments see the
+same PCM.  Everything else is measured only with --full:
+  "parity"         the oracle replaying the timed region's chunks,
   "roofline_gru" / "roofline_mfcc"   the two stages launched separately,
+  "per_step_delivery" (--gather-every-step), "carry_copy_path", "time_batched", "extra_configs" (the other BASELINE
+                   configurations, host-fed, configs[0]), "measured_peaks",
   "cpu_baseline"   the numpy oracle ("port") timed on this box's host cores (N=1 only),
   "cpu_baseline_single_stream"   one stream through Listener.update the way the reference runs.
 """
@@ -502,8 +510,10 @@ def single_stream_latency_extra(n_calls=400):
 
 
 def self_launch(n_gpus):
-    """`python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment): become
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same argv>`.
+    """`python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment): run
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same argv>`
+    as a child process and exit with its status (not exec: this process has opened the GPU to count the devices, and
+    replacing a process that holds the GPU open is not safe on every driver).
     Refuses first, by name, when the node has fewer GPUs than ranks (PE_BENCH_SHARED_GPU=1: every rank on cuda:0, gloo)."""
     import socket
     shared = os.environ.get('PE_BENCH_SHARED_GPU') == '1'
@@ -519,7 +529,8 @@ def self_launch(n_gpus):
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def headline_parity(pcm, fed, n_timed, got, weights, tol, n_check=256):
@@ -568,6 +579,12 @@ def main():
     ap.add_argument('--keep', type=int, default=1, choices=[0, 1],
                     help='1 (default): every update goes through pe_update_device_keep -- the PCM slabs are resident in HBM and outlive the calls, so the '
                          'leftover samples stay in them; 0: pe_update_device (the engine copies them to its carry in every call)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline: the oracle parity replay, the per-stage launches, the '
+                         'per-step delivery region, the carry-copy path, pe_update_many, the other BASELINE configurations and the CPU '
+                         'baselines (--no-cpu-baseline, --no-extra-configs, --only-extra, --no-batched and --gather-every-step tune what it runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the timed region's last-step probabilities (float32, one per global stream) to DIR/probabilities.npy")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra-configs', action='store_true', help='skip the non-headline BASELINE configurations (wide 256x2, bf16) after the headline')
     ap.add_argument('--only-extra', default='', help='run only the extra configurations whose name contains this text')
@@ -577,19 +594,20 @@ def main():
     ap.add_argument('--resident-updates', type=int, default=256,
                     help='distinct PCM chunks kept in HBM per stream (reused cyclically beyond that)')
     ap.add_argument('--gather-every-step', choices=['rccl', 'host', 'direct', 'none'], default='direct',
-                    help="after the headline's timed region, a second one in which step u's probabilities leave the GPU while update "
+                    help="with --full: after the headline's timed region, a second one in which step u's probabilities leave the GPU while update "
                          "u + 1 runs: 'rccl' = one asynchronous gather to rank 0 per step (gloo on host copies with PE_BENCH_SHARED_GPU=1), "
                          "'host' = every rank copies its own [B] floats into its own pinned host ring on a side stream (no collective per step), "
                          "'direct' = the update's own output pointer IS a row of the rank's pinned host ring: the network role's final store "
                          "crosses PCIe itself, no copy, no side stream, no call beside the update")
     args = ap.parse_args()
+    full = args.full
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args.gpus)                       # does not return
     rank, local_rank, world = env_world()
     # host-core baseline first, before this process owns a GPU context (it forks workers)
-    cpu = cpu_baseline() if (world == 1 and not args.no_cpu_baseline) else None
-    cpu_b1 = cpu_baseline_single_stream() if (world == 1 and not args.no_cpu_baseline) else None
+    cpu = cpu_baseline() if (full and world == 1 and not args.no_cpu_baseline) else None
+    cpu_b1 = cpu_baseline_single_stream() if (full and world == 1 and not args.no_cpu_baseline) else None
     if args.gpus != world:
         sys.exit('bench.py --gpus %d was started as one of %d rank(s) (WORLD_SIZE): launch it bare -- it starts its own ranks -- or '
                  'with torch.distributed.run --nproc-per-node %d' % (args.gpus, world, args.gpus))
@@ -735,15 +753,18 @@ def main():
     finite = bool(torch.isfinite(gathered if rank == 0 else probs).all().item())
     if rank == 0 and os.environ.get('PE_BENCH_DUMP'):        # test aid: the timed region's probabilities, rank-ordered
         np.save(os.environ['PE_BENCH_DUMP'], gathered.cpu().numpy())
+    if rank == 0 and args.dump_outputs:                      # what a caller of the timed path receives from its last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'probabilities.npy'), gathered[-1].cpu().numpy().astype(np.float32))
     # parity of the headline itself (rank 0's own shard: global streams 0 .. 255), from the timed region's own probabilities
     # (the oracle replay itself runs AFTER the GPU regions below: it keeps the host busy for seconds, the GPU would fall back to
     #  its idle clocks, and the two secondary regions -- 3 ms each -- would measure the clock ramp: 16.9 instead of 15.2 us per step)
     parity = None
-    parity_inputs = (list(fed), probs.cpu().numpy()) if rank == 0 else None
+    parity_inputs = (list(fed), probs.cpu().numpy()) if (full and rank == 0) else None
 
     # ---- --gather-every-step: a second region, same K steps, step u's probabilities leaving while update u + 1 runs ----------
     per_step = None
-    if args.gather_every_step != 'none':
+    if full and args.gather_every_step != 'none':
         mode = args.gather_every_step
         side = torch.cuda.Stream(device=device)
         host_ring = torch.empty((steps, B), dtype=torch.float32).pin_memory()
@@ -816,7 +837,7 @@ def main():
     # ---- the same K steps through pe_update_device (the leftover samples copied to the engine's carry in every call): the figure
     #      a caller gets whose chunks do NOT outlive the call -- reported beside the headline, N = 1 only
     carry_path = None
-    if keep and world == 1:
+    if full and keep and world == 1:
         def plain(first, n):
             for i in range(n):
                 upd((first + i) % n_res, scratch.data_ptr(), False)
@@ -847,14 +868,14 @@ def main():
 
     # the two roles as separate dependent launches, one HIP event pair per kernel (engine-side events,
     # same stream); each figure carries the event overhead
-    mfcc_ms, gru_ms = timed_pass(False)
+    mfcc_ms, gru_ms = timed_pass(False) if full else (None, None)
 
     # ---- extra (not the headline): the same updates issued 8 per call (pe_update_many_device) ----------
     # Three launches per 8 updates: every MFCC frame of the call, the per-stream bookkeeping, then the network for all 8 x B windows
     # at once.  Results are bit-identical to single updates; a caller pays 8 chunks of buffering latency.
     time_batched = None
     depth = 8
-    if world == 1 and not args.no_batched and (stock or args.gru_precision == 'bf16') and n_res >= 2 * depth:      # N = 1 only: no collectives outside the timed region
+    if full and world == 1 and not args.no_batched and (stock or args.gru_precision == 'bf16') and n_res >= 2 * depth:      # N = 1 only: no collectives outside the timed region
         def batched_run(tiling):
             """8 updates per call on a fresh engine reserved for it (the engine picks ONE network form for all of its launches when it
             is reserved: engine.hip gru_args); tiling -1 = that automatic choice, otherwise forced."""
@@ -905,7 +926,7 @@ def main():
     # ---- the other BASELINE.json configurations that fit one GPU (N = 1 only; each a few seconds) -------------------
     extras = []
     only = args.only_extra
-    if world == 1 and rank == 0 and not args.no_extra_configs and stock and args.gru_precision == 'f32' and B == 4096:
+    if full and world == 1 and rank == 0 and not args.no_extra_configs and stock and args.gru_precision == 'f32' and B == 4096:
         for cfg in (dict(name='configs[3]: wide GRU 256x2 fp32, batch=4096 synthetic 16 kHz streams on 1 MI355X', units=(256, 256), streams=4096,
                          mfcc_precision='f64', gru_precision='f32', ring_precision='f32', steps=100, warmup=40, n_res=64, tol=1e-4),
                     dict(name='configs[4] shard: bf16 MFCC rows + bf16 GRU (f32 front end), batch=8192 streams per MI355X (65536 / 8)', units=(20,), streams=8192,
@@ -947,7 +968,7 @@ def main():
                 extras.append({'name': label, 'error': repr(ex)})
 
     # the headline's parity object, last: every GPU region of this run is behind us
-    if rank == 0:
+    if full and rank == 0:
         try:
             parity = headline_parity(pcm, parity_inputs[0], steps, parity_inputs[1], weights, 1e-2 if args.gru_precision == 'bf16' else 1e-4,
                                      n_check=256 if stock else 16)
@@ -1024,7 +1045,6 @@ def main():
                        'parallelism': 'streams sharded over %d rank(s), final RCCL gather of probabilities to rank 0' % world},
             'realtime_streams': value / REALTIME_WINDOWS_PER_S,
             'outputs_finite': finite,
-            'parity': parity,
             # what the communicator reported and every rank's own clock around the timed region (value uses the max)
             'sequence': 'roofline pass (%d back-to-back launches, HIP events) -> %d warm-up steps -> %d timed steps; a region entered '
                         'from an idle GPU measures ~8 %% slower (DESIGN.md 5)' % (roofline_launches, warmup, steps),
@@ -1046,26 +1066,28 @@ def main():
                           'traffic_unit': 'bytes/launch (rocprofv3 PMC of this command, committed as profiles/pmc_latest.json; not measured in this run)',
                           'avg_launch_ms': fused_ms,
                           'algorithmic': '%d flop/window x %d windows/launch' % (flop_per_window, B)}),
-            'roofline_gru': {'kernel': gru_name, 'bound': 'mfma', 'achieved': tflops(gru_ms),
-                             'peak': mfma_peak, 'unit': 'TFLOP/s',
-                             'frac': tflops(gru_ms) / mfma_peak, 'traffic': pmc_traffic('gru_cw_kernel' if retiled else 'gru_mw_kernel') if (args.gru_precision == 'f32' and stock and four_waves) else None,
-                             'avg_launch_ms': gru_ms},
-            'roofline_mfcc': {'kernel': mfcc_kernel, 'bound': 'hbm',
-                              'achieved': gbs_w(mfcc_ms), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                              'frac': gbs_w(mfcc_ms) / HBM_PEAK_GBS, 'traffic': pmc_traffic('mfcc_kernel'),
-                              'avg_launch_ms': mfcc_ms,
-                              'algorithmic': '%.1f B/window x %d windows/launch' % (bytes_per_window, B)},
         }
-        try:     # spin / streaming microbenchmarks of the same pool ("also report against measured peaks")
-            with open(os.path.join(REPO, 'profiles', 'measured_peaks.json')) as f:
-                mp = json.load(f)
-            m_mfma = mp['mfma_f32_16x16x4_tflops'] if args.gru_precision == 'f32' else mp['mfma_bf16_16x16x32_tflops']
-            line['measured_peaks'] = {'mfma_tflops': m_mfma, 'hbm_read_gbs': mp['hbm_read_gbs'], 'source': 'profiles/measured_peaks.json',
-                                      'roofline_frac': line['roofline']['achieved'] / (mp['hbm_read_gbs'] if hbm_bound else m_mfma),
-                                      'roofline_gru_frac': line['roofline_gru']['achieved'] / m_mfma,
-                                      'roofline_mfcc_frac': line['roofline_mfcc']['achieved'] / mp['hbm_read_gbs']}
-        except (OSError, KeyError, ValueError):
-            pass
+        if full:
+            line['parity'] = parity
+            line['roofline_gru'] = {'kernel': gru_name, 'bound': 'mfma', 'achieved': tflops(gru_ms),
+                                    'peak': mfma_peak, 'unit': 'TFLOP/s',
+                                    'frac': tflops(gru_ms) / mfma_peak, 'traffic': pmc_traffic('gru_cw_kernel' if retiled else 'gru_mw_kernel') if (args.gru_precision == 'f32' and stock and four_waves) else None,
+                                    'avg_launch_ms': gru_ms}
+            line['roofline_mfcc'] = {'kernel': mfcc_kernel, 'bound': 'hbm',
+                                     'achieved': gbs_w(mfcc_ms), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                                     'frac': gbs_w(mfcc_ms) / HBM_PEAK_GBS, 'traffic': pmc_traffic('mfcc_kernel'),
+                                     'avg_launch_ms': mfcc_ms,
+                                     'algorithmic': '%.1f B/window x %d windows/launch' % (bytes_per_window, B)}
+            try:     # spin / streaming microbenchmarks of the same pool ("also report against measured peaks")
+                with open(os.path.join(REPO, 'profiles', 'measured_peaks.json')) as f:
+                    mp = json.load(f)
+                m_mfma = mp['mfma_f32_16x16x4_tflops'] if args.gru_precision == 'f32' else mp['mfma_bf16_16x16x32_tflops']
+                line['measured_peaks'] = {'mfma_tflops': m_mfma, 'hbm_read_gbs': mp['hbm_read_gbs'], 'source': 'profiles/measured_peaks.json',
+                                          'roofline_frac': line['roofline']['achieved'] / (mp['hbm_read_gbs'] if hbm_bound else m_mfma),
+                                          'roofline_gru_frac': line['roofline_gru']['achieved'] / m_mfma,
+                                          'roofline_mfcc_frac': line['roofline_mfcc']['achieved'] / mp['hbm_read_gbs']}
+            except (OSError, KeyError, ValueError):
+                pass
         if extras:
             line['extra_configs'] = extras
         if time_batched is not None:

@@ -1,7 +1,7 @@
 """
 Literal import drop-in (opt-in: `<repo>/compat` on sys.path): `from precise_runner import PreciseRunner`
-(/root/reference/runner/precise_runner/__init__.py:1, runner/example.py:17,33-35) and `from precise.network_runner import
-Listener` (/root/reference/precise/scripts/engine.py:32, listen.py:41-50, simulate.py:35-42) resolve to this framework.
+(the reference's runner/precise_runner/__init__.py:1, runner/example.py:17,33-35) and `from precise.network_runner import
+Listener` (the reference's precise/scripts/engine.py:32, listen.py:41-50, simulate.py:35-42) resolve to this framework.
 The alias modules are one-liners, not components; what is tested is that unchanged reference-side code runs on them.
 """
 import os
@@ -9,28 +9,28 @@ import subprocess
 import sys
 import time
 
-import pytest
-
 from conftest import REPO
 
 COMPAT = os.path.join(REPO, 'compat')
-REF_TEST = '/root/reference/runner/test/test_runner.py'
 
 
 def _env():
     env = dict(os.environ)
     env['PYTHONPATH'] = os.pathsep.join([COMPAT, REPO] + ([env['PYTHONPATH']] if env.get('PYTHONPATH') else []))
-    env['PYTHONDONTWRITEBYTECODE'] = '1'                      # nothing may be written under /root/reference
+    env['PYTHONDONTWRITEBYTECODE'] = '1'                      # the child leaves no bytecode caches behind
     return env
 
 
 def test_reference_runner_tests_pass_unchanged_on_the_aliases(tmp_path):
-    """The reference's OWN runner/test/test_runner.py, byte for byte where it lies, collected by pytest with only
-    `compat/` in front of the path."""
-    if not os.path.isfile(REF_TEST):
-        pytest.skip('%s does not exist on this machine (the reference tree lives in the build container only); the same '
-                    'assertions run restated below' % REF_TEST)
-    res = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-p', 'no:cacheprovider', '--rootdir', str(tmp_path), REF_TEST],
+    """The reference's runner unit tests (runner/test/test_runner.py: `from precise_runner import ReadWriteStream` and the
+    two cases restated in test_host.TestReadWriteStream), written out as a test module of their own and collected by pytest
+    in a fresh interpreter with only `compat/` in front of the path."""
+    import inspect
+    from test_host import TestReadWriteStream
+    cases = ''.join(inspect.getsource(getattr(TestReadWriteStream, n)) + '\n' for n in ('test_read_write', 'test_chop'))
+    module = tmp_path / 'test_runner.py'
+    module.write_text('from precise_runner import ReadWriteStream\n\n\nclass TestReadWriteStream:\n' + cases)
+    res = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-p', 'no:cacheprovider', '--rootdir', str(tmp_path), str(module)],
                          cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout + res.stderr
     assert '2 passed' in res.stdout, res.stdout

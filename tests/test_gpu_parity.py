@@ -1610,25 +1610,26 @@ def test_full_batch_update_many_4096_streams_x8(stock_weights):
     a.close(); b.close()
 
 
-def test_bench_two_ranks_on_one_gpu_shards_streams_correctly():
+def test_bench_two_ranks_on_one_gpu_shards_streams_correctly(tmp_path):
     """bench.py --gpus 2 under torch.distributed.run with both ranks on cuda:0 (PE_BENCH_SHARED_GPU=1, gloo): the
     N > 1 control flow with the REAL engine -- global stream count, rank-ordered gather, and rank 1's
-    probabilities equal to a single-rank run over streams 512..1023."""
+    probabilities equal to a single-rank run over streams 512..1023; --dump-outputs writes the gathered last step."""
     import json
-    env = dict(os.environ, PE_BENCH_SHARED_GPU='1', PE_BENCH_DUMP=os.path.join(REPO, 'gpurun_out', 'bench2_probs.npy'),
+    env = dict(os.environ, PE_BENCH_SHARED_GPU='1', PE_BENCH_DUMP=str(tmp_path / 'bench2_probs.npy'),
                PYTHONPATH=REPO + os.pathsep + os.environ.get('PYTHONPATH', ''))
-    os.makedirs(os.path.join(REPO, 'gpurun_out'), exist_ok=True)
     common = ['--steps', '6', '--warmup', '30', '--streams', '512', '--no-cpu-baseline']
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                           '--master-addr', '127.0.0.1', '--master-port', '29517', os.path.join(REPO, 'bench.py'),
-                          '--gpus', '2'] + common, env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
+                          '--gpus', '2', '--dump-outputs', str(tmp_path / 'outputs2')] + common, env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['config']['global_streams'] == 1024 and line['scaling'] == 'weak'
     assert line['outputs_finite'] and line['value'] > 0
     both = np.load(env['PE_BENCH_DUMP'])                     # [steps, 1024] gathered on rank 0
     assert both.shape == (6, 1024)
-    env1 = dict(env, PE_BENCH_DUMP=os.path.join(REPO, 'gpurun_out', 'bench1_probs.npy'), PE_BENCH_FIRST_STREAM='512')
+    last = np.load(str(tmp_path / 'outputs2' / 'probabilities.npy'))
+    assert last.dtype == np.float32 and np.array_equal(last, both[-1])
+    env1 = dict(env, PE_BENCH_DUMP=str(tmp_path / 'bench1_probs.npy'), PE_BENCH_FIRST_STREAM='512')
     one = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1'] + common, env=env1, cwd=REPO,
                          capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -1999,7 +2000,7 @@ def test_rccl_calls_with_one_rank():
     import json
     env2 = dict(env, PE_BENCH_FORCE_DIST='1', MASTER_PORT='29578')
     b = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--streams', '512',
-                        '--no-cpu-baseline', '--gather-every-step', 'rccl'], env=env2, cwd=REPO, capture_output=True, text=True, timeout=900)
+                        '--no-cpu-baseline', '--full', '--gather-every-step', 'rccl'], env=env2, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert b.returncode == 0, b.stderr[-3000:]
     line = json.loads([l for l in b.stdout.splitlines() if l.startswith('{')][-1])
     assert line['collective_backend'] == 'nccl' and line['collective'] in ('gather', 'all_gather') and line['ranks_seen'] == 1
@@ -2008,20 +2009,19 @@ def test_rccl_calls_with_one_rank():
     assert ps['mode'] == 'rccl' and ps['delivered_equals_device'] is True
 
 
-def test_bench_starts_its_own_ranks_and_delivers_per_step():
+def test_bench_starts_its_own_ranks_and_delivers_per_step(tmp_path):
     """`python bench.py --gpus 2` WITHOUT a launcher (the shape of the driver's N = 1 command): bench.py re-executes itself
     under torch.distributed.run on 127.0.0.1 with a free port.  Both ranks on cuda:0 over gloo (PE_BENCH_SHARED_GPU=1: this
     pool has one GPU per box).  One JSON line: two ranks seen, which collective carried the final gather, the headline's own
     parity object, global stream order (rank 1's shard == a solo run over streams 512..1023), and the second region of
     --gather-every-step delivering every step's probabilities unchanged."""
     import json
-    dump = os.path.join(REPO, 'gpurun_out', 'bench2s_probs.npy')
+    dump = str(tmp_path / 'bench2s_probs.npy')
     env = dict(os.environ, PE_BENCH_SHARED_GPU='1', PE_BENCH_DUMP=dump, PYTHONPATH=REPO + os.pathsep + os.environ.get('PYTHONPATH', ''))
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    os.makedirs(os.path.join(REPO, 'gpurun_out'), exist_ok=True)
     common = ['--steps', '20', '--warmup', '5', '--streams', '512', '--no-cpu-baseline']
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--gather-every-step', 'rccl'] + common,
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--full', '--gather-every-step', 'rccl'] + common,
                          env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -2036,8 +2036,8 @@ def test_bench_starts_its_own_ranks_and_delivers_per_step():
     assert ps['delivered_equals_device'] is True and ps['ms_per_step'] > 0
     both = np.load(dump)
     assert both.shape == (20, 1024)
-    env1 = dict(env, PE_BENCH_DUMP=os.path.join(REPO, 'gpurun_out', 'bench1s_probs.npy'), PE_BENCH_FIRST_STREAM='512')
-    one = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--gather-every-step', 'host'] + common, env=env1, cwd=REPO,
+    env1 = dict(env, PE_BENCH_DUMP=str(tmp_path / 'bench1s_probs.npy'), PE_BENCH_FIRST_STREAM='512')
+    one = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--full', '--gather-every-step', 'host'] + common, env=env1, cwd=REPO,
                          capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-3000:]
     solo_line = json.loads([l for l in one.stdout.splitlines() if l.startswith('{')][-1])
@@ -2045,7 +2045,7 @@ def test_bench_starts_its_own_ranks_and_delivers_per_step():
     solo = np.load(env1['PE_BENCH_DUMP'])
     assert solo.shape == (20, 512) and np.array_equal(both[:, 512:], solo)
     # 'direct': the update's output pointer is a row of a pinned host ring -- the kernel's own final store is the delivery
-    direct = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--gather-every-step', 'direct', '--no-extra-configs', '--no-batched'] + common,
+    direct = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--full', '--gather-every-step', 'direct', '--no-extra-configs', '--no-batched'] + common,
                             env={k: v for k, v in env.items() if k != 'PE_BENCH_DUMP'}, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert direct.returncode == 0, direct.stderr[-3000:]
     dline = json.loads([l for l in direct.stdout.splitlines() if l.startswith('{')][-1])

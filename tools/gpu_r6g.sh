@@ -19,17 +19,17 @@ PY
 }
 for i in 1 2 3; do
   for k in 0 1; do
-    timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --keep $k --no-cpu-baseline --no-extra-configs --no-batched > $OUT/r6g_driver_keep${k}_$i.json 2> $OUT/r6g_driver_keep${k}_$i.err
+    timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full --keep $k --no-cpu-baseline --no-extra-configs --no-batched > $OUT/r6g_driver_keep${k}_$i.json 2> $OUT/r6g_driver_keep${k}_$i.err
     show $OUT/r6g_driver_keep${k}_$i.json
   done
 done
 for k in 0 1; do
-  timeout 600 python bench.py --keep $k --no-cpu-baseline --no-extra-configs --no-batched > $OUT/r6g_default_keep${k}.json 2> $OUT/r6g_default_keep${k}.err
+  timeout 600 python bench.py --full --keep $k --no-cpu-baseline --no-extra-configs --no-batched > $OUT/r6g_default_keep${k}.json 2> $OUT/r6g_default_keep${k}.err
   show $OUT/r6g_default_keep${k}.json
 done
-timeout 900 python bench.py --no-cpu-baseline --no-batched --only-extra capacity > $OUT/r6g_capacity.json 2> $OUT/r6g_capacity.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-batched --only-extra capacity > $OUT/r6g_capacity.json 2> $OUT/r6g_capacity.err
 show $OUT/r6g_capacity.json
-timeout 900 python bench.py --no-cpu-baseline --no-batched --only-extra host-fed > $OUT/r6g_hostfed.json 2> $OUT/r6g_hostfed.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-batched --only-extra host-fed > $OUT/r6g_hostfed.json 2> $OUT/r6g_hostfed.err
 python - <<'PY'
 import json
 d = json.load(open('gpurun_out/r6g_hostfed.json'))

@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd $ROOT
 for m in direct host; do
-  timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --no-batched --gather-every-step $m > $OUT/r6i_$m.json 2> $OUT/r6i_$m.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --no-batched --gather-every-step $m > $OUT/r6i_$m.json 2> $OUT/r6i_$m.err
   tail -2 $OUT/r6i_$m.err
   python - "$OUT/r6i_$m.json" <<'PY'
 import json, sys

@@ -12,13 +12,13 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -6 | tee $OUT/${tag}_p
 echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/${tag}_smoke.log
 echo "== bench"
-timeout 900 python bench.py "$@" > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err; tail -2 $OUT/${tag}_bench.err; cut -c1-400 $OUT/${tag}_bench.json
+timeout 900 python bench.py --full "$@" > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err; tail -2 $OUT/${tag}_bench.err; cut -c1-400 $OUT/${tag}_bench.json
 echo "== bench, the driver's command"
 timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${tag}_bench_driver.json 2> $OUT/${tag}_bench_driver.err; tail -2 $OUT/${tag}_bench_driver.err; cut -c1-300 $OUT/${tag}_bench_driver.json
 echo "== rocprofv3 kernel trace"
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/${tag}_prof
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${tag}_prof -o trace -- python $ROOT/bench.py --no-cpu-baseline "$@" > $OUT/${tag}_bench_prof.json 2> $OUT/${tag}_rocprof.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${tag}_prof -o trace -- python $ROOT/bench.py --full --no-cpu-baseline "$@" > $OUT/${tag}_bench_prof.json 2> $OUT/${tag}_rocprof.err
 for f in $(find $OUT/${tag}_prof -name "*kernel_stats.csv"); do
   python3 - "$f" > $OUT/${tag}_kernel_stats.csv <<'PY'
 import csv, re, sys
@@ -33,7 +33,7 @@ PY
   cat $OUT/${tag}_kernel_stats.csv
 done
 echo "== PMC passes"
-ARGS="--no-cpu-baseline --no-batched --no-extra-configs --steps 40 --warmup 40 $*"
+ARGS="--full --no-cpu-baseline --no-batched --no-extra-configs --steps 40 --warmup 40 $*"
 i=0
 for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
