@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 7
+#define PE_ABI_VERSION 8
 
 typedef enum pe_status {
     PE_OK = 0,
@@ -109,6 +109,40 @@ int pe_create(const pe_params* params, const double* mel_filters, const pe_weigh
               int32_t n_streams, int32_t device, pe_engine** out);
 int pe_destroy(pe_engine* e);
 const char* pe_last_error(const pe_engine* e);
+
+/* Several wake-word models on the same streams (ABI 8).  The reference runs one model per listener:
+ * precise/scripts/engine.py builds one Listener(model_name, chunk_size) per process and
+ * runner/precise_runner/runner.py PreciseEngine(exe_file, model_file) one model, so two hotwords on the same
+ * audio take two listeners -- two front ends over identical PCM.  pe_create_models builds ONE engine with one
+ * front end, one feature window per stream and n_models networks: a Listener (network_runner.py:98-153) per
+ * model over shared MFCC frames.
+ *   - weights[0 .. n_models), 1 <= n_models <= 8 (else PE_ERR_INVALID).  Every model has model 0's n_layers,
+ *     units per layer and n_in per layer, else PE_ERR_UNSUPPORTED naming the model and the field; all of
+ *     this is checked before any device work.  The models share the whole pe_params (front end, feature
+ *     window, use_delta, precisions).  pe_create(...) == pe_create_models(..., n_models = 1, ...).
+ *   - Outputs: every entry point that writes network outputs writes n_models blocks, model first; block m is
+ *     bit for bit what a one-model engine with model m, the same params, n_streams and form
+ *     (pe_get_gru_tiling) writes: pe_update[_device|_device_keep], pe_run_device, pe_update_async (its pinned
+ *     landing zones are sized for it) [K][n_streams]; pe_update_subset[_device] [K][n_active];
+ *     pe_update_many[_device] [K][n_updates][n_streams]; pe_predict[_device] [K][n];
+ *     pe_evaluate [K][max_windows] (n_windows_out is the same for every model); pe_decode[_device] reads
+ *     raw[K][n_streams] and writes conf / fired [K][n_streams].  Entry points without a network (vectors,
+ *     clear, get / set_vectors, vectorize_*) are unchanged.
+ *   - Launches: a K-model engine never takes more launches than a one-model engine.  Where one model fuses the
+ *     update into one launch, K network roles run beside the one frame role in that launch (the network shape
+ *     chosen from K and the stream tiles); where one model takes two launches, the second is ONE
+ *     network launch for all K models; pe_update_many, pe_predict and pe_evaluate take one network launch for all
+ *     models; pe_decode is one launch over K x n_streams with per-model tables.  Exception: wide / stacked networks
+ *     (33..256 units) take one network launch per model -- each fills the machine on its own (configs[3]: 0.79
+ *     of the fp32 MFMA peak).
+ *   - Knobs apply to every model: pe_set_gru_tiling / pe_set_gru_waves / pe_set_fused give all models one
+ *     form; pe_set_input_projection(e, 1) on n_models > 1 returns PE_ERR_UNSUPPORTED (projection rows are
+ *     per model); pe_set_decoder / pe_set_trigger set every model, pe_set_decoder_model /
+ *     pe_set_trigger_model one (each model's .params threshold_config / threshold_center and each
+ *     hotword's sensitivity; one TriggerDetector per (model, stream)). */
+int pe_create_models(const pe_params* params, const double* mel_filters, const pe_weights* weights,
+                     int32_t n_models, int32_t n_streams, int32_t device, pe_engine** out);
+int pe_get_n_models(const pe_engine* e);
 
 /* Listener.clear (network_runner.py:121-123).  mask: n_streams bytes, non-zero = clear that
  * stream; NULL = clear all.  Runs on the NULL stream and synchronises: a caller that drives the
@@ -253,6 +287,9 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
  * one Listener.update returns, not the one a float64 logit would give. */
 int pe_set_decoder(pe_engine* e, const double* cd, int32_t cd_len, int32_t min_out, int32_t out_range, double center);
 int pe_set_trigger(pe_engine* e, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level);
+/* the same for model `model` of a pe_create_models engine (0 <= model < pe_get_n_models(e)) */
+int pe_set_decoder_model(pe_engine* e, int32_t model, const double* cd, int32_t cd_len, int32_t min_out, int32_t out_range, double center);
+int pe_set_trigger_model(pe_engine* e, int32_t model, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level);
 int pe_decode_device(pe_engine* e, const float* raw_dev, double* conf_out_dev, unsigned char* fired_out_dev, void* hip_stream);
 int pe_decode(pe_engine* e, const float* raw_host, double* conf_out_host, unsigned char* fired_out_host);
 

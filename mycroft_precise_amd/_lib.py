@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PE_LIB') or os.path.join(HERE, 'libprecise_engine.so')
 
 PE_OK, PE_ERR_INVALID, PE_ERR_HIP, PE_ERR_UNSUPPORTED, PE_ERR_NOMEM, PE_ERR_EOF = range(6)
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class PeParams(C.Structure):
@@ -47,6 +47,9 @@ EXPORTS = {
     'pe_last_global_error': (C.c_char_p, []),
     'pe_create': (C.c_int, [C.POINTER(PeParams), C.POINTER(C.c_double), C.POINTER(PeWeights), C.c_int32,
                             C.c_int32, C.POINTER(C.c_void_p)]),
+    'pe_create_models': (C.c_int, [C.POINTER(PeParams), C.POINTER(C.c_double), C.POINTER(PeWeights), C.c_int32, C.c_int32,
+                                   C.c_int32, C.POINTER(C.c_void_p)]),
+    'pe_get_n_models': (C.c_int, [C.c_void_p]),
     'pe_destroy': (C.c_int, [C.c_void_p]),
     'pe_last_error': (C.c_char_p, [C.c_void_p]),
     'pe_clear': (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -78,6 +81,8 @@ EXPORTS = {
                               C.POINTER(C.c_int64)]),
     'pe_set_decoder': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
     'pe_set_trigger': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
+    'pe_set_decoder_model': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
+    'pe_set_trigger_model': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
     'pe_decode_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_get_info': (C.c_int, [C.c_void_p, C.POINTER(PeInfo)]),
@@ -152,6 +157,9 @@ class HipEngine:
     One C-ABI engine: the streaming state of ``n_streams`` audio streams plus one network on one
     MI355X.  Thin, allocation-free wrapper; the reference-shaped classes live in
     ``network_runner.py``.
+
+    ``weights`` a LIST of weight dicts (same architecture) builds a K-model engine (pe_create_models): one
+    front end for all models, and every network output gains a leading model axis ``[K, ...]`` -- even for K = 1.
     """
 
     def __init__(self, params, weights, n_streams=1, device=0, mfcc_precision='f64', mel_filters=None,
@@ -181,29 +189,45 @@ class HipEngine:
         mel = np.ascontiguousarray(mel_filters, dtype=np.float64)
         if mel.shape != (params.n_filt, params.n_fft // 2 + 1):
             raise ValueError('mel filterbank has shape %r' % (mel.shape,))
-        layers = weights['gru']
+        self._multi = isinstance(weights, (list, tuple))
+        models = list(weights) if self._multi else [weights]
+        if not models:
+            raise ValueError('no models')
         keep = []                      # keep numpy buffers alive across the call
-        arr = (PeGruLayer * len(layers))()
-        for i, (k, rk, b) in enumerate(layers):
-            k = np.ascontiguousarray(k, dtype=np.float32)
-            rk = np.ascontiguousarray(rk, dtype=np.float32)
-            b = np.ascontiguousarray(b, dtype=np.float32)
-            units = rk.shape[0]
-            if k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
-                raise ValueError('GRU layer %d has inconsistent shapes' % i)
-            keep += [k, rk, b]
-            arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
-        dk = np.ascontiguousarray(weights['dense_kernel'], dtype=np.float32).reshape(-1)
-        db = float(np.asarray(weights['dense_bias'], dtype=np.float32).reshape(-1)[0])
-        w = PeWeights(len(layers), arr, _fptr(dk), db)
-        rc = self._lib.pe_create(C.byref(p), mel.ctypes.data_as(C.POINTER(C.c_double)), C.byref(w),
-                                 self.n_streams, int(device), C.byref(self._h))
+        ws = (PeWeights * len(models))()
+        for m, wm in enumerate(models):
+            layers = wm['gru']
+            arr = (PeGruLayer * len(layers))()
+            for i, (k, rk, b) in enumerate(layers):
+                k = np.ascontiguousarray(k, dtype=np.float32)
+                rk = np.ascontiguousarray(rk, dtype=np.float32)
+                b = np.ascontiguousarray(b, dtype=np.float32)
+                units = rk.shape[0]
+                if k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
+                    raise ValueError('GRU layer %d has inconsistent shapes' % i)
+                keep += [k, rk, b]
+                arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
+            dk = np.ascontiguousarray(wm['dense_kernel'], dtype=np.float32).reshape(-1)
+            db = float(np.asarray(wm['dense_bias'], dtype=np.float32).reshape(-1)[0])
+            keep += [arr, dk]
+            ws[m] = PeWeights(len(layers), arr, _fptr(dk), db)
+        if self._multi:
+            rc = self._lib.pe_create_models(C.byref(p), mel.ctypes.data_as(C.POINTER(C.c_double)), ws, len(models),
+                                            self.n_streams, int(device), C.byref(self._h))
+        else:
+            rc = self._lib.pe_create(C.byref(p), mel.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ws[0]),
+                                     self.n_streams, int(device), C.byref(self._h))
         if rc != PE_OK:
             msg = self._lib.pe_last_global_error().decode()
             self._h = C.c_void_p()
             self._raise(rc, msg)
-        self.units = layers[-1][1].shape[0]
+        self.units = models[0]['gru'][-1][1].shape[0]
+        self.n_models = len(models)
         self._win_hop = (int(params.window_samples), int(params.hop_samples))
+
+    def _lead(self, *shape):
+        """shape of a network output: a leading model axis on a K-model engine"""
+        return ((self.n_models,) if self._multi else ()) + shape
 
     # -- errors -------------------------------------------------------------------------
     @staticmethod
@@ -235,7 +259,7 @@ class HipEngine:
     def update(self, pcm) -> np.ndarray:
         """int16 [n_streams, chunk] -> raw network outputs float32 [n_streams]."""
         pcm = self._pcm(pcm)
-        out = np.empty(self.n_streams, dtype=np.float32)
+        out = np.empty(self._lead(self.n_streams), dtype=np.float32)
         self._check(self._lib.pe_update(self._h, pcm.ctypes.data, pcm.shape[1], out.ctypes.data))
         return out
 
@@ -248,7 +272,7 @@ class HipEngine:
             pcm = pcm.reshape(1, -1)
         if pcm.ndim != 2 or pcm.shape[0] != ids.size:
             raise ValueError('pcm must be int16 [%d active streams, chunk_samples], got %r' % (ids.size, pcm.shape))
-        out = np.empty(ids.size, dtype=np.float32)
+        out = np.empty(self._lead(ids.size), dtype=np.float32)
         self._check(self._lib.pe_update_subset(self._h, ids.ctypes.data, ids.size, pcm.ctypes.data, pcm.shape[1], out.ctypes.data))
         return out
 
@@ -288,10 +312,11 @@ class HipEngine:
         ``host_array``, but also ``torch.Tensor.pin_memory()`` / hipHostRegister'ed buffers -- is read by the DMA engine after
         the call returns and must stay untouched until ``wait()`` or until 3 more updates have been enqueued."""
         pcm = self._pcm(pcm)
+        n_out = self.n_models * self.n_streams
         if out is None:
-            out = np.empty(self.n_streams, dtype=np.float32)
-        if out.dtype != np.float32 or out.size != self.n_streams or not out.flags.c_contiguous:
-            raise ValueError('out must be a contiguous float32 array of %d elements' % self.n_streams)
+            out = np.empty(self._lead(self.n_streams), dtype=np.float32)
+        if out.dtype != np.float32 or out.size != n_out or not out.flags.c_contiguous:
+            raise ValueError('out must be a contiguous float32 array of %d elements' % n_out)
         self._check(self._lib.pe_update_async(self._h, pcm.ctypes.data, pcm.shape[1], out.ctypes.data))
         self._async_keep = (self._async_keep + [(pcm, out)])[-4:]          # the buffers of the updates in flight stay alive
         return out
@@ -310,7 +335,7 @@ class HipEngine:
         pcm = np.ascontiguousarray(pcm, dtype='<i2')
         if pcm.ndim != 3 or pcm.shape[1] != self.n_streams:
             raise ValueError('pcm must be int16 [n_updates, n_streams=%d, chunk_samples], got %r' % (self.n_streams, pcm.shape))
-        out = np.empty((pcm.shape[0], self.n_streams), dtype=np.float32)
+        out = np.empty(self._lead(pcm.shape[0], self.n_streams), dtype=np.float32)
         self._check(self._lib.pe_update_many(self._h, pcm.ctypes.data, pcm.shape[2], pcm.shape[0], out.ctypes.data))
         return out
 
@@ -341,7 +366,7 @@ class HipEngine:
         feats = np.ascontiguousarray(feats, dtype=np.float32)
         if feats.ndim != 3 or feats.shape[1:] != (self.n_features, self.feature_size):
             raise ValueError('inputs must be [N, %d, %d], got %r' % (self.n_features, self.feature_size, feats.shape))
-        out = np.empty((feats.shape[0], 1), dtype=np.float32)
+        out = np.empty(self._lead(feats.shape[0], 1), dtype=np.float32)
         self._check(self._lib.pe_predict(self._h, feats.ctypes.data, feats.shape[0], out.ctypes.data))
         return out
 
@@ -374,28 +399,35 @@ class HipEngine:
         win, hop = self._win_hop
         n_frames = 1 + (audio.size - win) // hop if audio.size >= win else 0
         n_win = max(0, -(-(n_frames - self.n_features) // int(hop_frames))) if n_frames > self.n_features else 0
-        out = np.empty((n_win, 1), dtype=np.float32)
+        out = np.empty(self._lead(n_win, 1), dtype=np.float32)
         n = C.c_int64(0)
         self._check(self._lib.pe_evaluate(self._h, audio.ctypes.data if audio.size else None, audio.size,
                                           int(hop_frames), out.ctypes.data if n_win else None, n_win, C.byref(n)))
-        return out[:n.value]
+        return out[:, :n.value] if self._multi else out[:n.value]
 
-    def set_decoder(self, decoder):
-        """Upload a ThresholdDecoder (its cumulative table and scalars) for pe_decode*."""
+    def set_decoder(self, decoder, model=None):
+        """Upload a ThresholdDecoder (its cumulative table and scalars) for pe_decode*: for every model, or for ``model``."""
         cd = np.ascontiguousarray(decoder.cd, dtype=np.float64)
-        self._check(self._lib.pe_set_decoder(self._h, cd.ctypes.data if cd.size else None, cd.size,
-                                             int(decoder.min_out), int(decoder.out_range), float(decoder.center)))
+        args = (cd.ctypes.data if cd.size else None, cd.size, int(decoder.min_out), int(decoder.out_range), float(decoder.center))
+        if model is None:
+            self._check(self._lib.pe_set_decoder(self._h, *args))
+        else:
+            self._check(self._lib.pe_set_decoder_model(self._h, int(model), *args))
 
-    def set_trigger(self, chunk_size: int, sensitivity: float = 0.5, trigger_level: int = 3):
-        self._check(self._lib.pe_set_trigger(self._h, int(chunk_size), float(sensitivity), int(trigger_level)))
+    def set_trigger(self, chunk_size: int, sensitivity: float = 0.5, trigger_level: int = 3, model=None):
+        if model is None:
+            self._check(self._lib.pe_set_trigger(self._h, int(chunk_size), float(sensitivity), int(trigger_level)))
+        else:
+            self._check(self._lib.pe_set_trigger_model(self._h, int(model), int(chunk_size), float(sensitivity), int(trigger_level)))
 
     def decode(self, raw, want_fired=False):
-        """raw float32 [n_streams] -> decoded confidences float64 [n_streams] (, fired bool [n_streams])."""
+        """raw float32 [n_streams] -> decoded confidences float64 [n_streams] (, fired bool [n_streams]); [K, n_streams]
+        each on a K-model engine."""
         raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(-1)
-        if raw.size != self.n_streams:
-            raise ValueError('expected %d raw outputs' % self.n_streams)
-        conf = np.empty(self.n_streams, dtype=np.float64)
-        fired = np.zeros(self.n_streams, dtype=np.uint8)
+        if raw.size != self.n_models * self.n_streams:
+            raise ValueError('expected %d raw outputs' % (self.n_models * self.n_streams))
+        conf = np.empty(self._lead(self.n_streams), dtype=np.float64)
+        fired = np.zeros(self._lead(self.n_streams), dtype=np.uint8)
         self._check(self._lib.pe_decode(self._h, raw.ctypes.data, conf.ctypes.data, fired.ctypes.data))
         return (conf, fired.astype(bool)) if want_fired else conf
 

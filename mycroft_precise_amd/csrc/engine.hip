@@ -27,6 +27,26 @@ struct DeviceBuf {
     size_t bytes = 0;
 };
 
+// one model's packed network (pe_create_models): the weight fields of pe_engine, set aside per model.  A weight field added to
+// pe_engine has to be added in five places: here, take_net / put_net and with_model (engine.hip), ModelNet / model_args
+// (pe_common.h) -- the static_assert below counts the fields of NetPack against that list.
+struct NetPack {
+    float dense_bias = 0.f;
+    float* wxd = nullptr; float* wx = nullptr; float* wr1 = nullptr; float* wr2 = nullptr; float* bias = nullptr; float* wd = nullptr;
+    float* cw_blob = nullptr;
+    float* wide_buf[2][6] = {{nullptr}}; float* wide_wd = nullptr;
+    float* wide3_buf[2][6] = {{nullptr}}; float* wide3_wd = nullptr;
+    uint16_t* wx_bf16 = nullptr; uint16_t* wr_bf16 = nullptr; float* wd_bf16 = nullptr;
+    uint32_t* b20_blob = nullptr; uint32_t* x3_blob = nullptr;
+};
+static_assert(sizeof(void*) == 8 && sizeof(NetPack) == 8 + 7 * 8 + 13 * 8 + 13 * 8 + 5 * 8,
+              "NetPack changed: update take_net / put_net / with_model and pe_common.h ModelNet / model_args");
+// one model's ThresholdDecoder / TriggerDetector settings (pe_set_decoder_model / pe_set_trigger_model)
+struct DecState {
+    double* cd = nullptr; int cd_len = 0, min_out = 0, out_range = 0; double center = 0.5;
+    double threshold = 0.5; int level = 3, rearm = -8; bool on = false;
+};
+
 }  // namespace
 
 struct pe_engine {
@@ -120,6 +140,11 @@ struct pe_engine {
     unsigned async_next = 0;
     int async_inflight = 0;
     std::vector<std::pair<char*, size_t>> pinned;               // pe_host_alloc'ed ranges (zero-copy sources / destinations)
+    // several models on the same streams (pe_create_models): the fields above hold model 0; nets[m] / dec[m] hold model m's
+    // packed network and decoder for m >= 1 (index 0 unused); `activation` is [n_models][n_padded]
+    int n_models = 1;
+    std::vector<NetPack> nets;
+    std::vector<DecState> dec;
 };
 
 namespace {
@@ -824,17 +849,18 @@ GruArgs gru_args(const pe_engine* e) {
 bool wide_uses_x3(const pe_engine* e) { return e->wide && e->gru_tiling == 2; }
 
 // Network launch for any input mode (0 explicit batch, 1 ring, 2 row sequence)
-int launch_network(pe_engine* e, const GruArgs& g, int mode, hipStream_t s) {
+int launch_network(pe_engine* e, const GruArgs& g, int mode, hipStream_t s, int model = 0) {
     if (e->wide) {
         // two forms of the streamed-weight network (pe_set_gru_tiling): 0 = f32-input MFMAs (gru_wide_device.h), 2 = float32
         // products on the bf16 pipe with the float32 weights split in registers (gru_wide_x3_device.h)
         const bool x3 = wide_uses_x3(e);
-        float* const (*buf)[6] = x3 ? e->wide3_buf : e->wide_buf;
+        const NetPack* own = model ? &e->nets[model] : nullptr;           // (model > 0: its weights, set aside at pe_create_models)
+        float* const (*buf)[6] = x3 ? (own ? own->wide3_buf : e->wide3_buf) : (own ? own->wide_buf : e->wide_buf);
         WideArgs wa{};
         wa.base = g;
         wa.n_layers = e->n_layers;
         wa.units = e->units;
-        wa.wd = x3 ? e->wide3_wd : e->wide_wd;
+        wa.wd = x3 ? (own ? own->wide3_wd : e->wide3_wd) : (own ? own->wide_wd : e->wide_wd);
         for (int l = 0; l < e->n_layers; ++l) {
             wa.layer[l].wx1 = reinterpret_cast<const float4*>(buf[l][0]);
             wa.layer[l].wr1 = reinterpret_cast<const float4*>(buf[l][1]);
@@ -852,11 +878,78 @@ int launch_network(pe_engine* e, const GruArgs& g, int mode, hipStream_t s) {
     return PE_OK;
 }
 
+// ---- several models (pe_create_models) ---------------------------------------------------------------------------
+NetPack take_net(const pe_engine* e) {
+    NetPack n;
+    n.dense_bias = e->dense_bias;
+    n.wxd = e->wxd; n.wx = e->wx; n.wr1 = e->wr1; n.wr2 = e->wr2; n.bias = e->bias; n.wd = e->wd;
+    n.cw_blob = e->cw_blob;
+    std::memcpy(n.wide_buf, e->wide_buf, sizeof(n.wide_buf)); n.wide_wd = e->wide_wd;
+    std::memcpy(n.wide3_buf, e->wide3_buf, sizeof(n.wide3_buf)); n.wide3_wd = e->wide3_wd;
+    n.wx_bf16 = e->wx_bf16; n.wr_bf16 = e->wr_bf16; n.wd_bf16 = e->wd_bf16;
+    n.b20_blob = e->b20_blob; n.x3_blob = e->x3_blob;
+    return n;
+}
+void put_net(pe_engine* e, const NetPack& n) {
+    e->dense_bias = n.dense_bias;
+    e->wxd = n.wxd; e->wx = n.wx; e->wr1 = n.wr1; e->wr2 = n.wr2; e->bias = n.bias; e->wd = n.wd;
+    e->cw_blob = n.cw_blob;
+    std::memcpy(e->wide_buf, n.wide_buf, sizeof(n.wide_buf)); e->wide_wd = n.wide_wd;
+    std::memcpy(e->wide3_buf, n.wide3_buf, sizeof(n.wide3_buf)); e->wide3_wd = n.wide3_wd;
+    e->wx_bf16 = n.wx_bf16; e->wr_bf16 = n.wr_bf16; e->wd_bf16 = n.wd_bf16;
+    e->b20_blob = n.b20_blob; e->x3_blob = n.x3_blob;
+}
+// a launch's arguments with model m's weights: the form (which blobs are read) is the engine's, the same for every model
+GruArgs with_model(const pe_engine* e, GruArgs a, int m) {
+    if (m == 0) return a;
+    const NetPack& n = e->nets[m];
+    a.wx = n.wx; a.wxd = n.wxd; a.wr1 = n.wr1; a.wr2 = n.wr2; a.bias = n.bias; a.wd = n.wd;
+    a.dense_bias = n.dense_bias;
+    a.wx_bf16 = n.wx_bf16; a.wr_bf16 = n.wr_bf16; a.wd_bf16 = n.wd_bf16;
+    a.b20 = a.b20 ? n.b20_blob : nullptr;
+    a.x3 = a.x3 ? n.x3_blob : nullptr;
+    a.cw = a.cw ? n.cw_blob : nullptr;
+    return a;
+}
+ModelSet model_set(const pe_engine* e, const GruArgs& a) {
+    ModelSet ms{};
+    for (int m = 0; m < e->n_models; ++m) {
+        const GruArgs b = with_model(e, a, m);
+        ms.net[m] = ModelNet{b.wx, b.wxd, b.wr1, b.wr2, b.bias, b.wd, b.cw, b.wx_bf16, b.wr_bf16, b.wd_bf16, b.b20, b.x3, b.dense_bias};
+    }
+    return ms;
+}
+// The network of every model of the engine over the windows of `g`; model m writes g.out + m * out_stride.  ONE launch for all
+// models (the K-model twin of the one-model kernel, kernels.hip gru_models_kernel); the wide / stacked networks take one
+// launch per model -- each fills the machine on its own.
+int launch_networks(pe_engine* e, const GruArgs& g, int mode, hipStream_t s, long long out_stride) {
+    if (e->n_models == 1) return launch_network(e, g, mode, s);
+    if (!e->wide) {
+        const ModelSet ms = model_set(e, g);
+        PE_HIP(e, launch_gru_small(g, mode, s, &ms, e->n_models, out_stride));
+        return PE_OK;
+    }
+    for (int m = 0; m < e->n_models; ++m) {
+        GruArgs gm = with_model(e, g, m);
+        gm.out = g.out + (size_t)m * (size_t)out_stride;
+        const int rc = launch_network(e, gm, mode, s, m);
+        if (rc) return rc;
+    }
+    return PE_OK;
+}
+// pe_update_many's batched network: out[model][update][window]
+int launch_networks_many(pe_engine* e, const GruArgs& g, int n_updates, hipStream_t s) {
+    if (e->n_models == 1) { PE_HIP(e, launch_gru_many(g, n_updates, e->n_padded, s)); return PE_OK; }
+    const ModelSet ms = model_set(e, g);
+    PE_HIP(e, launch_gru_many(g, n_updates, e->n_padded, s, &ms, e->n_models));
+    return PE_OK;
+}
+
 int launch_gru_ring(pe_engine* e, float* out_dev, hipStream_t s, const int32_t* ids = nullptr, int n_active = 0) {
     GruArgs a = gru_args(e);
     a.out = out_dev;
     if (ids) { a.ids = ids; a.n_streams = n_active; }
-    return launch_network(e, a, 1, s);
+    return launch_networks(e, a, 1, s, a.n_streams);
 }
 
 // ---- host-fed pipeline -------------------------------------------------------------------------------------------
@@ -995,7 +1088,12 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
         g.chunk = chunk;
         g.out = raw_out_dev;
         if (ids) { g.ids = ids; g.n_streams = n_active; }
-        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, e->n_cus, s));
+        if (e->n_models > 1) {           // K network roles beside the one frame role: outputs [K][windows]
+            const ModelSet ms = model_set(e, g);
+            if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_models_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, ms, e->n_models, e->n_cus, s));
+            else PE_HIP(e, launch_fused_models_f32(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, ms, e->n_models, e->n_cus, s));
+        }
+        else if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, e->n_cus, s));
         else PE_HIP(e, launch_fused_f32(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, e->n_cus, s));
         if (t) { PE_HIP(e, hipEventRecord(e->ev[1], s)); PE_HIP(e, hipEventRecord(e->ev[2], s)); e->ev_valid = true; e->ev_has_gru = false; }
     } else {
@@ -1021,8 +1119,10 @@ int pe_abi_version(void) { return PE_ABI_VERSION; }
 const char* pe_last_global_error(void) { return g_global_error.c_str(); }
 const char* pe_last_error(const pe_engine* e) { return e ? e->err.c_str() : g_global_error.c_str(); }
 
-int pe_create(const pe_params* p, const double* mel_filters, const pe_weights* w, int32_t n_streams,
-              int32_t device, pe_engine** out) {
+namespace {
+// pe_create / pe_create_models: w[0 .. n_models) (checked against w[0] by pe_create_models before it comes here)
+int create_engine(const pe_params* p, const double* mel_filters, const pe_weights* w, int32_t n_models, int32_t n_streams,
+                  int32_t device, pe_engine** out) {
     if (!p || !mel_filters || !w || !out) return fail(nullptr, PE_ERR_INVALID, "null argument to pe_create");
     *out = nullptr;
     if (n_streams <= 0) return fail(nullptr, PE_ERR_INVALID, "n_streams must be positive, got %d", n_streams);
@@ -1065,6 +1165,22 @@ int pe_create(const pe_params* p, const double* mel_filters, const pe_weights* w
     const int feature_size = p->use_delta ? 2 * p->n_mfcc : p->n_mfcc;          // params.py:99-109
     if (L.n_in != feature_size) return fail(nullptr, PE_ERR_INVALID, "layer n_in=%d does not match feature_size=%d", L.n_in, feature_size);
     if (!L.kernel || !L.recurrent_kernel || !L.bias || !w->dense_kernel) return fail(nullptr, PE_ERR_INVALID, "null weight pointer");
+
+    // further models: the same architecture (the K-model kernels run one network shape), checked before any device work
+    for (int m = 1; m < n_models; ++m) {
+        const pe_weights& wm = w[m];
+        if (wm.n_layers != w->n_layers || !wm.layers)
+            return fail(nullptr, PE_ERR_UNSUPPORTED, "model %d: n_layers=%d, model 0 has %d (the models of one engine share one architecture)", m, wm.n_layers, w->n_layers);
+        for (int l = 0; l < w->n_layers; ++l) {
+            if (wm.layers[l].units != w->layers[l].units)
+                return fail(nullptr, PE_ERR_UNSUPPORTED, "model %d: layer %d units=%d, model 0 has %d (the models of one engine share one architecture)", m, l, wm.layers[l].units, w->layers[l].units);
+            if (wm.layers[l].n_in != w->layers[l].n_in)
+                return fail(nullptr, PE_ERR_UNSUPPORTED, "model %d: layer %d n_in=%d, model 0 has %d (the models of one engine share one front end)", m, l, wm.layers[l].n_in, w->layers[l].n_in);
+            if (!wm.layers[l].kernel || !wm.layers[l].recurrent_kernel || !wm.layers[l].bias)
+                return fail(nullptr, PE_ERR_INVALID, "model %d: null weight pointer", m);
+        }
+        if (!wm.dense_kernel) return fail(nullptr, PE_ERR_INVALID, "model %d: null weight pointer", m);
+    }
 
     hipError_t herr = hipSetDevice(device);
     if (herr != hipSuccess) return fail(nullptr, PE_ERR_HIP, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(herr));
@@ -1116,37 +1232,63 @@ int pe_create(const pe_params* p, const double* mel_filters, const pe_weights* w
         if ((rc = dev_alloc(e, &e->carry, (size_t)2 * e->n_padded * e->carry_cap))) break;
         if ((rc = dev_alloc(e, &e->rec, (size_t)2 * e->n_padded))) break;
         if ((rc = dev_alloc(e, &e->ring, ring_floats(e)))) break;
-        if (wide) {
-            // Any width 33..256 (and stacked layers of different widths) runs on the streamed-weight kernel at the next
-            // multiple of 64: a padded unit has zero weights and zero bias everywhere, so z = r = 1/2, candidate = 0 and
-            // its state stays exactly 0 -- it neither receives nor contributes anything.
-            const int Hp = wide_units;
-            std::vector<std::vector<float>> kp(w->n_layers), rp(w->n_layers), bp(w->n_layers);
-            std::vector<pe_gru_layer> lp(w->n_layers);
-            for (int l = 0; l < w->n_layers; ++l) {
-                const pe_gru_layer& Ls = w->layers[l];
-                const int Hs = Ls.units, Fin = Ls.n_in, Fp = l == 0 ? Fin : Hp;
-                kp[l].assign((size_t)Fp * 3 * Hp, 0.f); rp[l].assign((size_t)Hp * 3 * Hp, 0.f); bp[l].assign((size_t)3 * Hp, 0.f);
-                for (int gate = 0; gate < 3; ++gate)
-                    for (int u = 0; u < Hs; ++u) {
-                        for (int k = 0; k < Fin; ++k) kp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.kernel[(size_t)k * 3 * Hs + gate * Hs + u];
-                        for (int k = 0; k < Hs; ++k) rp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.recurrent_kernel[(size_t)k * 3 * Hs + gate * Hs + u];
-                        bp[l][(size_t)gate * Hp + u] = Ls.bias[gate * Hs + u];
+        // one model's network in every layout the engine's forms read (into the weight fields of e)
+        auto pack_model = [&](const pe_weights* w) -> int {
+            const pe_gru_layer& L = w->layers[0];
+            int rc = PE_OK;
+            do {
+                if (wide) {
+                    // Any width 33..256 (and stacked layers of different widths) runs on the streamed-weight kernel at the next
+                    // multiple of 64: a padded unit has zero weights and zero bias everywhere, so z = r = 1/2, candidate = 0 and
+                    // its state stays exactly 0 -- it neither receives nor contributes anything.
+                    const int Hp = wide_units;
+                    std::vector<std::vector<float>> kp(w->n_layers), rp(w->n_layers), bp(w->n_layers);
+                    std::vector<pe_gru_layer> lp(w->n_layers);
+                    for (int l = 0; l < w->n_layers; ++l) {
+                        const pe_gru_layer& Ls = w->layers[l];
+                        const int Hs = Ls.units, Fin = Ls.n_in, Fp = l == 0 ? Fin : Hp;
+                        kp[l].assign((size_t)Fp * 3 * Hp, 0.f); rp[l].assign((size_t)Hp * 3 * Hp, 0.f); bp[l].assign((size_t)3 * Hp, 0.f);
+                        for (int gate = 0; gate < 3; ++gate)
+                            for (int u = 0; u < Hs; ++u) {
+                                for (int k = 0; k < Fin; ++k) kp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.kernel[(size_t)k * 3 * Hs + gate * Hs + u];
+                                for (int k = 0; k < Hs; ++k) rp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.recurrent_kernel[(size_t)k * 3 * Hs + gate * Hs + u];
+                                bp[l][(size_t)gate * Hp + u] = Ls.bias[gate * Hs + u];
+                            }
+                        lp[l] = pe_gru_layer{Fp, Hp, kp[l].data(), rp[l].data(), bp[l].data()};
                     }
-                lp[l] = pe_gru_layer{Fp, Hp, kp[l].data(), rp[l].data(), bp[l].data()};
+                    std::vector<float> dp(Hp, 0.f);
+                    const int Hlast = w->layers[w->n_layers - 1].units;
+                    for (int u = 0; u < Hlast; ++u) dp[u] = w->dense_kernel[u];
+                    pe_weights wp{w->n_layers, lp.data(), dp.data(), w->dense_bias};
+                    e->units = Hp;
+                    if ((rc = pack_gru_weights_wide(e, &wp))) break;
+                    if ((rc = pack_gru_weights_wide_x3(e, &wp))) break;
+                }
+                else if ((rc = pack_gru_weights(e, L, w->dense_kernel))) break;
+                if (p->gru_precision == 1 && (rc = pack_gru_weights_bf16(e, L, w->dense_kernel))) break;
+                if (!wide && b20_eligible(*p, L) && (rc = pack_gru_weights_b20(e, L, w->dense_kernel))) break;
+                if (!wide && x3_eligible(*p, L) && (rc = pack_gru_weights_x3(e, L, w->dense_kernel))) break;
+            } while (false);
+            return rc;
+        };
+        if ((rc = pack_model(w))) break;
+        if (n_models > 1) {
+            // models 1 .. K-1: packed the same way, then set aside (the engine's fields keep model 0)
+            const NetPack own = take_net(e);
+            const std::vector<float> pw = e->proj_w_host, pb = e->proj_b_host;
+            e->nets.assign((size_t)n_models, NetPack{});
+            e->dec.assign((size_t)n_models, DecState{});
+            for (int m = 1; m < n_models && !rc; ++m) {
+                put_net(e, NetPack{});
+                e->dense_bias = w[m].dense_bias;
+                rc = pack_model(&w[m]);
+                e->nets[m] = take_net(e);
             }
-            std::vector<float> dp(Hp, 0.f);
-            const int Hlast = w->layers[w->n_layers - 1].units;
-            for (int u = 0; u < Hlast; ++u) dp[u] = w->dense_kernel[u];
-            pe_weights wp{w->n_layers, lp.data(), dp.data(), w->dense_bias};
-            e->units = Hp;
-            if ((rc = pack_gru_weights_wide(e, &wp))) break;
-            if ((rc = pack_gru_weights_wide_x3(e, &wp))) break;
+            put_net(e, own);
+            e->proj_w_host = pw; e->proj_b_host = pb;
+            e->n_models = n_models;
+            if (rc) break;
         }
-        else if ((rc = pack_gru_weights(e, L, w->dense_kernel))) break;
-        if (p->gru_precision == 1 && (rc = pack_gru_weights_bf16(e, L, w->dense_kernel))) break;
-        if (!wide && b20_eligible(*p, L) && (rc = pack_gru_weights_b20(e, L, w->dense_kernel))) break;
-        if (!wide && x3_eligible(*p, L) && (rc = pack_gru_weights_x3(e, L, w->dense_kernel))) break;
         // the projection rows exist for the stock-width float32 network (3 R <= 16 slots: 4 output tiles, R = 5) fed
         // from the ring; they pay while the ring stays cache-resident (256 B per frame and stream)
         e->proj_ok = !wide && p->gru_precision == 0 && !p->use_delta && gru_small_regs(L.units) == 5 && !e->proj_w_host.empty();
@@ -1173,6 +1315,22 @@ int pe_create(const pe_params* p, const double* mel_filters, const pe_weights* w
     *out = e;
     return PE_OK;
 }
+}  // namespace
+
+int pe_create(const pe_params* p, const double* mel_filters, const pe_weights* w, int32_t n_streams,
+              int32_t device, pe_engine** out) {
+    return create_engine(p, mel_filters, w, 1, n_streams, device, out);
+}
+
+int pe_create_models(const pe_params* p, const double* mel_filters, const pe_weights* weights, int32_t n_models, int32_t n_streams,
+                     int32_t device, pe_engine** out) {
+    if (out) *out = nullptr;
+    if (n_models < 1 || n_models > kMaxModels) return fail(nullptr, PE_ERR_INVALID, "n_models must be in 1..%d, got %d", kMaxModels, n_models);
+    if (!weights) return fail(nullptr, PE_ERR_INVALID, "null argument to pe_create_models");
+    return create_engine(p, mel_filters, weights, n_models, n_streams, device, out);
+}
+
+int pe_get_n_models(const pe_engine* e) { return e ? e->n_models : -1; }
 
 int pe_destroy(pe_engine* e) {
     if (!e) return PE_OK;
@@ -1220,6 +1378,8 @@ int pe_clear(pe_engine* e, const uint8_t* mask_host) {
                 e->proj_on ? reinterpret_cast<const float*>(e->table_blob + e->table_layout.proj_b) : nullptr, e->row_floats};
     if (mask_dev) a.n_streams = e->n_streams;
     PE_HIP(e, launch_clear(a, nullptr));
+    if (e->n_models > 1 && e->activation)          // the further models' trigger rows
+        PE_HIP(e, launch_clear_activation(mask_dev, e->activation, a.n_streams, e->n_padded, e->n_models - 1, nullptr));
     PE_HIP(e, hipStreamSynchronize(nullptr));
     return PE_OK;
 }
@@ -1273,10 +1433,11 @@ int pe_update(pe_engine* e, const int16_t* pcm_host, int32_t chunk, float* raw_o
     PE_DRAIN(e);
     const size_t pcm_bytes = (size_t)e->n_streams * chunk * sizeof(int16_t);
     if ((rc = ensure(e, e->st_pcm, pcm_bytes))) return rc;
-    if ((rc = ensure(e, e->st_out, (size_t)e->n_streams * sizeof(float)))) return rc;
+    const size_t out_bytes = (size_t)e->n_models * e->n_streams * sizeof(float);
+    if ((rc = ensure(e, e->st_out, out_bytes))) return rc;
     PE_HIP(e, hipMemcpy(e->st_pcm.p, pcm_host, pcm_bytes, hipMemcpyHostToDevice));
     if ((rc = do_update(e, static_cast<const int16_t*>(e->st_pcm.p), chunk, static_cast<float*>(e->st_out.p), nullptr, nullptr))) return rc;
-    PE_HIP(e, hipMemcpy(raw_out_host, e->st_out.p, (size_t)e->n_streams * sizeof(float), hipMemcpyDeviceToHost));
+    PE_HIP(e, hipMemcpy(raw_out_host, e->st_out.p, out_bytes, hipMemcpyDeviceToHost));
     return PE_OK;
 }
 
@@ -1315,7 +1476,7 @@ int pe_update_subset(pe_engine* e, const int32_t* stream_ids_host, int32_t n_act
     }
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
-    const size_t pcm_bytes = (size_t)n_active * chunk * sizeof(int16_t), out_bytes = (size_t)n_active * sizeof(float), id_bytes = (size_t)n_active * sizeof(int32_t);
+    const size_t pcm_bytes = (size_t)n_active * chunk * sizeof(int16_t), out_bytes = (size_t)e->n_models * n_active * sizeof(float), id_bytes = (size_t)n_active * sizeof(int32_t);
     if ((rc = ensure(e, e->st_pcm, pcm_bytes))) return rc;
     if ((rc = ensure(e, e->st_out, out_bytes))) return rc;
     if ((rc = ensure(e, e->st_ids, id_bytes))) return rc;
@@ -1359,7 +1520,7 @@ int pe_update_async(pe_engine* e, const int16_t* pcm_host, int32_t chunk, float*
     if ((rc = async_init(e))) return rc;
     pe_engine::AsyncSlot& sl = e->aslot[e->async_next % pe_engine::kAsyncDepth];
     if ((rc = finish_slot(e, sl))) return rc;          // the ring is full: the oldest update is delivered first
-    const size_t pcm_bytes = (size_t)e->n_streams * chunk * sizeof(int16_t), out_bytes = (size_t)e->n_streams * sizeof(float);
+    const size_t pcm_bytes = (size_t)e->n_streams * chunk * sizeof(int16_t), out_bytes = (size_t)e->n_models * e->n_streams * sizeof(float);
     if ((rc = ensure(e, sl.dev_in, pcm_bytes))) return rc;
     if ((rc = ensure(e, sl.dev_out, out_bytes))) return rc;
     // (pageable memory: hipMemcpyAsync stages it through the runtime's own pinned buffers and returns once the last piece is
@@ -1475,7 +1636,7 @@ int pe_predict_device(pe_engine* e, const float* feats_dev, int32_t n, float* ou
     a.waves_per_tile = 1;
     a.feats = feats_dev;
     a.out = out_dev;
-    { int nrc = launch_network(e, a, 0, static_cast<hipStream_t>(stream)); if (nrc) return nrc; }
+    { int nrc = launch_networks(e, a, 0, static_cast<hipStream_t>(stream), n); if (nrc) return nrc; }
     return PE_OK;
 }
 
@@ -1487,10 +1648,10 @@ int pe_predict(pe_engine* e, const float* feats_host, int32_t n, float* out_host
     int rc;
     const size_t fb = (size_t)n * e->prm.n_features * (e->prm.use_delta ? 2 * e->n_in : e->n_in) * sizeof(float);
     if ((rc = ensure(e, e->st_feats, fb))) return rc;
-    if ((rc = ensure(e, e->st_out, (size_t)n * sizeof(float)))) return rc;
+    if ((rc = ensure(e, e->st_out, (size_t)e->n_models * n * sizeof(float)))) return rc;
     PE_HIP(e, hipMemcpy(e->st_feats.p, feats_host, fb, hipMemcpyHostToDevice));
     if ((rc = pe_predict_device(e, static_cast<const float*>(e->st_feats.p), n, static_cast<float*>(e->st_out.p), nullptr))) return rc;
-    PE_HIP(e, hipMemcpy(out_host, e->st_out.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    PE_HIP(e, hipMemcpy(out_host, e->st_out.p, (size_t)e->n_models * n * sizeof(float), hipMemcpyDeviceToHost));
     return PE_OK;
 }
 
@@ -1561,7 +1722,7 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
     const size_t ab = (size_t)n_samples * sizeof(double), rb = (size_t)n_frames * e->row_floats * sizeof(float);
     if ((rc = ensure(e, e->st_audio, ab))) return rc;
     if ((rc = ensure(e, e->st_feats, rb))) return rc;
-    if ((rc = ensure(e, e->st_out, (size_t)n_windows * sizeof(float)))) return rc;
+    if ((rc = ensure(e, e->st_out, (size_t)e->n_models * n_windows * sizeof(float)))) return rc;
     PE_HIP(e, hipMemcpy(e->st_audio.p, audio_host, ab, hipMemcpyHostToDevice));
     if (e->general) {
         if (e->prm.mfcc_precision == 0) {
@@ -1584,54 +1745,111 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
     g.row_stride = hop_frames;
     g.out = static_cast<float*>(e->st_out.p);
     g.waves_per_tile = 1;
-    if ((rc = launch_network(e, g, 2, nullptr))) return rc;
-    PE_HIP(e, hipMemcpy(out_host, e->st_out.p, (size_t)n_windows * sizeof(float), hipMemcpyDeviceToHost));
+    if ((rc = launch_networks(e, g, 2, nullptr, n_windows))) return rc;
+    for (int m = 0; m < e->n_models; ++m)           // out_host[K][max_windows]
+        PE_HIP(e, hipMemcpy(out_host + (size_t)m * max_windows, static_cast<float*>(e->st_out.p) + (size_t)m * n_windows, (size_t)n_windows * sizeof(float), hipMemcpyDeviceToHost));
     return PE_OK;
 }
+
+namespace {
+// model m's decoder (model 0: the engine's own fields)
+int set_decoder(pe_engine* e, int m, const double* cd, int32_t cd_len, int32_t min_out, int32_t out_range, double center) {
+    double*& dcd = m ? e->dec[m].cd : e->cd;
+    int& dlen = m ? e->dec[m].cd_len : e->cd_len;
+    dev_free(e, dcd, (size_t)(dlen ? dlen : 1) * sizeof(double));
+    dcd = nullptr; dlen = 0;
+    std::vector<double> host(cd, cd + cd_len);
+    int rc = dev_upload(e, &dcd, host);
+    if (rc) return rc;
+    dlen = cd_len;
+    if (m) { e->dec[m].min_out = min_out; e->dec[m].out_range = out_range; e->dec[m].center = center; }
+    else { e->dec_min_out = min_out; e->dec_out_range = out_range; e->dec_center = center; }
+    return PE_OK;
+}
+int set_trigger(pe_engine* e, int m, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level) {
+    if (!e->activation) {
+        int rc = dev_alloc(e, &e->activation, (size_t)e->n_models * e->n_padded);     // [n_models][n_padded]
+        if (rc) return rc;
+    }
+    PE_HIP(e, hipMemset(e->activation + (size_t)m * e->n_padded, 0, (size_t)e->n_padded * sizeof(int32_t)));
+    const int n = 8 * 2048;                                // -(8 * 2048) // chunk_size, floor division
+    const int rearm = -((n + chunk_size_bytes - 1) / chunk_size_bytes);
+    if (m) { e->dec[m].threshold = 1.0 - sensitivity; e->dec[m].level = trigger_level; e->dec[m].rearm = rearm; e->dec[m].on = true; }
+    else { e->trig_threshold = 1.0 - sensitivity; e->trig_level = trigger_level; e->trig_rearm = rearm; e->trig_on = true; }
+    return PE_OK;
+}
+}  // namespace
 
 int pe_set_decoder(pe_engine* e, const double* cd, int32_t cd_len, int32_t min_out, int32_t out_range, double center) {
     if (!e || cd_len < 0 || (cd_len > 0 && !cd)) return fail(e, PE_ERR_INVALID, "bad decoder table");
     if (out_range != 0 && cd_len < 1) return fail(e, PE_ERR_INVALID, "decoder needs a non-empty table when out_range != 0");
     PE_HIP(e, hipSetDevice(e->device));
     PE_HIP(e, hipDeviceSynchronize());                    // no decode launch may still read the old table
-    dev_free(e, e->cd, (size_t)(e->cd_len ? e->cd_len : 1) * sizeof(double));
-    e->cd = nullptr; e->cd_len = 0;
-    std::vector<double> host(cd, cd + cd_len);
-    int rc = dev_upload(e, &e->cd, host);
-    if (rc) return rc;
-    e->cd_len = cd_len; e->dec_min_out = min_out; e->dec_out_range = out_range; e->dec_center = center;
+    for (int m = 0; m < e->n_models; ++m) {               // (every model of the engine)
+        const int rc = set_decoder(e, m, cd, cd_len, min_out, out_range, center);
+        if (rc) return rc;
+    }
     return PE_OK;
+}
+
+int pe_set_decoder_model(pe_engine* e, int32_t model, const double* cd, int32_t cd_len, int32_t min_out, int32_t out_range, double center) {
+    if (!e || cd_len < 0 || (cd_len > 0 && !cd)) return fail(e, PE_ERR_INVALID, "bad decoder table");
+    if (model < 0 || model >= e->n_models) return fail(e, PE_ERR_INVALID, "model %d outside 0..%d", model, e->n_models - 1);
+    if (out_range != 0 && cd_len < 1) return fail(e, PE_ERR_INVALID, "decoder needs a non-empty table when out_range != 0");
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_HIP(e, hipDeviceSynchronize());
+    return set_decoder(e, model, cd, cd_len, min_out, out_range, center);
 }
 
 int pe_set_trigger(pe_engine* e, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level) {
     if (!e || chunk_size_bytes <= 0) return fail(e, PE_ERR_INVALID, "bad trigger parameters");
     PE_HIP(e, hipSetDevice(e->device));
-    if (!e->activation) {
-        int rc = dev_alloc(e, &e->activation, (size_t)e->n_padded);
+    for (int m = 0; m < e->n_models; ++m) {               // (every model of the engine)
+        const int rc = set_trigger(e, m, chunk_size_bytes, sensitivity, trigger_level);
         if (rc) return rc;
     }
-    PE_HIP(e, hipMemset(e->activation, 0, (size_t)e->n_padded * sizeof(int32_t)));
-    e->trig_threshold = 1.0 - sensitivity;
-    e->trig_level = trigger_level;
-    const int n = 8 * 2048;                                // -(8 * 2048) // chunk_size, floor division
-    e->trig_rearm = -((n + chunk_size_bytes - 1) / chunk_size_bytes);
-    e->trig_on = true;
     return PE_OK;
 }
 
+int pe_set_trigger_model(pe_engine* e, int32_t model, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level) {
+    if (!e || chunk_size_bytes <= 0) return fail(e, PE_ERR_INVALID, "bad trigger parameters");
+    if (model < 0 || model >= e->n_models) return fail(e, PE_ERR_INVALID, "model %d outside 0..%d", model, e->n_models - 1);
+    PE_HIP(e, hipSetDevice(e->device));
+    return set_trigger(e, model, chunk_size_bytes, sensitivity, trigger_level);
+}
+
+// raw_dev / conf_out_dev / fired_out_dev: [n_models][n_streams]; ONE decode launch (a K-model engine: per-model tables)
 int pe_decode_device(pe_engine* e, const float* raw_dev, double* conf_out_dev, unsigned char* fired_out_dev, void* stream) {
     if (!e || !raw_dev) return fail(e, PE_ERR_INVALID, "null argument to pe_decode_device");
-    if (!e->cd && e->dec_out_range != 0) return fail(e, PE_ERR_INVALID, "pe_set_decoder has not been called");
-    if (!e->cd_len && !e->cd) return fail(e, PE_ERR_INVALID, "pe_set_decoder has not been called");
+    for (int m = 0; m < e->n_models; ++m) {
+        const double* cd = m ? e->dec[m].cd : e->cd;
+        const int cd_len = m ? e->dec[m].cd_len : e->cd_len, out_range = m ? e->dec[m].out_range : e->dec_out_range;
+        if (!cd && out_range != 0) return fail(e, PE_ERR_INVALID, "pe_set_decoder has not been called");
+        if (!cd_len && !cd) return fail(e, PE_ERR_INVALID, m ? "pe_set_decoder has not been called for model %d" : "pe_set_decoder has not been called", m);
+    }
     PE_HIP(e, hipSetDevice(e->device));
-    DecodeArgs a{};
-    a.n_streams = e->n_streams; a.raw = raw_dev; a.cd = e->cd; a.cd_len = e->cd_len;
-    a.min_out = e->dec_min_out; a.out_range = e->dec_out_range; a.center = e->dec_center;
-    a.conf_out = conf_out_dev;
-    a.activation = e->trig_on ? e->activation : nullptr;
-    a.fired_out = fired_out_dev;
-    a.threshold = e->trig_threshold; a.trigger_level = e->trig_level; a.rearm = e->trig_rearm;
-    PE_HIP(e, launch_decode(a, static_cast<hipStream_t>(stream)));
+    const size_t n = (size_t)e->n_streams;
+    DecodeSet set{};
+    for (int m = 0; m < e->n_models; ++m) {
+        DecodeArgs& a = set.m[m];
+        a.n_streams = e->n_streams; a.raw = raw_dev + m * n;
+        a.conf_out = conf_out_dev ? conf_out_dev + m * n : nullptr;
+        a.fired_out = fired_out_dev ? fired_out_dev + m * n : nullptr;
+        if (m == 0) {
+            a.cd = e->cd; a.cd_len = e->cd_len;
+            a.min_out = e->dec_min_out; a.out_range = e->dec_out_range; a.center = e->dec_center;
+            a.activation = e->trig_on ? e->activation : nullptr;
+            a.threshold = e->trig_threshold; a.trigger_level = e->trig_level; a.rearm = e->trig_rearm;
+        } else {
+            const DecState& d = e->dec[m];
+            a.cd = d.cd; a.cd_len = d.cd_len;
+            a.min_out = d.min_out; a.out_range = d.out_range; a.center = d.center;
+            a.activation = d.on ? e->activation + (size_t)m * e->n_padded : nullptr;
+            a.threshold = d.threshold; a.trigger_level = d.level; a.rearm = d.rearm;
+        }
+    }
+    if (e->n_models == 1) PE_HIP(e, launch_decode(set.m[0], static_cast<hipStream_t>(stream)));
+    else PE_HIP(e, launch_decode_models(set, e->n_models, e->n_streams, static_cast<hipStream_t>(stream)));
     return PE_OK;
 }
 
@@ -1639,7 +1857,7 @@ int pe_decode(pe_engine* e, const float* raw_host, double* conf_out_host, unsign
     if (!e || !raw_host) return fail(e, PE_ERR_INVALID, "null argument to pe_decode");
     PE_HIP(e, hipSetDevice(e->device));
     int rc;
-    const size_t n = (size_t)e->n_streams;
+    const size_t n = (size_t)e->n_models * e->n_streams;
     if ((rc = ensure(e, e->st_out, n * sizeof(float)))) return rc;
     if ((rc = ensure(e, e->st_conf, n * sizeof(double)))) return rc;
     if ((rc = ensure(e, e->st_fired, n))) return rc;
@@ -1720,14 +1938,13 @@ int pe_update_many_device(pe_engine* e, const int16_t* pcm_dev, int32_t chunk, i
                 GruArgs gu = g;
                 gu.ke_plain = e->ke_hist + (size_t)u * e->n_padded;
                 gu.out = raw_out_dev + (size_t)u * e->n_streams;
-                int nrc = launch_network(e, gu, 1, s);
+                int nrc = launch_networks(e, gu, 1, s, (long long)n_updates * e->n_streams);
                 if (nrc) return nrc;
             }
             return PE_OK;
         }
         g.waves_per_tile = 1;
-        PE_HIP(e, launch_gru_many(g, n_updates, e->n_padded, s));
-        return PE_OK;
+        return launch_networks_many(e, g, n_updates, s);
     }
     // frames one stream can complete in this call: one task row per frame, at most kMaxFrameRows rows
     const int rows = max_frames_per_call(e, (long long)n_updates * chunk);
@@ -1752,14 +1969,13 @@ int pe_update_many_device(pe_engine* e, const int16_t* pcm_dev, int32_t chunk, i
             GruArgs gu = g;
             gu.ke_plain = e->ke_hist + (size_t)u * e->n_padded;
             gu.out = raw_out_dev + (size_t)u * e->n_streams;
-            int nrc = launch_network(e, gu, 1, s);
+            int nrc = launch_networks(e, gu, 1, s, (long long)n_updates * e->n_streams);
             if (nrc) return nrc;
         }
         return PE_OK;
     }
     g.waves_per_tile = 1;                                 // (the launcher picks one or four waves per window itself)
-    PE_HIP(e, launch_gru_many(g, n_updates, e->n_padded, s));
-    return PE_OK;
+    return launch_networks_many(e, g, n_updates, s);
 }
 
 int pe_update_many(pe_engine* e, const int16_t* pcm_host, int32_t chunk, int32_t n_updates, float* raw_out_host) {
@@ -1768,7 +1984,7 @@ int pe_update_many(pe_engine* e, const int16_t* pcm_host, int32_t chunk, int32_t
     if (!raw_out_host || n_updates < 1) return fail(e, PE_ERR_INVALID, "bad arguments to pe_update_many");
     PE_HIP(e, hipSetDevice(e->device));
     const size_t pcm_bytes = (size_t)n_updates * e->n_streams * chunk * sizeof(int16_t);
-    const size_t out_bytes = (size_t)n_updates * e->n_streams * sizeof(float);
+    const size_t out_bytes = (size_t)e->n_models * n_updates * e->n_streams * sizeof(float);
     if ((rc = ensure(e, e->st_pcm, pcm_bytes))) return rc;
     if ((rc = ensure(e, e->st_out, out_bytes))) return rc;
     PE_HIP(e, hipMemcpy(e->st_pcm.p, pcm_host, pcm_bytes, hipMemcpyHostToDevice));
@@ -1830,6 +2046,7 @@ int pe_set_input_projection(pe_engine* e, int32_t enabled) {
     if (!e) return PE_ERR_INVALID;
     if (enabled != 0 && enabled != 1) return fail(e, PE_ERR_INVALID, "input projection must be 0 or 1");
     if (enabled && !e->proj_ok) return fail(e, PE_ERR_UNSUPPORTED, "input-projection rows exist for the float32 network of 17..20 units without delta features only");
+    if (enabled && e->n_models > 1) return fail(e, PE_ERR_UNSUPPORTED, "input-projection rows are per model: an engine of %d models has none", e->n_models);
     if ((enabled != 0) == e->proj_on) return PE_OK;
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);

@@ -378,6 +378,176 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WP
     fused_update_body<R, SH, RG, MW, PROJ, CW>(m, t, g, n_gru_blocks, n_frame_blocks, n_tiles, frames_first);
 }
 
+// ---- the fused update of a K-model engine (pe_create_models): K network roles beside ONE frame role and ONE bookkeeping
+// role.  The network workgroups are the one-model launch's, n_gru_blocks per model, model-major: workgroup b of the network
+// runs block b % n_gru_blocks of model b / n_gru_blocks with that model's weights (ModelSet) and writes that model's block
+// of the output.  The network roles only READ the ring and the records (the frame and bookkeeping roles write rows and
+// record sides no window of this launch reads, §4.5), so K of them are as independent as one.  No input projection rows
+// (pe_set_input_projection refuses K > 1: the rows are per model).
+template <class R, class SH, int RG, bool MW, bool CW>
+__device__ __forceinline__ void fused_update_models_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ModelSet& ms,
+                                                         const int n_gru_blocks, const int n_models, const int n_frame_blocks,
+                                                         const int n_tiles, const int frames_first) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    touch_kernel_arguments<(int)(sizeof(MfccStreamArgs<R>) + sizeof(WaveTables<R>) + sizeof(GruArgs) + 20)>();
+    const int n_net = n_gru_blocks * n_models;
+    const int b = role_block(blockIdx.x, n_net, n_frame_blocks, frames_first & kFramesFirst);
+    if (b < n_net) {
+        const int mi = __builtin_amdgcn_readfirstlane(b / n_gru_blocks);
+        const int bl = b - mi * n_gru_blocks;
+        const GruArgs gm = model_args(g, ms.net[mi], mi, g.n_streams);
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        __builtin_amdgcn_s_setprio(3);
+        int role = wave;
+        if (CW && MW && (frames_first & kBySimd)) {
+            int* const slot = reinterpret_cast<int*>(smem) + kCwRoleSlot;
+            const int simd = wave_simd_id();
+            if ((threadIdx.x & 63) == 0) slot[wave] = simd;
+            __syncthreads();
+            if (((1 << slot[0]) | (1 << slot[1]) | (1 << slot[2]) | (1 << slot[3])) == 15) role = simd;
+        }
+        if constexpr (CW) {
+            static_assert(RG == 5, "the re-tiled shapes exist for the stock width");
+            if (MW) {
+                gru_tile_cw<false>(gm, bl, role, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+            } else {
+                const int tile = bl * 4 + wave;       // (no delta inputs on this shape: the launcher keeps four waves for use_delta)
+                if (tile < n_tiles) gru_tile_v<kRing, false>(gm, tile, threadIdx.x & 63);
+            }
+        } else if (MW) {
+            gru_tile_mw_any<RG, false>(gm, bl, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+        } else {
+            const int tile = bl * 4 + wave;
+            if (tile < n_tiles) gru_tile<RG, kRing, false>(gm, tile, threadIdx.x & 63);
+        }
+    } else if (b < n_net + n_frame_blocks) {
+        mfcc_frame_tasks<R, SH, true, true>(m, t, smem, (b - n_net) * kFrameWaves, n_frame_blocks * kFrameWaves, CW && MW && (frames_first & kBySimd));
+    } else {
+        mfcc_book_tile<R>(m, b - n_net - n_frame_blocks);
+    }
+}
+// (the integers first: they sit in the argument lines the prologue touches; the ModelSet behind them is read once the model is known)
+template <class R, class SH, int RG, bool MW, bool CW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) void fused_update_models_kernel(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
+                                                                  const int n_gru_blocks, const int n_models, const int n_frame_blocks,
+                                                                  const int n_tiles, const int frames_first, const ModelSet ms) {
+    fused_update_models_body<R, SH, RG, MW, CW>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
+}
+template <class R, class SH, int RG, bool MW, bool CW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) PE_NO_PK_F32 void fused_update_models_kernel_nopk(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
+                                                                  const int n_gru_blocks, const int n_models, const int n_frame_blocks,
+                                                                  const int n_tiles, const int frames_first, const ModelSet ms) {
+    fused_update_models_body<R, SH, RG, MW, CW>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
+}
+// ... and with the bf16 network role (four tiles per network workgroup, one wave each)
+template <class R, class SH, bool DELTA, bool RB>
+__device__ __forceinline__ void fused_update_bf16_models_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ModelSet& ms,
+                                                              const int n_gru_blocks, const int n_models, const int n_frame_blocks, const int n_tiles,
+                                                              const int frames_first) {
+    touch_kernel_arguments<(int)(sizeof(MfccStreamArgs<R>) + sizeof(WaveTables<R>) + sizeof(GruArgs) + 20)>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tpw = frames_first >> 8;
+    const int n_net = n_gru_blocks * n_models;
+    const int b = role_block(blockIdx.x, n_net, n_frame_blocks, frames_first & 1);
+    if (b < n_net) {
+        const int mi = __builtin_amdgcn_readfirstlane(b / n_gru_blocks);
+        const int bl = b - mi * n_gru_blocks;
+        const GruArgs gm = model_args(g, ms.net[mi], mi, g.n_streams);
+        const int wave = threadIdx.x >> 6;
+        const int tile = bl * tpw + wave;
+        if (wave < tpw && tile < n_tiles) {
+            if (gm.b20) { gru_tile_b20<kRing, DELTA, RB>(gm, tile, threadIdx.x & 63); return; }
+            gru_tile_bf16<kRing, DELTA, RB>(gm, tile, threadIdx.x & 63);
+        }
+    } else if (b < n_net + n_frame_blocks) {
+        mfcc_frame_tasks<R, SH, true>(m, t, smem, (b - n_net) * kFrameWaves, n_frame_blocks * kFrameWaves);
+    } else {
+        mfcc_book_tile<R>(m, b - n_net - n_frame_blocks);
+    }
+}
+template <class R, class SH, bool DELTA, bool RB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) void fused_update_bf16_models_kernel(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
+                                                                       const int n_gru_blocks, const int n_models, const int n_frame_blocks,
+                                                                       const int n_tiles, const int frames_first, const ModelSet ms) {
+    fused_update_bf16_models_body<R, SH, DELTA, RB>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
+}
+template <class R, class SH, bool DELTA, bool RB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) PE_NO_PK_F32 void fused_update_bf16_models_kernel_nopk(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
+                                                                       const int n_gru_blocks, const int n_models, const int n_frame_blocks,
+                                                                       const int n_tiles, const int frames_first, const ModelSet ms) {
+    fused_update_bf16_models_body<R, SH, DELTA, RB>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
+}
+
+// ---- the network of a K-model engine in ONE launch, every shape of the launchers below: NET names the one-model kernel's
+// tile function; workgroup b runs block b % per_model of model b / per_model (model-major outputs, out_stride apart)
+template <int R, int MODE, bool PROJ, int KX> struct NetSmall {          // gru_small_kernel / gru_many_kernel
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile<R, MODE, PROJ, KX>(a, tile, threadIdx.x); }
+};
+template <int R, bool PROJ, int KX> struct NetMw {                       // gru_mw_kernel / gru_many_mw_kernel
+    static constexpr int kThreads = 256; static constexpr size_t kLds = (3 * R * 64 + 256) * sizeof(float);
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char* smem) {
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        gru_tile_mw_any<R, PROJ, KX>(a, tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+    }
+};
+template <int MODE, bool DELTA> struct NetV {                            // gru_v_kernel / gru_many_v_kernel
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile_v<MODE, DELTA>(a, tile, threadIdx.x); }
+};
+struct NetCw {                                                           // gru_cw_kernel / gru_many_cw_kernel
+    static constexpr int kThreads = 256; static constexpr size_t kLds = kCwLdsBytes;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char* smem) {
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        gru_tile_cw<false>(a, tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+    }
+};
+template <int MODE, bool DELTA, bool RB> struct NetBf16 {                // gru_bf16_kernel / gru_many_bf16_kernel
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) {
+        if (a.b20) { gru_tile_b20<MODE, DELTA, RB>(a, tile, threadIdx.x); return; }
+        gru_tile_bf16<MODE, DELTA, RB>(a, tile, threadIdx.x);
+    }
+};
+template <int MODE> struct NetX3 {                                       // gru_x3_kernel / gru_many_x3_kernel
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile_x3<MODE>(a, tile, threadIdx.x); }
+};
+template <class NET>
+__global__ __launch_bounds__(NET::kThreads) void gru_models_kernel(const GruArgs a, const ModelSet ms, const int per_model, const long long out_stride) {
+    touch_kernel_arguments<(int)sizeof(GruArgs)>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int mi = __builtin_amdgcn_readfirstlane(blockIdx.x / per_model);
+    NET::run(model_args(a, ms.net[mi], mi, out_stride), blockIdx.x - mi * per_model, smem);
+}
+// pe_update_many: (model, update, tile) per workgroup, outputs [K][n_updates][windows]
+template <class NET>
+__global__ __launch_bounds__(NET::kThreads) void gru_many_models_kernel(const GruArgs a, const ModelSet ms, const int n_tiles, const int n_updates, const int n_padded) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int per_model = n_tiles * n_updates;
+    const int mi = __builtin_amdgcn_readfirstlane(blockIdx.x / per_model);
+    const int w = blockIdx.x - mi * per_model;
+    const int u = w / n_tiles, tile = w % n_tiles;
+    GruArgs b = model_args(a, ms.net[mi], mi, (long long)n_updates * a.n_streams);
+    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
+    b.out += (size_t)u * a.n_streams;
+    b.predict_ke = 0;
+    NET::run(b, tile, smem);
+}
+// what the launchers below take for a K-model engine (ms == null: the one-model kernels)
+struct NetModels { const ModelSet* ms; int n; long long out_stride; };
+// one network launch: KERNEL over GRID workgroups (one model), or gru_models_kernel<NET> over GRID x K
+#define PE_NET(NET, KERNEL, GRID, THREADS, LDS)                                                                              \
+    do {                                                                                                                     \
+        if (mm.ms) hipLaunchKernelGGL((gru_models_kernel<PE_UNPAREN NET>), dim3((GRID) * mm.n), dim3(THREADS), (PE_UNPAREN NET::kLds), s, a, *mm.ms, (int)(GRID), mm.out_stride); \
+        else hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(THREADS), LDS, s, a);                                              \
+    } while (0)
+#define PE_NET_MANY(NET, KERNEL, TILES, THREADS, LDS)                                                                        \
+    do {                                                                                                                     \
+        if (mm.ms) hipLaunchKernelGGL((gru_many_models_kernel<PE_UNPAREN NET>), dim3((TILES) * n_updates * mm.n), dim3(THREADS), (PE_UNPAREN NET::kLds), s, a, *mm.ms, (TILES), n_updates, n_padded); \
+        else hipLaunchKernelGGL(KERNEL, dim3((TILES) * n_updates), dim3(THREADS), LDS, s, a, (TILES), n_padded);           \
+    } while (0)
+
 
 // Workgroups of the frame role: one wave per task while that fits the machine (4 workgroups of 4 waves per compute
 // unit are resident: LDS and a 128-register budget), more tasks per wave beyond.
@@ -439,32 +609,36 @@ int gru_small_regs(int units) { return (units + 3) / 4; }
 int gru_small_tiles(int units) { return (3 * gru_small_regs(units) + 3) / 4; }
 
 template <int R>
-static hipError_t launch_r(const GruArgs& a, int mode, hipStream_t s) {
+static hipError_t launch_r(const GruArgs& a, int mode, hipStream_t s, const NetModels& mm) {
+    if (mm.ms && a.proj_ring) return hipErrorInvalidValue;        // (input projection rows are per model: refused for K > 1)
     const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
     if (tiles == 0) return hipSuccess;
     if (a.row_floats == 2 * kRowFloats) {           // 17..32 coefficients per frame: 32-float rows
         if constexpr (R == 5) {                     // (stock width, few tiles: four waves per tile, as the 16-float rows get)
             if (mode == kRing && a.waves_per_tile == 4) {
-                hipLaunchKernelGGL((gru_mw_kernel<R, false, 2>), dim3(tiles), dim3(256), 0, s, a);
+                // (K models: the one-wave twin -- the same form, the same bits; a second caller of gru_tile_mw_any<5, false, 2> would
+                //  change the code generated for gru_mw_kernel<5, false, 2>)
+                if (mm.ms) PE_NET((NetSmall<R, kRing, false, 2>), (gru_small_kernel<R, kRing, false, 2>), tiles, 64, 0);
+                else hipLaunchKernelGGL((gru_mw_kernel<R, false, 2>), dim3(tiles), dim3(256), 0, s, a);
                 return hipGetLastError();
             }
         }
-        if (mode == kRing) hipLaunchKernelGGL((gru_small_kernel<R, kRing, false, 2>), dim3(tiles), dim3(64), 0, s, a);
-        else if (mode == kRows) hipLaunchKernelGGL((gru_small_kernel<R, kRows, false, 2>), dim3(tiles), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((gru_small_kernel<R, kFeats, false, 2>), dim3(tiles), dim3(64), 0, s, a);
+        if (mode == kRing) PE_NET((NetSmall<R, kRing, false, 2>), (gru_small_kernel<R, kRing, false, 2>), tiles, 64, 0);
+        else if (mode == kRows) PE_NET((NetSmall<R, kRows, false, 2>), (gru_small_kernel<R, kRows, false, 2>), tiles, 64, 0);
+        else PE_NET((NetSmall<R, kFeats, false, 2>), (gru_small_kernel<R, kFeats, false, 2>), tiles, 64, 0);
         return hipGetLastError();
     }
     if constexpr (R == 5) {
         if (a.cw) {
-            if (mode == kRing && a.waves_per_tile == 4 && cw_four_waves_ok(a)) hipLaunchKernelGGL(gru_cw_kernel, dim3(tiles), dim3(256), kCwLdsBytes, s, a);
+            if (mode == kRing && a.waves_per_tile == 4 && cw_four_waves_ok(a)) PE_NET((NetCw), gru_cw_kernel, tiles, 256, kCwLdsBytes);
             else if (a.use_delta) {
-                if (mode == kRing) hipLaunchKernelGGL((gru_v_kernel<kRing, true>), dim3(tiles), dim3(64), 0, s, a);
-                else if (mode == kRows) hipLaunchKernelGGL((gru_v_kernel<kRows, true>), dim3(tiles), dim3(64), 0, s, a);
-                else hipLaunchKernelGGL((gru_v_kernel<kFeats, true>), dim3(tiles), dim3(64), 0, s, a);
+                if (mode == kRing) PE_NET((NetV<kRing, true>), (gru_v_kernel<kRing, true>), tiles, 64, 0);
+                else if (mode == kRows) PE_NET((NetV<kRows, true>), (gru_v_kernel<kRows, true>), tiles, 64, 0);
+                else PE_NET((NetV<kFeats, true>), (gru_v_kernel<kFeats, true>), tiles, 64, 0);
             }
-            else if (mode == kRing) hipLaunchKernelGGL((gru_v_kernel<kRing, false>), dim3(tiles), dim3(64), 0, s, a);
-            else if (mode == kRows) hipLaunchKernelGGL((gru_v_kernel<kRows, false>), dim3(tiles), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((gru_v_kernel<kFeats, false>), dim3(tiles), dim3(64), 0, s, a);
+            else if (mode == kRing) PE_NET((NetV<kRing, false>), (gru_v_kernel<kRing, false>), tiles, 64, 0);
+            else if (mode == kRows) PE_NET((NetV<kRows, false>), (gru_v_kernel<kRows, false>), tiles, 64, 0);
+            else PE_NET((NetV<kFeats, false>), (gru_v_kernel<kFeats, false>), tiles, 64, 0);
             return hipGetLastError();
         }
         if (mode == kRing && a.proj_ring) {
@@ -473,53 +647,56 @@ static hipError_t launch_r(const GruArgs& a, int mode, hipStream_t s) {
             return hipGetLastError();
         }
     }
-    if (mode == kRing && a.waves_per_tile == 4) hipLaunchKernelGGL((gru_mw_kernel<R>), dim3(tiles), dim3(256), 0, s, a);
-    else if (mode == kRing) hipLaunchKernelGGL((gru_small_kernel<R, kRing>), dim3(tiles), dim3(64), 0, s, a);
-    else if (mode == kRows) hipLaunchKernelGGL((gru_small_kernel<R, kRows>), dim3(tiles), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((gru_small_kernel<R, kFeats>), dim3(tiles), dim3(64), 0, s, a);
+    if (mode == kRing && a.waves_per_tile == 4) PE_NET((NetMw<R, false, 1>), (gru_mw_kernel<R>), tiles, 256, 0);
+    else if (mode == kRing) PE_NET((NetSmall<R, kRing, false, 1>), (gru_small_kernel<R, kRing>), tiles, 64, 0);
+    else if (mode == kRows) PE_NET((NetSmall<R, kRows, false, 1>), (gru_small_kernel<R, kRows>), tiles, 64, 0);
+    else PE_NET((NetSmall<R, kFeats, false, 1>), (gru_small_kernel<R, kFeats>), tiles, 64, 0);
     return hipGetLastError();
 }
 
-hipError_t launch_gru_small(const GruArgs& a, int from_ring, hipStream_t s) {
+hipError_t launch_gru_small(const GruArgs& a, int from_ring, hipStream_t s, const ModelSet* ms, int n_models, long long out_stride) {
+    const NetModels mm{ms, n_models, out_stride};
+    if (ms && (n_models < 1 || n_models > kMaxModels)) return hipErrorInvalidValue;
     if (a.x3) {
         const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
         if (tiles == 0) return hipSuccess;
-        if (from_ring == kRing) hipLaunchKernelGGL(gru_x3_kernel<kRing>, dim3(tiles), dim3(64), 0, s, a);
-        else if (from_ring == kRows) hipLaunchKernelGGL(gru_x3_kernel<kRows>, dim3(tiles), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL(gru_x3_kernel<kFeats>, dim3(tiles), dim3(64), 0, s, a);
+        if (from_ring == kRing) PE_NET((NetX3<kRing>), gru_x3_kernel<kRing>, tiles, 64, 0);
+        else if (from_ring == kRows) PE_NET((NetX3<kRows>), gru_x3_kernel<kRows>, tiles, 64, 0);
+        else PE_NET((NetX3<kFeats>), gru_x3_kernel<kFeats>, tiles, 64, 0);
         return hipGetLastError();
     }
     if (a.bf16) {
         const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
         if (tiles == 0) return hipSuccess;
         if (a.use_delta) {
-            if (from_ring == kRing && a.ring_bf16) hipLaunchKernelGGL((gru_bf16_kernel<kRing, true, true>), dim3(tiles), dim3(64), 0, s, a);
-            else if (from_ring == kRing) hipLaunchKernelGGL((gru_bf16_kernel<kRing, true>), dim3(tiles), dim3(64), 0, s, a);
-            else if (from_ring == kRows) hipLaunchKernelGGL((gru_bf16_kernel<kRows, true>), dim3(tiles), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((gru_bf16_kernel<kFeats, true>), dim3(tiles), dim3(64), 0, s, a);
+            if (from_ring == kRing && a.ring_bf16) PE_NET((NetBf16<kRing, true, true>), (gru_bf16_kernel<kRing, true, true>), tiles, 64, 0);
+            else if (from_ring == kRing) PE_NET((NetBf16<kRing, true, false>), (gru_bf16_kernel<kRing, true>), tiles, 64, 0);
+            else if (from_ring == kRows) PE_NET((NetBf16<kRows, true, false>), (gru_bf16_kernel<kRows, true>), tiles, 64, 0);
+            else PE_NET((NetBf16<kFeats, true, false>), (gru_bf16_kernel<kFeats, true>), tiles, 64, 0);
         } else {
-            if (from_ring == kRing && a.ring_bf16) hipLaunchKernelGGL((gru_bf16_kernel<kRing, false, true>), dim3(tiles), dim3(64), 0, s, a);
-            else if (from_ring == kRing) hipLaunchKernelGGL((gru_bf16_kernel<kRing, false>), dim3(tiles), dim3(64), 0, s, a);
-            else if (from_ring == kRows) hipLaunchKernelGGL((gru_bf16_kernel<kRows, false>), dim3(tiles), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((gru_bf16_kernel<kFeats, false>), dim3(tiles), dim3(64), 0, s, a);
+            if (from_ring == kRing && a.ring_bf16) PE_NET((NetBf16<kRing, false, true>), (gru_bf16_kernel<kRing, false, true>), tiles, 64, 0);
+            else if (from_ring == kRing) PE_NET((NetBf16<kRing, false, false>), (gru_bf16_kernel<kRing, false>), tiles, 64, 0);
+            else if (from_ring == kRows) PE_NET((NetBf16<kRows, false, false>), (gru_bf16_kernel<kRows, false>), tiles, 64, 0);
+            else PE_NET((NetBf16<kFeats, false, false>), (gru_bf16_kernel<kFeats, false>), tiles, 64, 0);
         }
         return hipGetLastError();
     }
     switch (gru_small_regs(a.units)) {
-        case 1: return launch_r<1>(a, from_ring, s);
-        case 2: return launch_r<2>(a, from_ring, s);
-        case 3: return launch_r<3>(a, from_ring, s);
-        case 4: return launch_r<4>(a, from_ring, s);
-        case 5: return launch_r<5>(a, from_ring, s);
-        case 6: return launch_r<6>(a, from_ring, s);
-        case 7: return launch_r<7>(a, from_ring, s);
-        case 8: return launch_r<8>(a, from_ring, s);
+        case 1: return launch_r<1>(a, from_ring, s, mm);
+        case 2: return launch_r<2>(a, from_ring, s, mm);
+        case 3: return launch_r<3>(a, from_ring, s, mm);
+        case 4: return launch_r<4>(a, from_ring, s, mm);
+        case 5: return launch_r<5>(a, from_ring, s, mm);
+        case 6: return launch_r<6>(a, from_ring, s, mm);
+        case 7: return launch_r<7>(a, from_ring, s, mm);
+        case 8: return launch_r<8>(a, from_ring, s, mm);
         default: return hipErrorInvalidValue;
     }
 }
 
 template <int R>
-static hipError_t launch_many_r(const GruArgs& a, int n_updates, int n_padded, hipStream_t s) {
+static hipError_t launch_many_r(const GruArgs& a, int n_updates, int n_padded, hipStream_t s, const NetModels& mm) {
+    if (mm.ms && a.proj_ring) return hipErrorInvalidValue;
     const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
     // up to ~1.5 windows per SIMD the four-wave kernel wins (4096 streams x 4 updates: 18.1 vs 20.1 us per
     // update), from 2 per SIMD on the one-wave kernel does (x 16: 12.5 vs 14.0)
@@ -527,9 +704,9 @@ static hipError_t launch_many_r(const GruArgs& a, int n_updates, int n_padded, h
     const bool mw = few && !a.use_delta;       // (classic tiling: the delta inputs are on the one-wave kernel only)
     if constexpr (R == 5) {
         if (a.cw) {
-            if (few && cw_four_waves_ok(a)) hipLaunchKernelGGL(gru_many_cw_kernel, dim3(tiles * n_updates), dim3(256), kCwLdsBytes, s, a, tiles, n_padded);
-            else if (a.use_delta) hipLaunchKernelGGL(gru_many_v_kernel<true>, dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
-            else hipLaunchKernelGGL(gru_many_v_kernel<false>, dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
+            if (few && cw_four_waves_ok(a)) PE_NET_MANY((NetCw), gru_many_cw_kernel, tiles, 256, kCwLdsBytes);
+            else if (a.use_delta) PE_NET_MANY((NetV<kRing, true>), gru_many_v_kernel<true>, tiles, 64, 0);
+            else PE_NET_MANY((NetV<kRing, false>), gru_many_v_kernel<false>, tiles, 64, 0);
             return hipGetLastError();
         }
         if (a.proj_ring) {
@@ -538,40 +715,51 @@ static hipError_t launch_many_r(const GruArgs& a, int n_updates, int n_padded, h
             return hipGetLastError();
         }
     }
-    if (mw) hipLaunchKernelGGL((gru_many_mw_kernel<R, false>), dim3(tiles * n_updates), dim3(256), 0, s, a, tiles, n_padded);
-    else hipLaunchKernelGGL((gru_many_kernel<R, false>), dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
+    if (mw) PE_NET_MANY((NetMw<R, false, 1>), (gru_many_mw_kernel<R, false>), tiles, 256, 0);
+    else PE_NET_MANY((NetSmall<R, kRing, false, 1>), (gru_many_kernel<R, false>), tiles, 64, 0);
     return hipGetLastError();
 }
 
-hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStream_t s) {
+hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStream_t s, const ModelSet* ms, int n_models) {
+    const NetModels mm{ms, n_models, 0};
+    if (ms && (n_models < 1 || n_models > kMaxModels)) return hipErrorInvalidValue;
     const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
     if (tiles == 0 || n_updates == 0) return hipSuccess;
     if (a.x3) {
-        hipLaunchKernelGGL(gru_many_x3_kernel, dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
+        PE_NET_MANY((NetX3<kRing>), gru_many_x3_kernel, tiles, 64, 0);
         return hipGetLastError();
     }
     if (a.bf16) {
-        if (a.use_delta && a.ring_bf16) hipLaunchKernelGGL((gru_many_bf16_kernel<true, true>), dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
-        else if (a.use_delta) hipLaunchKernelGGL((gru_many_bf16_kernel<true, false>), dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
-        else if (a.ring_bf16) hipLaunchKernelGGL((gru_many_bf16_kernel<false, true>), dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
-        else hipLaunchKernelGGL((gru_many_bf16_kernel<false, false>), dim3(tiles * n_updates), dim3(64), 0, s, a, tiles, n_padded);
+        if (a.use_delta && a.ring_bf16) PE_NET_MANY((NetBf16<kRing, true, true>), (gru_many_bf16_kernel<true, true>), tiles, 64, 0);
+        else if (a.use_delta) PE_NET_MANY((NetBf16<kRing, true, false>), (gru_many_bf16_kernel<true, false>), tiles, 64, 0);
+        else if (a.ring_bf16) PE_NET_MANY((NetBf16<kRing, false, true>), (gru_many_bf16_kernel<false, true>), tiles, 64, 0);
+        else PE_NET_MANY((NetBf16<kRing, false, false>), (gru_many_bf16_kernel<false, false>), tiles, 64, 0);
         return hipGetLastError();
     }
     switch (gru_small_regs(a.units)) {
-        case 1: return launch_many_r<1>(a, n_updates, n_padded, s);
-        case 2: return launch_many_r<2>(a, n_updates, n_padded, s);
-        case 3: return launch_many_r<3>(a, n_updates, n_padded, s);
-        case 4: return launch_many_r<4>(a, n_updates, n_padded, s);
-        case 5: return launch_many_r<5>(a, n_updates, n_padded, s);
-        case 6: return launch_many_r<6>(a, n_updates, n_padded, s);
-        case 7: return launch_many_r<7>(a, n_updates, n_padded, s);
-        case 8: return launch_many_r<8>(a, n_updates, n_padded, s);
+        case 1: return launch_many_r<1>(a, n_updates, n_padded, s, mm);
+        case 2: return launch_many_r<2>(a, n_updates, n_padded, s, mm);
+        case 3: return launch_many_r<3>(a, n_updates, n_padded, s, mm);
+        case 4: return launch_many_r<4>(a, n_updates, n_padded, s, mm);
+        case 5: return launch_many_r<5>(a, n_updates, n_padded, s, mm);
+        case 6: return launch_many_r<6>(a, n_updates, n_padded, s, mm);
+        case 7: return launch_many_r<7>(a, n_updates, n_padded, s, mm);
+        case 8: return launch_many_r<8>(a, n_updates, n_padded, s, mm);
         default: return hipErrorInvalidValue;
     }
 }
 
+// The network shape of the K-model fused launch (stock width, form 1), from (K, tiles).  The four-wave workgroup of one tile
+// holds 40 KB of LDS (mailboxes + the staged ring), and a launch gives every workgroup the same amount: once more than two of
+// them per compute unit are due, the frame role no longer finds room beside them, and the LDS-free one-wave shape (gru_tile_v,
+// the same form: the same bits) wins.  Measured at 4096 / 8192 streams, K = 2 / 4 / 8 (running the models of a tile
+// one after the other in fewer workgroups was measured too and never won).
+static bool fused_models_four_waves(int n_models, int tiles, int n_cus) { return (long long)n_models * tiles <= 2LL * n_cus; }
+
+// ms != null: the K-model launch (fused_update_models_kernel) -- the same shape with n_models network roles
 template <class R, int RG>
-static hipError_t launch_fused_rg(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, int n_cus, hipStream_t s) {
+static hipError_t launch_fused_rg(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, int n_cus, hipStream_t s,
+                                  const ModelSet* ms = nullptr, int n_models = 1) {
     const int tiles = (m.geo.n_streams + kTileStreams - 1) / kTileStreams;
     const size_t lds = frame_lds(t);
     // more network workgroups than the machine holds at once: frames first, three frame workgroups per CU, the network
@@ -589,6 +777,26 @@ static hipError_t launch_fused_rg(const MfccStreamArgs<R>& m, const WaveTables<R
     const int gru_blocks = g.waves_per_tile == 4 ? tiles : (tiles + 3) / 4;
     const int fb_ = fb, book = tiles;
     const dim3 grid(gru_blocks + fb_ + book);
+    if (ms) {
+        if (g.proj_ring) return hipErrorInvalidValue;       // (input projection rows are per model: refused for K > 1)
+        const dim3 mgrid(gru_blocks * n_models + fb_ + book);
+        if constexpr (RG == 5) {
+            if (g.cw) {
+                // (use_delta: four waves -- the one-wave fused shape has no delta inputs, as for one model, engine.hip can_fuse)
+                if ((g.use_delta || fused_models_four_waves(n_models, tiles, n_cus)) && g.waves_per_tile == 4 && cw_four_waves_ok(g)) {
+                    PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, true, true), mgrid, dim3(256), lds > kCwLdsBytes ? lds : kCwLdsBytes, s, m, t, g, gru_blocks, n_models, fb_, tiles, frames_first, *ms);
+                } else {                             // the one-wave shape (gru_tile_v, same form, same bits): no LDS of its own
+                    const int gb = (tiles + 3) / 4;
+                    PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, false, true), dim3(gb * n_models + fb_ + book), dim3(256), lds, s, m, t, g, gb, n_models, fb_, tiles, frames_first & ~kBySimd, *ms);
+                }
+                return hipGetLastError();
+            }
+        }
+        if (g.waves_per_tile == 4) PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, true, false), mgrid, dim3(256), lds, s, m, t, g, gru_blocks, n_models, fb_, tiles, frames_first, *ms);
+        else if constexpr (RG <= 5) PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, false, false), mgrid, dim3(256), lds, s, m, t, g, gru_blocks, n_models, fb_, tiles, frames_first, *ms);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     if constexpr (RG == 5) {
         if (g.cw) {                          // stock width, re-tiled: the four-wave shape wants its LDS (mailboxes + staged ring)
             if (g.waves_per_tile == 4 && cw_four_waves_ok(g)) {
@@ -615,7 +823,8 @@ static hipError_t launch_fused_rg(const MfccStreamArgs<R>& m, const WaveTables<R
 
 // (the fused kernels are built for the stock table shape only: engine.hip falls back to two launches otherwise)
 template <class R>
-static hipError_t launch_fused(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, int n_cus, hipStream_t s) {
+static hipError_t launch_fused(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, int n_cus, hipStream_t s,
+                               const ModelSet* ms = nullptr, int n_models = 1) {
     if (t.L.mel_pad != ShapeStock::MEL || !blob_matches_shape(t)) return hipErrorInvalidValue;
     if (g.bf16) {
         const int tiles = (m.geo.n_streams + kTileStreams - 1) / kTileStreams;
@@ -626,6 +835,14 @@ static hipError_t launch_fused(const MfccStreamArgs<R>& m, const WaveTables<R>& 
         const int fb = stream_frame_blocks(m.geo.n_streams, n_cus, ff ? 3 : 4);
         const int book = tiles;
         const dim3 grid(gru_blocks + fb + book);
+        if (ms) {
+            const dim3 mgrid(gru_blocks * n_models + fb + book);
+            if (g.use_delta && g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, true, true), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
+            else if (g.use_delta) PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, true, false), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
+            else if (g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, false, true), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
+            else PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, false, false), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
+            return hipGetLastError();
+        }
         if (g.use_delta && g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_kernel, (ShapeStock, true, true), grid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, fb, tiles, frames_first);
         else if (g.use_delta) PE_LAUNCH_R(R, fused_update_bf16_kernel, (ShapeStock, true, false), grid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, fb, tiles, frames_first);
         else if (g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_kernel, (ShapeStock, false, true), grid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, fb, tiles, frames_first);
@@ -633,20 +850,28 @@ static hipError_t launch_fused(const MfccStreamArgs<R>& m, const WaveTables<R>& 
         return hipGetLastError();
     }
     switch (gru_small_regs(g.units)) {
-        case 1: return launch_fused_rg<R, 1>(m, t, g, n_cus, s);
-        case 2: return launch_fused_rg<R, 2>(m, t, g, n_cus, s);
-        case 3: return launch_fused_rg<R, 3>(m, t, g, n_cus, s);
-        case 4: return launch_fused_rg<R, 4>(m, t, g, n_cus, s);
-        case 5: return launch_fused_rg<R, 5>(m, t, g, n_cus, s);
-        case 6: return launch_fused_rg<R, 6>(m, t, g, n_cus, s);
-        case 7: return launch_fused_rg<R, 7>(m, t, g, n_cus, s);
-        case 8: return launch_fused_rg<R, 8>(m, t, g, n_cus, s);
+        case 1: return launch_fused_rg<R, 1>(m, t, g, n_cus, s, ms, n_models);
+        case 2: return launch_fused_rg<R, 2>(m, t, g, n_cus, s, ms, n_models);
+        case 3: return launch_fused_rg<R, 3>(m, t, g, n_cus, s, ms, n_models);
+        case 4: return launch_fused_rg<R, 4>(m, t, g, n_cus, s, ms, n_models);
+        case 5: return launch_fused_rg<R, 5>(m, t, g, n_cus, s, ms, n_models);
+        case 6: return launch_fused_rg<R, 6>(m, t, g, n_cus, s, ms, n_models);
+        case 7: return launch_fused_rg<R, 7>(m, t, g, n_cus, s, ms, n_models);
+        case 8: return launch_fused_rg<R, 8>(m, t, g, n_cus, s, ms, n_models);
         default: return hipErrorInvalidValue;
     }
 }
 
 hipError_t launch_fused_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, int n_cus, hipStream_t s) { return launch_fused<double>(m, t, g, n_cus, s); }
 hipError_t launch_fused_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s) { return launch_fused<float>(m, t, g, n_cus, s); }
+hipError_t launch_fused_models_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s) {
+    if (n_models < 1 || n_models > kMaxModels) return hipErrorInvalidValue;
+    return launch_fused<double>(m, t, g, n_cus, s, &ms, n_models);
+}
+hipError_t launch_fused_models_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s) {
+    if (n_models < 1 || n_models > kMaxModels) return hipErrorInvalidValue;
+    return launch_fused<float>(m, t, g, n_cus, s, &ms, n_models);
+}
 
 // ---- general front end (mfcc_general_device.h): one wave per stream / per frame -------------------------------------
 // (<= 128 registers: four waves per SIMD -- a wave walks the LDS round trips of one frame at a time, the others hide them;
@@ -868,6 +1093,42 @@ hipError_t launch_project_rows(const float* ring, float* proj, const float* w, c
     return hipGetLastError();
 }
 
+// ThresholdDecoder.decode + TriggerDetector.update of stream s for decode_models_kernel: decode_kernel's body (kept apart from
+// decode_kernel, whose code the shared function changed -- the two must stay alike)
+__device__ __forceinline__ void decode_stream(const DecodeArgs& a, const int s) {
+    const float rawf = a.raw[s];
+    const double raw = (double)rawf;
+    double conf = raw;
+    if (raw != 1.0 && raw != 0.0) {                       // saturated sigmoid passes through (:46-47)
+        double cp;
+        if (a.out_range == 0) {
+            cp = raw > (double)a.min_out ? 1.0 : 0.0;
+        } else {
+            // asigmoid (functions.py:99-101) on the runner's float32 scalar: numpy evaluates `1 / x - 1` in
+            // float32 (two correctly rounded operations), math.log then takes that value as a double
+            const float odds = __fsub_rn(__fdiv_rn(1.0f, rawf), 1.0f);
+            double ratio = (-log((double)odds) - (double)a.min_out) / (double)a.out_range;
+            ratio = fmin(fmax(ratio, 0.0), 1.0);
+            cp = a.cd[(int)(ratio * (double)(a.cd_len - 1) + 0.5)];
+        }
+        conf = cp < a.center ? 0.5 * cp / a.center : 0.5 + 0.5 * (cp - a.center) / (1.0 - a.center);
+    }
+    if (a.conf_out) a.conf_out[s] = conf;
+    if (a.activation) {
+        int act = a.activation[s];
+        const bool hot = conf > a.threshold;
+        bool fired = false;
+        if (!hot && act >= 0) {
+            if (act > 0) act -= 1;
+        } else {
+            act += 1;
+            fired = act > a.trigger_level;
+            if (fired || (hot && act < 0)) act = a.rearm;
+        }
+        a.activation[s] = act;
+        if (a.fired_out) a.fired_out[s] = fired ? 1 : 0;
+    }
+}
 __global__ void decode_kernel(const DecodeArgs a) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= a.n_streams) return;
@@ -904,7 +1165,30 @@ __global__ void decode_kernel(const DecodeArgs a) {
         if (a.fired_out) a.fired_out[s] = fired ? 1 : 0;
     }
 }
+// a K-model engine: model blockIdx.y with its own table, thresholds and trigger rows, ONE launch for all models
+__global__ void decode_models_kernel(const DecodeSet d) {
+    const DecodeArgs& a = d.m[blockIdx.y];
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.n_streams) return;
+    decode_stream(a, s);
+}
+// the trigger rows of models 1 .. n_rows of a K-model engine, cleared as clear_kernel clears model 0's (mask: the streams cleared)
+__global__ void clear_activation_kernel(const uint8_t* mask, int32_t* activation, const int n_streams, const int n_padded) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_streams || (mask && !mask[s])) return;
+    activation[(size_t)(blockIdx.y + 1) * n_padded + s] = 0;
+}
 
+hipError_t launch_decode_models(const DecodeSet& d, int n_models, int n_streams, hipStream_t s) {
+    if (n_models < 1 || n_models > kMaxModels) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_models_kernel, dim3((n_streams + 255) / 256, n_models), dim3(256), 0, s, d);
+    return hipGetLastError();
+}
+hipError_t launch_clear_activation(const uint8_t* mask, int32_t* activation, int n_streams, int n_padded, int n_rows, hipStream_t s) {
+    if (n_rows < 1 || n_streams < 1) return hipSuccess;
+    hipLaunchKernelGGL(clear_activation_kernel, dim3((n_streams + 255) / 256, n_rows), dim3(256), 0, s, mask, activation, n_streams, n_padded);
+    return hipGetLastError();
+}
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s) {
     if (a.n_streams == 0) return hipSuccess;
     hipLaunchKernelGGL(decode_kernel, dim3((a.n_streams + 255) / 256), dim3(256), 0, s, a);

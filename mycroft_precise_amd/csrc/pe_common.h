@@ -219,6 +219,33 @@ struct GruArgs {
     int waves_per_tile;     // 1: one wave per tile (gru_tile);  4: four waves share a tile (gru_tile_mw)
 };
 
+// ---- several models on the same streams (pe_create_models) -----------------------------------------------------------
+// One engine, one front end, one ring and one set of records, K networks of the same shape: what differs per model is the
+// packed weights (and the dense bias).  The K-model kernels take the model from the workgroup index and run the one-model
+// tile function on a copy of the launch's GruArgs with that model's weights and its block of the output ([K][windows]).
+// The weights travel by value in the argument segment (≤ 8 x 104 bytes), so a model's pointers are one scalar load away,
+// as a one-model launch's are.
+constexpr int kMaxModels = 8;
+struct ModelNet {           // the weight fields of GruArgs, per model (null where the engine's form does not read them)
+    const float* wx; const float* wxd; const float* wr1; const float* wr2; const float* bias; const float* wd;
+    const float* cw;
+    const void* wx_bf16; const void* wr_bf16; const float* wd_bf16; const void* b20;
+    const void* x3;
+    float dense_bias;
+};
+struct ModelSet { ModelNet net[kMaxModels]; };
+// model m's view of a launch: its weights, its output block at out + m * out_stride
+__device__ __forceinline__ GruArgs model_args(const GruArgs& a, const ModelNet& n, const int m, const long long out_stride) {
+    GruArgs b = a;
+    b.wx = n.wx; b.wxd = n.wxd; b.wr1 = n.wr1; b.wr2 = n.wr2; b.bias = n.bias; b.wd = n.wd;
+    b.cw = n.cw;
+    b.wx_bf16 = n.wx_bf16; b.wr_bf16 = n.wr_bf16; b.wd_bf16 = n.wd_bf16; b.b20 = n.b20;
+    b.x3 = n.x3;
+    b.dense_bias = n.dense_bias;
+    b.out = a.out + (long long)m * out_stride;
+    return b;
+}
+
 // ---- which stream a lane of a network tile serves, and where its window ends ------------------------------------------
 // v = position in this launch (tile * 16 + j); padded lanes shadow position 0's stream (their results are never stored)
 __device__ __forceinline__ long long gru_stream_of(const GruArgs& a, const long long v, const bool valid) {
@@ -311,6 +338,10 @@ struct DecodeArgs {
     int trigger_level, rearm;   // rearm = -(8 * 2048) // chunk_size
 };
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
+struct DecodeSet { DecodeArgs m[kMaxModels]; };     // a K-model engine: model m's table, thresholds and trigger row
+hipError_t launch_decode_models(const DecodeSet& d, int n_models, int n_streams, hipStream_t s);
+// zero the trigger rows 1 .. n_rows of activation[n_models][n_padded] where mask (may be null) is set
+hipError_t launch_clear_activation(const uint8_t* mask, int32_t* activation, int n_streams, int n_padded, int n_rows, hipStream_t s);
 
 // launchers implemented in kernels.hip
 // MFCC of one call (n_updates chunks per stream): every frame the call completes as a task of one wave, then the
@@ -319,15 +350,20 @@ constexpr int kProjRow = pe_wave::kProjRow;
 hipError_t launch_mfcc_f64(const MfccStreamArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
 hipError_t launch_mfcc_f32(const MfccStreamArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
 // network for n_updates x n_streams windows, emitted counters from ke_hist, out[u][stream]
-hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStream_t s);
+hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1);   // ms: out[K][n_updates][streams]
 // one launch, three roles: GRU waves read the feature windows as they will be after this update while MFCC waves
 // compute this update's frames and the bookkeeping groups move the leftover (legal when chunk <= window -
 // frame_len: no frame computed now becomes visible now)
 hipError_t launch_fused_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, int n_cus, hipStream_t s);
 hipError_t launch_fused_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s);
+// the same launches for a K-model engine: K network roles (ModelSet), outputs [K][windows]
+hipError_t launch_fused_models_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s);
+hipError_t launch_fused_models_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s);
 hipError_t launch_mfcc_offline_f64(const MfccOfflineArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
 hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
-hipError_t launch_gru_small(const GruArgs& a, int input_mode, hipStream_t s);   // units <= 32; 0 feats, 1 ring, 2 rows
+// units <= 32; 0 feats, 1 ring, 2 rows.  ms != null: the n_models networks of a K-model engine in the same ONE launch, model m
+// writing out + m * out_stride
+hipError_t launch_gru_small(const GruArgs& a, int input_mode, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1, long long out_stride = 0);
 int gru_small_regs(int units);                  // R = ceil(units/4)
 int gru_wide_waves(int units);                  // waves per workgroup of the wide kernel (the weight packing follows it)
 int gru_small_tiles(int units);                 // NT = ceil(3R/4)

@@ -352,3 +352,81 @@ class BatchedListener:
         if not self._trigger:
             raise RuntimeError('call set_trigger() first')
         return self.engine.decode(self.update_raw(chunks), want_fired=True)
+
+
+class MultiModelListener(BatchedListener):
+    """
+    Several wake-word models over the same ``n_streams`` streams (pe_create_models): ONE front end, one feature window
+    per stream, and K networks -- what K reference ``Listener(model_name, chunk_size)`` objects over identical audio
+    compute (precise/scripts/engine.py builds one per model), at the cost of one front end.  ``models`` are model file
+    names (``.pb`` / ``.net`` plus their ``.params``) or weight dicts (``params=`` then gives the shared ListenerParams).
+    The models must agree on every front-end field; each keeps its own ``ThresholdDecoder`` (threshold_config /
+    threshold_center of its ``.params``) and its own trigger.  Every result gains a leading model axis: ``[K, n]``.
+    """
+    FRONT_END = ('sample_rate', 'window_samples', 'hop_samples', 'n_fft', 'n_filt', 'n_mfcc', 'n_features', 'use_delta',
+                 'vectorizer')
+
+    def __init__(self, models, n_streams: int, device: int = 0, mfcc_precision: str = 'f64', gru_precision: str = 'f32',
+                 ring_precision: str = 'f32', params=None):
+        models = list(models)
+        if not models:
+            raise ValueError('MultiModelListener needs at least one model')
+        prs, weights, self.names = [], [], []
+        for i, m in enumerate(models):
+            if isinstance(m, str):
+                prs.append(inject_params(m).copy())
+                weights.append(load_weights(m))
+                self.names.append(m)
+            else:
+                prs.append((params or pr).copy())
+                weights.append(m)
+                self.names.append('model%d' % i)
+        for i, p in enumerate(prs[1:], 1):
+            for field in self.FRONT_END:
+                a, b = getattr(prs[0], field), getattr(p, field)
+                if a != b:
+                    raise ValueError('model %d (%s): %s = %r, model 0 (%s) has %r -- the models of one listener share one front end'
+                                     % (i, self.names[i], field, b, self.names[0], a))
+        self.pr = prs[0]
+        self.params = prs
+        self.n_models = len(models)
+        self.n_streams = int(n_streams)
+        self.weights = weights
+        _require_streamable(self.pr)
+        self.engine = HipEngine(self.pr, weights, n_streams=self.n_streams, device=device,
+                                mfcc_precision=mfcc_precision, gru_precision=gru_precision, ring_precision=ring_precision)
+        self.threshold_decoders = [ThresholdDecoder(p.threshold_config, p.threshold_center) for p in prs]
+        for m, d in enumerate(self.threshold_decoders):
+            self.engine.set_decoder(d, model=m)
+        self._trigger = False
+
+    def set_trigger(self, chunk_size: int = 2048, sensitivity: float = 0.5, trigger_level: int = 3, model=None):
+        """One TriggerDetector per (model, stream); ``model=None`` sets every model, otherwise that model's hotword only."""
+        self.engine.set_trigger(chunk_size, sensitivity, trigger_level, model=model)
+        self._trigger = True
+
+    def update_raw(self, chunks, streams=None) -> np.ndarray:
+        """-> raw network outputs float32 [K, n_streams]; with ``streams=ids``: [K, len(ids)], in the order of ``ids``"""
+        if streams is None:
+            return self.engine.update(self._pcm(chunks))
+        ids = self._ids(streams)
+        if ids.size == 0:
+            return np.empty((self.n_models, 0), dtype=np.float32)
+        return self.engine.update_subset(ids, self._pcm(chunks, ids.size))
+
+    def update(self, chunks, streams=None) -> np.ndarray:
+        """-> decoded confidences float64 [K, n_streams] (each model's ThresholdDecoder); with ``streams=ids`` [K, len(ids)]"""
+        if streams is None:
+            return self.engine.decode(self.update_raw(chunks))
+        raw = self.update_raw(chunks, streams)
+        return np.array([[d.decode(r) for r in row] for d, row in zip(self.threshold_decoders, raw)], dtype=np.float64).reshape(raw.shape)
+
+    def update_raw_async(self, chunks, out: np.ndarray = None) -> np.ndarray:
+        """Enqueue one update; returns the float32 [K, n_streams] array its raw outputs land in after ``wait()``."""
+        return self.engine.update_async(self._pcm(chunks), out)
+
+    def update_detect(self, chunks):
+        """-> (confidences float64 [K, n_streams], activations bool [K, n_streams]); needs set_trigger()."""
+        if not self._trigger:
+            raise RuntimeError('call set_trigger() first')
+        return self.engine.decode(self.update_raw(chunks), want_fired=True)
