@@ -27,21 +27,24 @@ struct DeviceBuf {
     size_t bytes = 0;
 };
 
-// one model's packed network (pe_create_models): the weight fields of pe_engine, set aside per model.  A weight field added to
-// pe_engine has to be added in five places: here, take_net / put_net and with_model (engine.hip), ModelNet / model_args
-// (pe_common.h) -- the static_assert below counts the fields of NetPack against that list.
+// One model's packed network, in every layout the engine's forms read (null where a form does not apply).  A weight field is
+// named here and in model_net below (NetPack -> ModelNet, pe_common.h), nowhere else on the host.
 struct NetPack {
     float dense_bias = 0.f;
     float* wxd = nullptr; float* wx = nullptr; float* wr1 = nullptr; float* wr2 = nullptr; float* bias = nullptr; float* wd = nullptr;
-    float* cw_blob = nullptr;
+    float* cw_blob = nullptr;         // the stock width re-tiled (gru_cw_device.h)
+    // wide / stacked network (units 64..256, 1-2 layers): weight streams in MFMA A-operand order; per layer: wx1, wr1, wx2, wr2, b1, b2
     float* wide_buf[2][6] = {{nullptr}}; float* wide_wd = nullptr;
+    // the same network packed for gru_wide_x3_device.h (row i of tile tau = unit 16 tau + i; k-slot 8 gk + e = source unit 16 kappa + 4 gk + e)
     float* wide3_buf[2][6] = {{nullptr}}; float* wide3_wd = nullptr;
+    // bf16-operand network (pe_params.gru_precision = 1)
     uint16_t* wx_bf16 = nullptr; uint16_t* wr_bf16 = nullptr; float* wd_bf16 = nullptr;
-    uint32_t* b20_blob = nullptr; uint32_t* x3_blob = nullptr;
+    uint32_t* b20_blob = nullptr;     // the same network in the layout of gru_b20_device.h (<= 20 units, <= 14 features)
+    // float32 network as three bf16 pieces per operand on the XDL pipe (gru_x3_device.h; tiling 2): packed for every
+    // float32 network of <= 20 units and <= 15 inputs without delta features
+    uint32_t* x3_blob = nullptr;
 };
-static_assert(sizeof(void*) == 8 && sizeof(NetPack) == 8 + 7 * 8 + 13 * 8 + 13 * 8 + 5 * 8,
-              "NetPack changed: update take_net / put_net / with_model and pe_common.h ModelNet / model_args");
-// one model's ThresholdDecoder / TriggerDetector settings (pe_set_decoder_model / pe_set_trigger_model)
+// one model's on-device ThresholdDecoder / TriggerDetector settings (pe_set_decoder[_model] / pe_set_trigger[_model])
 struct DecState {
     double* cd = nullptr; int cd_len = 0, min_out = 0, out_range = 0; double center = 0.5;
     double threshold = 0.5; int level = 3, rearm = -8; bool on = false;
@@ -56,7 +59,6 @@ struct pe_engine {
     int units = 0, n_in = 0, n_layers = 0;
     int ring_slots = 0;
     int mel_nnz = 0;
-    float dense_bias = 0.f;
     std::string err;
     std::vector<void*> allocs;
     int64_t device_bytes = 0;
@@ -79,7 +81,6 @@ struct pe_engine {
     int carry_cap = kCarryCap;     // int16 samples of leftover PCM kept per stream (>= frame length)
     GeneralTables gtab{};
     int gru_tiling = -1;    // -1 = auto (stock width re-tiled while tiles <= 2 CUs; XDL form above 4 tiles per CU), 0 = classic, 1 = re-tiled (gru_cw_device.h), 2 = XDL form (gru_x3_device.h)
-    float* cw_blob = nullptr;
     int n_cus = 256;        // compute units of the device (MI355X: 256)
     float* ring = nullptr;
     // input projections x.W + b of every frame beside its feature row (stock-width float32 network, <= kProjMaxTiles
@@ -93,26 +94,14 @@ struct pe_engine {
     // constant tables of the MFCC frame kernel, laid out as they sit in LDS (mfcc_wave_tables.h)
     unsigned char* table_blob = nullptr;
     pe_wave::Layout table_layout{};
-    // packed network
-    float* wxd = nullptr;
-    float* wx = nullptr; float* wr1 = nullptr; float* wr2 = nullptr; float* bias = nullptr; float* wd = nullptr;
-    // wide / stacked network (units 64..256, 1-2 layers): weight streams in MFMA A-operand order
-    bool wide = false;
-    float* wide_buf[2][6] = {{nullptr}};     // per layer: wx1, wr1, wx2, wr2, b1, b2
+    // the networks of the engine (pe_create: one; pe_create_models: K on the same streams), each with its own decoder and
+    // trigger settings: nets[m] / dec[m] for model m, both of size n_models; `activation` is [n_models][n_padded]
+    int n_models = 1;
+    std::vector<NetPack> nets;
+    std::vector<DecState> dec;
+    bool wide = false;      // wide / stacked network (units 64..256, 1-2 layers)
     int wide_kx4[2] = {1, 1};
-    float* wide_wd = nullptr;
-    // the same network packed for gru_wide_x3_device.h (row i of tile tau = unit 16 tau + i; k-slot 8 gk + e = source unit 16 kappa + 4 gk + e)
-    float* wide3_buf[2][6] = {{nullptr}};
-    float* wide3_wd = nullptr;
-    // bf16-operand network (pe_params.gru_precision = 1)
-    uint16_t* wx_bf16 = nullptr; uint16_t* wr_bf16 = nullptr; float* wd_bf16 = nullptr;
-    uint32_t* b20_blob = nullptr;     // the same network in the layout of gru_b20_device.h (<= 20 units, <= 14 features)
-    // float32 network as three bf16 pieces per operand on the XDL pipe (gru_x3_device.h; tiling 2): packed for every
-    // float32 network of <= 20 units and <= 15 inputs without delta features
-    uint32_t* x3_blob = nullptr;
-    // on-device ThresholdDecoder / TriggerDetector (pe_set_decoder / pe_set_trigger)
-    double* cd = nullptr; int cd_len = 0, dec_min_out = 0, dec_out_range = 0; double dec_center = 0.5;
-    int32_t* activation = nullptr; double trig_threshold = 0.5; int trig_level = 3, trig_rearm = -8; bool trig_on = false;
+    int32_t* activation = nullptr;
     // staging for the host entry points (grown on demand)
     DeviceBuf st_pcm, st_out, st_feats, st_mask, st_audio, st_mfcc, st_conf, st_fired, st_ids;
     std::vector<uint8_t> seen_ids;          // pe_update_subset: duplicate check of the host entry point
@@ -140,11 +129,6 @@ struct pe_engine {
     unsigned async_next = 0;
     int async_inflight = 0;
     std::vector<std::pair<char*, size_t>> pinned;               // pe_host_alloc'ed ranges (zero-copy sources / destinations)
-    // several models on the same streams (pe_create_models): the fields above hold model 0; nets[m] / dec[m] hold model m's
-    // packed network and decoder for m >= 1 (index 0 unused); `activation` is [n_models][n_padded]
-    int n_models = 1;
-    std::vector<NetPack> nets;
-    std::vector<DecState> dec;
 };
 
 namespace {
@@ -335,7 +319,7 @@ int build_general_tables(pe_engine* e, const double* mel_filters) {
 }
 
 // Arrange the Keras matrices as MFMA A-operands (see the layout comment in gru_kernels.hip).
-int pack_gru_weights(pe_engine* e, const pe_gru_layer& L, const float* dense_kernel) {
+int pack_gru_weights(pe_engine* e, NetPack& n, const pe_gru_layer& L, const float* dense_kernel) {
     const int H = L.units, F = e->n_in;          // F = base features; with use_delta the kernel has 2F rows
     const bool delta = e->prm.use_delta != 0;
     const int R = gru_small_regs(H), NT = gru_small_tiles(H);
@@ -376,33 +360,37 @@ int pack_gru_weights(pe_engine* e, const pe_gru_layer& L, const float* dense_ker
             const int u = 4 * rho + (lane >> 4);
             if (u < H) wd[(size_t)rho * 64 + lane] = dense_kernel[u];
         }
-    // input-projection rows (mfcc_wave_device.h epilogue): element o = 16 g + 4 tile + q of a row is accumulator q of
-    // output tile `tile` in lane group g, i.e. slot 4 tile + q, unit 4 rho + g
-    if (NT <= 4 && !delta && KX == 1) {
-        e->proj_w_host.assign((size_t)F * kProjRow, 0.f);
-        e->proj_b_host.assign(kProjRow, 0.f);
-        for (int o = 0; o < kProjRow; ++o) {
-            const int g = o >> 4, tile = (o >> 2) & 3, q = o & 3;
-            const int slot = 4 * tile + q;
-            const int gate = slot / R, rho = slot % R, u = 4 * rho + g;
-            if (tile >= NT || slot >= 3 * R || u >= H) continue;
-            const int col = gate * H + u;
-            e->proj_b_host[o] = L.bias[col];
-            for (int c = 0; c < F; ++c) e->proj_w_host[(size_t)c * kProjRow + o] = L.kernel[(size_t)c * 3 * H + col];
-        }
-    }
     int rc;
-    if ((rc = dev_upload(e, &e->wx, wx))) return rc;
-    if ((rc = dev_upload(e, &e->wxd, wxd))) return rc;
-    if ((rc = dev_upload(e, &e->wr1, wr1))) return rc;
-    if ((rc = dev_upload(e, &e->wr2, wr2))) return rc;
-    if ((rc = dev_upload(e, &e->bias, bias))) return rc;
-    if ((rc = dev_upload(e, &e->wd, wd))) return rc;
+    if ((rc = dev_upload(e, &n.wx, wx))) return rc;
+    if ((rc = dev_upload(e, &n.wxd, wxd))) return rc;
+    if ((rc = dev_upload(e, &n.wr1, wr1))) return rc;
+    if ((rc = dev_upload(e, &n.wr2, wr2))) return rc;
+    if ((rc = dev_upload(e, &n.bias, bias))) return rc;
+    if ((rc = dev_upload(e, &n.wd, wd))) return rc;
     if (R == 5 && KX == 1) {                    // the stock width also in its re-tiled form (gru_cw_device.h)
         const std::vector<float> blob = pack_gru_cw(L.kernel, L.recurrent_kernel, L.bias, F, H, delta);
-        if ((rc = dev_upload(e, &e->cw_blob, blob))) return rc;
+        if ((rc = dev_upload(e, &n.cw_blob, blob))) return rc;
     }
     return PE_OK;
+}
+
+// The input-projection rows of the network (mfcc_wave_device.h epilogue; the engine's only model: pe_set_input_projection
+// refuses K > 1), in the slot order of pack_gru_weights: element o = 16 g + 4 tile + q of a row is accumulator q of output
+// tile `tile` in lane group g, i.e. slot 4 tile + q, unit 4 rho + g
+void pack_projection_rows(pe_engine* e, const pe_gru_layer& L) {
+    const int H = L.units, F = e->n_in, R = gru_small_regs(H), NT = gru_small_tiles(H);
+    if (NT > 4 || e->prm.use_delta || e->row_floats != kRowFloats) return;
+    e->proj_w_host.assign((size_t)F * kProjRow, 0.f);
+    e->proj_b_host.assign(kProjRow, 0.f);
+    for (int o = 0; o < kProjRow; ++o) {
+        const int g = o >> 4, tile = (o >> 2) & 3, q = o & 3;
+        const int slot = 4 * tile + q;
+        const int gate = slot / R, rho = slot % R, u = 4 * rho + g;
+        if (tile >= NT || slot >= 3 * R || u >= H) continue;
+        const int col = gate * H + u;
+        e->proj_b_host[o] = L.bias[col];
+        for (int c = 0; c < F; ++c) e->proj_w_host[(size_t)c * kProjRow + o] = L.kernel[(size_t)c * 3 * H + col];
+    }
 }
 
 // bf16 network operands (gru_bf16_device.h): unit u = 8 g + i; tile (gate, t): row 4 gout + q <-> unit
@@ -415,7 +403,7 @@ uint16_t to_bf16(float f) {
     return (uint16_t)(u >> 16);
 }
 
-int pack_gru_weights_bf16(pe_engine* e, const pe_gru_layer& L, const float* dense_kernel) {
+int pack_gru_weights_bf16(pe_engine* e, NetPack& n, const pe_gru_layer& L, const float* dense_kernel) {
     // with use_delta the layer has 2 F inputs: features in k = 0..15, their first differences in k = 16..31
     const bool delta = e->prm.use_delta != 0;
     const int H = L.units, F = delta ? L.n_in / 2 : L.n_in;
@@ -454,9 +442,9 @@ int pack_gru_weights_bf16(pe_engine* e, const pe_gru_layer& L, const float* dens
             if (u < H) wd[(size_t)i * 64 + lane] = dense_kernel[u];
         }
     int rc;
-    if ((rc = dev_upload(e, &e->wx_bf16, wx))) return rc;
-    if ((rc = dev_upload(e, &e->wr_bf16, wr))) return rc;
-    if ((rc = dev_upload(e, &e->wd_bf16, wd))) return rc;
+    if ((rc = dev_upload(e, &n.wx_bf16, wx))) return rc;
+    if ((rc = dev_upload(e, &n.wr_bf16, wr))) return rc;
+    if ((rc = dev_upload(e, &n.wd_bf16, wd))) return rc;
     return PE_OK;
 }
 
@@ -479,7 +467,7 @@ void split3_bf16(float v, uint16_t (&piece)[3]) {
 // (<= 20 units, <= 15 inputs, no use_delta: the caller checks x3_eligible)
 bool x3_eligible(const pe_params& p, const pe_gru_layer& L) { return p.gru_precision == 0 && !p.use_delta && L.units <= 20 && L.n_in <= 15 && p.n_mfcc <= kRowFloats; }
 
-int pack_gru_weights_x3(pe_engine* e, const pe_gru_layer& L, const float* dense_kernel) {
+int pack_gru_weights_x3(pe_engine* e, NetPack& n, const pe_gru_layer& L, const float* dense_kernel) {
     const int H = L.units, F = L.n_in;
     std::vector<uint32_t> blob((size_t)kX3BlobBytes / 4, 0u);
     uint16_t* const half = reinterpret_cast<uint16_t*>(blob.data());
@@ -522,7 +510,7 @@ int pack_gru_weights_x3(pe_engine* e, const pe_gru_layer& L, const float* dense_
             const int u = o < 4 ? 4 * (lane >> 4) + o : 16 + (lane >> 4);
             if (u < H) wd[o * 64 + lane] = dense_kernel[u];
         }
-    return dev_upload(e, &e->x3_blob, blob);
+    return dev_upload(e, &n.x3_blob, blob);
 }
 
 // bf16 network of <= 20 units in the five-values-per-lane layout (gru_b20_device.h): output tiles 0..2 = z / r / candidate
@@ -534,7 +522,7 @@ bool b20_eligible(const pe_params& p, const pe_gru_layer& L) {
     return p.gru_precision == 1 && L.units <= 20 && F <= 14 && p.n_mfcc <= kRowFloats;
 }
 
-int pack_gru_weights_b20(pe_engine* e, const pe_gru_layer& L, const float* dense_kernel) {
+int pack_gru_weights_b20(pe_engine* e, NetPack& n, const pe_gru_layer& L, const float* dense_kernel) {
     const bool delta = e->prm.use_delta != 0;
     const int H = L.units, F = delta ? L.n_in / 2 : L.n_in;
     std::vector<uint32_t> blob((size_t)kB20BlobBytes / 4, 0u);
@@ -574,13 +562,13 @@ int pack_gru_weights_b20(pe_engine* e, const pe_gru_layer& L, const float* dense
             const int u = o < 4 ? 4 * (lane >> 4) + o : 16 + (lane >> 4);
             if (u < H) wd[o * 64 + lane] = dense_kernel[u];
         }
-    return dev_upload(e, &e->b20_blob, blob);
+    return dev_upload(e, &n.b20_blob, blob);
 }
 
 // Wide / stacked network (gru_wide_device.h): wave w owns output tiles tau = w TPW + t of every gate;
 // row i of a tile <-> unit 16 tau + 4 (i & 3) + (i >> 2); k-step rho, k-slot gk <-> source unit 4 rho + gk
 // (layer 0 input: k-step kk <-> feature 4 gk + kk).  Streams: [wave][k-group][tile][lane] float4.
-int pack_gru_weights_wide(pe_engine* e, const pe_weights* w) {
+int pack_gru_weights_wide(pe_engine* e, NetPack& n, const pe_weights* w) {
     const int H = w->layers[0].units, WV = gru_wide_waves(H), TPW = H / (16 * WV), H16 = H / 16;
     for (int l = 0; l < w->n_layers; ++l) {
         const pe_gru_layer& L = w->layers[l];
@@ -614,9 +602,9 @@ int pack_gru_weights_wide(pe_engine* e, const pe_weights* w) {
                     }
                 }
             int rc;
-            if ((rc = dev_upload(e, &e->wide_buf[l][phase == 0 ? 0 : 2], wx))) return rc;
-            if ((rc = dev_upload(e, &e->wide_buf[l][phase == 0 ? 1 : 3], wr))) return rc;
-            if ((rc = dev_upload(e, &e->wide_buf[l][phase == 0 ? 4 : 5], bias))) return rc;
+            if ((rc = dev_upload(e, &n.wide_buf[l][phase == 0 ? 0 : 2], wx))) return rc;
+            if ((rc = dev_upload(e, &n.wide_buf[l][phase == 0 ? 1 : 3], wr))) return rc;
+            if ((rc = dev_upload(e, &n.wide_buf[l][phase == 0 ? 4 : 5], bias))) return rc;
         }
     }
     std::vector<float> wd((size_t)WV * TPW * 4 * 64, 0.f);
@@ -625,13 +613,13 @@ int pack_gru_weights_wide(pe_engine* e, const pe_weights* w) {
             for (int q = 0; q < 4; ++q)
                 for (int lane = 0; lane < 64; ++lane)
                     wd[(((size_t)wv * TPW + tp) * 4 + q) * 64 + lane] = w->dense_kernel[16 * (wv * TPW + tp) + 4 * q + (lane >> 4)];
-    return dev_upload(e, &e->wide_wd, wd);
+    return dev_upload(e, &n.wide_wd, wd);
 }
 
 // The same network for gru_wide_x3_device.h: float32 weights (split into bf16 pieces in registers, every timestep), wave w
 // owns output tiles tau = w TPW + t of every gate; row i of a tile <-> unit 16 tau + i; k-group kappa, lane (row i, k-group
 // slot gk) <-> source units 16 kappa + 4 gk + e, e = 0..3 (layer 0 input: feature 4 gk + e).  Streams: [wave][kappa][tile][lane] float4.
-int pack_gru_weights_wide_x3(pe_engine* e, const pe_weights* w) {
+int pack_gru_weights_wide_x3(pe_engine* e, NetPack& n, const pe_weights* w) {
     const int H = w->layers[0].units, WV = 4, TPW = H / (16 * WV), H16 = H / 16;
     for (int l = 0; l < w->n_layers; ++l) {
         const pe_gru_layer& L = w->layers[l];
@@ -665,9 +653,9 @@ int pack_gru_weights_wide_x3(pe_engine* e, const pe_weights* w) {
                     }
                 }
             int rc;
-            if ((rc = dev_upload(e, &e->wide3_buf[l][phase == 0 ? 0 : 2], wx))) return rc;
-            if ((rc = dev_upload(e, &e->wide3_buf[l][phase == 0 ? 1 : 3], wr))) return rc;
-            if ((rc = dev_upload(e, &e->wide3_buf[l][phase == 0 ? 4 : 5], bias))) return rc;
+            if ((rc = dev_upload(e, &n.wide3_buf[l][phase == 0 ? 0 : 2], wx))) return rc;
+            if ((rc = dev_upload(e, &n.wide3_buf[l][phase == 0 ? 1 : 3], wr))) return rc;
+            if ((rc = dev_upload(e, &n.wide3_buf[l][phase == 0 ? 4 : 5], bias))) return rc;
         }
     }
     std::vector<float> wd((size_t)WV * TPW * 4 * 64, 0.f);
@@ -676,7 +664,7 @@ int pack_gru_weights_wide_x3(pe_engine* e, const pe_weights* w) {
             for (int q = 0; q < 4; ++q)
                 for (int lane = 0; lane < 64; ++lane)
                     wd[(((size_t)wv * TPW + tp) * 4 + q) * 64 + lane] = w->dense_kernel[16 * (wv * TPW + tp) + 4 * (lane >> 4) + q];
-    return dev_upload(e, &e->wide3_wd, wd);
+    return dev_upload(e, &n.wide3_wd, wd);
 }
 
 // Samples of the virtual stream that must have arrived, counted from a frame's first sample, before the
@@ -789,15 +777,29 @@ int launch_mfcc(pe_engine* e, const int16_t* pcm_dev, int chunk, hipStream_t s, 
     return PE_OK;
 }
 
+// NetPack -> ModelNet: a model's weights as a launch of the form of `a` reads them.  The form -- which of the blobs b20 / x3 /
+// cw a launch reads -- is the engine's (gru_args), the same for every model.
+ModelNet model_net(const NetPack& n, const GruArgs& a) {
+    return ModelNet{n.wx, n.wxd, n.wr1, n.wr2, n.bias, n.wd, a.cw ? n.cw_blob : nullptr, n.wx_bf16, n.wr_bf16, n.wd_bf16,
+                    a.b20 ? n.b20_blob : nullptr, a.x3 ? n.x3_blob : nullptr, n.dense_bias};
+}
+// a launch's arguments with model m's weights
+GruArgs with_model(const pe_engine* e, const GruArgs& a, int m) { return model_args(a, model_net(e->nets[m], a), 0, 0); }
+ModelSet model_set(const pe_engine* e, const GruArgs& a) {
+    ModelSet ms{};
+    for (int m = 0; m < e->n_models; ++m) ms.net[m] = model_net(e->nets[m], a);
+    return ms;
+}
+
+// the arguments of a network launch: the engine's form, model 0's weights
 GruArgs gru_args(const pe_engine* e) {
+    const NetPack& n0 = e->nets[0];
     GruArgs a{};
     a.n_streams = e->n_streams;
     a.n_features = e->prm.n_features;
     a.n_in = e->n_in;
     a.units = e->units;
-    a.wxd = e->wxd; a.use_delta = e->prm.use_delta;
-    a.wx = e->wx; a.wr1 = e->wr1; a.wr2 = e->wr2; a.bias = e->bias; a.wd = e->wd;
-    a.dense_bias = e->dense_bias;
+    a.use_delta = e->prm.use_delta;
     a.ring = e->ring; a.ring_slots = e->ring_slots; a.ring_bf16 = e->prm.ring_precision;
     a.ids = nullptr; a.rec = e->rec; a.n_padded = (uint32_t)e->n_padded; a.ke_plain = nullptr;
     a.call = e->call_no + 1u;           // a reader behind every call so far (the network role of a fused launch: that call's own number)
@@ -807,8 +809,7 @@ GruArgs gru_args(const pe_engine* e) {
     a.window = emit_window(e->prm); a.hop = e->prm.hop_samples;
     a.frame_len = frame_len_of(e->prm);
     a.bf16 = e->prm.gru_precision == 1;
-    a.wx_bf16 = e->wx_bf16; a.wr_bf16 = e->wr_bf16; a.wd_bf16 = e->wd_bf16;
-    a.b20 = e->gru_tiling == 0 ? nullptr : e->b20_blob;      // bf16 network: five values per lane where it fits (pe_set_gru_tiling(e, 0): eight)
+    a.b20 = e->gru_tiling == 0 ? nullptr : n0.b20_blob;      // bf16 network: five values per lane where it fits (pe_set_gru_tiling(e, 0): eight)
     a.feats = nullptr; a.out = nullptr; a.row_stride = 0;
     a.row_floats = e->row_floats;
     // Four waves per tile cut the latency of a tile's chain; that only pays while every tile gets a CU of its
@@ -825,42 +826,50 @@ GruArgs gru_args(const pe_engine* e) {
     // do not.  Measured per update, two launches against the fused classic tiling: 54 vs 69 us at 20 480 streams, 59 vs 69 at
     // 24 576, 69 vs 79 at 32 768, 128 vs 154 us at 65 536 -- and 48 vs 43 us at 16 384 (one tile per SIMD: the classic network
     // still runs in one round of waves, and the missing fused launch costs more than the cheaper network saves).
-    const bool x3_ok = e->x3_blob && !a.bf16 && !e->wide && !a.proj_ring && e->row_floats == kRowFloats;
+    const bool x3_ok = n0.x3_blob && !a.bf16 && !e->wide && !a.proj_ring && e->row_floats == kRowFloats;
     // ... and so do engines reserved for several updates per call (pe_reserve_updates) whose batched network launch has more
     // (update, tile) windows than the machine has SIMDs: ONE form per engine (every launch of a form agrees bit for bit), chosen
     // for the launch the engine was reserved for -- its single updates then run the one-wave XDL kernel in two launches.
     // Measured at 4096 streams x 8 updates per call: 61.6 us for the batched network on the re-tiled f32-input form against
     // the XDL form's rate of ~26 us for the same 32 768 windows (profiles/round5/r5zz_kernel_stats.csv; round 6: profiles/round6).
     const bool many_windows = e->max_updates > 1 && (long long)e->max_updates * e->n_tiles > 4LL * e->n_cus;
-    a.x3 = x3_ok && (e->gru_tiling == 2 || (e->gru_tiling < 0 && (e->n_tiles > 4 * e->n_cus || many_windows))) ? e->x3_blob : nullptr;
-    const bool cw_ok = e->cw_blob && e->row_floats == kRowFloats && !a.proj_ring && !a.bf16 && !a.x3 && !e->wide;
+    a.x3 = x3_ok && (e->gru_tiling == 2 || (e->gru_tiling < 0 && (e->n_tiles > 4 * e->n_cus || many_windows))) ? n0.x3_blob : nullptr;
+    const bool cw_ok = n0.cw_blob && e->row_floats == kRowFloats && !a.proj_ring && !a.bf16 && !a.x3 && !e->wide;
     const bool retile = cw_ok && (e->gru_tiling == 1 || (e->gru_tiling < 0 && e->n_tiles <= 2 * e->n_cus));
     const int auto_waves = retile ? (e->n_tiles <= 2 * e->n_cus ? 4 : 1) : (e->n_tiles <= e->n_cus ? 4 : 1);
     a.waves_per_tile = a.x3 ? 1 : e->gru_waves ? e->gru_waves : auto_waves;
     if (e->prm.use_delta && !retile) a.waves_per_tile = 1;       // (classic tiling: only the one-wave kernel carries the delta inputs)
     if (e->row_floats != kRowFloats && !(gru_small_regs(e->units) == 5 && !e->prm.use_delta && a.waves_per_tile == 4))
         a.waves_per_tile = 1;       // ... and the 32-float feature rows (stock width: four waves per tile exist, gru_tile_mw5<.., 2>)
-    a.cw = retile ? e->cw_blob : nullptr;
-    return a;
+    a.cw = retile ? n0.cw_blob : nullptr;
+    return with_model(e, a, 0);
 }
 
 // which form a wide engine's launches take: the XDL form when asked for (pe_set_gru_tiling(e, 2)); the default stays the
 // f32-input MFMA kernel -- measured equal (1.26 ms per launch at 256 x 2, profiles/round5/r5f_wide_forms.log) and float32-exact
 bool wide_uses_x3(const pe_engine* e) { return e->wide && e->gru_tiling == 2; }
 
-// Network launch for any input mode (0 explicit batch, 1 ring, 2 row sequence)
-int launch_network(pe_engine* e, const GruArgs& g, int mode, hipStream_t s, int model = 0) {
-    if (e->wide) {
-        // two forms of the streamed-weight network (pe_set_gru_tiling): 0 = f32-input MFMAs (gru_wide_device.h), 2 = float32
-        // products on the bf16 pipe with the float32 weights split in registers (gru_wide_x3_device.h)
-        const bool x3 = wide_uses_x3(e);
-        const NetPack* own = model ? &e->nets[model] : nullptr;           // (model > 0: its weights, set aside at pe_create_models)
-        float* const (*buf)[6] = x3 ? (own ? own->wide3_buf : e->wide3_buf) : (own ? own->wide_buf : e->wide_buf);
+// The network of every model of the engine over the windows of `g`, for any input mode (0 explicit batch, 1 ring, 2 row
+// sequence); model m writes g.out + m * out_stride.  ONE launch (K models: kernels.hip gru_models_kernel, the same tile function);
+// the wide / stacked networks take one launch per model -- each fills the machine on its own.
+int launch_networks(pe_engine* e, const GruArgs& g, int mode, hipStream_t s, long long out_stride) {
+    if (!e->wide) {
+        const ModelSet ms = model_set(e, g);
+        PE_HIP(e, launch_gru_small(g, mode, s, e->n_models > 1 ? &ms : nullptr, e->n_models, out_stride));
+        return PE_OK;
+    }
+    // two forms of the streamed-weight network (pe_set_gru_tiling): 0 = f32-input MFMAs (gru_wide_device.h), 2 = float32
+    // products on the bf16 pipe with the float32 weights split in registers (gru_wide_x3_device.h)
+    const bool x3 = wide_uses_x3(e);
+    for (int m = 0; m < e->n_models; ++m) {
+        const NetPack& n = e->nets[m];
+        float* const (*buf)[6] = x3 ? n.wide3_buf : n.wide_buf;
         WideArgs wa{};
-        wa.base = g;
+        wa.base = with_model(e, g, m);
+        wa.base.out = g.out + (size_t)m * (size_t)out_stride;
         wa.n_layers = e->n_layers;
         wa.units = e->units;
-        wa.wd = x3 ? (own ? own->wide3_wd : e->wide3_wd) : (own ? own->wide_wd : e->wide_wd);
+        wa.wd = x3 ? n.wide3_wd : n.wide_wd;
         for (int l = 0; l < e->n_layers; ++l) {
             wa.layer[l].wx1 = reinterpret_cast<const float4*>(buf[l][0]);
             wa.layer[l].wr1 = reinterpret_cast<const float4*>(buf[l][1]);
@@ -872,76 +881,13 @@ int launch_network(pe_engine* e, const GruArgs& g, int mode, hipStream_t s, int 
         }
         if (x3) PE_HIP(e, launch_gru_wide_x3(wa, mode, s));
         else PE_HIP(e, launch_gru_wide(wa, mode, s));
-        return PE_OK;
-    }
-    PE_HIP(e, launch_gru_small(g, mode, s));
-    return PE_OK;
-}
-
-// ---- several models (pe_create_models) ---------------------------------------------------------------------------
-NetPack take_net(const pe_engine* e) {
-    NetPack n;
-    n.dense_bias = e->dense_bias;
-    n.wxd = e->wxd; n.wx = e->wx; n.wr1 = e->wr1; n.wr2 = e->wr2; n.bias = e->bias; n.wd = e->wd;
-    n.cw_blob = e->cw_blob;
-    std::memcpy(n.wide_buf, e->wide_buf, sizeof(n.wide_buf)); n.wide_wd = e->wide_wd;
-    std::memcpy(n.wide3_buf, e->wide3_buf, sizeof(n.wide3_buf)); n.wide3_wd = e->wide3_wd;
-    n.wx_bf16 = e->wx_bf16; n.wr_bf16 = e->wr_bf16; n.wd_bf16 = e->wd_bf16;
-    n.b20_blob = e->b20_blob; n.x3_blob = e->x3_blob;
-    return n;
-}
-void put_net(pe_engine* e, const NetPack& n) {
-    e->dense_bias = n.dense_bias;
-    e->wxd = n.wxd; e->wx = n.wx; e->wr1 = n.wr1; e->wr2 = n.wr2; e->bias = n.bias; e->wd = n.wd;
-    e->cw_blob = n.cw_blob;
-    std::memcpy(e->wide_buf, n.wide_buf, sizeof(n.wide_buf)); e->wide_wd = n.wide_wd;
-    std::memcpy(e->wide3_buf, n.wide3_buf, sizeof(n.wide3_buf)); e->wide3_wd = n.wide3_wd;
-    e->wx_bf16 = n.wx_bf16; e->wr_bf16 = n.wr_bf16; e->wd_bf16 = n.wd_bf16;
-    e->b20_blob = n.b20_blob; e->x3_blob = n.x3_blob;
-}
-// a launch's arguments with model m's weights: the form (which blobs are read) is the engine's, the same for every model
-GruArgs with_model(const pe_engine* e, GruArgs a, int m) {
-    if (m == 0) return a;
-    const NetPack& n = e->nets[m];
-    a.wx = n.wx; a.wxd = n.wxd; a.wr1 = n.wr1; a.wr2 = n.wr2; a.bias = n.bias; a.wd = n.wd;
-    a.dense_bias = n.dense_bias;
-    a.wx_bf16 = n.wx_bf16; a.wr_bf16 = n.wr_bf16; a.wd_bf16 = n.wd_bf16;
-    a.b20 = a.b20 ? n.b20_blob : nullptr;
-    a.x3 = a.x3 ? n.x3_blob : nullptr;
-    a.cw = a.cw ? n.cw_blob : nullptr;
-    return a;
-}
-ModelSet model_set(const pe_engine* e, const GruArgs& a) {
-    ModelSet ms{};
-    for (int m = 0; m < e->n_models; ++m) {
-        const GruArgs b = with_model(e, a, m);
-        ms.net[m] = ModelNet{b.wx, b.wxd, b.wr1, b.wr2, b.bias, b.wd, b.cw, b.wx_bf16, b.wr_bf16, b.wd_bf16, b.b20, b.x3, b.dense_bias};
-    }
-    return ms;
-}
-// The network of every model of the engine over the windows of `g`; model m writes g.out + m * out_stride.  ONE launch for all
-// models (the K-model twin of the one-model kernel, kernels.hip gru_models_kernel); the wide / stacked networks take one
-// launch per model -- each fills the machine on its own.
-int launch_networks(pe_engine* e, const GruArgs& g, int mode, hipStream_t s, long long out_stride) {
-    if (e->n_models == 1) return launch_network(e, g, mode, s);
-    if (!e->wide) {
-        const ModelSet ms = model_set(e, g);
-        PE_HIP(e, launch_gru_small(g, mode, s, &ms, e->n_models, out_stride));
-        return PE_OK;
-    }
-    for (int m = 0; m < e->n_models; ++m) {
-        GruArgs gm = with_model(e, g, m);
-        gm.out = g.out + (size_t)m * (size_t)out_stride;
-        const int rc = launch_network(e, gm, mode, s, m);
-        if (rc) return rc;
     }
     return PE_OK;
 }
 // pe_update_many's batched network: out[model][update][window]
 int launch_networks_many(pe_engine* e, const GruArgs& g, int n_updates, hipStream_t s) {
-    if (e->n_models == 1) { PE_HIP(e, launch_gru_many(g, n_updates, e->n_padded, s)); return PE_OK; }
     const ModelSet ms = model_set(e, g);
-    PE_HIP(e, launch_gru_many(g, n_updates, e->n_padded, s, &ms, e->n_models));
+    PE_HIP(e, launch_gru_many(g, n_updates, e->n_padded, s, e->n_models > 1 ? &ms : nullptr, e->n_models));
     return PE_OK;
 }
 
@@ -1088,13 +1034,10 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
         g.chunk = chunk;
         g.out = raw_out_dev;
         if (ids) { g.ids = ids; g.n_streams = n_active; }
-        if (e->n_models > 1) {           // K network roles beside the one frame role: outputs [K][windows]
-            const ModelSet ms = model_set(e, g);
-            if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_models_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, ms, e->n_models, e->n_cus, s));
-            else PE_HIP(e, launch_fused_models_f32(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, ms, e->n_models, e->n_cus, s));
-        }
-        else if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, e->n_cus, s));
-        else PE_HIP(e, launch_fused_f32(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, e->n_cus, s));
+        const ModelSet ms = model_set(e, g);             // K > 1: K network roles beside the one frame role, outputs [K][windows]
+        const ModelSet* const models = e->n_models > 1 ? &ms : nullptr;
+        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, e->n_cus, s, models, e->n_models));
+        else PE_HIP(e, launch_fused(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, e->n_cus, s, models, e->n_models));
         if (t) { PE_HIP(e, hipEventRecord(e->ev[1], s)); PE_HIP(e, hipEventRecord(e->ev[2], s)); e->ev_valid = true; e->ev_has_gru = false; }
     } else {
         if ((rc = launch_mfcc(e, pcm_dev, chunk, s, call, ids, n_active))) return rc;
@@ -1221,7 +1164,9 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
     e->n_tiles = (n_streams + kTileStreams - 1) / kTileStreams;
     e->n_padded = e->n_tiles * kTileStreams;
     e->units = L.units; e->n_in = p->n_mfcc; e->n_layers = w->n_layers; e->wide = wide;
-    e->dense_bias = w->dense_bias;
+    e->n_models = n_models;
+    e->nets.assign((size_t)n_models, NetPack{});
+    e->dec.assign((size_t)n_models, DecState{});
     if (e->prm.vectorizer == 0) e->prm.vectorizer = 2;
     // frames computed (first flen samples arrived) but not yet emitted (whole window arrived):
     // at most ceil((window - flen) / hop) of them exist at any time; T + that many rows are live
@@ -1232,10 +1177,11 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
         if ((rc = dev_alloc(e, &e->carry, (size_t)2 * e->n_padded * e->carry_cap))) break;
         if ((rc = dev_alloc(e, &e->rec, (size_t)2 * e->n_padded))) break;
         if ((rc = dev_alloc(e, &e->ring, ring_floats(e)))) break;
-        // one model's network in every layout the engine's forms read (into the weight fields of e)
-        auto pack_model = [&](const pe_weights* w) -> int {
+        // one model's network in every layout the engine's forms read
+        auto pack_model = [&](NetPack& n, const pe_weights* w) -> int {
             const pe_gru_layer& L = w->layers[0];
             int rc = PE_OK;
+            n.dense_bias = w->dense_bias;
             do {
                 if (wide) {
                     // Any width 33..256 (and stacked layers of different widths) runs on the streamed-weight kernel at the next
@@ -1261,34 +1207,19 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
                     for (int u = 0; u < Hlast; ++u) dp[u] = w->dense_kernel[u];
                     pe_weights wp{w->n_layers, lp.data(), dp.data(), w->dense_bias};
                     e->units = Hp;
-                    if ((rc = pack_gru_weights_wide(e, &wp))) break;
-                    if ((rc = pack_gru_weights_wide_x3(e, &wp))) break;
+                    if ((rc = pack_gru_weights_wide(e, n, &wp))) break;
+                    if ((rc = pack_gru_weights_wide_x3(e, n, &wp))) break;
                 }
-                else if ((rc = pack_gru_weights(e, L, w->dense_kernel))) break;
-                if (p->gru_precision == 1 && (rc = pack_gru_weights_bf16(e, L, w->dense_kernel))) break;
-                if (!wide && b20_eligible(*p, L) && (rc = pack_gru_weights_b20(e, L, w->dense_kernel))) break;
-                if (!wide && x3_eligible(*p, L) && (rc = pack_gru_weights_x3(e, L, w->dense_kernel))) break;
+                else if ((rc = pack_gru_weights(e, n, L, w->dense_kernel))) break;
+                if (p->gru_precision == 1 && (rc = pack_gru_weights_bf16(e, n, L, w->dense_kernel))) break;
+                if (!wide && b20_eligible(*p, L) && (rc = pack_gru_weights_b20(e, n, L, w->dense_kernel))) break;
+                if (!wide && x3_eligible(*p, L) && (rc = pack_gru_weights_x3(e, n, L, w->dense_kernel))) break;
             } while (false);
             return rc;
         };
-        if ((rc = pack_model(w))) break;
-        if (n_models > 1) {
-            // models 1 .. K-1: packed the same way, then set aside (the engine's fields keep model 0)
-            const NetPack own = take_net(e);
-            const std::vector<float> pw = e->proj_w_host, pb = e->proj_b_host;
-            e->nets.assign((size_t)n_models, NetPack{});
-            e->dec.assign((size_t)n_models, DecState{});
-            for (int m = 1; m < n_models && !rc; ++m) {
-                put_net(e, NetPack{});
-                e->dense_bias = w[m].dense_bias;
-                rc = pack_model(&w[m]);
-                e->nets[m] = take_net(e);
-            }
-            put_net(e, own);
-            e->proj_w_host = pw; e->proj_b_host = pb;
-            e->n_models = n_models;
-            if (rc) break;
-        }
+        for (int m = 0; m < n_models && !rc; ++m) rc = pack_model(e->nets[m], &w[m]);
+        if (rc) break;
+        if (!wide) pack_projection_rows(e, L);
         // the projection rows exist for the stock-width float32 network (3 R <= 16 slots: 4 output tiles, R = 5) fed
         // from the ring; they pay while the ring stays cache-resident (256 B per frame and stream)
         e->proj_ok = !wide && p->gru_precision == 0 && !p->use_delta && gru_small_regs(L.units) == 5 && !e->proj_w_host.empty();
@@ -1378,7 +1309,7 @@ int pe_clear(pe_engine* e, const uint8_t* mask_host) {
                 e->proj_on ? reinterpret_cast<const float*>(e->table_blob + e->table_layout.proj_b) : nullptr, e->row_floats};
     if (mask_dev) a.n_streams = e->n_streams;
     PE_HIP(e, launch_clear(a, nullptr));
-    if (e->n_models > 1 && e->activation)          // the further models' trigger rows
+    if (e->activation)                              // the further models' trigger rows (n_models - 1 of them)
         PE_HIP(e, launch_clear_activation(mask_dev, e->activation, a.n_streams, e->n_padded, e->n_models - 1, nullptr));
     PE_HIP(e, hipStreamSynchronize(nullptr));
     return PE_OK;
@@ -1752,18 +1683,14 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
 }
 
 namespace {
-// model m's decoder (model 0: the engine's own fields)
 int set_decoder(pe_engine* e, int m, const double* cd, int32_t cd_len, int32_t min_out, int32_t out_range, double center) {
-    double*& dcd = m ? e->dec[m].cd : e->cd;
-    int& dlen = m ? e->dec[m].cd_len : e->cd_len;
-    dev_free(e, dcd, (size_t)(dlen ? dlen : 1) * sizeof(double));
-    dcd = nullptr; dlen = 0;
+    DecState& d = e->dec[m];
+    dev_free(e, d.cd, (size_t)(d.cd_len ? d.cd_len : 1) * sizeof(double));
+    d.cd = nullptr; d.cd_len = 0;
     std::vector<double> host(cd, cd + cd_len);
-    int rc = dev_upload(e, &dcd, host);
+    int rc = dev_upload(e, &d.cd, host);
     if (rc) return rc;
-    dlen = cd_len;
-    if (m) { e->dec[m].min_out = min_out; e->dec[m].out_range = out_range; e->dec[m].center = center; }
-    else { e->dec_min_out = min_out; e->dec_out_range = out_range; e->dec_center = center; }
+    d.cd_len = cd_len; d.min_out = min_out; d.out_range = out_range; d.center = center;
     return PE_OK;
 }
 int set_trigger(pe_engine* e, int m, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level) {
@@ -1773,9 +1700,8 @@ int set_trigger(pe_engine* e, int m, int32_t chunk_size_bytes, double sensitivit
     }
     PE_HIP(e, hipMemset(e->activation + (size_t)m * e->n_padded, 0, (size_t)e->n_padded * sizeof(int32_t)));
     const int n = 8 * 2048;                                // -(8 * 2048) // chunk_size, floor division
-    const int rearm = -((n + chunk_size_bytes - 1) / chunk_size_bytes);
-    if (m) { e->dec[m].threshold = 1.0 - sensitivity; e->dec[m].level = trigger_level; e->dec[m].rearm = rearm; e->dec[m].on = true; }
-    else { e->trig_threshold = 1.0 - sensitivity; e->trig_level = trigger_level; e->trig_rearm = rearm; e->trig_on = true; }
+    DecState& d = e->dec[m];
+    d.threshold = 1.0 - sensitivity; d.level = trigger_level; d.rearm = -((n + chunk_size_bytes - 1) / chunk_size_bytes); d.on = true;
     return PE_OK;
 }
 }  // namespace
@@ -1822,10 +1748,9 @@ int pe_set_trigger_model(pe_engine* e, int32_t model, int32_t chunk_size_bytes, 
 int pe_decode_device(pe_engine* e, const float* raw_dev, double* conf_out_dev, unsigned char* fired_out_dev, void* stream) {
     if (!e || !raw_dev) return fail(e, PE_ERR_INVALID, "null argument to pe_decode_device");
     for (int m = 0; m < e->n_models; ++m) {
-        const double* cd = m ? e->dec[m].cd : e->cd;
-        const int cd_len = m ? e->dec[m].cd_len : e->cd_len, out_range = m ? e->dec[m].out_range : e->dec_out_range;
-        if (!cd && out_range != 0) return fail(e, PE_ERR_INVALID, "pe_set_decoder has not been called");
-        if (!cd_len && !cd) return fail(e, PE_ERR_INVALID, m ? "pe_set_decoder has not been called for model %d" : "pe_set_decoder has not been called", m);
+        const DecState& d = e->dec[m];
+        if (!d.cd && d.out_range != 0) return fail(e, PE_ERR_INVALID, "pe_set_decoder has not been called");
+        if (!d.cd_len && !d.cd) return fail(e, PE_ERR_INVALID, m ? "pe_set_decoder has not been called for model %d" : "pe_set_decoder has not been called", m);
     }
     PE_HIP(e, hipSetDevice(e->device));
     const size_t n = (size_t)e->n_streams;
@@ -1835,18 +1760,11 @@ int pe_decode_device(pe_engine* e, const float* raw_dev, double* conf_out_dev, u
         a.n_streams = e->n_streams; a.raw = raw_dev + m * n;
         a.conf_out = conf_out_dev ? conf_out_dev + m * n : nullptr;
         a.fired_out = fired_out_dev ? fired_out_dev + m * n : nullptr;
-        if (m == 0) {
-            a.cd = e->cd; a.cd_len = e->cd_len;
-            a.min_out = e->dec_min_out; a.out_range = e->dec_out_range; a.center = e->dec_center;
-            a.activation = e->trig_on ? e->activation : nullptr;
-            a.threshold = e->trig_threshold; a.trigger_level = e->trig_level; a.rearm = e->trig_rearm;
-        } else {
-            const DecState& d = e->dec[m];
-            a.cd = d.cd; a.cd_len = d.cd_len;
-            a.min_out = d.min_out; a.out_range = d.out_range; a.center = d.center;
-            a.activation = d.on ? e->activation + (size_t)m * e->n_padded : nullptr;
-            a.threshold = d.threshold; a.trigger_level = d.level; a.rearm = d.rearm;
-        }
+        const DecState& d = e->dec[m];
+        a.cd = d.cd; a.cd_len = d.cd_len;
+        a.min_out = d.min_out; a.out_range = d.out_range; a.center = d.center;
+        a.activation = d.on ? e->activation + (size_t)m * e->n_padded : nullptr;
+        a.threshold = d.threshold; a.trigger_level = d.level; a.rearm = d.rearm;
     }
     if (e->n_models == 1) PE_HIP(e, launch_decode(set.m[0], static_cast<hipStream_t>(stream)));
     else PE_HIP(e, launch_decode_models(set, e->n_models, e->n_streams, static_cast<hipStream_t>(stream)));
@@ -2076,9 +1994,9 @@ int pe_set_gru_tiling(pe_engine* e, int32_t tiling) {
         e->gru_tiling = tiling;
         return PE_OK;
     }
-    if (tiling == 2 && !e->x3_blob)
+    if (tiling == 2 && !e->nets[0].x3_blob)
         return fail(e, PE_ERR_UNSUPPORTED, "the XDL form of the float32 network (tiling 2) takes <= 20 units, <= 15 inputs, float32 operands, no use_delta");
-    if (tiling == 1 && e->prm.gru_precision == 1 && !e->b20_blob)
+    if (tiling == 1 && e->prm.gru_precision == 1 && !e->nets[0].b20_blob)
         return fail(e, PE_ERR_UNSUPPORTED, "the five-values layout of the bf16 network (tiling 1) takes <= 20 units and <= 14 features");
     PE_DRAIN(e);
     e->gru_tiling = tiling;

@@ -1,6 +1,9 @@
 // Every __global__ entry point of libprecise_engine.so and its launcher.  The device code lives
 // in mfcc_wave_device.h / mfcc_device.h (MFCC front end: frames / bookkeeping) and gru_*_device.h (GRU + Dense
-// on the matrix cores).
+// on the matrix cores).  What is said once here: a network shape (tile function, threads, LDS) is a Net* functor, run by
+// its one-model kernel, by gru_models_kernel and by the pe_update_many kernels (three kernels write the same call out: noted there); a fused update has one body per role layout
+// (float32 network, bf16 network) with a compile-time flag for "several models"; a `name` / `name_nopk` pair whose body is one call is one
+// PE_KERNEL_PAIR; a runtime mode / flag becomes a template argument through with_const.
 #include <cstdlib>
 #include <type_traits>
 #include "mfcc_device.h"
@@ -50,12 +53,26 @@ __device__ __forceinline__ void touch_kernel_arguments() {
 #define PE_NO_PK_F32            // (the host pass only sees the launch stubs)
 #endif
 #define PE_UNPAREN(...) __VA_ARGS__
+// `NAME` and its twin `NAME_nopk` (the same body under PE_NO_PK_F32): TEMPLATE and ATTRS in parentheses, the body last
+#define PE_KERNEL_PAIR(TEMPLATE, ATTRS, NAME, PARAMS, ...)                                                   \
+    PE_UNPAREN TEMPLATE __global__ PE_UNPAREN ATTRS void NAME PARAMS __VA_ARGS__                            \
+    PE_UNPAREN TEMPLATE __global__ PE_UNPAREN ATTRS PE_NO_PK_F32 void NAME##_nopk PARAMS __VA_ARGS__
+#define PE_FRAME_KERNEL(THREADS, WPE) (__launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))))
 // launch KERNEL<R, TARGS...> -- its _nopk twin when R is float
 #define PE_LAUNCH_R(R, KERNEL, TARGS, ...)                                                                   \
     do {                                                                                                     \
         if constexpr (std::is_same<R, float>::value) hipLaunchKernelGGL((KERNEL##_nopk<R, PE_UNPAREN TARGS>), __VA_ARGS__); \
         else hipLaunchKernelGGL((KERNEL<R, PE_UNPAREN TARGS>), __VA_ARGS__);                                 \
     } while (0)
+
+// A runtime value as a compile-time one: f(std::integral_constant<int, V>{}) for the V that equals v; false if none does.
+// The launchers turn the input mode (kRing / kRows / kFeats), flags and small counts into template arguments with it.
+template <int... V, class F>
+static bool with_const(int v, F&& f) { return ((v == V ? (f(std::integral_constant<int, V>{}), true) : false) || ...); }
+// (the input mode: anything that is neither the ring nor a row sequence is an explicit batch, as the ladders had it)
+template <class F> static bool with_mode(int mode, F&& f) { return with_const<kRing, kRows, kFeats>(mode == kRing || mode == kRows ? mode : kFeats, f); }
+template <class F> static bool with_flag(bool on, F&& f) { return with_const<0, 1>(on ? 1 : 0, f); }
+#define PE_CONST(X) decltype(X)::value
 
 // SINGLE: one update, no projection rows (the launcher knows): the frame loop without the several-updates arithmetic
 template <class R, class SH, bool SINGLE>
@@ -65,72 +82,11 @@ __device__ __forceinline__ void mfcc_kernel_body(const MfccStreamArgs<R>& a, con
     if ((int)blockIdx.x < n_frame_blocks) mfcc_frame_tasks<R, SH, SINGLE, SINGLE>(a, t, smem, (int)blockIdx.x * kFrameWaves, n_frame_blocks * kFrameWaves);
     else mfcc_book_tile<R>(a, (int)blockIdx.x - n_frame_blocks);
 }
-template <class R, class SH, bool SINGLE = false>
-__global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_eu(SH::WPE))) void mfcc_kernel(const MfccStreamArgs<R> a, const WaveTables<R> t, const int n_frame_blocks) {
-    mfcc_kernel_body<R, SH, SINGLE>(a, t, n_frame_blocks);
-}
-template <class R, class SH, bool SINGLE = false>
-__global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_eu(SH::WPE))) PE_NO_PK_F32 void mfcc_kernel_nopk(const MfccStreamArgs<R> a, const WaveTables<R> t, const int n_frame_blocks) {
-    mfcc_kernel_body<R, SH, SINGLE>(a, t, n_frame_blocks);
-}
+PE_KERNEL_PAIR((template <class R, class SH, bool SINGLE = false>), PE_FRAME_KERNEL(64 * kFrameWaves, SH::WPE), mfcc_kernel,
+               (const MfccStreamArgs<R> a, const WaveTables<R> t, const int n_frame_blocks),
+               { mfcc_kernel_body<R, SH, SINGLE>(a, t, n_frame_blocks); })
 
-
-// network for a whole batch of updates: workgroup (one wave) b serves update b / n_tiles, tile b % n_tiles
-template <int R, bool PROJ>
-__global__ __launch_bounds__(64) void gru_many_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
-    const int u = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    GruArgs b = a;
-    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
-    b.out = a.out + (size_t)u * a.n_streams;
-    b.predict_ke = 0;
-    gru_tile<R, kRing, PROJ>(b, tile, threadIdx.x);
-}
-
-// same, four waves sharing each (update, tile) -- few tiles per SIMD: latency matters more than issue slots
-template <int R, bool PROJ>
-__global__ __launch_bounds__(256) void gru_many_mw_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
-    __shared__ __attribute__((aligned(16))) float S[3 * R * 64 + 256];
-    const int u = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    GruArgs b = a;
-    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
-    b.out = a.out + (size_t)u * a.n_streams;
-    b.predict_ke = 0;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    gru_tile_mw_any<R, PROJ>(b, tile, wave, threadIdx.x & 63, S);
-}
-
-// the same two for the re-tiled stock width (gru_cw_device.h)
-template <bool DELTA>
-__global__ __launch_bounds__(64) void gru_many_v_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
-    const int u = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    GruArgs b = a;
-    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
-    b.out = a.out + (size_t)u * a.n_streams;
-    b.predict_ke = 0;
-    gru_tile_v<kRing, DELTA>(b, tile, threadIdx.x);
-}
-__global__ __launch_bounds__(256) void gru_many_cw_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int u = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    GruArgs b = a;
-    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
-    b.out = a.out + (size_t)u * a.n_streams;
-    b.predict_ke = 0;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    gru_tile_cw<false>(b, tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
-}
-
-template <bool DELTA, bool RB>
-__global__ __launch_bounds__(64) void gru_many_bf16_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
-    const int u = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    GruArgs b = a;
-    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
-    b.out = a.out + (size_t)u * a.n_streams;
-    b.predict_ke = 0;
-    if (b.b20) { gru_tile_b20<kRing, DELTA, RB>(b, tile, threadIdx.x); return; }      // <= 20 units: five values per lane
-    gru_tile_bf16<kRing, DELTA, RB>(b, tile, threadIdx.x);
-}
-
+// (pairs whose body is more than a call are written out)
 template <class R, class SH>
 __global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_eu(SH::WPE))) void mfcc_offline_kernel(const MfccOfflineArgs<R> a, const WaveTables<R> t) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -142,27 +98,166 @@ __global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_e
     mfcc_offline_frames<R, SH>(a, t, smem);
 }
 
-// ---- GRU: one wave per 16-stream tile ----------------------------------------------------------
+// ---- network shapes: the tile function of a workgroup, its threads and its LDS, said once -------------------------------
+// run(a, tile, smem) is the whole network of tile `tile` of the launch `a`.  The one-model kernel of a shape (the names
+// the profiles know), gru_models_kernel (K models) and the pe_update_many kernels all run it.  kLds: dynamic LDS of a workgroup;
+// kOwnLds: what the shape's one-model kernel asks for at launch (gru_mw_kernel declares its LDS statically).
+template <int R, int MODE, bool PROJ, int KX> struct NetSmall {          // one wave per 16-stream tile
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0, kOwnLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile<R, MODE, PROJ, KX>(a, tile, threadIdx.x); }
+};
+template <int R, bool PROJ, int KX> struct NetMw {                       // four waves per tile (few tiles: fills all four SIMDs of a CU)
+    static constexpr int kThreads = 256; static constexpr size_t kLds = (3 * R * 64 + 256) * sizeof(float), kOwnLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char* smem) {
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        gru_tile_mw_any<R, PROJ, KX>(a, tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+    }
+};
+template <int MODE, bool DELTA> struct NetV {                            // stock width re-tiled (gru_cw_device.h), one wave per tile
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0, kOwnLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile_v<MODE, DELTA>(a, tile, threadIdx.x); }
+};
+struct NetCw {                                                           // ... four waves per tile
+    static constexpr int kThreads = 256; static constexpr size_t kLds = kCwLdsBytes, kOwnLds = kCwLdsBytes;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char* smem) {
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        gru_tile_cw<false>(a, tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+    }
+};
+template <int MODE, bool DELTA, bool RB> struct NetBf16 {                // bf16 operands, one wave per tile
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0, kOwnLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) {
+        if (a.b20) { gru_tile_b20<MODE, DELTA, RB>(a, tile, threadIdx.x); return; }      // <= 20 units: five values per lane (gru_b20_device.h)
+        gru_tile_bf16<MODE, DELTA, RB>(a, tile, threadIdx.x);
+    }
+};
+template <int MODE> struct NetX3 {                                       // float32 as three bf16 pieces per operand on the XDL pipe
+    static constexpr int kThreads = 64; static constexpr size_t kLds = 0, kOwnLds = 0;
+    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile_x3<MODE>(a, tile, threadIdx.x); }
+};
+
+// ---- the one-model kernel of every shape ----------------------------------------------------------------------------------
 template <int R, int MODE, bool PROJ = false, int KX = 1>
 __global__ __launch_bounds__(64) void gru_small_kernel(const GruArgs a) {
     touch_kernel_arguments<(int)sizeof(GruArgs)>();
-    gru_tile<R, MODE, PROJ, KX>(a, blockIdx.x, threadIdx.x);
+    NetSmall<R, MODE, PROJ, KX>::run(a, blockIdx.x, nullptr);
 }
-
-// ---- GRU, stock width re-tiled (gru_cw_device.h): one wave per tile / four waves per tile ------------------------
+template <int R, bool PROJ = false, int KX = 1>
+__global__ __launch_bounds__(256) void gru_mw_kernel(const GruArgs a) {
+    // (NetMw<R, PROJ, KX>::run, written out over the kernel's static LDS: through the functor the code of the K-model
+    //  kernels of NetMw<7, false, 1> changes)
+    __shared__ __attribute__((aligned(16))) float S[3 * R * 64 + 256];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    gru_tile_mw_any<R, PROJ, KX>(a, blockIdx.x, wave, threadIdx.x & 63, S);
+}
 template <int MODE, bool DELTA>
 __global__ __launch_bounds__(64) void gru_v_kernel(const GruArgs a) {
     touch_kernel_arguments<(int)sizeof(GruArgs)>();
-    gru_tile_v<MODE, DELTA>(a, blockIdx.x, threadIdx.x);
+    NetV<MODE, DELTA>::run(a, blockIdx.x, nullptr);
 }
 __global__ __launch_bounds__(256) void gru_cw_kernel(const GruArgs a) {
     touch_kernel_arguments<(int)sizeof(GruArgs)>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    gru_tile_cw<false>(a, blockIdx.x, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+    NetCw::run(a, blockIdx.x, smem);
 }
 // the four-wave shape stages the tile's whole ring in LDS and walks at most 32 timesteps of it
 static bool cw_four_waves_ok(const GruArgs& a) { return a.ring_slots == kCwSlots && a.n_features <= kCwSlots; }
+template <int MODE, bool DELTA, bool RB = false>
+__global__ __launch_bounds__(64) void gru_bf16_kernel(const GruArgs a) {
+    touch_kernel_arguments<(int)sizeof(GruArgs)>();
+    NetBf16<MODE, DELTA, RB>::run(a, blockIdx.x, nullptr);
+}
+template <int MODE>
+__global__ __launch_bounds__(64) void gru_x3_kernel(const GruArgs a) {
+    touch_kernel_arguments<(int)sizeof(GruArgs)>();
+    NetX3<MODE>::run(a, blockIdx.x, nullptr);
+}
+
+// ---- the network for a whole batch of updates (pe_update_many): workgroup b serves update b / n_tiles, tile b % n_tiles ----
+// b becomes the arguments of update u of the call: its row of the emitted-frame history, its block of the output
+__device__ __forceinline__ void select_update(GruArgs& b, const int u, const int n_padded) {
+    b.ke_plain += (size_t)u * n_padded;
+    b.out += (size_t)u * b.n_streams;
+    b.predict_ke = 0;
+}
+template <int R, bool PROJ>
+__global__ __launch_bounds__(64) void gru_many_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
+    GruArgs b = a;
+    select_update(b, blockIdx.x / n_tiles, n_padded);
+    NetSmall<R, kRing, PROJ, 1>::run(b, blockIdx.x % n_tiles, nullptr);
+}
+// (four waves sharing each (update, tile) -- few tiles per SIMD: latency matters more than issue slots)
+template <int R, bool PROJ>
+__global__ __launch_bounds__(256) void gru_many_mw_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
+    __shared__ __attribute__((aligned(16))) float S[3 * R * 64 + 256];
+    GruArgs b = a;
+    select_update(b, blockIdx.x / n_tiles, n_padded);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    gru_tile_mw_any<R, PROJ>(b, blockIdx.x % n_tiles, wave, threadIdx.x & 63, S);       // (written out, as in gru_mw_kernel)
+}
+template <bool DELTA>
+__global__ __launch_bounds__(64) void gru_many_v_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
+    GruArgs b = a;
+    select_update(b, blockIdx.x / n_tiles, n_padded);
+    NetV<kRing, DELTA>::run(b, blockIdx.x % n_tiles, nullptr);
+}
+__global__ __launch_bounds__(256) void gru_many_cw_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    GruArgs b = a;
+    select_update(b, blockIdx.x / n_tiles, n_padded);
+    NetCw::run(b, blockIdx.x % n_tiles, smem);
+}
+template <bool DELTA, bool RB>
+__global__ __launch_bounds__(64) void gru_many_bf16_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
+    // (NetBf16<kRing, DELTA, RB>::run, written out: through the functor this kernel compiles to other code than it did)
+    const int tile = blockIdx.x % n_tiles;
+    GruArgs b = a;
+    select_update(b, blockIdx.x / n_tiles, n_padded);
+    if (b.b20) { gru_tile_b20<kRing, DELTA, RB>(b, tile, threadIdx.x); return; }
+    gru_tile_bf16<kRing, DELTA, RB>(b, tile, threadIdx.x);
+}
+__global__ __launch_bounds__(64) void gru_many_x3_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
+    GruArgs b = a;
+    select_update(b, blockIdx.x / n_tiles, n_padded);
+    NetX3<kRing>::run(b, blockIdx.x % n_tiles, nullptr);
+}
+
+// ---- the network of a K-model engine (pe_create_models) in ONE launch, any shape: workgroup b runs block b % per_model of
+// model b / per_model with that model's weights (ModelSet); model-major outputs, out_stride apart
+template <class NET>
+__global__ __launch_bounds__(NET::kThreads) void gru_models_kernel(const GruArgs a, const ModelSet ms, const int per_model, const long long out_stride) {
+    touch_kernel_arguments<(int)sizeof(GruArgs)>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int mi = __builtin_amdgcn_readfirstlane(blockIdx.x / per_model);
+    NET::run(model_args(a, ms.net[mi], mi, out_stride), blockIdx.x - mi * per_model, smem);
+}
+// pe_update_many: (model, update, tile) per workgroup, outputs [K][n_updates][windows]
+template <class NET>
+__global__ __launch_bounds__(NET::kThreads) void gru_many_models_kernel(const GruArgs a, const ModelSet ms, const int n_tiles, const int n_updates, const int n_padded) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int per_model = n_tiles * n_updates;
+    const int mi = __builtin_amdgcn_readfirstlane(blockIdx.x / per_model);
+    const int w = blockIdx.x - mi * per_model;
+    const int u = w / n_tiles, tile = w % n_tiles;
+    GruArgs b = model_args(a, ms.net[mi], mi, (long long)n_updates * a.n_streams);
+    select_update(b, u, n_padded);
+    NET::run(b, tile, smem);
+}
+// what the launchers below take for a K-model engine (ms == null: the one-model kernels)
+struct NetModels { const ModelSet* ms; int n; long long out_stride; };
+// one network launch of shape NET: its one-model KERNEL over GRID workgroups, or gru_models_kernel<NET> over GRID x K
+#define PE_NET(NET, KERNEL, GRID)                                                                                            \
+    do {                                                                                                                     \
+        using Net_ = PE_UNPAREN NET;                                                                                         \
+        if (mm.ms) hipLaunchKernelGGL((gru_models_kernel<Net_>), dim3((GRID) * mm.n), dim3(Net_::kThreads), Net_::kLds, s, a, *mm.ms, (int)(GRID), mm.out_stride); \
+        else hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(Net_::kThreads), Net_::kOwnLds, s, a);                              \
+    } while (0)
+#define PE_NET_MANY(NET, KERNEL, TILES)                                                                                      \
+    do {                                                                                                                     \
+        using Net_ = PE_UNPAREN NET;                                                                                         \
+        if (mm.ms) hipLaunchKernelGGL((gru_many_models_kernel<Net_>), dim3((TILES) * n_updates * mm.n), dim3(Net_::kThreads), Net_::kLds, s, a, *mm.ms, (TILES), n_updates, n_padded); \
+        else hipLaunchKernelGGL(KERNEL, dim3((TILES) * n_updates), dim3(Net_::kThreads), Net_::kOwnLds, s, a, (TILES), n_padded); \
+    } while (0)
 
 // ---- wide / stacked GRU: one workgroup per 16-stream tile, weights streamed from L2 -------------------
 template <int TPW, int MODE, int WAVES>
@@ -180,9 +275,7 @@ static hipError_t launch_wide_t(const WideArgs& a, int mode, hipStream_t s) {
     const int tiles = (a.base.n_streams + kTileStreams - 1) / kTileStreams;
     if (tiles == 0) return hipSuccess;
     const size_t lds = (size_t)4 * (TPW * WAVES) * 256 * sizeof(float);      // 2 layers x {h, r*h}
-    if (mode == kRing) hipLaunchKernelGGL((gru_wide_kernel<TPW, kRing, WAVES>), dim3(tiles), dim3(64 * WAVES), lds, s, a);
-    else if (mode == kRows) hipLaunchKernelGGL((gru_wide_kernel<TPW, kRows, WAVES>), dim3(tiles), dim3(64 * WAVES), lds, s, a);
-    else hipLaunchKernelGGL((gru_wide_kernel<TPW, kFeats, WAVES>), dim3(tiles), dim3(64 * WAVES), lds, s, a);
+    if (!with_mode(mode, [&](auto M) { hipLaunchKernelGGL((gru_wide_kernel<TPW, PE_CONST(M), WAVES>), dim3(tiles), dim3(64 * WAVES), lds, s, a); })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -203,20 +296,14 @@ static hipError_t launch_wide_x3_t(const WideArgs& a, int mode, hipStream_t s) {
     if (tiles == 0) return hipSuccess;
     constexpr int KS = (PE_WIDE_X3_KS == 2 && TPW % 2 == 0) ? 2 : 1;
     const size_t lds = wide_x3_lds_bytes<TPW>();          // three state vectors + partial sums / z / float32 state of the lead waves
-    if (mode == kRing) hipLaunchKernelGGL((gru_wide_x3_kernel<TPW, kRing, KS>), dim3(tiles), dim3(256 * KS), lds, s, a);
-    else if (mode == kRows) hipLaunchKernelGGL((gru_wide_x3_kernel<TPW, kRows, KS>), dim3(tiles), dim3(256 * KS), lds, s, a);
-    else hipLaunchKernelGGL((gru_wide_x3_kernel<TPW, kFeats, KS>), dim3(tiles), dim3(256 * KS), lds, s, a);
+    if (!with_mode(mode, [&](auto M) { hipLaunchKernelGGL((gru_wide_x3_kernel<TPW, PE_CONST(M), KS>), dim3(tiles), dim3(256 * KS), lds, s, a); })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
 hipError_t launch_gru_wide_x3(const WideArgs& a, int mode, hipStream_t s) {
-    switch (a.units / 64) {
-        case 1: return launch_wide_x3_t<1>(a, mode, s);
-        case 2: return launch_wide_x3_t<2>(a, mode, s);
-        case 3: return launch_wide_x3_t<3>(a, mode, s);
-        case 4: return launch_wide_x3_t<4>(a, mode, s);
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t err = hipErrorInvalidValue;
+    with_const<1, 2, 3, 4>(a.units / 64, [&](auto T) { err = launch_wide_x3_t<PE_CONST(T)>(a, mode, s); });
+    return err;
 }
 
 // 8 waves per workgroup (two per SIMD) for H = 128 / 256 was measured and is NOT faster: 256 x 2 layers, 4096
@@ -236,29 +323,6 @@ hipError_t launch_gru_wide(const WideArgs& a, int mode, hipStream_t s) {
     }
 }
 
-// ---- GRU, bf16 operands: one wave per 16-stream tile --------------------------------------------------
-template <int MODE, bool DELTA, bool RB = false>
-__global__ __launch_bounds__(64) void gru_bf16_kernel(const GruArgs a) {
-    touch_kernel_arguments<(int)sizeof(GruArgs)>();
-    if (a.b20) { gru_tile_b20<MODE, DELTA, RB>(a, blockIdx.x, threadIdx.x); return; }      // <= 20 units: five values per lane (gru_b20_device.h)
-    gru_tile_bf16<MODE, DELTA, RB>(a, blockIdx.x, threadIdx.x);
-}
-
-// ---- GRU, float32 as three bf16 pieces per operand on the XDL pipe: one wave per 16-stream tile ------------------
-template <int MODE>
-__global__ __launch_bounds__(64) void gru_x3_kernel(const GruArgs a) {
-    touch_kernel_arguments<(int)sizeof(GruArgs)>();
-    gru_tile_x3<MODE>(a, blockIdx.x, threadIdx.x);
-}
-__global__ __launch_bounds__(64) void gru_many_x3_kernel(const GruArgs a, const int n_tiles, const int n_padded) {
-    const int u = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    GruArgs b = a;
-    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
-    b.out = a.out + (size_t)u * a.n_streams;
-    b.predict_ke = 0;
-    gru_tile_x3<kRing>(b, tile, threadIdx.x);
-}
-
 // Dispatch order of the roles of a fused launch.  Workgroups are handed to the CUs in blockIdx order; `frames_first`
 // puts the (few, long-lived, VALU-bound) frame workgroups in front of the (many, MFMA-bound) network workgroups so
 // that at large batches the two kinds are resident TOGETHER -- with the network first, its workgroups fill every
@@ -272,68 +336,74 @@ __device__ __forceinline__ int role_block(const int b, const int n_gru, const in
     return b < n_frames ? n_gru + b : b - n_frames;
 }
 
-// fused update with the bf16 network role (four tiles per GRU workgroup, one wave each)
-template <class R, class SH, bool DELTA, bool RB>
-__device__ __forceinline__ void fused_update_bf16_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g,
-                                                       const int n_gru_blocks, const int n_frame_blocks, const int n_tiles, const int frames_first) {
-    touch_kernel_arguments<(int)(sizeof(MfccStreamArgs<R>) + sizeof(WaveTables<R>) + sizeof(GruArgs) + 16)>();
+// ---- fused update: network role(s) || MFCC frame role || bookkeeping role in ONE launch -------------------------------
+// Workgroups [0, n_net) run the network on the feature windows as they will stand after this update (they are dispatched
+// first: the long pole); the next n_frame_blocks compute this update's MFCC frames, one frame task per wave; the last
+// n_tiles move the leftover samples and the counters.
+// MODELS (a K-model engine, pe_create_models): n_models network roles beside ONE frame role and ONE bookkeeping role.  The
+// network workgroups are the one-model launch's, n_gru_blocks per model, model-major: workgroup b of the network runs block
+// b % n_gru_blocks of model b / n_gru_blocks with that model's weights (ModelSet) and writes that model's block of the output.
+// The network roles only READ the ring and the records (the frame and bookkeeping roles write rows and record sides no window
+// of this launch reads), so K of them are as independent as one.  !MODELS: ms is not read, n_models is 1.
+// network_args: the arguments of network workgroup b -- the launch's own, or (K models) a copy with the model's weights and
+// its block of the output; b becomes the block within the model.
+__device__ __forceinline__ const GruArgs& network_args(std::false_type, const GruArgs& g, const ModelSet*, const int, int&) { return g; }
+__device__ __forceinline__ GruArgs network_args(std::true_type, const GruArgs& g, const ModelSet* ms, const int n_gru_blocks, int& b) {
+    const int mi = __builtin_amdgcn_readfirstlane(b / n_gru_blocks);
+    b -= mi * n_gru_blocks;
+    return model_args(g, ms->net[mi], mi, g.n_streams);
+}
+// (the argument lines the prologue touches: the integers behind GruArgs -- four, and n_models for a K-model launch, whose
+//  ModelSet behind them is read once the model is known)
+template <class R, bool MODELS>
+static constexpr int kFusedArgBytes = (int)(sizeof(MfccStreamArgs<R>) + sizeof(WaveTables<R>) + sizeof(GruArgs) + (MODELS ? 20 : 16));
+
+// bf16 network role: frames_first bits 8.. = network tiles per workgroup, one wave each (1, 2 or 4: with few tiles, one or
+// two network waves on EVERY compute unit disturb the frame waves less than four on every second one)
+template <class R, class SH, bool DELTA, bool RB, bool MODELS>
+__device__ __forceinline__ void fused_update_bf16_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ModelSet* ms,
+                                                       const int n_gru_blocks, const int n_models, const int n_frame_blocks, const int n_tiles, const int frames_first) {
+    touch_kernel_arguments<kFusedArgBytes<R, MODELS>>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // frames_first: bit 0 = frame workgroups dispatched first; bits 8.. = network tiles per workgroup (1, 2 or 4: with few
-    // tiles, one or two network waves on EVERY compute unit disturb the frame waves less than four on every second one)
     const int tpw = frames_first >> 8;
-    const int b = role_block(blockIdx.x, n_gru_blocks, n_frame_blocks, frames_first & 1);
-    if (b < n_gru_blocks) {
+    const int n_net = MODELS ? n_gru_blocks * n_models : n_gru_blocks;
+    const int b = role_block(blockIdx.x, n_net, n_frame_blocks, frames_first & 1);
+    if (b < n_net) {
+        int bl = b;
+        const GruArgs& gm = network_args(std::integral_constant<bool, MODELS>{}, g, ms, n_gru_blocks, bl);
         const int wave = threadIdx.x >> 6;
-        const int tile = b * tpw + wave;
+        const int tile = bl * tpw + wave;
         if (wave < tpw && tile < n_tiles) {
-            if (g.b20) { gru_tile_b20<kRing, DELTA, RB>(g, tile, threadIdx.x & 63); return; }
-            gru_tile_bf16<kRing, DELTA, RB>(g, tile, threadIdx.x & 63);
+            if (gm.b20) { gru_tile_b20<kRing, DELTA, RB>(gm, tile, threadIdx.x & 63); return; }
+            gru_tile_bf16<kRing, DELTA, RB>(gm, tile, threadIdx.x & 63);
         }
-    } else if (b < n_gru_blocks + n_frame_blocks) {
-        mfcc_frame_tasks<R, SH, true>(m, t, smem, (b - n_gru_blocks) * kFrameWaves, n_frame_blocks * kFrameWaves);
+    } else if (b < n_net + n_frame_blocks) {
+        mfcc_frame_tasks<R, SH, true>(m, t, smem, (b - n_net) * kFrameWaves, n_frame_blocks * kFrameWaves);
     } else {
-        mfcc_book_tile<R>(m, b - n_gru_blocks - n_frame_blocks);
+        mfcc_book_tile<R>(m, b - n_net - n_frame_blocks);
     }
 }
-template <class R, class SH, bool DELTA, bool RB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) void fused_update_bf16_kernel(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                                const int n_gru_blocks, const int n_frame_blocks, const int n_tiles, const int frames_first) {
-    fused_update_bf16_body<R, SH, DELTA, RB>(m, t, g, n_gru_blocks, n_frame_blocks, n_tiles, frames_first);
-}
-template <class R, class SH, bool DELTA, bool RB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) PE_NO_PK_F32 void fused_update_bf16_kernel_nopk(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                                const int n_gru_blocks, const int n_frame_blocks, const int n_tiles, const int frames_first) {
-    fused_update_bf16_body<R, SH, DELTA, RB>(m, t, g, n_gru_blocks, n_frame_blocks, n_tiles, frames_first);
-}
 
-// ---- GRU: four waves per 16-stream tile (few tiles: fills all four SIMDs of a CU) -----------------
-template <int R, bool PROJ = false, int KX = 1>
-__global__ __launch_bounds__(256) void gru_mw_kernel(const GruArgs a) {
-    __shared__ __attribute__((aligned(16))) float S[3 * R * 64 + 256];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    gru_tile_mw_any<R, PROJ, KX>(a, blockIdx.x, wave, threadIdx.x & 63, S);
-}
-
-
-// ---- fused update: GRU role || MFCC frame role || bookkeeping role in ONE launch -------------------------------
-// Workgroups [0, n_gru_blocks) run the network on the feature windows as they will stand after this update (they
-// are dispatched first: the long pole); the next n_frame_blocks compute this update's MFCC frames, one frame task
-// per wave; the last n_tiles move the leftover samples and the counters.  MW = true: one GRU workgroup per tile,
-// its four waves share the tile (gru_tile_mw); MW = false: four tiles per GRU workgroup, one wave each.
-template <class R, class SH, int RG, bool MW, bool PROJ, bool CW>
-__device__ __forceinline__ void fused_update_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g,
-                                                  const int n_gru_blocks, const int n_frame_blocks, const int n_tiles, const int frames_first) {
+// float32 network role.  MW = true: one network workgroup per tile, its four waves share the tile (gru_tile_mw / gru_tile_cw);
+// MW = false: four tiles per network workgroup, one wave each.  CW: stock width, re-tiled (gru_cw_device.h).
+template <class R, class SH, int RG, bool MW, bool PROJ, bool CW, bool MODELS>
+__device__ __forceinline__ void fused_update_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ModelSet* ms,
+                                                  const int n_gru_blocks, const int n_models, const int n_frame_blocks, const int n_tiles, const int frames_first) {
+    static_assert(!(MODELS && PROJ), "input projection rows are per model: pe_set_input_projection refuses K > 1");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    touch_kernel_arguments<(int)(sizeof(MfccStreamArgs<R>) + sizeof(WaveTables<R>) + sizeof(GruArgs) + 16)>();
-    const int b = role_block(blockIdx.x, n_gru_blocks, n_frame_blocks, frames_first & kFramesFirst);
-    if (b < n_gru_blocks) {
+    touch_kernel_arguments<kFusedArgBytes<R, MODELS>>();
+    const int n_net = MODELS ? n_gru_blocks * n_models : n_gru_blocks;
+    const int b = role_block(blockIdx.x, n_net, n_frame_blocks, frames_first & kFramesFirst);
+    if (b < n_net) {
+        int bl = b;
+        const GruArgs& gm = network_args(std::integral_constant<bool, MODELS>{}, g, ms, n_gru_blocks, bl);
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #if defined(PE_PRIO_R)
         if (wave == 0) __builtin_amdgcn_s_setprio(PE_PRIO_R); else __builtin_amdgcn_s_setprio(PE_PRIO_H);
 #else
         __builtin_amdgcn_s_setprio(3);          // the network role is the long pole: it wins every issue arbitration
 #endif
-        if constexpr (CW) {                     // stock width, re-tiled (gru_cw_device.h)
+        if constexpr (CW) {
             static_assert(RG == 5 && !PROJ, "the re-tiled shapes exist for the stock width, without projection rows");
             if (MW) {
                 // kBySimd: the four roles sit on SIMDs 0..3 in a fixed order (R on 0, Z1, Z2, P) so that the frame waves of
@@ -348,205 +418,38 @@ __device__ __forceinline__ void fused_update_body(const MfccStreamArgs<R>& m, co
                     __syncthreads();
                     if (((1 << slot[0]) | (1 << slot[1]) | (1 << slot[2]) | (1 << slot[3])) == 15) role = simd;
                 }
-                gru_tile_cw<false>(g, b, role, threadIdx.x & 63, reinterpret_cast<float*>(smem));
-            } else {
-                const int tile = b * 4 + wave;
-                if (tile < n_tiles) gru_tile_v<kRing, false>(g, tile, threadIdx.x & 63);       // (use_delta on this shape: two launches, engine.hip can_fuse)
-            }
-        } else if (MW) {
-            gru_tile_mw_any<RG, PROJ>(g, b, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
-        } else {
-            const int tile = b * 4 + wave;
-            if (tile < n_tiles) gru_tile<RG, kRing, PROJ>(g, tile, threadIdx.x & 63);
-        }
-    } else if (b < n_gru_blocks + n_frame_blocks) {
-        mfcc_frame_tasks<R, SH, true, !PROJ>(m, t, smem, (b - n_gru_blocks) * kFrameWaves, n_frame_blocks * kFrameWaves, CW && MW && (frames_first & kBySimd));
-    } else {
-        mfcc_book_tile<R>(m, b - n_gru_blocks - n_frame_blocks);
-    }
-}
-template <class R, class SH, int RG, bool MW, bool PROJ, bool CW = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) void fused_update_kernel(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                           const int n_gru_blocks, const int n_frame_blocks, const int n_tiles, const int frames_first) {
-    fused_update_body<R, SH, RG, MW, PROJ, CW>(m, t, g, n_gru_blocks, n_frame_blocks, n_tiles, frames_first);
-}
-// (R = float: the float32 network role inside loses its packed gate arithmetic too -- 16.2 vs 15.7 us per fused update at 4096
-//  streams for the float32 front end + float32 network, which is no BASELINE configuration; the headline kernel is R = double)
-template <class R, class SH, int RG, bool MW, bool PROJ, bool CW = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) PE_NO_PK_F32 void fused_update_kernel_nopk(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                           const int n_gru_blocks, const int n_frame_blocks, const int n_tiles, const int frames_first) {
-    fused_update_body<R, SH, RG, MW, PROJ, CW>(m, t, g, n_gru_blocks, n_frame_blocks, n_tiles, frames_first);
-}
-
-// ---- the fused update of a K-model engine (pe_create_models): K network roles beside ONE frame role and ONE bookkeeping
-// role.  The network workgroups are the one-model launch's, n_gru_blocks per model, model-major: workgroup b of the network
-// runs block b % n_gru_blocks of model b / n_gru_blocks with that model's weights (ModelSet) and writes that model's block
-// of the output.  The network roles only READ the ring and the records (the frame and bookkeeping roles write rows and
-// record sides no window of this launch reads, §4.5), so K of them are as independent as one.  No input projection rows
-// (pe_set_input_projection refuses K > 1: the rows are per model).
-template <class R, class SH, int RG, bool MW, bool CW>
-__device__ __forceinline__ void fused_update_models_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ModelSet& ms,
-                                                         const int n_gru_blocks, const int n_models, const int n_frame_blocks,
-                                                         const int n_tiles, const int frames_first) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    touch_kernel_arguments<(int)(sizeof(MfccStreamArgs<R>) + sizeof(WaveTables<R>) + sizeof(GruArgs) + 20)>();
-    const int n_net = n_gru_blocks * n_models;
-    const int b = role_block(blockIdx.x, n_net, n_frame_blocks, frames_first & kFramesFirst);
-    if (b < n_net) {
-        const int mi = __builtin_amdgcn_readfirstlane(b / n_gru_blocks);
-        const int bl = b - mi * n_gru_blocks;
-        const GruArgs gm = model_args(g, ms.net[mi], mi, g.n_streams);
-        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        __builtin_amdgcn_s_setprio(3);
-        int role = wave;
-        if (CW && MW && (frames_first & kBySimd)) {
-            int* const slot = reinterpret_cast<int*>(smem) + kCwRoleSlot;
-            const int simd = wave_simd_id();
-            if ((threadIdx.x & 63) == 0) slot[wave] = simd;
-            __syncthreads();
-            if (((1 << slot[0]) | (1 << slot[1]) | (1 << slot[2]) | (1 << slot[3])) == 15) role = simd;
-        }
-        if constexpr (CW) {
-            static_assert(RG == 5, "the re-tiled shapes exist for the stock width");
-            if (MW) {
                 gru_tile_cw<false>(gm, bl, role, threadIdx.x & 63, reinterpret_cast<float*>(smem));
             } else {
-                const int tile = bl * 4 + wave;       // (no delta inputs on this shape: the launcher keeps four waves for use_delta)
+                const int tile = bl * 4 + wave;       // (use_delta on this shape: two launches, engine.hip can_fuse; K models: four waves)
                 if (tile < n_tiles) gru_tile_v<kRing, false>(gm, tile, threadIdx.x & 63);
             }
         } else if (MW) {
-            gru_tile_mw_any<RG, false>(gm, bl, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+            gru_tile_mw_any<RG, PROJ>(gm, bl, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
         } else {
             const int tile = bl * 4 + wave;
-            if (tile < n_tiles) gru_tile<RG, kRing, false>(gm, tile, threadIdx.x & 63);
+            if (tile < n_tiles) gru_tile<RG, kRing, PROJ>(gm, tile, threadIdx.x & 63);
         }
     } else if (b < n_net + n_frame_blocks) {
-        mfcc_frame_tasks<R, SH, true, true>(m, t, smem, (b - n_net) * kFrameWaves, n_frame_blocks * kFrameWaves, CW && MW && (frames_first & kBySimd));
+        mfcc_frame_tasks<R, SH, true, !PROJ>(m, t, smem, (b - n_net) * kFrameWaves, n_frame_blocks * kFrameWaves, CW && MW && (frames_first & kBySimd));
     } else {
         mfcc_book_tile<R>(m, b - n_net - n_frame_blocks);
     }
-}
-// (the integers first: they sit in the argument lines the prologue touches; the ModelSet behind them is read once the model is known)
-template <class R, class SH, int RG, bool MW, bool CW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) void fused_update_models_kernel(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                                  const int n_gru_blocks, const int n_models, const int n_frame_blocks,
-                                                                  const int n_tiles, const int frames_first, const ModelSet ms) {
-    fused_update_models_body<R, SH, RG, MW, CW>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
-}
-template <class R, class SH, int RG, bool MW, bool CW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) PE_NO_PK_F32 void fused_update_models_kernel_nopk(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                                  const int n_gru_blocks, const int n_models, const int n_frame_blocks,
-                                                                  const int n_tiles, const int frames_first, const ModelSet ms) {
-    fused_update_models_body<R, SH, RG, MW, CW>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
-}
-// ... and with the bf16 network role (four tiles per network workgroup, one wave each)
-template <class R, class SH, bool DELTA, bool RB>
-__device__ __forceinline__ void fused_update_bf16_models_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ModelSet& ms,
-                                                              const int n_gru_blocks, const int n_models, const int n_frame_blocks, const int n_tiles,
-                                                              const int frames_first) {
-    touch_kernel_arguments<(int)(sizeof(MfccStreamArgs<R>) + sizeof(WaveTables<R>) + sizeof(GruArgs) + 20)>();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tpw = frames_first >> 8;
-    const int n_net = n_gru_blocks * n_models;
-    const int b = role_block(blockIdx.x, n_net, n_frame_blocks, frames_first & 1);
-    if (b < n_net) {
-        const int mi = __builtin_amdgcn_readfirstlane(b / n_gru_blocks);
-        const int bl = b - mi * n_gru_blocks;
-        const GruArgs gm = model_args(g, ms.net[mi], mi, g.n_streams);
-        const int wave = threadIdx.x >> 6;
-        const int tile = bl * tpw + wave;
-        if (wave < tpw && tile < n_tiles) {
-            if (gm.b20) { gru_tile_b20<kRing, DELTA, RB>(gm, tile, threadIdx.x & 63); return; }
-            gru_tile_bf16<kRing, DELTA, RB>(gm, tile, threadIdx.x & 63);
-        }
-    } else if (b < n_net + n_frame_blocks) {
-        mfcc_frame_tasks<R, SH, true>(m, t, smem, (b - n_net) * kFrameWaves, n_frame_blocks * kFrameWaves);
-    } else {
-        mfcc_book_tile<R>(m, b - n_net - n_frame_blocks);
-    }
-}
-template <class R, class SH, bool DELTA, bool RB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) void fused_update_bf16_models_kernel(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                                       const int n_gru_blocks, const int n_models, const int n_frame_blocks,
-                                                                       const int n_tiles, const int frames_first, const ModelSet ms) {
-    fused_update_bf16_models_body<R, SH, DELTA, RB>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
-}
-template <class R, class SH, bool DELTA, bool RB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PE_FRAME_WPE))) PE_NO_PK_F32 void fused_update_bf16_models_kernel_nopk(const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g,
-                                                                       const int n_gru_blocks, const int n_models, const int n_frame_blocks,
-                                                                       const int n_tiles, const int frames_first, const ModelSet ms) {
-    fused_update_bf16_models_body<R, SH, DELTA, RB>(m, t, g, ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first);
 }
 
-// ---- the network of a K-model engine in ONE launch, every shape of the launchers below: NET names the one-model kernel's
-// tile function; workgroup b runs block b % per_model of model b / per_model (model-major outputs, out_stride apart)
-template <int R, int MODE, bool PROJ, int KX> struct NetSmall {          // gru_small_kernel / gru_many_kernel
-    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
-    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile<R, MODE, PROJ, KX>(a, tile, threadIdx.x); }
-};
-template <int R, bool PROJ, int KX> struct NetMw {                       // gru_mw_kernel / gru_many_mw_kernel
-    static constexpr int kThreads = 256; static constexpr size_t kLds = (3 * R * 64 + 256) * sizeof(float);
-    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char* smem) {
-        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        gru_tile_mw_any<R, PROJ, KX>(a, tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
-    }
-};
-template <int MODE, bool DELTA> struct NetV {                            // gru_v_kernel / gru_many_v_kernel
-    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
-    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile_v<MODE, DELTA>(a, tile, threadIdx.x); }
-};
-struct NetCw {                                                           // gru_cw_kernel / gru_many_cw_kernel
-    static constexpr int kThreads = 256; static constexpr size_t kLds = kCwLdsBytes;
-    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char* smem) {
-        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        gru_tile_cw<false>(a, tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
-    }
-};
-template <int MODE, bool DELTA, bool RB> struct NetBf16 {                // gru_bf16_kernel / gru_many_bf16_kernel
-    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
-    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) {
-        if (a.b20) { gru_tile_b20<MODE, DELTA, RB>(a, tile, threadIdx.x); return; }
-        gru_tile_bf16<MODE, DELTA, RB>(a, tile, threadIdx.x);
-    }
-};
-template <int MODE> struct NetX3 {                                       // gru_x3_kernel / gru_many_x3_kernel
-    static constexpr int kThreads = 64; static constexpr size_t kLds = 0;
-    static __device__ __forceinline__ void run(const GruArgs& a, int tile, unsigned char*) { gru_tile_x3<MODE>(a, tile, threadIdx.x); }
-};
-template <class NET>
-__global__ __launch_bounds__(NET::kThreads) void gru_models_kernel(const GruArgs a, const ModelSet ms, const int per_model, const long long out_stride) {
-    touch_kernel_arguments<(int)sizeof(GruArgs)>();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int mi = __builtin_amdgcn_readfirstlane(blockIdx.x / per_model);
-    NET::run(model_args(a, ms.net[mi], mi, out_stride), blockIdx.x - mi * per_model, smem);
-}
-// pe_update_many: (model, update, tile) per workgroup, outputs [K][n_updates][windows]
-template <class NET>
-__global__ __launch_bounds__(NET::kThreads) void gru_many_models_kernel(const GruArgs a, const ModelSet ms, const int n_tiles, const int n_updates, const int n_padded) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int per_model = n_tiles * n_updates;
-    const int mi = __builtin_amdgcn_readfirstlane(blockIdx.x / per_model);
-    const int w = blockIdx.x - mi * per_model;
-    const int u = w / n_tiles, tile = w % n_tiles;
-    GruArgs b = model_args(a, ms.net[mi], mi, (long long)n_updates * a.n_streams);
-    b.ke_plain = a.ke_plain + (size_t)u * n_padded;      // row u of the emitted-frame history
-    b.out += (size_t)u * a.n_streams;
-    b.predict_ke = 0;
-    NET::run(b, tile, smem);
-}
-// what the launchers below take for a K-model engine (ms == null: the one-model kernels)
-struct NetModels { const ModelSet* ms; int n; long long out_stride; };
-// one network launch: KERNEL over GRID workgroups (one model), or gru_models_kernel<NET> over GRID x K
-#define PE_NET(NET, KERNEL, GRID, THREADS, LDS)                                                                              \
-    do {                                                                                                                     \
-        if (mm.ms) hipLaunchKernelGGL((gru_models_kernel<PE_UNPAREN NET>), dim3((GRID) * mm.n), dim3(THREADS), (PE_UNPAREN NET::kLds), s, a, *mm.ms, (int)(GRID), mm.out_stride); \
-        else hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(THREADS), LDS, s, a);                                              \
-    } while (0)
-#define PE_NET_MANY(NET, KERNEL, TILES, THREADS, LDS)                                                                        \
-    do {                                                                                                                     \
-        if (mm.ms) hipLaunchKernelGGL((gru_many_models_kernel<PE_UNPAREN NET>), dim3((TILES) * n_updates * mm.n), dim3(THREADS), (PE_UNPAREN NET::kLds), s, a, *mm.ms, (TILES), n_updates, n_padded); \
-        else hipLaunchKernelGGL(KERNEL, dim3((TILES) * n_updates), dim3(THREADS), LDS, s, a, (TILES), n_padded);           \
-    } while (0)
+// The entry points: thin wrappers.  (R = float: the float32 network role inside loses its packed gate arithmetic too -- 16.2 vs
+// 15.7 us per fused update at 4096 streams for the float32 front end + float32 network, which is no BASELINE configuration;
+// the headline kernel is R = double.)  K models: the integers first -- they sit in the argument lines the prologue touches.
+#define PE_FUSED_PARAMS (const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g, const int n_gru_blocks, const int n_frame_blocks, const int n_tiles, const int frames_first)
+#define PE_FUSED_MODELS_PARAMS (const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g, const int n_gru_blocks, const int n_models, const int n_frame_blocks, \
+                                const int n_tiles, const int frames_first, const ModelSet ms)
+PE_KERNEL_PAIR((template <class R, class SH, bool DELTA, bool RB>), PE_FRAME_KERNEL(256, PE_FRAME_WPE), fused_update_bf16_kernel, PE_FUSED_PARAMS,
+               { fused_update_bf16_body<R, SH, DELTA, RB, false>(m, t, g, nullptr, n_gru_blocks, 1, n_frame_blocks, n_tiles, frames_first); })
+PE_KERNEL_PAIR((template <class R, class SH, bool DELTA, bool RB>), PE_FRAME_KERNEL(256, PE_FRAME_WPE), fused_update_bf16_models_kernel, PE_FUSED_MODELS_PARAMS,
+               { fused_update_bf16_body<R, SH, DELTA, RB, true>(m, t, g, &ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first); })
+PE_KERNEL_PAIR((template <class R, class SH, int RG, bool MW, bool PROJ, bool CW = false>), PE_FRAME_KERNEL(256, PE_FRAME_WPE), fused_update_kernel, PE_FUSED_PARAMS,
+               { fused_update_body<R, SH, RG, MW, PROJ, CW, false>(m, t, g, nullptr, n_gru_blocks, 1, n_frame_blocks, n_tiles, frames_first); })
+PE_KERNEL_PAIR((template <class R, class SH, int RG, bool MW, bool CW>), PE_FRAME_KERNEL(256, PE_FRAME_WPE), fused_update_models_kernel, PE_FUSED_MODELS_PARAMS,
+               { fused_update_body<R, SH, RG, MW, false, CW, true>(m, t, g, &ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first); })
 
 
 // Workgroups of the frame role: one wave per task while that fits the machine (4 workgroups of 4 waves per compute
@@ -590,7 +493,6 @@ static hipError_t launch_mfcc(const MfccStreamArgs<R>& a, const WaveTables<R>& t
     }
     return hipGetLastError();
 }
-// four frames per wave: the frame role of ONE update of a stock-shape engine whose geometry allows dword sample pairs
 hipError_t launch_mfcc_f64(const MfccStreamArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s) { return launch_mfcc<double>(a, t, n_cus, s); }
 hipError_t launch_mfcc_f32(const MfccStreamArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s) { return launch_mfcc<float>(a, t, n_cus, s); }
 
@@ -613,33 +515,25 @@ static hipError_t launch_r(const GruArgs& a, int mode, hipStream_t s, const NetM
     if (mm.ms && a.proj_ring) return hipErrorInvalidValue;        // (input projection rows are per model: refused for K > 1)
     const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
     if (tiles == 0) return hipSuccess;
+    bool ok = true;
     if (a.row_floats == 2 * kRowFloats) {           // 17..32 coefficients per frame: 32-float rows
-        if constexpr (R == 5) {                     // (stock width, few tiles: four waves per tile, as the 16-float rows get)
-            if (mode == kRing && a.waves_per_tile == 4) {
-                // (K models: the one-wave twin -- the same form, the same bits; a second caller of gru_tile_mw_any<5, false, 2> would
-                //  change the code generated for gru_mw_kernel<5, false, 2>)
-                if (mm.ms) PE_NET((NetSmall<R, kRing, false, 2>), (gru_small_kernel<R, kRing, false, 2>), tiles, 64, 0);
-                else hipLaunchKernelGGL((gru_mw_kernel<R, false, 2>), dim3(tiles), dim3(256), 0, s, a);
+        // (stock width, few tiles: four waves per tile, as the 16-float rows get.  K models: the one-wave twin -- the same form,
+        //  the same bits; a second caller of gru_tile_mw_any<5, false, 2> changes the code generated for gru_mw_kernel<5, false, 2>)
+        if constexpr (R == 5) {
+            if (mode == kRing && a.waves_per_tile == 4 && !mm.ms) {
+                hipLaunchKernelGGL((gru_mw_kernel<R, false, 2>), dim3(tiles), dim3(256), 0, s, a);
                 return hipGetLastError();
             }
         }
-        if (mode == kRing) PE_NET((NetSmall<R, kRing, false, 2>), (gru_small_kernel<R, kRing, false, 2>), tiles, 64, 0);
-        else if (mode == kRows) PE_NET((NetSmall<R, kRows, false, 2>), (gru_small_kernel<R, kRows, false, 2>), tiles, 64, 0);
-        else PE_NET((NetSmall<R, kFeats, false, 2>), (gru_small_kernel<R, kFeats, false, 2>), tiles, 64, 0);
-        return hipGetLastError();
+        ok = with_mode(mode, [&](auto M) { PE_NET((NetSmall<R, PE_CONST(M), false, 2>), (gru_small_kernel<R, PE_CONST(M), false, 2>), tiles); });
+        return ok ? hipGetLastError() : hipErrorInvalidValue;
     }
     if constexpr (R == 5) {
         if (a.cw) {
-            if (mode == kRing && a.waves_per_tile == 4 && cw_four_waves_ok(a)) PE_NET((NetCw), gru_cw_kernel, tiles, 256, kCwLdsBytes);
-            else if (a.use_delta) {
-                if (mode == kRing) PE_NET((NetV<kRing, true>), (gru_v_kernel<kRing, true>), tiles, 64, 0);
-                else if (mode == kRows) PE_NET((NetV<kRows, true>), (gru_v_kernel<kRows, true>), tiles, 64, 0);
-                else PE_NET((NetV<kFeats, true>), (gru_v_kernel<kFeats, true>), tiles, 64, 0);
-            }
-            else if (mode == kRing) PE_NET((NetV<kRing, false>), (gru_v_kernel<kRing, false>), tiles, 64, 0);
-            else if (mode == kRows) PE_NET((NetV<kRows, false>), (gru_v_kernel<kRows, false>), tiles, 64, 0);
-            else PE_NET((NetV<kFeats, false>), (gru_v_kernel<kFeats, false>), tiles, 64, 0);
-            return hipGetLastError();
+            if (mode == kRing && a.waves_per_tile == 4 && cw_four_waves_ok(a)) PE_NET((NetCw), gru_cw_kernel, tiles);
+            else ok = with_mode(mode, [&](auto M) { with_flag(a.use_delta, [&](auto D) {
+                PE_NET((NetV<PE_CONST(M), PE_CONST(D)>), (gru_v_kernel<PE_CONST(M), PE_CONST(D)>), tiles); }); });
+            return ok ? hipGetLastError() : hipErrorInvalidValue;
         }
         if (mode == kRing && a.proj_ring) {
             if (a.waves_per_tile == 4) hipLaunchKernelGGL((gru_mw_kernel<R, true>), dim3(tiles), dim3(256), 0, s, a);
@@ -647,51 +541,28 @@ static hipError_t launch_r(const GruArgs& a, int mode, hipStream_t s, const NetM
             return hipGetLastError();
         }
     }
-    if (mode == kRing && a.waves_per_tile == 4) PE_NET((NetMw<R, false, 1>), (gru_mw_kernel<R>), tiles, 256, 0);
-    else if (mode == kRing) PE_NET((NetSmall<R, kRing, false, 1>), (gru_small_kernel<R, kRing>), tiles, 64, 0);
-    else if (mode == kRows) PE_NET((NetSmall<R, kRows, false, 1>), (gru_small_kernel<R, kRows>), tiles, 64, 0);
-    else PE_NET((NetSmall<R, kFeats, false, 1>), (gru_small_kernel<R, kFeats>), tiles, 64, 0);
-    return hipGetLastError();
+    if (mode == kRing && a.waves_per_tile == 4) PE_NET((NetMw<R, false, 1>), (gru_mw_kernel<R>), tiles);
+    else ok = with_mode(mode, [&](auto M) { PE_NET((NetSmall<R, PE_CONST(M), false, 1>), (gru_small_kernel<R, PE_CONST(M)>), tiles); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-hipError_t launch_gru_small(const GruArgs& a, int from_ring, hipStream_t s, const ModelSet* ms, int n_models, long long out_stride) {
+hipError_t launch_gru_small(const GruArgs& a, int mode, hipStream_t s, const ModelSet* ms, int n_models, long long out_stride) {
     const NetModels mm{ms, n_models, out_stride};
     if (ms && (n_models < 1 || n_models > kMaxModels)) return hipErrorInvalidValue;
-    if (a.x3) {
+    if (a.x3 || a.bf16) {
         const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
         if (tiles == 0) return hipSuccess;
-        if (from_ring == kRing) PE_NET((NetX3<kRing>), gru_x3_kernel<kRing>, tiles, 64, 0);
-        else if (from_ring == kRows) PE_NET((NetX3<kRows>), gru_x3_kernel<kRows>, tiles, 64, 0);
-        else PE_NET((NetX3<kFeats>), gru_x3_kernel<kFeats>, tiles, 64, 0);
-        return hipGetLastError();
+        bool ok = true;
+        if (a.x3) ok = with_mode(mode, [&](auto M) { PE_NET((NetX3<PE_CONST(M)>), gru_x3_kernel<PE_CONST(M)>, tiles); });
+        else with_flag(a.use_delta, [&](auto D) {          // (bf16 rows: read from the ring only)
+            if (mode == kRing && a.ring_bf16) PE_NET((NetBf16<kRing, PE_CONST(D), true>), (gru_bf16_kernel<kRing, PE_CONST(D), true>), tiles);
+            else ok = with_mode(mode, [&](auto M) { PE_NET((NetBf16<PE_CONST(M), PE_CONST(D), false>), (gru_bf16_kernel<PE_CONST(M), PE_CONST(D)>), tiles); });
+        });
+        return ok ? hipGetLastError() : hipErrorInvalidValue;
     }
-    if (a.bf16) {
-        const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
-        if (tiles == 0) return hipSuccess;
-        if (a.use_delta) {
-            if (from_ring == kRing && a.ring_bf16) PE_NET((NetBf16<kRing, true, true>), (gru_bf16_kernel<kRing, true, true>), tiles, 64, 0);
-            else if (from_ring == kRing) PE_NET((NetBf16<kRing, true, false>), (gru_bf16_kernel<kRing, true>), tiles, 64, 0);
-            else if (from_ring == kRows) PE_NET((NetBf16<kRows, true, false>), (gru_bf16_kernel<kRows, true>), tiles, 64, 0);
-            else PE_NET((NetBf16<kFeats, true, false>), (gru_bf16_kernel<kFeats, true>), tiles, 64, 0);
-        } else {
-            if (from_ring == kRing && a.ring_bf16) PE_NET((NetBf16<kRing, false, true>), (gru_bf16_kernel<kRing, false, true>), tiles, 64, 0);
-            else if (from_ring == kRing) PE_NET((NetBf16<kRing, false, false>), (gru_bf16_kernel<kRing, false>), tiles, 64, 0);
-            else if (from_ring == kRows) PE_NET((NetBf16<kRows, false, false>), (gru_bf16_kernel<kRows, false>), tiles, 64, 0);
-            else PE_NET((NetBf16<kFeats, false, false>), (gru_bf16_kernel<kFeats, false>), tiles, 64, 0);
-        }
-        return hipGetLastError();
-    }
-    switch (gru_small_regs(a.units)) {
-        case 1: return launch_r<1>(a, from_ring, s, mm);
-        case 2: return launch_r<2>(a, from_ring, s, mm);
-        case 3: return launch_r<3>(a, from_ring, s, mm);
-        case 4: return launch_r<4>(a, from_ring, s, mm);
-        case 5: return launch_r<5>(a, from_ring, s, mm);
-        case 6: return launch_r<6>(a, from_ring, s, mm);
-        case 7: return launch_r<7>(a, from_ring, s, mm);
-        case 8: return launch_r<8>(a, from_ring, s, mm);
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t err = hipErrorInvalidValue;
+    with_const<1, 2, 3, 4, 5, 6, 7, 8>(gru_small_regs(a.units), [&](auto R) { err = launch_r<PE_CONST(R)>(a, mode, s, mm); });
+    return err;
 }
 
 template <int R>
@@ -704,9 +575,8 @@ static hipError_t launch_many_r(const GruArgs& a, int n_updates, int n_padded, h
     const bool mw = few && !a.use_delta;       // (classic tiling: the delta inputs are on the one-wave kernel only)
     if constexpr (R == 5) {
         if (a.cw) {
-            if (few && cw_four_waves_ok(a)) PE_NET_MANY((NetCw), gru_many_cw_kernel, tiles, 256, kCwLdsBytes);
-            else if (a.use_delta) PE_NET_MANY((NetV<kRing, true>), gru_many_v_kernel<true>, tiles, 64, 0);
-            else PE_NET_MANY((NetV<kRing, false>), gru_many_v_kernel<false>, tiles, 64, 0);
+            if (few && cw_four_waves_ok(a)) PE_NET_MANY((NetCw), gru_many_cw_kernel, tiles);
+            else with_flag(a.use_delta, [&](auto D) { PE_NET_MANY((NetV<kRing, PE_CONST(D)>), gru_many_v_kernel<PE_CONST(D)>, tiles); });
             return hipGetLastError();
         }
         if (a.proj_ring) {
@@ -715,8 +585,8 @@ static hipError_t launch_many_r(const GruArgs& a, int n_updates, int n_padded, h
             return hipGetLastError();
         }
     }
-    if (mw) PE_NET_MANY((NetMw<R, false, 1>), (gru_many_mw_kernel<R, false>), tiles, 256, 0);
-    else PE_NET_MANY((NetSmall<R, kRing, false, 1>), (gru_many_kernel<R, false>), tiles, 64, 0);
+    if (mw) PE_NET_MANY((NetMw<R, false, 1>), (gru_many_mw_kernel<R, false>), tiles);
+    else PE_NET_MANY((NetSmall<R, kRing, false, 1>), (gru_many_kernel<R, false>), tiles);
     return hipGetLastError();
 }
 
@@ -726,27 +596,17 @@ hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStr
     const int tiles = (a.n_streams + kTileStreams - 1) / kTileStreams;
     if (tiles == 0 || n_updates == 0) return hipSuccess;
     if (a.x3) {
-        PE_NET_MANY((NetX3<kRing>), gru_many_x3_kernel, tiles, 64, 0);
+        PE_NET_MANY((NetX3<kRing>), gru_many_x3_kernel, tiles);
         return hipGetLastError();
     }
     if (a.bf16) {
-        if (a.use_delta && a.ring_bf16) PE_NET_MANY((NetBf16<kRing, true, true>), (gru_many_bf16_kernel<true, true>), tiles, 64, 0);
-        else if (a.use_delta) PE_NET_MANY((NetBf16<kRing, true, false>), (gru_many_bf16_kernel<true, false>), tiles, 64, 0);
-        else if (a.ring_bf16) PE_NET_MANY((NetBf16<kRing, false, true>), (gru_many_bf16_kernel<false, true>), tiles, 64, 0);
-        else PE_NET_MANY((NetBf16<kRing, false, false>), (gru_many_bf16_kernel<false, false>), tiles, 64, 0);
+        with_flag(a.use_delta, [&](auto D) { with_flag(a.ring_bf16, [&](auto RB) {
+            PE_NET_MANY((NetBf16<kRing, PE_CONST(D), PE_CONST(RB)>), (gru_many_bf16_kernel<PE_CONST(D), PE_CONST(RB)>), tiles); }); });
         return hipGetLastError();
     }
-    switch (gru_small_regs(a.units)) {
-        case 1: return launch_many_r<1>(a, n_updates, n_padded, s, mm);
-        case 2: return launch_many_r<2>(a, n_updates, n_padded, s, mm);
-        case 3: return launch_many_r<3>(a, n_updates, n_padded, s, mm);
-        case 4: return launch_many_r<4>(a, n_updates, n_padded, s, mm);
-        case 5: return launch_many_r<5>(a, n_updates, n_padded, s, mm);
-        case 6: return launch_many_r<6>(a, n_updates, n_padded, s, mm);
-        case 7: return launch_many_r<7>(a, n_updates, n_padded, s, mm);
-        case 8: return launch_many_r<8>(a, n_updates, n_padded, s, mm);
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t err = hipErrorInvalidValue;
+    with_const<1, 2, 3, 4, 5, 6, 7, 8>(gru_small_regs(a.units), [&](auto R) { err = launch_many_r<PE_CONST(R)>(a, n_updates, n_padded, s, mm); });
+    return err;
 }
 
 // The network shape of the K-model fused launch (stock width, form 1), from (K, tiles).  The four-wave workgroup of one tile
@@ -756,10 +616,22 @@ hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStr
 // one after the other in fewer workgroups was measured too and never won).
 static bool fused_models_four_waves(int n_models, int tiles, int n_cus) { return (long long)n_models * tiles <= 2LL * n_cus; }
 
-// ms != null: the K-model launch (fused_update_models_kernel) -- the same shape with n_models network roles
+// what a fused launch is made of once its network shape is known: GB network workgroups per model, then fb frame workgroups,
+// then one bookkeeping workgroup per tile; ms != null: the K-model entry point, the same shape with n_models network roles
+struct FusedLaunch { const ModelSet* ms; int n_models, fb, tiles; hipStream_t s; };
+#define PE_FUSED(KERNEL, MODELS_KERNEL, TARGS, MODELS_TARGS, GB, LDS, FF)                                                    \
+    do {                                                                                                                     \
+        if (f.ms) PE_LAUNCH_R(R, MODELS_KERNEL, MODELS_TARGS, dim3((GB) * f.n_models + f.fb + f.tiles), dim3(256), LDS, f.s, m, t, g, GB, f.n_models, f.fb, f.tiles, FF, *f.ms); \
+        else PE_LAUNCH_R(R, KERNEL, TARGS, dim3((GB) + f.fb + f.tiles), dim3(256), LDS, f.s, m, t, g, GB, f.fb, f.tiles, FF); \
+    } while (0)
+// float32 network role <MW, PROJ, CW> of RG registers per gate
+#define PE_FUSED_F32(MW, PROJ, CW, GB, LDS, FF) \
+    PE_FUSED(fused_update_kernel, fused_update_models_kernel, (ShapeStock, RG, MW, PROJ, CW), (ShapeStock, RG, MW, CW), GB, LDS, FF)
+
 template <class R, int RG>
 static hipError_t launch_fused_rg(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, int n_cus, hipStream_t s,
-                                  const ModelSet* ms = nullptr, int n_models = 1) {
+                                  const ModelSet* ms, int n_models) {
+    if (ms && g.proj_ring) return hipErrorInvalidValue;       // (input projection rows are per model: refused for K > 1)
     const int tiles = (m.geo.n_streams + kTileStreams - 1) / kTileStreams;
     const size_t lds = frame_lds(t);
     // more network workgroups than the machine holds at once: frames first, three frame workgroups per CU, the network
@@ -774,57 +646,35 @@ static hipError_t launch_fused_rg(const MfccStreamArgs<R>& m, const WaveTables<R
     // disturb that chain less than four (measured, 4096 streams: 20.6 vs 20.9 us in phase, 21.1 vs 22.5 us with
     // desynchronised streams); larger batches want every wave slot
     const int fb = stream_frame_blocks(m.geo.n_streams, n_cus, tiles <= n_cus ? 2 : (frames_first & kFramesFirst) ? 3 : 4);
-    const int gru_blocks = g.waves_per_tile == 4 ? tiles : (tiles + 3) / 4;
-    const int fb_ = fb, book = tiles;
-    const dim3 grid(gru_blocks + fb_ + book);
-    if (ms) {
-        if (g.proj_ring) return hipErrorInvalidValue;       // (input projection rows are per model: refused for K > 1)
-        const dim3 mgrid(gru_blocks * n_models + fb_ + book);
-        if constexpr (RG == 5) {
-            if (g.cw) {
-                // (use_delta: four waves -- the one-wave fused shape has no delta inputs, as for one model, engine.hip can_fuse)
-                if ((g.use_delta || fused_models_four_waves(n_models, tiles, n_cus)) && g.waves_per_tile == 4 && cw_four_waves_ok(g)) {
-                    PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, true, true), mgrid, dim3(256), lds > kCwLdsBytes ? lds : kCwLdsBytes, s, m, t, g, gru_blocks, n_models, fb_, tiles, frames_first, *ms);
-                } else {                             // the one-wave shape (gru_tile_v, same form, same bits): no LDS of its own
-                    const int gb = (tiles + 3) / 4;
-                    PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, false, true), dim3(gb * n_models + fb_ + book), dim3(256), lds, s, m, t, g, gb, n_models, fb_, tiles, frames_first & ~kBySimd, *ms);
-                }
-                return hipGetLastError();
-            }
-        }
-        if (g.waves_per_tile == 4) PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, true, false), mgrid, dim3(256), lds, s, m, t, g, gru_blocks, n_models, fb_, tiles, frames_first, *ms);
-        else if constexpr (RG <= 5) PE_LAUNCH_R(R, fused_update_models_kernel, (ShapeStock, RG, false, false), mgrid, dim3(256), lds, s, m, t, g, gru_blocks, n_models, fb_, tiles, frames_first, *ms);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
+    const FusedLaunch f{ms, n_models, fb, tiles, s};
+    const int one_per_tile = tiles, four_per_block = (tiles + 3) / 4;       // network workgroups: four waves per tile / one wave per tile
     if constexpr (RG == 5) {
-        if (g.cw) {                          // stock width, re-tiled: the four-wave shape wants its LDS (mailboxes + staged ring)
-            if (g.waves_per_tile == 4 && cw_four_waves_ok(g)) {
-                PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, true, false, true), grid, dim3(256), lds > kCwLdsBytes ? lds : kCwLdsBytes, s, m, t, g, gru_blocks, fb_, tiles, frames_first);
-            } else {
-                const int gb = (tiles + 3) / 4;
-                PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, false, false, true), dim3(gb + fb_ + book), dim3(256), lds, s, m, t, g, gb, fb_, tiles, frames_first);
-            }
+        if (g.cw) {
+            // stock width, re-tiled: the four-wave shape wants its LDS (mailboxes + staged ring).  K models: while it wins
+            // (fused_models_four_waves), and always with use_delta -- the one-wave fused shape (gru_tile_v, same form, same bits,
+            // no LDS of its own) has no delta inputs, as for one model (engine.hip can_fuse)
+            const bool four = g.waves_per_tile == 4 && cw_four_waves_ok(g) && (!ms || g.use_delta || fused_models_four_waves(n_models, tiles, n_cus));
+            if (four) PE_FUSED_F32(true, false, true, one_per_tile, lds > kCwLdsBytes ? lds : kCwLdsBytes, frames_first);
+            else PE_FUSED_F32(false, false, true, four_per_block, lds, frames_first & ~kBySimd);
+            return hipGetLastError();
+        }
+        if (g.proj_ring) {                   // (projection rows exist for the stock width only, and for one model)
+            if (g.waves_per_tile == 4) PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, true, true), dim3(one_per_tile + fb + tiles), dim3(256), lds, s, m, t, g, one_per_tile, fb, tiles, frames_first);
+            else PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, false, true), dim3(four_per_block + fb + tiles), dim3(256), lds, s, m, t, g, four_per_block, fb, tiles, frames_first);
             return hipGetLastError();
         }
     }
-    if constexpr (RG == 5) {                 // (projection rows exist for the stock width only)
-        if (g.proj_ring) {
-            if (g.waves_per_tile == 4) PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, true, true), grid, dim3(256), lds, s, m, t, g, gru_blocks, fb_, tiles, frames_first);
-            else PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, false, true), grid, dim3(256), lds, s, m, t, g, gru_blocks, fb_, tiles, frames_first);
-            return hipGetLastError();
-        }
-    }
-    if (g.waves_per_tile == 4) PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, true, false), grid, dim3(256), lds, s, m, t, g, gru_blocks, fb_, tiles, frames_first);
-    else if constexpr (RG <= 5) PE_LAUNCH_R(R, fused_update_kernel, (ShapeStock, RG, false, false), grid, dim3(256), lds, s, m, t, g, gru_blocks, fb_, tiles, frames_first);
+    if (g.waves_per_tile == 4) PE_FUSED_F32(true, false, false, one_per_tile, lds, frames_first);
+    else if constexpr (RG <= 5) PE_FUSED_F32(false, false, false, four_per_block, lds, frames_first);
     else return hipErrorInvalidValue;        // (21..32 units on the one-wave kernel: engine.hip takes two launches, can_fuse)
     return hipGetLastError();
 }
 
 // (the fused kernels are built for the stock table shape only: engine.hip falls back to two launches otherwise)
 template <class R>
-static hipError_t launch_fused(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, int n_cus, hipStream_t s,
-                               const ModelSet* ms = nullptr, int n_models = 1) {
+static hipError_t launch_fused_t(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, int n_cus, hipStream_t s,
+                                 const ModelSet* ms, int n_models) {
+    if (ms && (n_models < 1 || n_models > kMaxModels)) return hipErrorInvalidValue;
     if (t.L.mel_pad != ShapeStock::MEL || !blob_matches_shape(t)) return hipErrorInvalidValue;
     if (g.bf16) {
         const int tiles = (m.geo.n_streams + kTileStreams - 1) / kTileStreams;
@@ -832,58 +682,44 @@ static hipError_t launch_fused(const MfccStreamArgs<R>& m, const WaveTables<R>& 
         const int gru_blocks = (tiles + tpw - 1) / tpw;
         const int ff = tiles >= 4 * n_cus ? 1 : 0;
         const int frames_first = (ff & 1) | (tpw << 8);
-        const int fb = stream_frame_blocks(m.geo.n_streams, n_cus, ff ? 3 : 4);
-        const int book = tiles;
-        const dim3 grid(gru_blocks + fb + book);
-        if (ms) {
-            const dim3 mgrid(gru_blocks * n_models + fb + book);
-            if (g.use_delta && g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, true, true), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
-            else if (g.use_delta) PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, true, false), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
-            else if (g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, false, true), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
-            else PE_LAUNCH_R(R, fused_update_bf16_models_kernel, (ShapeStock, false, false), mgrid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, n_models, fb, tiles, frames_first, *ms);
-            return hipGetLastError();
-        }
-        if (g.use_delta && g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_kernel, (ShapeStock, true, true), grid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, fb, tiles, frames_first);
-        else if (g.use_delta) PE_LAUNCH_R(R, fused_update_bf16_kernel, (ShapeStock, true, false), grid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, fb, tiles, frames_first);
-        else if (g.ring_bf16) PE_LAUNCH_R(R, fused_update_bf16_kernel, (ShapeStock, false, true), grid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, fb, tiles, frames_first);
-        else PE_LAUNCH_R(R, fused_update_bf16_kernel, (ShapeStock, false, false), grid, dim3(256), frame_lds(t), s, m, t, g, gru_blocks, fb, tiles, frames_first);
+        const FusedLaunch f{ms, n_models, stream_frame_blocks(m.geo.n_streams, n_cus, ff ? 3 : 4), tiles, s};
+        with_flag(g.use_delta, [&](auto D) { with_flag(g.ring_bf16, [&](auto RB) {
+            PE_FUSED(fused_update_bf16_kernel, fused_update_bf16_models_kernel, (ShapeStock, PE_CONST(D), PE_CONST(RB)), (ShapeStock, PE_CONST(D), PE_CONST(RB)),
+                     gru_blocks, frame_lds(t), frames_first); }); });
         return hipGetLastError();
     }
-    switch (gru_small_regs(g.units)) {
-        case 1: return launch_fused_rg<R, 1>(m, t, g, n_cus, s, ms, n_models);
-        case 2: return launch_fused_rg<R, 2>(m, t, g, n_cus, s, ms, n_models);
-        case 3: return launch_fused_rg<R, 3>(m, t, g, n_cus, s, ms, n_models);
-        case 4: return launch_fused_rg<R, 4>(m, t, g, n_cus, s, ms, n_models);
-        case 5: return launch_fused_rg<R, 5>(m, t, g, n_cus, s, ms, n_models);
-        case 6: return launch_fused_rg<R, 6>(m, t, g, n_cus, s, ms, n_models);
-        case 7: return launch_fused_rg<R, 7>(m, t, g, n_cus, s, ms, n_models);
-        case 8: return launch_fused_rg<R, 8>(m, t, g, n_cus, s, ms, n_models);
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t err = hipErrorInvalidValue;
+    with_const<1, 2, 3, 4, 5, 6, 7, 8>(gru_small_regs(g.units), [&](auto RG) { err = launch_fused_rg<R, PE_CONST(RG)>(m, t, g, n_cus, s, ms, n_models); });
+    return err;
 }
 
-hipError_t launch_fused_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, int n_cus, hipStream_t s) { return launch_fused<double>(m, t, g, n_cus, s); }
-hipError_t launch_fused_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s) { return launch_fused<float>(m, t, g, n_cus, s); }
-hipError_t launch_fused_models_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s) {
-    if (n_models < 1 || n_models > kMaxModels) return hipErrorInvalidValue;
-    return launch_fused<double>(m, t, g, n_cus, s, &ms, n_models);
+hipError_t launch_fused(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms, int n_models) {
+    return launch_fused_t<double>(m, t, g, n_cus, s, ms, n_models);
 }
-hipError_t launch_fused_models_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s) {
-    if (n_models < 1 || n_models > kMaxModels) return hipErrorInvalidValue;
-    return launch_fused<float>(m, t, g, n_cus, s, &ms, n_models);
+hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms, int n_models) {
+    return launch_fused_t<float>(m, t, g, n_cus, s, ms, n_models);
 }
 
 // ---- general front end (mfcc_general_device.h): one wave per stream / per frame -------------------------------------
 // (<= 128 registers: four waves per SIMD -- a wave walks the LDS round trips of one frame at a time, the others hide them;
 //  BITS = log2(n_fft / 2): the per-lane loops of a frame are unrolled for the transform length)
 // (n_fft = 2048: 25 KB of LDS per wave in float64 leave six waves per compute unit anyway: no register cap there)
-template <class R, int BITS, bool BLUE = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) void mfcc_general_stream_kernel(const GeneralStreamArgs<R> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// float32 butterflies without packed float32 here too (round 6, advisor r5): the general front end may run beside the
+// five-values bf16 network of ANOTHER engine on the same compute unit, the combination whose stock-shape twin went wrong
+// with packed instructions (see PE_NO_PK_F32 above); tests/test_gpu_parity.py soaks it
 #ifndef PE_GEN_TWO_WAVES
 #define PE_GEN_TWO_WAVES 0      // two waves per stream (one per frame-row parity): measured SLOWER (62.6 vs 47.7 us per update at 4096 streams:
                                 // the launch is bound by rounds of resident waves, and this doubles the waves)
 #endif
+template <class R, int BITS, bool BLUE = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) void mfcc_general_stream_kernel(const GeneralStreamArgs<R> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int s = PE_GEN_TWO_WAVES ? blockIdx.x >> 1 : blockIdx.x;
+    if (s < a.geo.n_streams) general_stream<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), s, PE_GEN_TWO_WAVES ? blockIdx.x & 1 : 0, threadIdx.x, PE_GEN_TWO_WAVES ? 2 : 1);
+}
+template <class R, int BITS, bool BLUE = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) PE_NO_PK_F32 void mfcc_general_stream_kernel_nopk(const GeneralStreamArgs<R> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int s = PE_GEN_TWO_WAVES ? blockIdx.x >> 1 : blockIdx.x;
     if (s < a.geo.n_streams) general_stream<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), s, PE_GEN_TWO_WAVES ? blockIdx.x & 1 : 0, threadIdx.x, PE_GEN_TWO_WAVES ? 2 : 1);
 }
@@ -892,79 +728,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ?
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     general_offline<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), blockIdx.x, gridDim.x, threadIdx.x);
 }
-// float32 butterflies without packed float32 here too (round 6, advisor r5): the general front end may run beside the
-// five-values bf16 network of ANOTHER engine on the same compute unit, the combination whose stock-shape twin went wrong
-// with packed instructions (see PE_NO_PK_F32 above); tests/test_gpu_parity.py soaks it
-template <class R, int BITS, bool BLUE = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) PE_NO_PK_F32 void mfcc_general_stream_kernel_nopk(const GeneralStreamArgs<R> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int s = PE_GEN_TWO_WAVES ? blockIdx.x >> 1 : blockIdx.x;
-    if (s < a.geo.n_streams) general_stream<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), s, PE_GEN_TWO_WAVES ? blockIdx.x & 1 : 0, threadIdx.x, PE_GEN_TWO_WAVES ? 2 : 1);
-}
 template <class R, int BITS, bool BLUE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) PE_NO_PK_F32 void mfcc_general_offline_kernel_nopk(const GeneralOfflineArgs<R> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     general_offline<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), blockIdx.x, gridDim.x, threadIdx.x);
 }
-template <class R, int BITS, bool BLUE = false>
-static void launch_general_stream_b(const GeneralStreamArgs<R>& a, hipStream_t s) {
-    PE_LAUNCH_R(R, mfcc_general_stream_kernel, (BITS, BLUE), dim3((PE_GEN_TWO_WAVES ? 2 : 1) * (unsigned)a.geo.n_streams), dim3(64), general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds), s, a);
-}
-template <class R, int BITS, bool BLUE = false>
-static void launch_general_offline_b(const GeneralOfflineArgs<R>& a, unsigned blocks, hipStream_t s) {
-    PE_LAUNCH_R(R, mfcc_general_offline_kernel, (BITS, BLUE), dim3(blocks), dim3(64), general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds), s, a);
+// the transform length as a template argument: n_fft not a power of two (chirp) = Bluestein over L = 2^log2m points
+template <class F>
+static bool with_general_bits(const GeneralTables& tab, F&& f) {
+    if (tab.chirp) return with_const<7, 8, 9, 10, 11>(tab.log2m, [&](auto B) { f(B, std::true_type{}); });
+    return with_const<5, 6, 7, 8, 9, 10>(tab.log2m, [&](auto B) { f(B, std::false_type{}); });
 }
 template <class R>
 static hipError_t launch_general_stream_t(const GeneralStreamArgs<R>& a, hipStream_t s) {
     if (a.geo.n_streams == 0) return hipSuccess;
-    if (a.tab.chirp) {                      // n_fft not a power of two: Bluestein over L = 2^log2m points
-        switch (a.tab.log2m) {
-            case 7: launch_general_stream_b<R, 7, true>(a, s); break;
-            case 8: launch_general_stream_b<R, 8, true>(a, s); break;
-            case 9: launch_general_stream_b<R, 9, true>(a, s); break;
-            case 10: launch_general_stream_b<R, 10, true>(a, s); break;
-            case 11: launch_general_stream_b<R, 11, true>(a, s); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (a.tab.log2m) {
-        case 5: launch_general_stream_b<R, 5>(a, s); break;
-        case 6: launch_general_stream_b<R, 6>(a, s); break;
-        case 7: launch_general_stream_b<R, 7>(a, s); break;
-        case 8: launch_general_stream_b<R, 8>(a, s); break;
-        case 9: launch_general_stream_b<R, 9>(a, s); break;
-        case 10: launch_general_stream_b<R, 10>(a, s); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const bool ok = with_general_bits(a.tab, [&](auto B, auto BLUE) {
+        PE_LAUNCH_R(R, mfcc_general_stream_kernel, (PE_CONST(B), PE_CONST(BLUE)), dim3((PE_GEN_TWO_WAVES ? 2 : 1) * (unsigned)a.geo.n_streams), dim3(64), lds, s, a); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 template <class R>
 static hipError_t launch_general_offline_t(const GeneralOfflineArgs<R>& a, int n_cus, hipStream_t s) {
     if (a.n_frames <= 0) return hipSuccess;
     const long long cap = (long long)n_cus * 16;
     const unsigned blocks = (unsigned)(a.n_frames < cap ? a.n_frames : cap);
-    if (a.tab.chirp) {
-        switch (a.tab.log2m) {
-            case 7: launch_general_offline_b<R, 7, true>(a, blocks, s); break;
-            case 8: launch_general_offline_b<R, 8, true>(a, blocks, s); break;
-            case 9: launch_general_offline_b<R, 9, true>(a, blocks, s); break;
-            case 10: launch_general_offline_b<R, 10, true>(a, blocks, s); break;
-            case 11: launch_general_offline_b<R, 11, true>(a, blocks, s); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (a.tab.log2m) {
-        case 5: launch_general_offline_b<R, 5>(a, blocks, s); break;
-        case 6: launch_general_offline_b<R, 6>(a, blocks, s); break;
-        case 7: launch_general_offline_b<R, 7>(a, blocks, s); break;
-        case 8: launch_general_offline_b<R, 8>(a, blocks, s); break;
-        case 9: launch_general_offline_b<R, 9>(a, blocks, s); break;
-        case 10: launch_general_offline_b<R, 10>(a, blocks, s); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const bool ok = with_general_bits(a.tab, [&](auto B, auto BLUE) {
+        PE_LAUNCH_R(R, mfcc_general_offline_kernel, (PE_CONST(B), PE_CONST(BLUE)), dim3(blocks), dim3(64), lds, s, a); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s) { return launch_general_stream_t<double>(a, s); }
 hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s) { return launch_general_stream_t<float>(a, s); }
@@ -1093,8 +884,7 @@ hipError_t launch_project_rows(const float* ring, float* proj, const float* w, c
     return hipGetLastError();
 }
 
-// ThresholdDecoder.decode + TriggerDetector.update of stream s for decode_models_kernel: decode_kernel's body (kept apart from
-// decode_kernel, whose code the shared function changed -- the two must stay alike)
+// ThresholdDecoder.decode + TriggerDetector.update of stream s (decode_kernel, decode_models_kernel)
 __device__ __forceinline__ void decode_stream(const DecodeArgs& a, const int s) {
     const float rawf = a.raw[s];
     const double raw = (double)rawf;
@@ -1132,38 +922,7 @@ __device__ __forceinline__ void decode_stream(const DecodeArgs& a, const int s) 
 __global__ void decode_kernel(const DecodeArgs a) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= a.n_streams) return;
-    const float rawf = a.raw[s];
-    const double raw = (double)rawf;
-    double conf = raw;
-    if (raw != 1.0 && raw != 0.0) {                       // saturated sigmoid passes through (:46-47)
-        double cp;
-        if (a.out_range == 0) {
-            cp = raw > (double)a.min_out ? 1.0 : 0.0;
-        } else {
-            // asigmoid (functions.py:99-101) on the runner's float32 scalar: numpy evaluates `1 / x - 1` in
-            // float32 (two correctly rounded operations), math.log then takes that value as a double
-            const float odds = __fsub_rn(__fdiv_rn(1.0f, rawf), 1.0f);
-            double ratio = (-log((double)odds) - (double)a.min_out) / (double)a.out_range;
-            ratio = fmin(fmax(ratio, 0.0), 1.0);
-            cp = a.cd[(int)(ratio * (double)(a.cd_len - 1) + 0.5)];
-        }
-        conf = cp < a.center ? 0.5 * cp / a.center : 0.5 + 0.5 * (cp - a.center) / (1.0 - a.center);
-    }
-    if (a.conf_out) a.conf_out[s] = conf;
-    if (a.activation) {
-        int act = a.activation[s];
-        const bool hot = conf > a.threshold;
-        bool fired = false;
-        if (!hot && act >= 0) {
-            if (act > 0) act -= 1;
-        } else {
-            act += 1;
-            fired = act > a.trigger_level;
-            if (fired || (hot && act < 0)) act = a.rearm;
-        }
-        a.activation[s] = act;
-        if (a.fired_out) a.fired_out[s] = fired ? 1 : 0;
-    }
+    decode_stream(a, s);
 }
 // a K-model engine: model blockIdx.y with its own table, thresholds and trigger rows, ONE launch for all models
 __global__ void decode_models_kernel(const DecodeSet d) {
@@ -1207,8 +966,6 @@ hipError_t launch_clear(const ClearArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(clear_kernel, dim3(a.n_streams), dim3(64), 0, s, a);
     return hipGetLastError();
 }
-
-
 
 }  // namespace pe
 

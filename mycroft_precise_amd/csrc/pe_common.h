@@ -234,8 +234,9 @@ struct ModelNet {           // the weight fields of GruArgs, per model (null whe
     float dense_bias;
 };
 struct ModelSet { ModelNet net[kMaxModels]; };
-// model m's view of a launch: its weights, its output block at out + m * out_stride
-__device__ __forceinline__ GruArgs model_args(const GruArgs& a, const ModelNet& n, const int m, const long long out_stride) {
+// model m's view of a launch: its weights, its output block at out + m * out_stride (the host fills a one-model launch's
+// GruArgs with it too: engine.hip with_model -- ModelNet and this function are the device side's list of weight fields)
+__host__ __device__ __forceinline__ GruArgs model_args(const GruArgs& a, const ModelNet& n, const int m, const long long out_stride) {
     GruArgs b = a;
     b.wx = n.wx; b.wxd = n.wxd; b.wr1 = n.wr1; b.wr2 = n.wr2; b.bias = n.bias; b.wd = n.wd;
     b.cw = n.cw;
@@ -354,11 +355,9 @@ hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStr
 // one launch, three roles: GRU waves read the feature windows as they will be after this update while MFCC waves
 // compute this update's frames and the bookkeeping groups move the leftover (legal when chunk <= window -
 // frame_len: no frame computed now becomes visible now)
-hipError_t launch_fused_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, int n_cus, hipStream_t s);
-hipError_t launch_fused_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s);
-// the same launches for a K-model engine: K network roles (ModelSet), outputs [K][windows]
-hipError_t launch_fused_models_f64(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s);
-hipError_t launch_fused_models_f32(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ModelSet& ms, int n_models, int n_cus, hipStream_t s);
+// (ms != null: a K-model engine -- K network roles, outputs [K][windows])
+hipError_t launch_fused(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1);
+hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1);
 hipError_t launch_mfcc_offline_f64(const MfccOfflineArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
 hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
 // units <= 32; 0 feats, 1 ring, 2 rows.  ms != null: the n_models networks of a K-model engine in the same ONE launch, model m

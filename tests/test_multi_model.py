@@ -48,6 +48,7 @@ CONFIGS = [
     ('use_delta_one_wave_9000', 9000, {'use_delta': True}, 'f64', 'f32', 'f32', 26, (20,)),
     ('units32', 48, {}, 'f64', 'f32', 'f32', 13, (32,)),
     ('units12_classic', 200, {}, 'f64', 'f32', 'f32', 13, (12,)),
+    ('units28_four_waves', 256, {}, 'f64', 'f32', 'f32', 13, (28,)),
     ('general_front_end', 40, {'n_fft': 1024, 'n_filt': 40, 'n_mfcc': 20}, 'f64', 'f32', 'f32', 20, (20,)),
     ('wide64', 64, {}, 'f64', 'f32', 'f32', 13, (64,)),
 ]
@@ -139,7 +140,7 @@ def test_every_block_equals_a_one_model_engine(cfg, stock_weights):
 
 @pytest.mark.parametrize('K', [2, 4, 8])
 def test_fused_shape_of_every_model_count(stock_weights, K):
-    """The K-model fused launch picks its network shape from (K, tiles) (kernels.hip fused_models_shape): whatever it picks,
+    """The K-model fused launch picks its network shape from (K, tiles) (kernels.hip fused_models_four_waves): whatever it picks,
     every block equals a one-model engine's, through updates at 4096 streams in both leftover styles."""
     import torch
     n, n_up = 4096, 8
