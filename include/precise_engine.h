@@ -275,6 +275,32 @@ int pe_vectorize_mels(pe_engine* e, const double* audio_host, int64_t n_samples,
 int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32_t hop_frames,
                 float* out_host, int64_t max_windows, int64_t* n_windows_out);
 
+/* vectorize() of vectorization.py:62-84 for n_clips buffers at once, and the batch the dataset tools build from it
+ * (train_data.py:195-196: vectorizer(load_audio(x)) for every wav of a folder; scripts/test.py:48-53 and eval.py:103-105:
+ * predict(inputs) over those vectors; vectorize_inhibit, vectorization.py:92-105: cropped copies of one clip).
+ * Clip c is samples [offsets[c], offsets[c + 1]) of audio_host; offsets[n_clips + 1] is non-decreasing and starts at 0.
+ * sample_format: 0 = float64 samples (as pe_vectorize_raw takes), 1 = float32 samples (what load_audio returns,
+ * util.py:45-65), widened on the device -- exact, so both formats give the same bits.
+ * Per clip, as vectorize does: the last max_samples samples (max_samples <= 0: no crop), the frames of what is left
+ * (anchored at its start; one fewer with vectorizer = 3), the last n_features of them, all-zero rows in front up to
+ * n_features; a clip shorter than one window gives an all-zero window.
+ * pe_vectorize_clips: feats_out[n_clips][n_features][n_mfcc] float64, or -- mels = 1, the Vectorizer.mels entry --
+ * [n_clips][n_features][n_filt] log-mel rows.
+ * pe_score_clips: the network over every clip's window, out[n_models][n_clips] raw outputs (use_delta models: the deltas
+ * of the padded window, zero in its first row, as vectorize_delta forms them, vectorization.py:87-89).
+ * One front-end launch and (scores) one network launch per pass; the clips are staged in passes of 256 MiB of audio (a pass
+ * takes at least one clip) and the results do not depend on the pass size.  An empty clip is PE_ERR_INVALID (the
+ * reference raises InvalidAudio) and the message names it; so are decreasing offsets, null pointers with n_clips > 0 and
+ * n_clips < 0 -- all checked before any device work, the outputs untouched.  n_clips = 0 does nothing.  Stateless (the
+ * engine's streams are untouched); updates of pe_update_async still in flight finish first. */
+int pe_vectorize_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host,
+                       int32_t n_clips, int64_t max_samples, int32_t mels, double* feats_out_host);
+int pe_score_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host,
+                   int32_t n_clips, int64_t max_samples, float* out_host);
+/* Test aid: the audio bytes one pass of the two calls above stages (>= 1; default 256 MiB), so that a small test can cross
+ * pass boundaries. */
+int pe_set_clip_pass_bytes(pe_engine* e, int64_t bytes);
+
 /* ThresholdDecoder.decode (threshold_decoder.py:45-57) and TriggerDetector.update
  * (runner/precise_runner/runner.py:127-142) for every stream, on the device.
  * pe_set_decoder: cd = the decoder's cumulative table (np.cumsum of the summed normal pdfs,
@@ -359,7 +385,10 @@ int pe_get_gru_tiling(const pe_engine* e);
 
 /* HIP-event timing of the kernels launched by the last *_device/host update on this engine
  * (milliseconds; measured on the stream the kernels ran on).  Enabled with pe_set_timing(e,1).
- * With a fused launch mfcc_ms is the whole update and gru_ms is 0. */
+ * With a fused launch mfcc_ms is the whole update and gru_ms is 0.
+ * pe_vectorize_clips / pe_score_clips: the front-end launch and the network launch of the LAST pass only (every pass records
+ * the same events again; one pass unless the audio exceeds the pass target).  pe_vectorize_clips launches no network:
+ * gru_ms is 0 there. */
 int pe_set_timing(pe_engine* e, int32_t enabled);
 int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms);
 

@@ -79,6 +79,9 @@ EXPORTS = {
                                    C.POINTER(C.c_int64)]),
     'pe_evaluate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                               C.POINTER(C.c_int64)]),
+    'pe_vectorize_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    'pe_score_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    'pe_set_clip_pass_bytes': (C.c_int, [C.c_void_p, C.c_int64]),
     'pe_set_decoder': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
     'pe_set_trigger': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     'pe_set_decoder_model': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
@@ -404,6 +407,55 @@ class HipEngine:
         self._check(self._lib.pe_evaluate(self._h, audio.ctypes.data if audio.size else None, audio.size,
                                           int(hop_frames), out.ctypes.data if n_win else None, n_win, C.byref(n)))
         return out[:, :n.value] if self._multi else out[:n.value]
+
+    @staticmethod
+    def _clips(clips):
+        """a sequence of 1-D sample arrays -> (samples concatenated once, int64 offsets [n + 1], sample_format): float32 if
+        every clip is float32, else float64"""
+        clips = [np.asarray(c) for c in clips]
+        for c in clips:
+            if c.ndim != 1:
+                raise ValueError('every clip must be a 1-D array of samples, got shape %r' % (c.shape,))
+        f32 = bool(clips) and all(c.dtype == np.float32 for c in clips)
+        dtype = np.float32 if f32 else np.float64
+        offsets = np.zeros(len(clips) + 1, dtype=np.int64)
+        np.cumsum([c.size for c in clips], out=offsets[1:])
+        audio = np.empty(int(offsets[-1]), dtype=dtype)
+        if clips:
+            np.concatenate(clips, out=audio, casting='same_kind')
+        return audio, offsets, int(f32)
+
+    def vectorize_clips(self, clips, max_samples, mels=False, out=None) -> np.ndarray:
+        """vectorize (vectorization.py:62-84) of every clip in one call: a sequence of 1-D sample arrays of any lengths ->
+        float64 [n, n_features, n_mfcc] (mels: [n, n_features, n_filt] log-mel rows); max_samples <= 0 = no crop."""
+        audio, offsets, fmt = self._clips(clips)
+        n = offsets.size - 1
+        shape = (n, self.n_features, self.n_filt if mels else self.n_mfcc)
+        if out is None:
+            out = np.empty(shape, dtype=np.float64)
+        if out.dtype != np.float64 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError('out must be a contiguous float64 array of shape %r' % (shape,))
+        self._check(self._lib.pe_vectorize_clips(self._h, audio.ctypes.data if n else None, fmt, offsets.ctypes.data, n,
+                                                 int(max_samples), int(bool(mels)), out.ctypes.data if n else None))
+        return out
+
+    def score_clips(self, clips, max_samples, out=None) -> np.ndarray:
+        """The network over vectorize (use_delta models: vectorize_delta) of every clip, without the per-clip loop: raw
+        outputs float32 [n, 1] as ``predict`` returns them ([K, n, 1] on a K-model engine)."""
+        audio, offsets, fmt = self._clips(clips)
+        n = offsets.size - 1
+        shape = self._lead(n, 1)
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        if out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError('out must be a contiguous float32 array of shape %r' % (shape,))
+        self._check(self._lib.pe_score_clips(self._h, audio.ctypes.data if n else None, fmt, offsets.ctypes.data, n,
+                                             int(max_samples), out.ctypes.data if n else None))
+        return out
+
+    def set_clip_pass_bytes(self, n_bytes: int):
+        """Test aid: audio bytes per pass of vectorize_clips / score_clips (default 256 MiB)."""
+        self._check(self._lib.pe_set_clip_pass_bytes(self._h, int(n_bytes)))
 
     def set_decoder(self, decoder, model=None):
         """Upload a ThresholdDecoder (its cumulative table and scalars) for pe_decode*: for every model, or for ``model``."""

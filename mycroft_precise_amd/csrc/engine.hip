@@ -22,6 +22,11 @@ namespace {
 
 thread_local std::string g_global_error;
 
+// pe_vectorize_clips / pe_score_clips work through their clips in passes of about this many bytes of audio (a pass always
+// takes at least one clip); at most kClipPassRows window rows per pass bound the result buffers when the clips are tiny
+constexpr int64_t kClipPassBytes = 256ll << 20;
+constexpr int64_t kClipPassRows = 1ll << 21;
+
 struct DeviceBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -104,6 +109,8 @@ struct pe_engine {
     int32_t* activation = nullptr;
     // staging for the host entry points (grown on demand)
     DeviceBuf st_pcm, st_out, st_feats, st_mask, st_audio, st_mfcc, st_conf, st_fired, st_ids;
+    DeviceBuf st_clips;                     // pe_vectorize_clips / pe_score_clips: the clip table of a pass
+    int64_t clip_pass_bytes = kClipPassBytes;  // audio bytes a pass of those entry points stages (pe_set_clip_pass_bytes: tests)
     std::vector<uint8_t> seen_ids;          // pe_update_subset: duplicate check of the host entry point
     // timing
     bool timing = false;
@@ -1268,7 +1275,7 @@ int pe_destroy(pe_engine* e) {
     (void)hipSetDevice(e->device);
     (void)drain_async(e);
     for (void* p : e->allocs) (void)hipFree(p);
-    for (DeviceBuf* b : {&e->st_pcm, &e->st_out, &e->st_feats, &e->st_mask, &e->st_audio, &e->st_mfcc, &e->st_conf, &e->st_fired, &e->st_ids})
+    for (DeviceBuf* b : {&e->st_pcm, &e->st_out, &e->st_feats, &e->st_mask, &e->st_audio, &e->st_mfcc, &e->st_conf, &e->st_fired, &e->st_ids, &e->st_clips})
         if (b->p) (void)hipFree(b->p);
     for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->s_compute) (void)hipStreamSynchronize(e->s_compute);
@@ -1679,6 +1686,119 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
     if ((rc = launch_networks(e, g, 2, nullptr, n_windows))) return rc;
     for (int m = 0; m < e->n_models; ++m)           // out_host[K][max_windows]
         PE_HIP(e, hipMemcpy(out_host + (size_t)m * max_windows, static_cast<float*>(e->st_out.p) + (size_t)m * n_windows, (size_t)n_windows * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+namespace {
+// pe_vectorize_clips (feats_out_host) / pe_score_clips (score_out_host): validation, then pass by pass one copy in, the
+// front-end launch, the network launch (scores), one copy out
+int run_clips(pe_engine* e, const char* who, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_clips,
+              int64_t max_samples, bool mels, double* feats_out_host, float* score_out_host) {
+    if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
+    if (n_clips < 0) return fail(e, PE_ERR_INVALID, "%s: n_clips=%d", who, n_clips);
+    if (n_clips == 0) return PE_OK;
+    if (!audio_host || !offsets_host || !(feats_out_host || score_out_host)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (sample_format != 0 && sample_format != 1) return fail(e, PE_ERR_INVALID, "%s: sample_format must be 0 (float64) or 1 (float32), got %d", who, sample_format);
+    if (offsets_host[0] != 0) return fail(e, PE_ERR_INVALID, "%s: offsets[0] must be 0, got %lld", who, (long long)offsets_host[0]);
+    for (int32_t c = 0; c < n_clips; ++c) {
+        if (offsets_host[c + 1] < offsets_host[c]) return fail(e, PE_ERR_INVALID, "%s: offsets decrease at clip %d (%lld after %lld)", who, c, (long long)offsets_host[c + 1], (long long)offsets_host[c]);
+        if (offsets_host[c + 1] == offsets_host[c]) return fail(e, PE_ERR_INVALID, "%s: clip %d is empty (the reference raises InvalidAudio: cannot vectorize empty audio)", who, c);
+    }
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    int rc;
+    const int T = e->prm.n_features;
+    const int width = mels ? e->prm.n_filt : e->prm.n_mfcc;
+    const size_t elem = sample_format == 1 ? sizeof(float) : sizeof(double);
+    if (score_out_host && (rc = ensure(e, e->st_out, (size_t)e->n_models * n_clips * sizeof(float)))) return rc;
+    std::vector<ClipDesc> desc;
+    std::vector<uint32_t> prefix;
+    const bool t = e->timing;
+    for (int32_t c0 = 0; c0 < n_clips;) {
+        // the clips of this pass: at least one, then as many as stay within the byte target (and the row bound)
+        int32_t c1 = c0 + 1;
+        while (c1 < n_clips && (int64_t)(offsets_host[c1 + 1] - offsets_host[c0]) * (int64_t)elem <= e->clip_pass_bytes && (int64_t)(c1 + 1 - c0) * T <= kClipPassRows) ++c1;
+        const int n = c1 - c0;
+        const int64_t base = offsets_host[c0], n_samples = offsets_host[c1] - base;
+        desc.resize((size_t)n); prefix.resize((size_t)n + 1);
+        uint32_t tasks = 0;
+        for (int i = 0; i < n; ++i) {
+            const int64_t len = offsets_host[c0 + i + 1] - offsets_host[c0 + i];
+            const int64_t cut = max_samples > 0 && len > max_samples ? max_samples : len;        // vectorize: audio[-max_samples:]
+            const int64_t frames = frames_of_buffer(e->prm, cut);
+            const int64_t kept = frames < T ? frames : T;                                          // ... feats[-n_features:]
+            desc[(size_t)i] = ClipDesc{offsets_host[c0 + i + 1] - cut - base, (int)(frames - kept), (int)kept, (int)(T - kept), 0};
+            prefix[(size_t)i] = tasks;
+            tasks += (uint32_t)kept;
+        }
+        prefix[(size_t)n] = tasks;
+        const size_t db = (size_t)n * sizeof(ClipDesc), pb = ((size_t)n + 1) * sizeof(uint32_t);
+        if ((rc = ensure(e, e->st_audio, (size_t)n_samples * elem))) return rc;
+        if ((rc = ensure(e, e->st_clips, db + pb))) return rc;
+        PE_HIP(e, hipMemcpy(e->st_audio.p, static_cast<const char*>(audio_host) + (size_t)base * elem, (size_t)n_samples * elem, hipMemcpyHostToDevice));
+        PE_HIP(e, hipMemcpy(e->st_clips.p, desc.data(), db, hipMemcpyHostToDevice));
+        PE_HIP(e, hipMemcpy(static_cast<char*>(e->st_clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
+        const ClipTable ct{static_cast<const ClipDesc*>(e->st_clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->st_clips.p) + db),
+                           n, tasks, e->st_audio.p, sample_format == 1 ? 1 : 0};
+        double* dev_out = nullptr;
+        float* dev_rows = nullptr;
+        const size_t fb = (size_t)n * T * width * sizeof(double), rb = (size_t)n * T * e->row_floats * sizeof(float);
+        if (feats_out_host) { if ((rc = ensure(e, e->st_mfcc, fb))) return rc; dev_out = static_cast<double*>(e->st_mfcc.p); }
+        else { if ((rc = ensure(e, e->st_feats, rb))) return rc; dev_rows = static_cast<float*>(e->st_feats.p); }
+        if (t) PE_HIP(e, hipEventRecord(e->ev[0], nullptr));
+        if (e->general) {
+            if (e->prm.mfcc_precision == 0) {
+                GeneralClipArgs<double> a{geom(e), e->gtab, ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr, e->row_floats};
+                PE_HIP(e, launch_general_clips_f64(a, e->n_cus, nullptr));
+            } else {
+                GeneralClipArgs<float> a{geom(e), e->gtab, ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr, e->row_floats};
+                PE_HIP(e, launch_general_clips_f32(a, e->n_cus, nullptr));
+            }
+        } else if (e->prm.mfcc_precision == 0) {
+            MfccClipArgs<double> a{geom(e), ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr};
+            PE_HIP(e, launch_mfcc_clips_f64(a, tables<double>(e), e->n_cus, nullptr));
+        } else {
+            MfccClipArgs<float> a{geom(e), ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr};
+            PE_HIP(e, launch_mfcc_clips_f32(a, tables<float>(e), e->n_cus, nullptr));
+        }
+        if (t) PE_HIP(e, hipEventRecord(e->ev[1], nullptr));
+        if (feats_out_host) {
+            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)c0 * T * width, dev_out, fb, hipMemcpyDeviceToHost));
+        } else {
+            // clip c's window is rows [c T, c T + T) of the pass: the row-sequence input of pe_evaluate with a stride of T rows
+            // (its deltas, use_delta, are formed inside a window: zero at the window's first row)
+            GruArgs g = gru_args(e);
+            g.n_streams = n;
+            g.feats = dev_rows;
+            g.row_stride = T;
+            g.out = static_cast<float*>(e->st_out.p) + c0;          // model m: + m * n_clips
+            g.waves_per_tile = 1;
+            if ((rc = launch_networks(e, g, 2, nullptr, n_clips))) return rc;
+        }
+        if (t) { PE_HIP(e, hipEventRecord(e->ev[2], nullptr)); e->ev_valid = true; e->ev_has_gru = score_out_host != nullptr; }
+        c0 = c1;
+    }
+    if (score_out_host) PE_HIP(e, hipMemcpy(score_out_host, e->st_out.p, (size_t)e->n_models * n_clips * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+}  // namespace
+
+int pe_vectorize_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_clips,
+                       int64_t max_samples, int32_t mels, double* feats_out_host) {
+    if (e && n_clips > 0 && !feats_out_host) return fail(e, PE_ERR_INVALID, "null argument to pe_vectorize_clips");
+    return run_clips(e, "pe_vectorize_clips", audio_host, sample_format, offsets_host, n_clips, max_samples, mels != 0, feats_out_host, nullptr);
+}
+
+int pe_score_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_clips,
+                   int64_t max_samples, float* out_host) {
+    if (e && n_clips > 0 && !out_host) return fail(e, PE_ERR_INVALID, "null argument to pe_score_clips");
+    return run_clips(e, "pe_score_clips", audio_host, sample_format, offsets_host, n_clips, max_samples, false, nullptr, out_host);
+}
+
+int pe_set_clip_pass_bytes(pe_engine* e, int64_t bytes) {
+    if (!e) return PE_ERR_INVALID;
+    if (bytes < 1) return fail(e, PE_ERR_INVALID, "the pass target must be at least 1 byte, got %lld", (long long)bytes);
+    e->clip_pass_bytes = bytes;
     return PE_OK;
 }
 

@@ -97,6 +97,10 @@ __global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_e
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     mfcc_offline_frames<R, SH>(a, t, smem);
 }
+// many clips in one launch (pe_vectorize_clips / pe_score_clips): frame tasks found in the clip table (pe_common.h: ClipTable)
+PE_KERNEL_PAIR((template <class R, class SH>), PE_FRAME_KERNEL(64 * kFrameWaves, SH::WPE), mfcc_clips_kernel,
+               (const MfccClipArgs<R> a, const WaveTables<R> t),
+               { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; mfcc_clip_frames<R, SH>(a, t, smem); })
 
 // ---- network shapes: the tile function of a workgroup, its threads and its LDS, said once -------------------------------
 // run(a, tile, smem) is the whole network of tile `tile` of the launch `a`.  The one-model kernel of a shape (the names
@@ -507,6 +511,19 @@ static hipError_t launch_offline(const MfccOfflineArgs<R>& a, const WaveTables<R
 hipError_t launch_mfcc_offline_f64(const MfccOfflineArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s) { return launch_offline<double>(a, t, n_cus, s); }
 hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s) { return launch_offline<float>(a, t, n_cus, s); }
 
+template <class R>
+static hipError_t launch_clips(const MfccClipArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s) {
+    if (a.clips.n_clips <= 0) return hipSuccess;
+    if (!blob_matches_shape(t)) return hipErrorInvalidValue;
+    // (a launch without frame tasks still stores the pad rows: one workgroup at least)
+    const long long work = a.clips.n_tasks > (uint32_t)a.clips.n_clips ? (long long)a.clips.n_tasks : (long long)a.clips.n_clips;
+    if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_clips_kernel, (ShapeStock), dim3(frame_blocks(work, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
+    else PE_LAUNCH_R(R, mfcc_clips_kernel, (ShapeAny), dim3(frame_blocks(work, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
+    return hipGetLastError();
+}
+hipError_t launch_mfcc_clips_f64(const MfccClipArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s) { return launch_clips<double>(a, t, n_cus, s); }
+hipError_t launch_mfcc_clips_f32(const MfccClipArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s) { return launch_clips<float>(a, t, n_cus, s); }
+
 int gru_small_regs(int units) { return (units + 3) / 4; }
 int gru_small_tiles(int units) { return (3 * gru_small_regs(units) + 3) / 4; }
 
@@ -733,6 +750,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ?
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     general_offline<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), blockIdx.x, gridDim.x, threadIdx.x);
 }
+PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false>), (__launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4)))), mfcc_general_clips_kernel,
+               (const GeneralClipArgs<R> a),
+               { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; general_clips<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), (int)blockIdx.x, (int)gridDim.x, threadIdx.x); })
 // the transform length as a template argument: n_fft not a power of two (chirp) = Bluestein over L = 2^log2m points
 template <class F>
 static bool with_general_bits(const GeneralTables& tab, F&& f) {
@@ -757,6 +777,19 @@ static hipError_t launch_general_offline_t(const GeneralOfflineArgs<R>& a, int n
         PE_LAUNCH_R(R, mfcc_general_offline_kernel, (PE_CONST(B), PE_CONST(BLUE)), dim3(blocks), dim3(64), lds, s, a); });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
+template <class R>
+static hipError_t launch_general_clips_t(const GeneralClipArgs<R>& a, int n_cus, hipStream_t s) {
+    if (a.clips.n_clips <= 0) return hipSuccess;
+    const long long cap = (long long)n_cus * 16;
+    const long long work = a.clips.n_tasks > (uint32_t)a.clips.n_clips ? (long long)a.clips.n_tasks : (long long)a.clips.n_clips;
+    const unsigned blocks = (unsigned)(work < cap ? work : cap);
+    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const bool ok = with_general_bits(a.tab, [&](auto B, auto BLUE) {
+        PE_LAUNCH_R(R, mfcc_general_clips_kernel, (PE_CONST(B), PE_CONST(BLUE)), dim3(blocks), dim3(64), lds, s, a); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s) { return launch_general_clips_t<double>(a, n_cus, s); }
+hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s) { return launch_general_clips_t<float>(a, n_cus, s); }
 hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s) { return launch_general_stream_t<double>(a, s); }
 hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s) { return launch_general_stream_t<float>(a, s); }
 hipError_t launch_general_offline_f64(const GeneralOfflineArgs<double>& a, int n_cus, hipStream_t s) { return launch_general_offline_t<double>(a, n_cus, s); }

@@ -520,33 +520,71 @@ struct GeneralOfflineArgs {
     int row_floats;
 };
 
+// one frame of both whole-buffer forms: samples x[0 .. frame_len) (float64, or float32 widened here: exact) -> row `row` of
+// whichever outputs are given.  The arithmetic of a frame is this one function, whichever entry point asked for it.
+template <class R, int BITS, bool BLUE, class X>
+__device__ __forceinline__ void general_offline_frame(const StreamGeom& geo, const GeneralTables& tab, R* S, const int lane, const X* x, const long long row,
+                                                      double* out, float* out_rows, double* out_mels, const int row_floats) {
+    const int M = BLUE ? (1 << BITS) : (tab.n_fft >> 1);          // (BLUE: reals before LM = 2 L)
+    R coeff[1];
+    const int flen = geo.frame_len;
+    int lane_k = lane;                                  // (per-frame recomputation of the lane invariants: general_stream)
+    asm volatile("" : "+v"(lane_k));
+    if constexpr (BLUE) general_frame_blue<R, BITS>(tab, S, lane_k, [&](int n) -> R { return n < flen ? (R)(double)x[n] : R(0); }, coeff);
+    else general_frame<R, BITS>(tab, S, lane_k, [&](int n) -> cplx<R> {
+        const int m0 = 2 * n, m1 = 2 * n + 1;                             // (clamped indices: plain loads, selected afterwards)
+        const double x0 = (double)x[m0 < flen ? m0 : 0], x1 = (double)x[m1 < flen ? m1 : 0];
+        return cplx<R>{m0 < flen ? (R)x0 : R(0), m1 < flen ? (R)x1 : R(0)};
+    }, coeff);
+    if (out && lane < geo.n_mfcc) out[row * geo.n_mfcc + lane] = (double)coeff[0];
+    if (out_rows && lane < row_floats) out_rows[row * row_floats + lane] = lane < geo.n_mfcc ? (float)coeff[0] : 0.0f;
+    if (out_mels) {
+        const R* LM = S + 2 * M + ((BLUE || general_overlay(tab.n_fft)) ? 0 : M + 1);
+        for (int f = lane; f < geo.n_filt; f += 64) out_mels[row * geo.n_filt + f] = (double)LM[f];
+    }
+    group_sync();
+}
+
 template <class R, int BITS, bool BLUE = false>
 __device__ __forceinline__ void general_offline(const GeneralOfflineArgs<R>& a, R* S, const long long first, const long long stride, const int lane) {
+    for (long long fr = first; fr < a.n_frames; fr += stride)
+        general_offline_frame<R, BITS, BLUE>(a.geo, a.tab, S, lane, a.audio + fr * a.geo.hop, fr, a.out, a.out_rows, a.out_mels, a.row_floats);
+}
+
+// ---- the same, for many clips of different lengths (pe_vectorize_clips / pe_score_clips; pe_common.h: ClipTable) -------
+template <class R>
+struct GeneralClipArgs {
+    StreamGeom geo;
+    GeneralTables tab;
+    ClipTable clips;
+    double* out;                // [n_clips][n_features][n_mfcc] float64, may be null
+    float* out_rows;            // [n_clips][n_features][row_floats] float32 rows, may be null
+    double* out_mels;           // [n_clips][n_features][n_filt] log-mel energies, may be null
+    int row_floats;
+};
+
+// one wave per workgroup: wave `first` of `stride` takes the frame tasks first, first + stride, ... and the pad rows of the
+// clips first, first + stride, ...
+template <class R, int BITS, bool BLUE = false>
+__device__ __forceinline__ void general_clips(const GeneralClipArgs<R>& a, R* S, const int first, const int stride, const int lane) {
     const StreamGeom& geo = a.geo;
-    const int M = BLUE ? (1 << BITS) : (a.tab.n_fft >> 1);          // (BLUE: reals before LM = 2 L)
-    for (long long fr = first; fr < a.n_frames; fr += stride) {
-        const double* x = a.audio + fr * geo.hop;
-        R coeff[1];
-        const int flen = geo.frame_len;
-        int lane_k = lane;                                  // (per-frame recomputation of the lane invariants: general_stream)
-        asm volatile("" : "+v"(lane_k));
-        if constexpr (BLUE) general_frame_blue<R, BITS>(a.tab, S, lane_k, [&](int n) -> R { return n < flen ? (R)x[n] : R(0); }, coeff);
-        else general_frame<R, BITS>(a.tab, S, lane_k, [&](int n) -> cplx<R> {
-            const int m0 = 2 * n, m1 = 2 * n + 1;                             // (clamped indices: plain loads, selected afterwards)
-            const double x0 = x[m0 < flen ? m0 : 0], x1 = x[m1 < flen ? m1 : 0];
-            return cplx<R>{m0 < flen ? (R)x0 : R(0), m1 < flen ? (R)x1 : R(0)};
-        }, coeff);
-        if (a.out && lane < geo.n_mfcc) a.out[fr * geo.n_mfcc + lane] = (double)coeff[0];
-        if (a.out_rows && lane < a.row_floats) a.out_rows[fr * a.row_floats + lane] = lane < geo.n_mfcc ? (float)coeff[0] : 0.0f;
-        if (a.out_mels) {
-            const R* LM = S + 2 * M + ((BLUE || general_overlay(a.tab.n_fft)) ? 0 : M + 1);
-            for (int f = lane; f < geo.n_filt; f += 64) a.out_mels[fr * geo.n_filt + f] = (double)LM[f];
-        }
-        group_sync();
+    const int T = geo.n_features;
+    clip_zero_pads(a.clips, a.out, geo.n_mfcc, T, first, stride, lane);
+    clip_zero_pads(a.clips, a.out_rows, a.row_floats, T, first, stride, lane);
+    clip_zero_pads(a.clips, a.out_mels, geo.n_filt, T, first, stride, lane);
+    int c = 0;
+    for (uint32_t g = (uint32_t)first; g < a.clips.n_tasks; g += (uint32_t)stride) {
+        c = clip_of_task(a.clips, g, c);
+        const ClipTask task = clip_task(a.clips, g, c, geo.hop, T);
+        // (the sample format is chosen once per frame, outside the loads)
+        if (a.clips.audio_f32) general_offline_frame<R, BITS, BLUE>(geo, a.tab, S, lane, static_cast<const float*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels, a.row_floats);
+        else general_offline_frame<R, BITS, BLUE>(geo, a.tab, S, lane, static_cast<const double*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels, a.row_floats);
     }
 }
 
 // launchers (kernels.hip)
+hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s);
+hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s);
 hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s);
 hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s);
 hipError_t launch_general_offline_f64(const GeneralOfflineArgs<double>& a, int n_cus, hipStream_t s);

@@ -678,6 +678,30 @@ __device__ __forceinline__ void mfcc_frame_tasks(const MfccStreamArgs<R>& a, con
     }
 }
 
+// one frame of both whole-buffer forms: samples x[0 .. frame_len) (float64, or float32 widened here: exact) -> row `row` of
+// whichever outputs are given.  The arithmetic of a frame is this one function, whichever entry point asked for it.
+template <class R, class SH, class X>
+__device__ __forceinline__ void mfcc_offline_frame(const StreamGeom& geo, const pe_wave::Tab<R>& tab, const pe_wave::LaneConsts<R>& lc, const LaneRuns& lr,
+                                                   R* S, const int lane, const X* x, const long long row, double* out, float* out_rows, double* out_mels) {
+    const int flen = geo.frame_len;
+    pe_wave::Regs<R> v;
+#pragma unroll
+    for (int a4 = 0; a4 < 4; ++a4) {
+        const int n = 2 * (lane + 64 * a4);
+        v.re[a4] = n < flen ? (R)(double)x[n] : R(0);
+        v.im[a4] = n + 1 < flen ? (R)(double)x[n + 1] : R(0);
+    }
+    const R coeff = mfcc_wave_frame<R, SH>(tab, lc, lr, S, lane, geo.n_filt, geo.n_mfcc, v, RealK<R>::INV_FFT, geo.log_mode);
+    const int c = lane >> 2;
+    if ((lane & 3) == 0) {
+        if (out && c < geo.n_mfcc) out[row * geo.n_mfcc + c] = (double)coeff;
+        if (out_rows) out_rows[row * kRowFloats + c] = c < geo.n_mfcc ? (float)coeff : 0.0f;
+    }
+    if (out_mels)             // the log-mel energies are still in this wave's scratch
+        for (int f = lane; f < geo.n_filt; f += 64) out_mels[row * geo.n_filt + f] = (double)S[pe_wave::kLogMelOff + f];
+    group_sync();
+}
+
 // ---- stateless whole-buffer form (vectorize_raw): one frame per wave, float64 samples in -------------------------
 template <class R, class SH>
 __device__ __forceinline__ void mfcc_offline_frames(const MfccOfflineArgs<R>& a, const WaveTables<R>& wt, unsigned char* smem) {
@@ -694,25 +718,40 @@ __device__ __forceinline__ void mfcc_offline_frames(const MfccOfflineArgs<R>& a,
 #endif
     const LaneRuns lr = lane_runs(tab, lane, geo.n_filt);
     wave_scratch_init(S, lane);
-    const int flen = geo.frame_len;
-    for (long long fr = (long long)blockIdx.x * waves + wave; fr < a.n_frames; fr += (long long)gridDim.x * waves) {
-        const double* x = a.audio + fr * geo.hop;
-        pe_wave::Regs<R> v;
-#pragma unroll
-        for (int a4 = 0; a4 < 4; ++a4) {
-            const int n = 2 * (lane + 64 * a4);
-            v.re[a4] = n < flen ? (R)x[n] : R(0);
-            v.im[a4] = n + 1 < flen ? (R)x[n + 1] : R(0);
-        }
-        const R coeff = mfcc_wave_frame<R, SH>(tab, lc, lr, S, lane, geo.n_filt, geo.n_mfcc, v, RealK<R>::INV_FFT, geo.log_mode);
-        const int c = lane >> 2;
-        if ((lane & 3) == 0) {
-            if (a.out && c < geo.n_mfcc) a.out[fr * geo.n_mfcc + c] = (double)coeff;
-            if (a.out_rows) a.out_rows[fr * kRowFloats + c] = c < geo.n_mfcc ? (float)coeff : 0.0f;
-        }
-        if (a.out_mels)             // the log-mel energies are still in this wave's scratch
-            for (int f = lane; f < geo.n_filt; f += 64) a.out_mels[fr * geo.n_filt + f] = (double)S[pe_wave::kLogMelOff + f];
-        group_sync();
+    for (long long fr = (long long)blockIdx.x * waves + wave; fr < a.n_frames; fr += (long long)gridDim.x * waves)
+        mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, a.audio + fr * geo.hop, fr, a.out, a.out_rows, a.out_mels);
+}
+
+// ---- the same, for many clips of different lengths (pe_vectorize_clips / pe_score_clips) --------------------------
+// One frame per wave as above, the frame arithmetic the same call; what differs is where a task's samples come from and
+// where its row goes (pe_common.h: ClipTable).  Task, clip and addresses are wave-uniform.
+template <class R, class SH>
+__device__ __forceinline__ void mfcc_clip_frames(const MfccClipArgs<R>& a, const WaveTables<R>& wt, unsigned char* smem) {
+    const StreamGeom& geo = a.geo;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
+    const TabRegs tab_regs = wave_tables_issue<R>(wt);
+    const int wave_id = (int)blockIdx.x * waves + wave, n_waves = (int)gridDim.x * waves;
+    const int T = geo.n_features;
+    clip_zero_pads(a.clips, a.out, geo.n_mfcc, T, wave_id, n_waves, lane);
+    clip_zero_pads(a.clips, a.out_rows, kRowFloats, T, wave_id, n_waves, lane);
+    clip_zero_pads(a.clips, a.out_mels, geo.n_filt, T, wave_id, n_waves, lane);
+    wave_tables_commit<R>(smem, wt, tab_regs);
+    const pe_wave::Tab<R> tab = wave_bind<R, SH>(smem + kWaveImageBase<R>, wt.L);
+    R* S = reinterpret_cast<R*>(smem) + (size_t)wave * kWaveScratchReals;
+#if PE_TW_LDS == 2
+    const pe_wave::LaneConsts<R> lc{};
+#else
+    const pe_wave::LaneConsts<R> lc = pe_wave::lane_consts(pe_wave::bind<R>(static_cast<const unsigned char*>(wt.blob), wt.L), lane);
+#endif
+    const LaneRuns lr = lane_runs(tab, lane, geo.n_filt);
+    wave_scratch_init(S, lane);
+    int c = 0;
+    for (uint32_t g = (uint32_t)wave_id; g < a.clips.n_tasks; g += (uint32_t)n_waves) {
+        c = clip_of_task(a.clips, g, c);
+        const ClipTask task = clip_task(a.clips, g, c, geo.hop, T);
+        // (the sample format is chosen once per frame, outside the loads; the loads themselves are the offline form's)
+        if (a.clips.audio_f32) mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const float*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels);
+        else mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const double*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels);
     }
 }
 

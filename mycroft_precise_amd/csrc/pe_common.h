@@ -142,6 +142,72 @@ struct MfccOfflineArgs {
     double* out_mels;       // [n_frames][n_filt] float64 log-mel energies (Vectorizer.mels), may be null
 };
 
+// ---- many clips of different lengths in one launch (pe_vectorize_clips / pe_score_clips) -----------------------------
+// vectorize() of vectorization.py:62-84 per clip: the last max_samples samples, frames anchored at the start of what is
+// left, the last n_features of them, zero rows in front up to n_features.  The host works that out per clip (ClipDesc);
+// the launch's frame tasks g = 0 .. n_tasks - 1 are the kept frames of all clips one after the other, and a wave finds
+// the clip of its task in the exclusive prefix sum of the kept counts.
+struct ClipDesc {
+    long long start;        // first sample of the clip after the crop, in samples from `audio`
+    int first;              // first kept frame (frames before it fell out of the window)
+    int kept;               // kept frames: rows [pad, pad + kept) of the clip's window
+    int pad;                // all-zero rows in front (n_features - kept)
+    int reserved_;
+};
+struct ClipTable {
+    const ClipDesc* desc;       // [n_clips]
+    const uint32_t* prefix;     // [n_clips + 1] exclusive prefix sum of `kept`; prefix[n_clips] == n_tasks
+    int n_clips;
+    uint32_t n_tasks;
+    const void* audio;          // the samples of every clip of the launch: float64, or float32 (widened here: exact)
+    int audio_f32;
+};
+// The table as wave-uniform loads: tasks and clips are per wave, and nothing writes the table while a launch reads it, so it
+// is read through the constant address space -- scalar loads into SGPRs, no LDS broadcast, no vector load per lane.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PE_UNIFORM_PTR(T, p) (reinterpret_cast<const __attribute__((address_space(4))) T*>(reinterpret_cast<uintptr_t>(p)))
+#else
+#define PE_UNIFORM_PTR(T, p) (p)
+#endif
+// clip c with prefix[c] <= g < prefix[c + 1], searched from clip `lo` on (a wave's tasks only move forward); g < n_tasks
+__device__ __forceinline__ int clip_of_task(const ClipTable& ct, const uint32_t g, int lo) {
+    const auto prefix = PE_UNIFORM_PTR(uint32_t, ct.prefix);
+    int hi = ct.n_clips;                                        // invariant: prefix[lo] <= g < prefix[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (prefix[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+struct ClipTask { long long x; long long row; };        // sample index of the frame's first sample, output row
+__device__ __forceinline__ ClipTask clip_task(const ClipTable& ct, const uint32_t g, const int c, const int hop, const int n_features) {
+    const auto desc = PE_UNIFORM_PTR(ClipDesc, ct.desc);
+    const auto prefix = PE_UNIFORM_PTR(uint32_t, ct.prefix);
+    const int j = (int)(g - prefix[c]);
+    return ClipTask{desc[c].start + (long long)(desc[c].first + j) * hop, (long long)c * n_features + desc[c].pad + j};
+}
+// the pad rows of the clips wave_id, wave_id + n_waves, ...: contiguous zeros at the head of each clip's window, stored by
+// the launch that computes the frames (before them: nothing waits for a store)
+template <class T>
+__device__ __forceinline__ void clip_zero_pads(const ClipTable& ct, T* out, const int width, const int n_features, const int wave_id, const int n_waves, const int lane) {
+    if (!out) return;
+    const auto desc = PE_UNIFORM_PTR(ClipDesc, ct.desc);
+    for (int c = wave_id; c < ct.n_clips; c += n_waves) {
+        const int n = desc[c].pad * width;
+        T* const p = out + (size_t)c * n_features * width;
+        for (int i = lane; i < n; i += 64) p[i] = T(0);
+    }
+}
+
+template <class R>
+struct MfccClipArgs {
+    StreamGeom geo;
+    ClipTable clips;
+    double* out;            // [n_clips][n_features][n_mfcc] float64, may be null
+    float* out_rows;        // [n_clips][n_features][16] float32 rows (coefficients + zero padding), may be null
+    double* out_mels;       // [n_clips][n_features][n_filt] float64 log-mel energies, may be null
+};
+
 // ---------------------------------------------------------------------------------------
 // GRU + Dense head (model.py:76-82), register-resident weights, one wave per 16-stream tile
 // ---------------------------------------------------------------------------------------
@@ -360,6 +426,9 @@ hipError_t launch_fused(const MfccStreamArgs<double>& m, const WaveTables<double
 hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1);
 hipError_t launch_mfcc_offline_f64(const MfccOfflineArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
 hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
+// the same frames for many clips at once, every clip's window padded in place (ClipTable)
+hipError_t launch_mfcc_clips_f64(const MfccClipArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
+hipError_t launch_mfcc_clips_f32(const MfccClipArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
 // units <= 32; 0 feats, 1 ring, 2 rows.  ms != null: the n_models networks of a K-model engine in the same ONE launch, model m
 // writing out + m * out_stride
 hipError_t launch_gru_small(const GruArgs& a, int input_mode, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1, long long out_stride = 0);

@@ -24,7 +24,7 @@ from .model import load_weights
 from .params import inject_params, pr, Vectorizer
 from .threshold_decoder import ThresholdDecoder
 from .util import pcm16_from
-from .vectorization import add_deltas, vectorize_raw
+from .vectorization import _require_clips, add_deltas, vectorize_raw
 
 
 class Runner(metaclass=ABCMeta):
@@ -75,6 +75,13 @@ class HipRunner(Runner):
 
     def run(self, inp: np.ndarray) -> float:
         return self.predict(np.asarray(inp)[np.newaxis])[0][0]
+
+    def predict_clips(self, audios) -> np.ndarray:
+        """``predict(np.array([vectorize(a) for a in audios]))`` (``vectorize_delta`` for use_delta models) without the
+        per-clip loop: every clip goes through the front end and the network in one device call each (the dataset tools'
+        path: train_data.py:195-196, then scripts/test.py:48-53 / eval.py:103-105).  -> raw outputs [N, 1]."""
+        audios = _require_clips(audios)             # (InvalidAudio for an empty clip, before the GPU is touched)
+        return self.engine.score_clips(audios, pr.max_samples)
 
     def evaluate(self, audio: np.ndarray, chunk_size: int = 4096) -> np.ndarray:
         """The reference's offline batch evaluation (precise/scripts/simulate.py:92-104) in one device

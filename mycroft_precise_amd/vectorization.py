@@ -99,10 +99,13 @@ def speechpy_filterbank(sample_rate: int, num_filt: int, n_bins: int) -> np.ndar
 _offline = {}
 
 
-def _offline_engine(vectorizer=Vectorizer.mfccs):
-    """One stateless engine per parameter set, created on first use."""
+def _offline_engine(vectorizer=Vectorizer.mfccs, windows=False):
+    """One stateless engine per parameter set, created on first use.  ``windows``: the caller takes whole n_features-row
+    windows from the engine (vectorize_clips), so the window length is part of the parameter set; frames alone
+    (vectorize_raw / vectorize_mels) do not depend on it."""
     from ._lib import HipEngine
-    key = (pr.sample_rate, pr.window_samples, pr.hop_samples, pr.n_fft, pr.n_filt, pr.n_mfcc, int(vectorizer))
+    key = (pr.sample_rate, pr.window_samples, pr.hop_samples, pr.n_fft, pr.n_filt, pr.n_mfcc, int(vectorizer),
+           pr.n_features if windows else None)
     eng = _offline.get(key)
     if eng is None:
         snap = pr.copy()
@@ -169,3 +172,25 @@ def vectorize(audio: np.ndarray) -> np.ndarray:
 def vectorize_delta(audio: np.ndarray) -> np.ndarray:
     """vectorize + deltas (vectorization.py:87-89)."""
     return add_deltas(vectorize(audio))
+
+
+def _require_clips(audios):
+    """the clips as arrays; InvalidAudio for an empty one, as vectorize_raw raises it -- before anything touches the GPU"""
+    audios = [np.asarray(a) for a in audios]
+    for i, a in enumerate(audios):
+        if a.size == 0:
+            raise InvalidAudio('Cannot vectorize empty audio! (clip %d)' % i)
+    return audios
+
+
+def vectorize_batch(audios) -> np.ndarray:
+    """``vectorize`` -- ``vectorize_delta`` with ``pr.use_delta`` -- of many clips of any lengths in ONE device call instead of
+    one per clip (train_data.py:195-196 calls the vectorizer once per wav of a data folder): -> [n, n_features, feature_size]
+    float64.  Honours ``pr.vectorizer``, ``pr.max_samples`` and ``pr.use_delta`` as the per-clip functions do."""
+    audios = _require_clips(audios)
+    if not audios:
+        return np.zeros((0, pr.n_features, pr.feature_size))
+    vec = int(pr.vectorizer)
+    eng = _offline_engine(Vectorizer.speechpy_mfccs if vec == Vectorizer.speechpy_mfccs else Vectorizer.mfccs, windows=True)
+    feats = eng.vectorize_clips(audios, pr.max_samples, mels=vec == Vectorizer.mels)
+    return np.stack([add_deltas(f) for f in feats]) if pr.use_delta else feats      # (add_deltas differences its FIRST axis: per clip)
