@@ -301,6 +301,58 @@ int pe_score_clips(pe_engine* e, const void* audio_host, int32_t sample_format, 
  * pass boundaries. */
 int pe_set_clip_pass_bytes(pe_engine* e, int64_t bytes);
 
+/* precise-simulate (scripts/simulate.py:106-129) and AnnoyanceEstimator.compute_nww_annoyances (annoyance_estimator.py:56-73)
+ * for a whole folder of long recordings in one call: per recording the whole-file MFCC, one prediction every hop_frames
+ * frames (pe_evaluate, above), a fresh TriggerDetector over the predictions, three sums, and a count of the predictions
+ * above each threshold of a table.
+ * Recording r is samples [offsets[r], offsets[r + 1]) of audio_host; audio_host / sample_format / offsets as
+ * pe_vectorize_clips takes them.  There is no crop.  A zero-length recording is allowed: it has no window (pe_evaluate with
+ * n_samples = 0; simulate.py:110 skips such files).  Frames and windows are counted per recording as pe_evaluate counts them:
+ * windows end at frames range(n_features, n_frames, hop_frames).  window_offsets[n_rec + 1] is the exclusive prefix sum of the
+ * window counts; pe_evaluate_clips_layout computes it on the host without any device work, so that a caller can size `out`.
+ * pe_evaluate_clips: out[n_models][max_windows]; model m, recording r, window j at out[m * max_windows + window_offsets[r] + j],
+ * bit for bit what pe_evaluate returns for that recording alone on this engine: the frames are the same function, and the
+ * recordings' rows are laid out so that pe_evaluate's network launch serves all of them at once.
+ * pe_simulate_scores: the metrics alone, over predictions the caller holds: raw[n_models][stride], recording r's at
+ * raw[m * stride + window_offsets[r] ...].  Every comparison is made on (double)p, the float32 prediction widened:
+ *   activated_chunks  p > chunk_threshold                                   ((predictions > sensitivity).sum(), simulate.py:119)
+ *   activations       True returns of TriggerDetector(chunk_size, sensitivity, trigger_level).update (runner.py:127-142: hot is
+ *                     p > 1.0 - sensitivity, rearm is -(8 * 2048) // chunk_size), fresh per (model, recording)  (simulate.py:114,120)
+ *   activation_sum    the sum of p in float64, in an order that depends on the recording's length alone: the same bits in
+ *                     every run, with any pass size and whatever else the call holds                          (simulate.py:121)
+ *   buckets_out[n_models][n_thresholds]: windows of ALL recordings of the call with p > thresholds[j]
+ *                     (annoyance_estimator.py:70-71).  thresholds: non-decreasing, no NaN, n_thresholds in 0..4096;
+ *                     n_thresholds = 0: buckets_out may be NULL.
+ * simulate.py compares against `sensitivity` at :119 and against `1 - sensitivity` at :114/:142, hence two arguments; the
+ * script passes its --threshold for both.  (numpy may make the :119 comparison in float32: it differs from this one only
+ * where a prediction equals the float32 rounding of the threshold.)
+ * pe_simulate_clips: pe_evaluate_clips and pe_simulate_scores in one call, the predictions staying on the device; out
+ * (may be NULL) receives them as pe_evaluate_clips lays them out.  metrics_out[n_models][n_rec].
+ * Passes as for pe_vectorize_clips (pe_set_clip_pass_bytes applies): whole recordings, at least one per pass -- a recording
+ * larger than the target travels alone -- and no result depends on the pass size.  One front-end launch, one network launch
+ * and the two metrics kernels per pass.  At most 2^31 - 1 frames per recording and windows per call.
+ * PE_ERR_INVALID, checked before any device work and with the outputs untouched: null pointers with n_rec > 0, n_rec < 0,
+ * decreasing offsets, offsets[0] != 0, hop_frames < 1, chunk_size < 1, sensitivity or chunk_threshold NaN, max_windows too
+ * small when out is given, thresholds out of order or NaN, n_thresholds out of range.  n_rec = 0 does nothing.  Stateless;
+ * updates of pe_update_async still in flight finish first. */
+typedef struct pe_sim_metric {      /* one (model, recording); simulate.py:116-122 */
+    int64_t n_windows;
+    int64_t activated_chunks;
+    int64_t activations;
+    double  activation_sum;
+} pe_sim_metric;
+int pe_evaluate_clips_layout(pe_engine* e, const int64_t* offsets_host, int32_t n_rec, int32_t hop_frames,
+                             int64_t* window_offsets_out);
+int pe_evaluate_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_rec,
+                      int32_t hop_frames, float* out_host, int64_t max_windows);
+int pe_simulate_scores(pe_engine* e, const float* raw_host, int64_t stride, const int64_t* window_offsets, int32_t n_rec,
+                       double chunk_threshold, double sensitivity, int32_t trigger_level, int32_t chunk_size,
+                       const double* thresholds, int32_t n_thresholds, pe_sim_metric* metrics_out, int64_t* buckets_out);
+int pe_simulate_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_rec,
+                      int32_t hop_frames, double chunk_threshold, double sensitivity, int32_t trigger_level, int32_t chunk_size,
+                      const double* thresholds, int32_t n_thresholds, pe_sim_metric* metrics_out, int64_t* buckets_out,
+                      float* out_host, int64_t max_windows);
+
 /* ThresholdDecoder.decode (threshold_decoder.py:45-57) and TriggerDetector.update
  * (runner/precise_runner/runner.py:127-142) for every stream, on the device.
  * pe_set_decoder: cd = the decoder's cumulative table (np.cumsum of the summed normal pdfs,
@@ -388,7 +440,8 @@ int pe_get_gru_tiling(const pe_engine* e);
  * With a fused launch mfcc_ms is the whole update and gru_ms is 0.
  * pe_vectorize_clips / pe_score_clips: the front-end launch and the network launch of the LAST pass only (every pass records
  * the same events again; one pass unless the audio exceeds the pass target).  pe_vectorize_clips launches no network:
- * gru_ms is 0 there. */
+ * gru_ms is 0 there.  pe_evaluate_clips / pe_simulate_clips: likewise the last pass that had a window; the metrics kernels
+ * run after the network launch and are not inside either figure. */
 int pe_set_timing(pe_engine* e, int32_t enabled);
 int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms);
 

@@ -82,6 +82,12 @@ EXPORTS = {
     'pe_vectorize_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     'pe_score_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     'pe_set_clip_pass_bytes': (C.c_int, [C.c_void_p, C.c_int64]),
+    'pe_evaluate_clips_layout': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    'pe_evaluate_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+    'pe_simulate_scores': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                     C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'pe_simulate_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                    C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     'pe_set_decoder': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
     'pe_set_trigger': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     'pe_set_decoder_model': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
@@ -98,6 +104,9 @@ EXPORTS = {
     'pe_set_timing': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_get_last_timing': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
+
+# pe_sim_metric: one (model, recording) of pe_simulate_scores / pe_simulate_clips
+SIM_METRIC = np.dtype([('n_windows', '<i8'), ('activated_chunks', '<i8'), ('activations', '<i8'), ('activation_sum', '<f8')])
 
 _lib = None
 
@@ -454,8 +463,82 @@ class HipEngine:
         return out
 
     def set_clip_pass_bytes(self, n_bytes: int):
-        """Test aid: audio bytes per pass of vectorize_clips / score_clips (default 256 MiB)."""
+        """Test aid: audio bytes per pass of vectorize_clips / score_clips / evaluate_clips / simulate_clips (default 256 MiB)."""
         self._check(self._lib.pe_set_clip_pass_bytes(self._h, int(n_bytes)))
+
+    def evaluate_clips_layout(self, offsets, hop_frames: int) -> np.ndarray:
+        """int64 sample offsets [n + 1] of n recordings -> int64 window offsets [n + 1]: the exclusive prefix sum of the
+        windows ``evaluate`` returns per recording (host arithmetic, pe_evaluate_clips_layout)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size < 1:
+            raise ValueError('offsets must hold n + 1 entries')
+        out = np.zeros(offsets.size, dtype=np.int64)
+        self._check(self._lib.pe_evaluate_clips_layout(self._h, offsets.ctypes.data, offsets.size - 1, int(hop_frames), out.ctypes.data))
+        return out
+
+    def _split(self, flat, window_offsets):
+        """[K?, total] predictions -> per recording [n_w, 1] ([K, n_w, 1]) views, as ``evaluate`` shapes them"""
+        return [flat[..., a:b, np.newaxis] for a, b in zip(window_offsets[:-1], window_offsets[1:])]
+
+    def evaluate_clips(self, audios, hop_frames: int) -> list:
+        """``evaluate`` (simulate.py:92-104) of every recording of a sequence in one call -- one front-end launch and one
+        network launch per pass instead of a call per recording: -> a list of raw outputs [n_w, 1] ([K, n_w, 1] on a K-model
+        engine), bit for bit what ``evaluate`` gives per recording.  An empty recording has no window."""
+        audio, offsets, fmt = self._clips(audios)
+        n = offsets.size - 1
+        woff = self.evaluate_clips_layout(offsets, hop_frames)
+        total = int(woff[-1])
+        out = np.empty(self._lead(max(total, 1)), dtype=np.float32)
+        if n:
+            self._check(self._lib.pe_evaluate_clips(self._h, audio.ctypes.data, fmt, offsets.ctypes.data, n, int(hop_frames),
+                                                    out.ctypes.data, out.shape[-1]))
+        return self._split(out[..., :total], woff)
+
+    @staticmethod
+    def _thresholds(thresholds):
+        thr = np.zeros(0) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        return thr, (thr.ctypes.data if thr.size else None)
+
+    def simulate_scores(self, scores, chunk_threshold: float, sensitivity: float, trigger_level: int, chunk_size: int,
+                        thresholds=None):
+        """The metrics of simulate.py:114-122 and the buckets of annoyance_estimator.py:70-71 over predictions the caller
+        holds (pe_simulate_scores): ``scores`` a sequence with one array of raw outputs per recording ([n_w] or [n_w, 1];
+        [K, n_w] or [K, n_w, 1] on a K-model engine).  -> (metrics, buckets): a SIM_METRIC array [n_rec] ([K, n_rec]) and
+        int64 [n_thresholds] ([K, n_thresholds]) counts of windows above each of ``thresholds`` (non-decreasing)."""
+        K = self.n_models
+        rows = [np.asarray(s, dtype=np.float32).reshape(K, -1) for s in scores]
+        n = len(rows)
+        woff = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([r.shape[1] for r in rows], out=woff[1:])
+        raw = np.zeros((K, max(int(woff[-1]), 1)), dtype=np.float32)
+        if n:
+            raw[:, :woff[-1]] = np.concatenate(rows, axis=1)
+        thr, thr_p = self._thresholds(thresholds)
+        metrics = np.zeros(self._lead(n), dtype=SIM_METRIC)
+        buckets = np.zeros(self._lead(thr.size), dtype=np.int64)
+        self._check(self._lib.pe_simulate_scores(self._h, raw.ctypes.data, raw.shape[1], woff.ctypes.data, n, float(chunk_threshold),
+                                                 float(sensitivity), int(trigger_level), int(chunk_size), thr_p, thr.size,
+                                                 metrics.ctypes.data if n else None, buckets.ctypes.data if thr.size else None))
+        return metrics, buckets
+
+    def simulate_clips(self, audios, hop_frames: int, chunk_threshold: float, sensitivity: float, trigger_level: int,
+                       chunk_size: int, thresholds=None, return_scores: bool = False):
+        """``evaluate_clips`` and ``simulate_scores`` in one call, the predictions staying on the device (pe_simulate_clips):
+        -> (metrics, buckets, scores): scores the list ``evaluate_clips`` returns, or None without ``return_scores``."""
+        audio, offsets, fmt = self._clips(audios)
+        n = offsets.size - 1
+        woff = self.evaluate_clips_layout(offsets, hop_frames)
+        total = int(woff[-1])
+        thr, thr_p = self._thresholds(thresholds)
+        metrics = np.zeros(self._lead(n), dtype=SIM_METRIC)
+        buckets = np.zeros(self._lead(thr.size), dtype=np.int64)
+        out = np.empty(self._lead(max(total, 1)), dtype=np.float32) if return_scores else None
+        if n:
+            self._check(self._lib.pe_simulate_clips(self._h, audio.ctypes.data, fmt, offsets.ctypes.data, n, int(hop_frames),
+                                                    float(chunk_threshold), float(sensitivity), int(trigger_level), int(chunk_size),
+                                                    thr_p, thr.size, metrics.ctypes.data, buckets.ctypes.data if thr.size else None,
+                                                    out.ctypes.data if return_scores else None, out.shape[-1] if return_scores else 0))
+        return metrics, buckets, (self._split(out[..., :total], woff) if return_scores else None)
 
     def set_decoder(self, decoder, model=None):
         """Upload a ThresholdDecoder (its cumulative table and scalars) for pe_decode*: for every model, or for ``model``."""

@@ -110,6 +110,9 @@ struct pe_engine {
     // staging for the host entry points (grown on demand)
     DeviceBuf st_pcm, st_out, st_feats, st_mask, st_audio, st_mfcc, st_conf, st_fired, st_ids;
     DeviceBuf st_clips;                     // pe_vectorize_clips / pe_score_clips: the clip table of a pass
+    // pe_evaluate_clips / pe_simulate_*: the tables of a pass, its padded predictions, the call's thresholds + histogram +
+    // metrics, a pass's mask words + partial sums
+    DeviceBuf st_recs, st_pred, st_sim, st_simw;
     int64_t clip_pass_bytes = kClipPassBytes;  // audio bytes a pass of those entry points stages (pe_set_clip_pass_bytes: tests)
     std::vector<uint8_t> seen_ids;          // pe_update_subset: duplicate check of the host entry point
     // timing
@@ -1275,7 +1278,7 @@ int pe_destroy(pe_engine* e) {
     (void)hipSetDevice(e->device);
     (void)drain_async(e);
     for (void* p : e->allocs) (void)hipFree(p);
-    for (DeviceBuf* b : {&e->st_pcm, &e->st_out, &e->st_feats, &e->st_mask, &e->st_audio, &e->st_mfcc, &e->st_conf, &e->st_fired, &e->st_ids, &e->st_clips})
+    for (DeviceBuf* b : {&e->st_pcm, &e->st_out, &e->st_feats, &e->st_mask, &e->st_audio, &e->st_mfcc, &e->st_conf, &e->st_fired, &e->st_ids, &e->st_clips, &e->st_recs, &e->st_pred, &e->st_sim, &e->st_simw})
         if (b->p) (void)hipFree(b->p);
     for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->s_compute) (void)hipStreamSynchronize(e->s_compute);
@@ -1793,6 +1796,285 @@ int pe_score_clips(pe_engine* e, const void* audio_host, int32_t sample_format, 
                    int64_t max_samples, float* out_host) {
     if (e && n_clips > 0 && !out_host) return fail(e, PE_ERR_INVALID, "null argument to pe_score_clips");
     return run_clips(e, "pe_score_clips", audio_host, sample_format, offsets_host, n_clips, max_samples, false, nullptr, out_host);
+}
+
+namespace {
+static_assert(sizeof(pe_sim_metric) == sizeof(SimMetric) && sizeof(SimMetric) == 32, "pe_sim_metric is what the device writes");
+
+// what pe_simulate_scores / pe_simulate_clips compute besides predictions (null for pe_evaluate_clips)
+struct SimRequest {
+    double chunk_threshold, sensitivity;
+    int32_t trigger_level, chunk_size;
+    const double* thresholds; int32_t n_thresholds;
+    pe_sim_metric* metrics_out; int64_t* buckets_out;
+};
+int check_sim_request(pe_engine* e, const char* who, const SimRequest& q) {
+    if (!q.metrics_out) return fail(e, PE_ERR_INVALID, "null argument to %s (metrics_out)", who);
+    if (q.chunk_size < 1) return fail(e, PE_ERR_INVALID, "%s: chunk_size must be >= 1, got %d", who, q.chunk_size);
+    if (q.sensitivity != q.sensitivity) return fail(e, PE_ERR_INVALID, "%s: sensitivity is NaN", who);
+    if (q.chunk_threshold != q.chunk_threshold) return fail(e, PE_ERR_INVALID, "%s: chunk_threshold is NaN", who);
+    if (q.n_thresholds < 0 || q.n_thresholds > 4096) return fail(e, PE_ERR_INVALID, "%s: n_thresholds must lie in 0..4096, got %d", who, q.n_thresholds);
+    if (q.n_thresholds > 0 && (!q.thresholds || !q.buckets_out)) return fail(e, PE_ERR_INVALID, "null argument to %s (thresholds / buckets_out with n_thresholds = %d)", who, q.n_thresholds);
+    for (int32_t j = 0; j < q.n_thresholds; ++j) {
+        if (q.thresholds[j] != q.thresholds[j]) return fail(e, PE_ERR_INVALID, "%s: thresholds[%d] is NaN", who, j);
+        if (j && q.thresholds[j] < q.thresholds[j - 1]) return fail(e, PE_ERR_INVALID, "%s: thresholds decrease at %d (%g after %g)", who, j, q.thresholds[j], q.thresholds[j - 1]);
+    }
+    return PE_OK;
+}
+// windows of every recording as pe_evaluate counts them (simulate.py:96-99), as an exclusive prefix sum [n_rec + 1]
+int recording_layout(pe_engine* e, const char* who, const int64_t* offsets, int32_t n_rec, int32_t hop_frames, std::vector<int64_t>& woff) {
+    if (hop_frames < 1) return fail(e, PE_ERR_INVALID, "%s: hop_frames must be >= 1 (chunk_size // hop_samples), got %d", who, hop_frames);
+    if (offsets[0] != 0) return fail(e, PE_ERR_INVALID, "%s: offsets[0] must be 0, got %lld", who, (long long)offsets[0]);
+    const int64_t T = e->prm.n_features;
+    woff.assign((size_t)n_rec + 1, 0);
+    for (int32_t r = 0; r < n_rec; ++r) {
+        if (offsets[r + 1] < offsets[r]) return fail(e, PE_ERR_INVALID, "%s: offsets decrease at recording %d (%lld after %lld)", who, r, (long long)offsets[r + 1], (long long)offsets[r]);
+        const int64_t n_frames = frames_of_buffer(e->prm, offsets[r + 1] - offsets[r]);
+        const int64_t n_windows = n_frames > T ? (n_frames - T + hop_frames - 1) / hop_frames : 0;
+        // frames of one launch are 32-bit tasks, and a recording is never split
+        if (n_frames > 0x7fffffff) return fail(e, PE_ERR_INVALID, "%s: recording %d has %lld frames, more than one pass holds (2^31 - 1)", who, r, (long long)n_frames);
+        woff[(size_t)r + 1] = woff[(size_t)r] + n_windows;
+        if (woff[(size_t)r + 1] > 0x7fffffff) return fail(e, PE_ERR_INVALID, "%s: more than 2^31 - 1 windows in one call (at recording %d)", who, r);
+    }
+    return PE_OK;
+}
+
+// the call-wide device side of a SimRequest: thresholds, a zeroed histogram [K][n_thresholds + 1], metrics [K][n_rec]
+struct SimDevice {
+    double* thresholds; unsigned long long* hist; SimMetric* metrics;
+    double trigger_threshold; int rearm;
+};
+int sim_begin(pe_engine* e, const SimRequest& q, int32_t n_rec, SimDevice& d) {
+    const size_t K = (size_t)e->n_models, nb = (size_t)q.n_thresholds + 1;
+    const size_t tb = (size_t)q.n_thresholds * sizeof(double), hb = K * nb * sizeof(unsigned long long), mb = K * (size_t)n_rec * sizeof(SimMetric);
+    int rc;
+    if ((rc = ensure(e, e->st_sim, tb + hb + mb))) return rc;
+    char* p = static_cast<char*>(e->st_sim.p);
+    d.thresholds = reinterpret_cast<double*>(p);
+    d.hist = q.n_thresholds ? reinterpret_cast<unsigned long long*>(p + tb) : nullptr;
+    d.metrics = reinterpret_cast<SimMetric*>(p + tb + hb);
+    d.trigger_threshold = 1.0 - q.sensitivity;                                  // runner.py:142
+    d.rearm = (int)-((8 * 2048 + (int64_t)q.chunk_size - 1) / q.chunk_size);    // -(8 * 2048) // chunk_size, runner.py:150
+    if (q.n_thresholds) {
+        PE_HIP(e, hipMemcpy(d.thresholds, q.thresholds, tb, hipMemcpyHostToDevice));
+        PE_HIP(e, hipMemset(d.hist, 0, hb));
+    }
+    return PE_OK;
+}
+// metrics and histogram back; buckets[m][j] = windows above thresholds[j] = the bins above j (a suffix sum)
+int sim_end(pe_engine* e, const SimRequest& q, int32_t n_rec, const SimDevice& d) {
+    const size_t K = (size_t)e->n_models, nb = (size_t)q.n_thresholds + 1;
+    PE_HIP(e, hipMemcpy(q.metrics_out, d.metrics, K * (size_t)n_rec * sizeof(SimMetric), hipMemcpyDeviceToHost));
+    if (!q.n_thresholds) return PE_OK;
+    std::vector<unsigned long long> hist(K * nb);
+    PE_HIP(e, hipMemcpy(hist.data(), d.hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t m = 0; m < K; ++m) {
+        int64_t above = 0;
+        for (size_t j = nb - 1; j-- > 0;) {
+            above += (int64_t)hist[m * nb + j + 1];
+            q.buckets_out[m * (nb - 1) + j] = above;
+        }
+    }
+    return PE_OK;
+}
+// the metrics kernels over `n` recordings whose SimRec table and word prefix sum the caller has built on the host
+int sim_launch(pe_engine* e, const SimRequest* q, const SimDevice* d, const std::vector<SimRec>& recs, const std::vector<uint32_t>& word_prefix,
+               const float* src, int64_t src_stride, float* dst, int64_t dst_stride, int64_t first_rec, int32_t n_rec_call) {
+    const int n = (int)recs.size();
+    const uint32_t n_words = word_prefix[(size_t)n];
+    if (!q && !n_words) return PE_OK;           // nothing to compact
+    const size_t K = (size_t)e->n_models, rb = (size_t)n * sizeof(SimRec), pb = ((size_t)n + 1) * sizeof(uint32_t);
+    int rc;
+    if ((rc = ensure(e, e->st_recs, rb + pb))) return rc;
+    PE_HIP(e, hipMemcpy(e->st_recs.p, recs.data(), rb, hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(static_cast<char*>(e->st_recs.p) + rb, word_prefix.data(), pb, hipMemcpyHostToDevice));
+    SimArgs a{};
+    a.recs = static_cast<const SimRec*>(e->st_recs.p);
+    a.word_prefix = reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->st_recs.p) + rb);
+    a.n_rec = n; a.n_words = n_words;
+    a.src = src; a.src_stride = src_stride; a.dst = dst; a.dst_stride = dst_stride;
+    if (q) {
+        const size_t wb = K * n_words * sizeof(unsigned long long);
+        if ((rc = ensure(e, e->st_simw, 2 * wb + K * n_words * sizeof(uint32_t)))) return rc;
+        char* p = static_cast<char*>(e->st_simw.p);
+        a.trig = reinterpret_cast<unsigned long long*>(p);
+        a.partial = reinterpret_cast<double*>(p + wb);
+        a.chunk_count = reinterpret_cast<uint32_t*>(p + 2 * wb);
+        a.chunk_threshold = q->chunk_threshold; a.trigger_threshold = d->trigger_threshold;
+        a.trigger_level = q->trigger_level; a.rearm = d->rearm;
+        a.thresholds = d->thresholds; a.n_thresholds = q->n_thresholds; a.hist = d->hist;
+        a.metrics = d->metrics + first_rec; a.metric_stride = n_rec_call;
+    }
+    PE_HIP(e, launch_simulate(a, e->n_models, e->n_cus, nullptr));
+    return PE_OK;
+}
+
+// pe_evaluate_clips (q null) / pe_simulate_clips: validation, then pass by pass one copy in, the front-end launch, ONE network
+// launch over the padded row layout (pe_common.h: RecDesc), the metrics kernels; one copy out at the end
+int run_recordings(pe_engine* e, const char* who, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_rec,
+                   int32_t hop_frames, const SimRequest* q, float* out_host, int64_t max_windows) {
+    if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
+    if (n_rec < 0) return fail(e, PE_ERR_INVALID, "%s: n_rec=%d", who, n_rec);
+    if (n_rec == 0) return PE_OK;
+    if (!offsets_host || !audio_host || (!q && !out_host)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (sample_format != 0 && sample_format != 1) return fail(e, PE_ERR_INVALID, "%s: sample_format must be 0 (float64) or 1 (float32), got %d", who, sample_format);
+    int rc;
+    std::vector<int64_t> woff;
+    if ((rc = recording_layout(e, who, offsets_host, n_rec, hop_frames, woff))) return rc;
+    if (q && (rc = check_sim_request(e, who, *q))) return rc;
+    const int64_t total = woff[(size_t)n_rec];
+    if (out_host && max_windows < total) return fail(e, PE_ERR_INVALID, "%s: output holds %lld windows per model, need %lld", who, (long long)max_windows, (long long)total);
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    const int64_t T = e->prm.n_features, hop = hop_frames;
+    const size_t elem = sample_format == 1 ? sizeof(float) : sizeof(double);
+    SimDevice dev{};
+    if (q && (rc = sim_begin(e, *q, n_rec, dev))) return rc;
+    if (out_host && (rc = ensure(e, e->st_out, (size_t)e->n_models * (size_t)total * sizeof(float)))) return rc;
+    std::vector<RecDesc> desc;
+    std::vector<uint32_t> prefix, word_prefix;
+    std::vector<SimRec> sim;
+    const bool t = e->timing;
+    for (int32_t c0 = 0; c0 < n_rec;) {
+        // the recordings of this pass: at least one, then as many as stay within the byte target (and 32-bit frame tasks / windows)
+        desc.clear(); prefix.clear(); word_prefix.clear(); sim.clear();
+        int64_t rows = 0, tasks = 0, words = 0;         // rows: the first free row, a multiple of hop_frames
+        int32_t c1 = c0;
+        for (; c1 < n_rec; ++c1) {
+            const int64_t W = woff[(size_t)c1 + 1] - woff[(size_t)c1];
+            const int64_t used = W ? (W - 1) * hop + T : 0;            // frames its windows read; without a window, none
+            if (c1 > c0 && ((offsets_host[c1 + 1] - offsets_host[c0]) * (int64_t)elem > e->clip_pass_bytes || tasks + used > 0x7fffffff ||
+                            (rows + used + hop) / hop > 0x7fffffff)) break;
+            desc.push_back(RecDesc{offsets_host[c1] - offsets_host[c0], rows});
+            sim.push_back(SimRec{rows / hop, woff[(size_t)c1] - woff[(size_t)c0], W});
+            prefix.push_back((uint32_t)tasks);
+            word_prefix.push_back((uint32_t)words);
+            tasks += used;
+            words += (W + 63) / 64;
+            rows = (rows + used + hop - 1) / hop * hop;
+        }
+        prefix.push_back((uint32_t)tasks);
+        word_prefix.push_back((uint32_t)words);
+        const int n = c1 - c0;
+        // windows of the launch: up to the last one of the last recording that has any; its T rows end the row buffer
+        int64_t padded = 0;
+        for (int i = 0; i < n; ++i) if (sim[(size_t)i].n_windows) padded = sim[(size_t)i].src0 + sim[(size_t)i].n_windows;
+        if (padded > 0) {
+            const int64_t base = offsets_host[c0], n_samples = offsets_host[c1] - base;
+            const int64_t n_rows = (padded - 1) * hop + T;
+            const size_t db = (size_t)n * sizeof(RecDesc), pb = ((size_t)n + 1) * sizeof(uint32_t), rb = (size_t)n_rows * e->row_floats * sizeof(float);
+            if ((rc = ensure(e, e->st_audio, (size_t)n_samples * elem))) return rc;
+            if ((rc = ensure(e, e->st_clips, db + pb))) return rc;
+            if ((rc = ensure(e, e->st_feats, rb))) return rc;
+            if ((rc = ensure(e, e->st_pred, (size_t)e->n_models * (size_t)padded * sizeof(float)))) return rc;
+            PE_HIP(e, hipMemcpy(e->st_audio.p, static_cast<const char*>(audio_host) + (size_t)base * elem, (size_t)n_samples * elem, hipMemcpyHostToDevice));
+            PE_HIP(e, hipMemcpy(e->st_clips.p, desc.data(), db, hipMemcpyHostToDevice));
+            PE_HIP(e, hipMemcpy(static_cast<char*>(e->st_clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
+            PE_HIP(e, hipMemsetAsync(e->st_feats.p, 0, rb, nullptr));      // the rows between two recordings: read by the windows that are dropped
+            const RecTable rt{static_cast<const RecDesc*>(e->st_clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->st_clips.p) + db),
+                              n, (uint32_t)tasks, e->st_audio.p, sample_format == 1 ? 1 : 0};
+            float* dev_rows = static_cast<float*>(e->st_feats.p);
+            if (t) PE_HIP(e, hipEventRecord(e->ev[0], nullptr));
+            if (e->general) {
+                if (e->prm.mfcc_precision == 0) {
+                    GeneralRecArgs<double> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
+                    PE_HIP(e, launch_general_recs_f64(a, e->n_cus, nullptr));
+                } else {
+                    GeneralRecArgs<float> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
+                    PE_HIP(e, launch_general_recs_f32(a, e->n_cus, nullptr));
+                }
+            } else if (e->prm.mfcc_precision == 0) {
+                MfccRecArgs<double> a{geom(e), rt, dev_rows};
+                PE_HIP(e, launch_mfcc_recs_f64(a, tables<double>(e), e->n_cus, nullptr));
+            } else {
+                MfccRecArgs<float> a{geom(e), rt, dev_rows};
+                PE_HIP(e, launch_mfcc_recs_f32(a, tables<float>(e), e->n_cus, nullptr));
+            }
+            if (t) PE_HIP(e, hipEventRecord(e->ev[1], nullptr));
+            // pe_evaluate's network launch: window w = rows [w hop_frames, + T) -- recording i's window j is window src0 + j
+            GruArgs g = gru_args(e);
+            g.n_streams = (int)padded;
+            g.feats = dev_rows;
+            g.row_stride = hop_frames;
+            g.out = static_cast<float*>(e->st_pred.p);
+            g.waves_per_tile = 1;
+            if ((rc = launch_networks(e, g, 2, nullptr, padded))) return rc;
+            if (t) { PE_HIP(e, hipEventRecord(e->ev[2], nullptr)); e->ev_valid = true; e->ev_has_gru = true; }
+        }
+        // (a pass without a window still has metrics: all zero)
+        if ((rc = sim_launch(e, q, q ? &dev : nullptr, sim, word_prefix, static_cast<const float*>(e->st_pred.p), padded,
+                             out_host ? static_cast<float*>(e->st_out.p) + woff[(size_t)c0] : nullptr, total, c0, n_rec))) return rc;
+        c0 = c1;
+    }
+    if (out_host && total > 0)
+        for (int m = 0; m < e->n_models; ++m)           // out_host[K][max_windows]
+            PE_HIP(e, hipMemcpy(out_host + (size_t)m * max_windows, static_cast<float*>(e->st_out.p) + (size_t)m * total, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+    return q ? sim_end(e, *q, n_rec, dev) : PE_OK;
+}
+}  // namespace
+
+int pe_evaluate_clips_layout(pe_engine* e, const int64_t* offsets_host, int32_t n_rec, int32_t hop_frames, int64_t* window_offsets_out) {
+    const char* who = "pe_evaluate_clips_layout";
+    if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
+    if (n_rec < 0) return fail(e, PE_ERR_INVALID, "%s: n_rec=%d", who, n_rec);
+    if (!window_offsets_out || (n_rec > 0 && !offsets_host)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    std::vector<int64_t> woff(1, 0);
+    int rc;
+    if (n_rec > 0 && (rc = recording_layout(e, who, offsets_host, n_rec, hop_frames, woff))) return rc;
+    std::copy(woff.begin(), woff.end(), window_offsets_out);
+    return PE_OK;
+}
+
+int pe_evaluate_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_rec,
+                      int32_t hop_frames, float* out_host, int64_t max_windows) {
+    return run_recordings(e, "pe_evaluate_clips", audio_host, sample_format, offsets_host, n_rec, hop_frames, nullptr, out_host, max_windows);
+}
+
+int pe_simulate_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_rec,
+                      int32_t hop_frames, double chunk_threshold, double sensitivity, int32_t trigger_level, int32_t chunk_size,
+                      const double* thresholds, int32_t n_thresholds, pe_sim_metric* metrics_out, int64_t* buckets_out,
+                      float* out_host, int64_t max_windows) {
+    const SimRequest q{chunk_threshold, sensitivity, trigger_level, chunk_size, thresholds, n_thresholds, metrics_out, buckets_out};
+    return run_recordings(e, "pe_simulate_clips", audio_host, sample_format, offsets_host, n_rec, hop_frames, &q, out_host, max_windows);
+}
+
+int pe_simulate_scores(pe_engine* e, const float* raw_host, int64_t stride, const int64_t* window_offsets, int32_t n_rec,
+                       double chunk_threshold, double sensitivity, int32_t trigger_level, int32_t chunk_size,
+                       const double* thresholds, int32_t n_thresholds, pe_sim_metric* metrics_out, int64_t* buckets_out) {
+    const char* who = "pe_simulate_scores";
+    if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
+    if (n_rec < 0) return fail(e, PE_ERR_INVALID, "%s: n_rec=%d", who, n_rec);
+    if (n_rec == 0) return PE_OK;
+    if (!window_offsets || !raw_host) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (window_offsets[0] != 0) return fail(e, PE_ERR_INVALID, "%s: window_offsets[0] must be 0, got %lld", who, (long long)window_offsets[0]);
+    for (int32_t r = 0; r < n_rec; ++r)
+        if (window_offsets[r + 1] < window_offsets[r]) return fail(e, PE_ERR_INVALID, "%s: window_offsets decrease at recording %d (%lld after %lld)", who, r, (long long)window_offsets[r + 1], (long long)window_offsets[r]);
+    const int64_t total = window_offsets[n_rec];
+    if (total > 0x7fffffff) return fail(e, PE_ERR_INVALID, "%s: more than 2^31 - 1 windows in one call", who);
+    if (stride < total) return fail(e, PE_ERR_INVALID, "%s: stride %lld is less than the %lld windows of a model", who, (long long)stride, (long long)total);
+    const SimRequest q{chunk_threshold, sensitivity, trigger_level, chunk_size, thresholds, n_thresholds, metrics_out, buckets_out};
+    int rc;
+    if ((rc = check_sim_request(e, who, q))) return rc;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    SimDevice dev{};
+    if ((rc = sim_begin(e, q, n_rec, dev))) return rc;
+    if ((rc = ensure(e, e->st_pred, (size_t)e->n_models * (size_t)total * sizeof(float)))) return rc;
+    if (total > 0)
+        for (int m = 0; m < e->n_models; ++m)
+            PE_HIP(e, hipMemcpy(static_cast<float*>(e->st_pred.p) + (size_t)m * total, raw_host + (size_t)m * stride, (size_t)total * sizeof(float), hipMemcpyHostToDevice));
+    std::vector<SimRec> sim((size_t)n_rec);
+    std::vector<uint32_t> word_prefix((size_t)n_rec + 1);
+    int64_t words = 0;
+    for (int32_t r = 0; r < n_rec; ++r) {
+        const int64_t W = window_offsets[r + 1] - window_offsets[r];
+        sim[(size_t)r] = SimRec{window_offsets[r], 0, W};
+        word_prefix[(size_t)r] = (uint32_t)words;
+        words += (W + 63) / 64;
+    }
+    word_prefix[(size_t)n_rec] = (uint32_t)words;
+    if ((rc = sim_launch(e, &q, &dev, sim, word_prefix, static_cast<const float*>(e->st_pred.p), total, nullptr, 0, 0, n_rec))) return rc;
+    return sim_end(e, q, n_rec, dev);
 }
 
 int pe_set_clip_pass_bytes(pe_engine* e, int64_t bytes) {

@@ -101,6 +101,10 @@ __global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_e
 PE_KERNEL_PAIR((template <class R, class SH>), PE_FRAME_KERNEL(64 * kFrameWaves, SH::WPE), mfcc_clips_kernel,
                (const MfccClipArgs<R> a, const WaveTables<R> t),
                { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; mfcc_clip_frames<R, SH>(a, t, smem); })
+// many whole recordings in one launch (pe_evaluate_clips / pe_simulate_clips): frame tasks found in the recording table (RecTable)
+PE_KERNEL_PAIR((template <class R, class SH>), PE_FRAME_KERNEL(64 * kFrameWaves, SH::WPE), mfcc_recs_kernel,
+               (const MfccRecArgs<R> a, const WaveTables<R> t),
+               { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; mfcc_rec_frames<R, SH>(a, t, smem); })
 
 // ---- network shapes: the tile function of a workgroup, its threads and its LDS, said once -------------------------------
 // run(a, tile, smem) is the whole network of tile `tile` of the launch `a`.  The one-model kernel of a shape (the names
@@ -524,6 +528,17 @@ static hipError_t launch_clips(const MfccClipArgs<R>& a, const WaveTables<R>& t,
 hipError_t launch_mfcc_clips_f64(const MfccClipArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s) { return launch_clips<double>(a, t, n_cus, s); }
 hipError_t launch_mfcc_clips_f32(const MfccClipArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s) { return launch_clips<float>(a, t, n_cus, s); }
 
+template <class R>
+static hipError_t launch_recs(const MfccRecArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s) {
+    if (a.recs.n_tasks == 0) return hipSuccess;
+    if (!blob_matches_shape(t)) return hipErrorInvalidValue;
+    if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_recs_kernel, (ShapeStock), dim3(frame_blocks((long long)a.recs.n_tasks, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
+    else PE_LAUNCH_R(R, mfcc_recs_kernel, (ShapeAny), dim3(frame_blocks((long long)a.recs.n_tasks, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
+    return hipGetLastError();
+}
+hipError_t launch_mfcc_recs_f64(const MfccRecArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s) { return launch_recs<double>(a, t, n_cus, s); }
+hipError_t launch_mfcc_recs_f32(const MfccRecArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s) { return launch_recs<float>(a, t, n_cus, s); }
+
 int gru_small_regs(int units) { return (units + 3) / 4; }
 int gru_small_tiles(int units) { return (3 * gru_small_regs(units) + 3) / 4; }
 
@@ -753,6 +768,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ?
 PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false>), (__launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4)))), mfcc_general_clips_kernel,
                (const GeneralClipArgs<R> a),
                { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; general_clips<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), (int)blockIdx.x, (int)gridDim.x, threadIdx.x); })
+PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false>), (__launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4)))), mfcc_general_recs_kernel,
+               (const GeneralRecArgs<R> a),
+               { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; general_recs<R, BITS, BLUE>(a, reinterpret_cast<R*>(smem), (int)blockIdx.x, (int)gridDim.x, threadIdx.x); })
 // the transform length as a template argument: n_fft not a power of two (chirp) = Bluestein over L = 2^log2m points
 template <class F>
 static bool with_general_bits(const GeneralTables& tab, F&& f) {
@@ -790,6 +808,18 @@ static hipError_t launch_general_clips_t(const GeneralClipArgs<R>& a, int n_cus,
 }
 hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s) { return launch_general_clips_t<double>(a, n_cus, s); }
 hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s) { return launch_general_clips_t<float>(a, n_cus, s); }
+template <class R>
+static hipError_t launch_general_recs_t(const GeneralRecArgs<R>& a, int n_cus, hipStream_t s) {
+    if (a.recs.n_tasks == 0) return hipSuccess;
+    const long long cap = (long long)n_cus * 16;
+    const unsigned blocks = (unsigned)((long long)a.recs.n_tasks < cap ? (long long)a.recs.n_tasks : cap);
+    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const bool ok = with_general_bits(a.tab, [&](auto B, auto BLUE) {
+        PE_LAUNCH_R(R, mfcc_general_recs_kernel, (PE_CONST(B), PE_CONST(BLUE)), dim3(blocks), dim3(64), lds, s, a); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+hipError_t launch_general_recs_f64(const GeneralRecArgs<double>& a, int n_cus, hipStream_t s) { return launch_general_recs_t<double>(a, n_cus, s); }
+hipError_t launch_general_recs_f32(const GeneralRecArgs<float>& a, int n_cus, hipStream_t s) { return launch_general_recs_t<float>(a, n_cus, s); }
 hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s) { return launch_general_stream_t<double>(a, s); }
 hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s) { return launch_general_stream_t<float>(a, s); }
 hipError_t launch_general_offline_f64(const GeneralOfflineArgs<double>& a, int n_cus, hipStream_t s) { return launch_general_offline_t<double>(a, n_cus, s); }
@@ -984,6 +1014,99 @@ hipError_t launch_clear_activation(const uint8_t* mask, int32_t* activation, int
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s) {
     if (a.n_streams == 0) return hipSuccess;
     hipLaunchKernelGGL(decode_kernel, dim3((a.n_streams + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- the metrics of simulate.py:114-122 / annoyance_estimator.py:70-71 (pe_common.h: SimArgs) --------------------------
+// One wave per word of 64 predictions of one recording, model blockIdx.y.  Every comparison is made on the prediction
+// widened to float64.  The word's sum is a butterfly over its 64 slots (absent ones add +0.0): a fixed shape, so the sum of a
+// recording depends on its predictions alone.  The bin of a prediction is the number of thresholds below it (a NaN
+// prediction: none); a workgroup counts bins in LDS and adds what it counted to the global histogram with integer atomics.
+constexpr int kSimWaves = 4;
+__global__ __launch_bounds__(64 * kSimWaves) void sim_scan_kernel(const SimArgs a) {
+    extern __shared__ uint32_t sim_bins[];
+    const int m = (int)blockIdx.y, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_bins = a.n_thresholds + 1;
+    if (a.hist) {
+        for (int i = threadIdx.x; i < n_bins; i += 64 * kSimWaves) sim_bins[i] = 0;
+        __syncthreads();
+    }
+    const auto recs = PE_UNIFORM_PTR(SimRec, a.recs);
+    const auto word_prefix = PE_UNIFORM_PTR(uint32_t, a.word_prefix);
+    const float* const src = a.src + (size_t)m * a.src_stride;
+    float* const dst = a.dst ? a.dst + (size_t)m * a.dst_stride : nullptr;
+    const size_t row = (size_t)m * a.n_words;
+    int r = 0;
+    for (uint32_t w = blockIdx.x * kSimWaves + wave; w < a.n_words; w += gridDim.x * kSimWaves) {
+        r = slot_of_task(a.word_prefix, a.n_rec, w, r);
+        const long long j = (long long)(w - word_prefix[r]) * 64 + lane;
+        const bool valid = j < recs[r].n_windows;
+        const float pf = valid ? src[recs[r].src0 + j] : 0.0f;
+        if (dst && valid) dst[recs[r].dst0 + j] = pf;
+        const double p = (double)pf;
+        const unsigned long long chunk = __ballot(valid && p > a.chunk_threshold), trig = __ballot(valid && p > a.trigger_threshold);
+        double sum = p;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);        // (a + b = b + a: every lane ends with the same bits)
+        if (a.trig && lane == 0) {
+            a.trig[row + w] = trig;
+            a.chunk_count[row + w] = (uint32_t)__popcll(chunk);
+            a.partial[row + w] = sum;
+        }
+        if (a.hist && valid) {
+            int lo = 0, hi = a.n_thresholds;            // thresholds[0 .. lo) < p, thresholds[hi ..) are not
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (a.thresholds[mid] < p) lo = mid + 1; else hi = mid;
+            }
+            atomicAdd(&sim_bins[lo], 1u);
+        }
+    }
+    if (a.hist) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < n_bins; i += 64 * kSimWaves)
+            if (sim_bins[i]) atomicAdd(&a.hist[(size_t)m * n_bins + i], (unsigned long long)sim_bins[i]);
+    }
+}
+// One lane per (recording, model blockIdx.y): TriggerDetector.update (runner.py:127-142, decode_stream above) over the
+// recording's trigger bits in order, from a fresh detector.  A word without a hot bit met with activation >= 0 only decays the
+// counter: the common case, taken in one step.  The word sums are added in word order.
+__global__ void sim_fold_kernel(const SimArgs a) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x, m = (int)blockIdx.y;
+    if (r >= a.n_rec) return;
+    const long long n = a.recs[r].n_windows;
+    const size_t first = (size_t)m * a.n_words + a.word_prefix[r];
+    int act = 0;
+    long long fired = 0, chunks = 0;
+    double sum = 0.0;
+    for (long long k = 0; k * 64 < n; ++k) {
+        const unsigned long long word = a.trig[first + k];
+        chunks += a.chunk_count[first + k];
+        sum += a.partial[first + k];
+        const int bits = n - k * 64 < 64 ? (int)(n - k * 64) : 64;
+        if (word == 0 && act >= 0) { act = act > bits ? act - bits : 0; continue; }
+        for (int b = 0; b < bits; ++b) {
+            const bool hot = (word >> b) & 1;
+            if (!hot && act >= 0) {
+                if (act > 0) act -= 1;
+            } else {
+                act += 1;
+                const bool f = act > a.trigger_level;
+                if (f || (hot && act < 0)) act = a.rearm;
+                fired += f ? 1 : 0;
+            }
+        }
+    }
+    a.metrics[(size_t)m * a.metric_stride + r] = SimMetric{n, chunks, fired, sum};
+}
+hipError_t launch_simulate(const SimArgs& a, int n_models, int n_cus, hipStream_t s) {
+    if (a.n_rec <= 0 || n_models < 1) return hipSuccess;
+    if (a.n_words) {
+        const long long want = ((long long)a.n_words + kSimWaves - 1) / kSimWaves, cap = (long long)n_cus * 8;
+        hipLaunchKernelGGL(sim_scan_kernel, dim3((unsigned)(want < cap ? want : cap), n_models), dim3(64 * kSimWaves),
+                           a.hist ? (size_t)(a.n_thresholds + 1) * sizeof(uint32_t) : 0, s, a);
+    }
+    if (a.metrics) hipLaunchKernelGGL(sim_fold_kernel, dim3((a.n_rec + 63) / 64, n_models), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

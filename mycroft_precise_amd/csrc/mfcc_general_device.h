@@ -582,7 +582,29 @@ __device__ __forceinline__ void general_clips(const GeneralClipArgs<R>& a, R* S,
     }
 }
 
+// ---- ... and for many whole recordings (pe_evaluate_clips / pe_simulate_clips; pe_common.h: RecTable) ------------------
+template <class R>
+struct GeneralRecArgs {
+    StreamGeom geo;
+    GeneralTables tab;
+    RecTable recs;
+    float* out_rows;            // [rows of the pass][row_floats] float32 rows
+    int row_floats;
+};
+template <class R, int BITS, bool BLUE = false>
+__device__ __forceinline__ void general_recs(const GeneralRecArgs<R>& a, R* S, const int first, const int stride, const int lane) {
+    int r = 0;
+    for (uint32_t g = (uint32_t)first; g < a.recs.n_tasks; g += (uint32_t)stride) {
+        r = slot_of_task(a.recs.prefix, a.recs.n_rec, g, r);
+        const ClipTask task = rec_task(a.recs, g, r, a.geo.hop);
+        if (a.recs.audio_f32) general_offline_frame<R, BITS, BLUE>(a.geo, a.tab, S, lane, static_cast<const float*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr, a.row_floats);
+        else general_offline_frame<R, BITS, BLUE>(a.geo, a.tab, S, lane, static_cast<const double*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr, a.row_floats);
+    }
+}
+
 // launchers (kernels.hip)
+hipError_t launch_general_recs_f64(const GeneralRecArgs<double>& a, int n_cus, hipStream_t s);
+hipError_t launch_general_recs_f32(const GeneralRecArgs<float>& a, int n_cus, hipStream_t s);
 hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s);
 hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s);
 hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s);

@@ -755,4 +755,31 @@ __device__ __forceinline__ void mfcc_clip_frames(const MfccClipArgs<R>& a, const
     }
 }
 
+// ---- the same, for many whole recordings (pe_evaluate_clips / pe_simulate_clips; pe_common.h: RecTable) ------------
+// No crop and no pad rows: a task is frame j of its recording, its row is the recording's row base + j.
+template <class R, class SH>
+__device__ __forceinline__ void mfcc_rec_frames(const MfccRecArgs<R>& a, const WaveTables<R>& wt, unsigned char* smem) {
+    const StreamGeom& geo = a.geo;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
+    const TabRegs tab_regs = wave_tables_issue<R>(wt);
+    const int wave_id = (int)blockIdx.x * waves + wave, n_waves = (int)gridDim.x * waves;
+    wave_tables_commit<R>(smem, wt, tab_regs);
+    const pe_wave::Tab<R> tab = wave_bind<R, SH>(smem + kWaveImageBase<R>, wt.L);
+    R* S = reinterpret_cast<R*>(smem) + (size_t)wave * kWaveScratchReals;
+#if PE_TW_LDS == 2
+    const pe_wave::LaneConsts<R> lc{};
+#else
+    const pe_wave::LaneConsts<R> lc = pe_wave::lane_consts(pe_wave::bind<R>(static_cast<const unsigned char*>(wt.blob), wt.L), lane);
+#endif
+    const LaneRuns lr = lane_runs(tab, lane, geo.n_filt);
+    wave_scratch_init(S, lane);
+    int r = 0;
+    for (uint32_t g = (uint32_t)wave_id; g < a.recs.n_tasks; g += (uint32_t)n_waves) {
+        r = slot_of_task(a.recs.prefix, a.recs.n_rec, g, r);
+        const ClipTask task = rec_task(a.recs, g, r, geo.hop);
+        if (a.recs.audio_f32) mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const float*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr);
+        else mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const double*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr);
+    }
+}
+
 }  // namespace pe

@@ -169,16 +169,18 @@ struct ClipTable {
 #else
 #define PE_UNIFORM_PTR(T, p) (p)
 #endif
-// clip c with prefix[c] <= g < prefix[c + 1], searched from clip `lo` on (a wave's tasks only move forward); g < n_tasks
-__device__ __forceinline__ int clip_of_task(const ClipTable& ct, const uint32_t g, int lo) {
-    const auto prefix = PE_UNIFORM_PTR(uint32_t, ct.prefix);
-    int hi = ct.n_clips;                                        // invariant: prefix[lo] <= g < prefix[hi]
+// slot c of an exclusive prefix sum prefix[n + 1] with prefix[c] <= g < prefix[c + 1], searched from slot `lo` on; g < prefix[n]
+__device__ __forceinline__ int slot_of_task(const uint32_t* prefix_global, const int n, const uint32_t g, int lo) {
+    const auto prefix = PE_UNIFORM_PTR(uint32_t, prefix_global);
+    int hi = n;                                                 // invariant: prefix[lo] <= g < prefix[hi]
     while (hi - lo > 1) {
         const int mid = lo + ((hi - lo) >> 1);
         if (prefix[mid] <= g) lo = mid; else hi = mid;
     }
     return lo;
 }
+// clip c with prefix[c] <= g < prefix[c + 1], searched from clip `lo` on (a wave's tasks only move forward); g < n_tasks
+__device__ __forceinline__ int clip_of_task(const ClipTable& ct, const uint32_t g, int lo) { return slot_of_task(ct.prefix, ct.n_clips, g, lo); }
 struct ClipTask { long long x; long long row; };        // sample index of the frame's first sample, output row
 __device__ __forceinline__ ClipTask clip_task(const ClipTable& ct, const uint32_t g, const int c, const int hop, const int n_features) {
     const auto desc = PE_UNIFORM_PTR(ClipDesc, ct.desc);
@@ -206,6 +208,69 @@ struct MfccClipArgs {
     double* out;            // [n_clips][n_features][n_mfcc] float64, may be null
     float* out_rows;        // [n_clips][n_features][16] float32 rows (coefficients + zero padding), may be null
     double* out_mels;       // [n_clips][n_features][n_filt] float64 log-mel energies, may be null
+};
+
+// ---- many whole recordings in one launch (pe_evaluate_clips / pe_simulate_clips) -------------------------------------
+// simulate.py:92-104 per recording: every frame that a window ending at range(T, n_frames, hop_frames) reads.  Recording r's
+// rows start at a row base of its own, a multiple of hop_frames, so that the network's uniform row-sequence addressing
+// (window w = rows [w hop_frames, + T)) serves all recordings of a pass in ONE launch: window j of recording r is window
+// row_base / hop_frames + j of the launch; the few windows that straddle two recordings are computed and dropped.
+// A recording without a window has no frame tasks.  The task -> recording search is the clips' (slot_of_task).
+struct RecDesc {
+    long long start;        // first sample of the recording, in samples from `audio`
+    long long row_base;     // row of its frame 0
+};
+struct RecTable {
+    const RecDesc* desc;        // [n_rec]
+    const uint32_t* prefix;     // [n_rec + 1] exclusive prefix sum of the frames used; prefix[n_rec] == n_tasks
+    int n_rec;
+    uint32_t n_tasks;
+    const void* audio;          // float64 or float32 samples, as ClipTable's
+    int audio_f32;
+};
+__device__ __forceinline__ ClipTask rec_task(const RecTable& rt, const uint32_t g, const int r, const int hop) {
+    const auto desc = PE_UNIFORM_PTR(RecDesc, rt.desc);
+    const auto prefix = PE_UNIFORM_PTR(uint32_t, rt.prefix);
+    const long long j = (long long)(g - prefix[r]);
+    return ClipTask{desc[r].start + j * hop, desc[r].row_base + j};
+}
+template <class R>
+struct MfccRecArgs {
+    StreamGeom geo;
+    RecTable recs;
+    float* out_rows;        // [rows of the pass][16] float32 rows
+};
+
+// ---- the metrics of simulate.py:114-122 and the buckets of annoyance_estimator.py:70-71 on the device -----------------
+// Per (model, recording): predictions p[0 .. n_windows) at src[model * src_stride + src0 ...].  sim_scan_kernel takes them 64
+// at a time (one wave per word): the compacted copy, the two hot masks by ballot, a float64 partial sum of the word in a
+// fixed shape, and the threshold bin of every prediction into a histogram.  sim_fold_kernel then walks a recording's
+// trigger words in order through the TriggerDetector automaton and adds the partial sums up in word order.
+struct SimRec {
+    long long src0;         // first prediction of the recording in a model's src row
+    long long dst0;         // ... and in a model's dst row (the compacted layout: window_offsets[r])
+    long long n_windows;    // ceil(n_windows / 64) words
+};
+struct SimMetric {          // = pe_sim_metric (precise_engine.h)
+    long long n_windows, activated_chunks, activations;
+    double activation_sum;
+};
+struct SimArgs {
+    const SimRec* recs;             // [n_rec]
+    const uint32_t* word_prefix;    // [n_rec + 1] exclusive prefix sum of the words; word_prefix[n_rec] == n_words
+    int n_rec;
+    uint32_t n_words;
+    const float* src; long long src_stride;
+    float* dst; long long dst_stride;       // may be null
+    double chunk_threshold, trigger_threshold;      // (double)p > ...
+    int trigger_level, rearm;                       // rearm = -(8 * 2048) // chunk_size
+    const double* thresholds; int n_thresholds;     // non-decreasing; may be null / 0
+    unsigned long long* hist;       // [n_models][n_thresholds + 1] += windows by the number of thresholds below the prediction
+    unsigned long long* trig;       // [n_models][n_words] trigger mask words
+    uint32_t* chunk_count;          // [n_models][n_words] popcounts of the chunk mask words
+    double* partial;                // [n_models][n_words] partial sums
+    SimMetric* metrics;             // [n_models][metric_stride] (+ the recording's index)
+    long long metric_stride;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -429,6 +494,11 @@ hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTa
 // the same frames for many clips at once, every clip's window padded in place (ClipTable)
 hipError_t launch_mfcc_clips_f64(const MfccClipArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
 hipError_t launch_mfcc_clips_f32(const MfccClipArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
+// ... and for many whole recordings, each at a row base of its own (RecTable)
+hipError_t launch_mfcc_recs_f64(const MfccRecArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
+hipError_t launch_mfcc_recs_f32(const MfccRecArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
+// sim_scan_kernel, then sim_fold_kernel (SimArgs); a.hist is added to, everything else is written
+hipError_t launch_simulate(const SimArgs& a, int n_models, int n_cus, hipStream_t s);
 // units <= 32; 0 feats, 1 ring, 2 rows.  ms != null: the n_models networks of a K-model engine in the same ONE launch, model m
 // writing out + m * out_stride
 hipError_t launch_gru_small(const GruArgs& a, int input_mode, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1, long long out_stride = 0);

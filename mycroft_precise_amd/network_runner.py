@@ -92,6 +92,28 @@ class HipRunner(Runner):
             raise ValueError('chunk_size must be at least hop_samples (%d)' % pr.hop_samples)
         return self.engine.evaluate(audio, hops)
 
+    @staticmethod
+    def _hops(chunk_size):
+        hops = int(chunk_size) // pr.hop_samples
+        if hops < 1:
+            raise ValueError('chunk_size must be at least hop_samples (%d)' % pr.hop_samples)
+        return hops
+
+    def evaluate_clips(self, audios, chunk_size: int = 4096) -> list:
+        """``[evaluate(a, chunk_size) for a in audios]`` -- the same bits -- with one front-end launch and one network launch
+        for all recordings instead of a device call per recording."""
+        return self.engine.evaluate_clips(audios, self._hops(chunk_size))
+
+    def simulate(self, audios, chunk_size: int = 4096, threshold: float = 0.5, thresholds=None, return_scores: bool = False):
+        """What precise-simulate computes per recording (scripts/simulate.py:113-122) for a whole folder of recordings in one
+        device call: ``evaluate``, a fresh ``TriggerDetector(chunk_size, trigger_level=0, sensitivity=threshold)`` over the
+        predictions, ``(predictions > threshold).sum()`` and ``predictions.sum()`` -- and, with ``thresholds``, the windows of
+        all recordings above each of them (annoyance_estimator.py:70-71).  -> (metrics, buckets, scores or None) as
+        ``HipEngine.simulate_clips`` returns them.  As the script does, ``threshold`` serves both comparisons (:119 against
+        it, :114 against ``1 - threshold``); both are made on the float32 prediction widened to float64, where numpy may
+        make :119 in float32: the counts differ only if a prediction equals the float32 rounding of ``threshold``."""
+        return self.engine.simulate_clips(audios, self._hops(chunk_size), threshold, threshold, 0, chunk_size, thresholds, return_scores)
+
 
 # The reference's two runner names (network_runner.py:45-95): `from precise.network_runner import Listener, KerasRunner`
 # (scripts/train_incremental.py:45) and `TensorFlowRunner` resolve to the one implementation here, whatever the file format.
