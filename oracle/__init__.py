@@ -22,6 +22,10 @@ What is restated, and how firmly each piece is pinned
   (``requirements.txt:11,38``), not vendored, not installable.  ``oracle/keras_gru.py``
   restates ``GRUCell.call`` (implementation 1, reset_after=False, hard_sigmoid) and the
   Dense+sigmoid head.  **PARITY UNPINNED** against real Keras/TF bits.
+* The bf16-operand network (``gru_precision='bf16'``; not in the reference) -- ``oracle/bf16_gru.py``
+  restates the arithmetic contract of ``csrc/gru_bf16_device.h`` / ``gru_b20_device.h`` (which values
+  are rounded to bfloat16, and where) on top of ``keras_gru.py``: with the rounding switched off it IS
+  ``keras_gru.predict(dtype=float64)`` (``tests/test_bf16_contract_host.py``).
 
 So: the golden fixtures pin *the reference's own code* (everything the reference repo
 actually owns on this path) with the restated third-party arithmetic plugged into its
