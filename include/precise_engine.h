@@ -445,6 +445,69 @@ int pe_get_gru_tiling(const pe_engine* e);
 int pe_set_timing(pe_engine* e, int32_t enabled);
 int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms);
 
+/* Training: precise-train's model.fit (scripts/train.py:159-166) on Sequential[GRU(units, linear, dropout), Dense(1,
+ * sigmoid)] compiled with rmsprop and weighted_log_loss (model.py:76-90, functions.py:39-50).  Additive to ABI 8.  A
+ * pe_trainer is independent of every pe_engine: it owns the parameters, the RMSprop accumulators and (pe_trainer_set_data) a
+ * dataset on ONE device; it is not thread-safe; every entry point takes host pointers and synchronises.  The arithmetic
+ * contract -- forward with Keras' per-gate input dropout, loss, backward, RMSprop -- is DESIGN.md 4.9; everything is float32.
+ * Scope: ONE GRU layer of 1..32 units, feature_size 1..32, n_features 1..64; anything else is PE_ERR_UNSUPPORTED naming the
+ * field, before any device work (stacked / wide networks and bf16 have no training kernel).
+ * Flat parameter order, used for weights, gradients and accumulators alike (Keras layout, gate order z|r|h):
+ *   kernel[F][3H] | recurrent_kernel[H][3H] | bias[3H] | dense_kernel[H] | dense_bias      = pe_trainer_n_params floats.
+ * PE_ERR_INVALID, before any device work and with the outputs untouched: null pointers, n <= 0, indices outside the dataset,
+ * targets outside [0, 1] (NaN included), a dropout rate outside [0, 1).
+ * pe_trainer_last_error(NULL) returns the message of a failed pe_trainer_create / pe_train_dropout_masks. */
+typedef struct pe_trainer pe_trainer;
+int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t device, pe_trainer** out);
+int pe_trainer_destroy(pe_trainer* t);
+const char* pe_trainer_last_error(const pe_trainer* t);
+int pe_trainer_n_params(const pe_trainer* t);          /* -1 for a null trainer */
+
+/* The parameters / the RMSprop accumulators in the flat order.  pe_trainer_set_weights leaves the accumulators as they are;
+ * pe_trainer_reset_optimizer zeroes them (a fresh keras.optimizers.RMSprop). */
+int pe_trainer_get_weights(pe_trainer* t, float* flat_out);
+int pe_trainer_set_weights(pe_trainer* t, const float* flat);
+int pe_trainer_get_accumulators(pe_trainer* t, float* flat_out);
+int pe_trainer_reset_optimizer(pe_trainer* t);
+
+/* Loss and its gradient for one batch, no state changed: feats[n][n_features][feature_size], targets[n] in [0, 1],
+ * masks[3][n][feature_size] the per-gate (z, r, h) input dropout masks of the batch -- each multiplies x_t before that gate's
+ * input product, the same for every timestep -- or NULL for no dropout.  loss_out[1] = weighted_log_loss with
+ * loss_bias (functions.py:47-50, both means over the n samples of the call), grads_out in the flat order, probs_out[n]
+ * (may be NULL) the network outputs under those masks.  The same inputs give the same bits in every call: partial sums are
+ * added in a fixed order, no floating-point atomics. */
+int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, const float* masks_host,
+                         float loss_bias, float* loss_out, float* grads_out, float* probs_out);
+
+/* One RMSprop update from given gradients (keras.optimizers.RMSprop: a = rho a + (1 - rho) g^2, theta -= lr g / (sqrt(a) + eps);
+ * Keras 2.2.4 defaults lr 1e-3, rho 0.9, eps 1e-7).  frozen_mask: bit 0 = the GRU layer, bit 1 = the Dense layer keep their
+ * parameters AND accumulators (model.py:84-85 freeze_till: layers[:freeze_till] -> mask (1 << freeze_till) - 1). */
+int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho, float eps, int32_t frozen_mask);
+
+/* model.fit's inner step without leaving the device: pe_trainer_set_data uploads the dataset once
+ * (feats[N][n_features][feature_size], targets[N]); pe_trainer_step gathers rows indices[0 .. n), runs forward, backward,
+ * the reduction and the RMSprop update, and returns the batch loss.  Dropout masks are generated in the kernel from
+ * (seed, step, gate, position in the batch, feature) -- pe_train_dropout_masks below is the same function on the host.
+ * Bit for bit: pe_trainer_loss_grad on the gathered rows with those masks, then pe_trainer_apply. */
+int pe_trainer_set_data(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n);
+int pe_trainer_step(pe_trainer* t, const int32_t* indices_host, int32_t n, float dropout_rate, uint64_t seed, uint64_t step,
+                    float loss_bias, float lr, float rho, float eps, int32_t frozen_mask, float* loss_out);
+
+/* model.evaluate / model.predict: dropout off.  loss_out[1], acc_out[1] = mean(round(p) == y) (Keras binary_accuracy),
+ * probs_out[n]; each may be NULL.  targets may be NULL when neither loss nor accuracy is asked for. */
+int pe_trainer_evaluate(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, float loss_bias,
+                        float* loss_out, float* acc_out, float* probs_out);
+
+/* The dropout masks of one step, on the host (no GPU call; works on a machine without one): out[3][n][feature_size], gate
+ * order z, r, h.  With mix(v) the splitmix64 finaliser (v ^= v >> 30; v *= 0xBF58476D1CE4E5B9; v ^= v >> 27;
+ * v *= 0x94D049BB133111EB; v ^= v >> 31), G = 0x9E3779B97F4A7C15 and every operation modulo 2^64:
+ *   key  = mix(mix(seed + G) ^ (step + G))
+ *   ctr  = (i << 7) | (gate << 5) | f                 i = position in the batch, f = feature
+ *   bits = mix(key + G (ctr + 1))
+ * and element (gate, i, f) is kept iff (float)(bits >> 40) / 2^24 >= rate (both float32; the quotient is exact).  A kept
+ * element is 1 / (1 - rate) evaluated in float32, a dropped one 0. */
+int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feature_size, float rate, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,23 @@ EXPORTS = {
     'pe_set_input_projection': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_set_timing': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_get_last_timing': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    # training (pe_trainer)
+    'pe_trainer_create': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.POINTER(C.c_void_p)]),
+    'pe_trainer_destroy': (C.c_int, [C.c_void_p]),
+    'pe_trainer_last_error': (C.c_char_p, [C.c_void_p]),
+    'pe_trainer_n_params': (C.c_int, [C.c_void_p]),
+    'pe_trainer_get_weights': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'pe_trainer_set_weights': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'pe_trainer_get_accumulators': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'pe_trainer_reset_optimizer': (C.c_int, [C.c_void_p]),
+    'pe_trainer_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    'pe_trainer_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int32]),
+    'pe_trainer_set_data': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    'pe_trainer_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
+                                  C.c_float, C.c_float, C.c_int32, C.c_void_p]),
+    'pe_trainer_evaluate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pe_train_dropout_masks': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
 }
 
 # pe_sim_metric: one (model, recording) of pe_simulate_scores / pe_simulate_clips
@@ -646,6 +663,155 @@ class HipEngine:
                     pass
                 return
             self._lib.pe_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def dropout_masks(seed: int, step: int, n: int, feature_size: int, rate: float) -> np.ndarray:
+    """The per-gate input dropout masks of one training step, float32 [3, n, feature_size] (pe_train_dropout_masks: host
+    arithmetic, no GPU): what ``HipTrainer.step`` generates inside its kernel for the same (seed, step)."""
+    lib = load()
+    out = np.empty((3, int(n), int(feature_size)), dtype=np.float32)
+    rc = lib.pe_train_dropout_masks(int(seed), int(step), int(n), int(feature_size), float(rate), out.ctypes.data)
+    if rc != PE_OK:
+        HipEngine._raise(rc, lib.pe_trainer_last_error(None).decode())
+    return out
+
+
+class HipTrainer:
+    """
+    One C-ABI trainer (pe_trainer): the parameters of Sequential[GRU(units), Dense(1, sigmoid)], their RMSprop accumulators
+    and, after ``set_data``, a dataset on one MI355X.  Parameters, gradients and accumulators travel as ONE flat float32 vector
+    (kernel | recurrent_kernel | bias | dense_kernel | dense_bias); ``train.py`` holds the reference-shaped ``Trainer``.
+    """
+
+    def __init__(self, weights, n_features, feature_size, device=0):
+        self._lib = load()
+        self._h = C.c_void_p()
+        layers = weights['gru']
+        arr = (PeGruLayer * len(layers))()
+        keep = []
+        for i, (k, rk, b) in enumerate(layers):
+            k = np.ascontiguousarray(k, dtype=np.float32)
+            rk = np.ascontiguousarray(rk, dtype=np.float32)
+            b = np.ascontiguousarray(b, dtype=np.float32)
+            units = rk.shape[0]
+            if k.ndim != 2 or k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
+                raise ValueError('GRU layer %d has inconsistent shapes' % i)
+            keep += [k, rk, b]
+            arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
+        dk = np.ascontiguousarray(weights['dense_kernel'], dtype=np.float32).reshape(-1)
+        db = float(np.asarray(weights['dense_bias'], dtype=np.float32).reshape(-1)[0])
+        if dk.size != layers[-1][1].shape[0]:
+            raise ValueError('dense_kernel has %d entries for %d units' % (dk.size, layers[-1][1].shape[0]))
+        w = PeWeights(len(layers), arr, _fptr(dk), db)
+        rc = self._lib.pe_trainer_create(int(n_features), int(feature_size), C.byref(w), int(device), C.byref(self._h))
+        if rc != PE_OK:
+            msg = self._lib.pe_trainer_last_error(None).decode()
+            self._h = C.c_void_p()
+            HipEngine._raise(rc, msg)
+        self.n_features, self.feature_size = int(n_features), int(feature_size)
+        self.units = layers[0][1].shape[0]
+        self.n_params = int(self._lib.pe_trainer_n_params(self._h))
+
+    def _check(self, rc):
+        if rc != PE_OK:
+            HipEngine._raise(rc, self._lib.pe_trainer_last_error(self._h).decode())
+
+    def _feats(self, feats):
+        feats = np.ascontiguousarray(feats, dtype=np.float32)
+        if feats.ndim != 3 or feats.shape[1:] != (self.n_features, self.feature_size):
+            raise ValueError('inputs must be [N, %d, %d], got %r' % (self.n_features, self.feature_size, feats.shape))
+        return feats
+
+    @staticmethod
+    def _targets(targets, n):
+        targets = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
+        if targets.size != n:
+            raise ValueError('%d targets for %d inputs' % (targets.size, n))
+        return targets
+
+    def _flat(self, v, what):
+        v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+        if v.size != self.n_params:
+            raise ValueError('%s must hold %d values, got %d' % (what, self.n_params, v.size))
+        return v
+
+    def get_weights(self) -> np.ndarray:
+        out = np.empty(self.n_params, dtype=np.float32)
+        self._check(self._lib.pe_trainer_get_weights(self._h, out.ctypes.data))
+        return out
+
+    def set_weights(self, flat):
+        flat = self._flat(flat, 'weights')
+        self._check(self._lib.pe_trainer_set_weights(self._h, flat.ctypes.data))
+
+    def get_accumulators(self) -> np.ndarray:
+        out = np.empty(self.n_params, dtype=np.float32)
+        self._check(self._lib.pe_trainer_get_accumulators(self._h, out.ctypes.data))
+        return out
+
+    def reset_optimizer(self):
+        self._check(self._lib.pe_trainer_reset_optimizer(self._h))
+
+    def loss_grad(self, feats, targets, masks=None, loss_bias=0.7, want_probs=True):
+        """-> (loss, flat gradient float32 [n_params], probabilities float32 [n] or None); changes no state."""
+        feats = self._feats(feats)
+        n = feats.shape[0]
+        targets = self._targets(targets, n)
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.float32)
+            if masks.shape != (3, n, self.feature_size):
+                raise ValueError('masks must be [3, %d, %d], got %r' % (n, self.feature_size, masks.shape))
+        loss = np.zeros(1, dtype=np.float32)
+        grads = np.zeros(self.n_params, dtype=np.float32)
+        probs = np.zeros(n, dtype=np.float32) if want_probs else None
+        self._check(self._lib.pe_trainer_loss_grad(self._h, feats.ctypes.data if n else None, targets.ctypes.data if n else None, n,
+                                                   masks.ctypes.data if masks is not None else None, float(loss_bias),
+                                                   loss.ctypes.data, grads.ctypes.data, probs.ctypes.data if want_probs else None))
+        return float(loss[0]), grads, probs
+
+    def apply(self, grads, lr=1e-3, rho=0.9, eps=1e-7, frozen_mask=0):
+        grads = self._flat(grads, 'gradients')
+        self._check(self._lib.pe_trainer_apply(self._h, grads.ctypes.data, float(lr), float(rho), float(eps), int(frozen_mask)))
+
+    def set_data(self, feats, targets):
+        feats = self._feats(feats)
+        targets = self._targets(targets, feats.shape[0])
+        self._check(self._lib.pe_trainer_set_data(self._h, feats.ctypes.data if feats.size else None,
+                                                  targets.ctypes.data if targets.size else None, feats.shape[0]))
+
+    def step(self, indices, dropout_rate=0.0, seed=0, step=0, loss_bias=0.7, lr=1e-3, rho=0.9, eps=1e-7, frozen_mask=0) -> float:
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        loss = np.zeros(1, dtype=np.float32)
+        self._check(self._lib.pe_trainer_step(self._h, idx.ctypes.data if idx.size else None, idx.size, float(dropout_rate), int(seed),
+                                              int(step), float(loss_bias), float(lr), float(rho), float(eps), int(frozen_mask),
+                                              loss.ctypes.data))
+        return float(loss[0])
+
+    def evaluate(self, feats, targets=None, loss_bias=0.7):
+        """-> (loss, accuracy, probabilities float32 [n]); loss and accuracy are None without targets.  Dropout off."""
+        feats = self._feats(feats)
+        n = feats.shape[0]
+        probs = np.zeros(n, dtype=np.float32)
+        if targets is None:
+            self._check(self._lib.pe_trainer_evaluate(self._h, feats.ctypes.data if n else None, None, n, float(loss_bias), None, None,
+                                                      probs.ctypes.data))
+            return None, None, probs
+        targets = self._targets(targets, n)
+        loss, acc = np.zeros(1, dtype=np.float32), np.zeros(1, dtype=np.float32)
+        self._check(self._lib.pe_trainer_evaluate(self._h, feats.ctypes.data if n else None, targets.ctypes.data if n else None, n,
+                                                  float(loss_bias), loss.ctypes.data, acc.ctypes.data, probs.ctypes.data))
+        return float(loss[0]), float(acc[0]), probs
+
+    def close(self):
+        if getattr(self, '_h', None) and self._h.value:
+            self._lib.pe_trainer_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

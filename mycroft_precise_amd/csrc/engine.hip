@@ -6,6 +6,7 @@
 #include "pe_common.h"
 #include "gru_cw_pack.h"
 #include "mfcc_general_device.h"
+#include "gru_train_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2429,6 +2430,339 @@ int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms) {
     PE_HIP(e, hipEventElapsedTime(&b, e->ev[1], e->ev[2]));
     if (mfcc_ms) *mfcc_ms = a;      // fused launch: the whole update; else the MFCC kernel
     if (gru_ms) *gru_ms = e->ev_has_gru ? b : 0.f;
+    return PE_OK;
+}
+
+}  // extern "C"
+
+// ---- training (kernels: gru_train_device.h) ----------------------------------------------------------------
+struct pe_trainer {
+    int device = 0;
+    int T = 0, F = 0, H = 0, n_params = 0;
+    std::string err;
+    float* theta = nullptr;         // flat parameters
+    float* accum = nullptr;         // RMSprop accumulators
+    float* grads = nullptr;
+    float* loss = nullptr;
+    const float* data_feats = nullptr;      // pe_trainer_set_data
+    const float* data_targets = nullptr;
+    int data_n = 0;
+    // buffers that grow with the largest call: 0 feats, 1 targets, 2 masks, 3 indices, 4 tape, 5 partial, 6 probs, 7 / 8 dataset
+    DeviceBuf buf[9];
+};
+
+namespace {
+
+int tfail(pe_trainer* t, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (t) t->err = buf; else g_global_error = buf;
+    return code;
+}
+
+#define PE_THIP(t, call)                                                                                   \
+    do {                                                                                                   \
+        hipError_t _err = (call);                                                                          \
+        if (_err != hipSuccess)                                                                            \
+            return tfail((t), PE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
+    } while (0)
+
+int train_reserve(pe_trainer* t, int which, size_t bytes) {
+    DeviceBuf& b = t->buf[which];
+    if (b.bytes >= bytes && b.p) return PE_OK;
+    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
+    hipError_t err = hipMalloc(&b.p, bytes ? bytes : 1);
+    if (err != hipSuccess) { b.p = nullptr; return tfail(t, PE_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(err)); }
+    b.bytes = bytes;
+    return PE_OK;
+}
+
+float train_keep_scale(float rate) { return 1.0f / (1.0f - rate); }
+
+int train_check_targets(pe_trainer* t, const float* y, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!(y[i] >= 0.0f && y[i] <= 1.0f)) return tfail(t, PE_ERR_INVALID, "targets[%d] = %g is outside [0, 1]", i, (double)y[i]);
+    return PE_OK;
+}
+
+// forward (+ backward) over n samples and the reduction; the caller has filled a.feats / targets / indices / mask_*
+int train_run(pe_trainer* t, TrainArgs a, bool backward, float loss_bias, const TrainReduceArgs* apply) {
+    const int blocks = (a.n + kTrainTile - 1) / kTrainTile;
+    a.T = t->T; a.F = t->F; a.H = t->H;
+    a.theta = t->theta;
+    a.beta = loss_bias;
+    a.inv_n = 1.0f / (float)a.n;
+    a.n_grad = backward ? t->n_params : 0;
+    int rc = train_reserve(t, 5, (size_t)blocks * (a.n_grad + 2) * sizeof(float));
+    if (rc) return rc;
+    if (backward && (rc = train_reserve(t, 4, (size_t)blocks * t->T * 4 * train_threads(t->H) * sizeof(float)))) return rc;
+    if ((rc = train_reserve(t, 6, (size_t)a.n * sizeof(float)))) return rc;
+    a.tape = static_cast<float*>(t->buf[4].p);
+    a.partial = static_cast<float*>(t->buf[5].p);
+    a.probs = static_cast<float*>(t->buf[6].p);
+    PE_THIP(t, launch_train(a, backward, nullptr));
+    TrainReduceArgs r{};
+    if (apply) r = *apply;
+    r.partial = a.partial;
+    r.n_blocks = blocks;
+    r.n_grad = a.n_grad;
+    r.grads = backward ? t->grads : nullptr;
+    r.loss = t->loss;
+    r.beta = loss_bias;
+    r.inv_n = a.inv_n;
+    r.theta = t->theta;
+    r.accum = t->accum;
+    r.n_gru = train_n_gru(t->F, t->H);
+    PE_THIP(t, launch_train_reduce(r, nullptr));
+    return PE_OK;
+}
+
+int train_upload_batch(pe_trainer* t, const float* feats_host, const float* targets_host, int n, TrainArgs* a) {
+    const size_t fb = (size_t)n * t->T * t->F * sizeof(float);
+    int rc = train_reserve(t, 0, fb);
+    if (rc) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[0].p, feats_host, fb, hipMemcpyHostToDevice));
+    a->feats = static_cast<const float*>(t->buf[0].p);
+    a->targets = nullptr;
+    if (targets_host) {
+        if ((rc = train_reserve(t, 1, (size_t)n * sizeof(float)))) return rc;
+        PE_THIP(t, hipMemcpy(t->buf[1].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        a->targets = static_cast<const float*>(t->buf[1].p);
+    }
+    a->n = n;
+    return PE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* pe_trainer_last_error(const pe_trainer* t) { return t ? t->err.c_str() : g_global_error.c_str(); }
+
+int pe_trainer_destroy(pe_trainer* t) {
+    if (!t) return PE_OK;
+    (void)hipSetDevice(t->device);
+    (void)hipDeviceSynchronize();
+    for (DeviceBuf& b : t->buf) if (b.p) (void)hipFree(b.p);
+    for (float* p : {t->theta, t->accum, t->grads, t->loss}) if (p) (void)hipFree(p);
+    delete t;
+    return PE_OK;
+}
+
+int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t device, pe_trainer** out) {
+    if (!init || !out) return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: null argument");
+    *out = nullptr;
+    if (init->n_layers != 1)
+        return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: n_layers = %d (one GRU layer has a training kernel)", init->n_layers);
+    if (!init->layers || !init->layers[0].kernel || !init->layers[0].recurrent_kernel || !init->layers[0].bias || !init->dense_kernel)
+        return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: null weight array");
+    const int H = init->layers[0].units;
+    if (H < 1 || H > kTrainMaxUnits) return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: units = %d (1..%d)", H, kTrainMaxUnits);
+    if (feature_size < 1 || feature_size > kTrainMaxFeat)
+        return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: feature_size = %d (1..%d)", feature_size, kTrainMaxFeat);
+    if (n_features < 1 || n_features > kTrainMaxSteps)
+        return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: n_features = %d (1..%d)", n_features, kTrainMaxSteps);
+    if (init->layers[0].n_in != feature_size)
+        return tfail(nullptr, PE_ERR_INVALID, "the GRU layer takes %d inputs, feature_size is %d", init->layers[0].n_in, feature_size);
+    hipError_t herr = hipSetDevice(device);
+    if (herr != hipSuccess) return tfail(nullptr, PE_ERR_HIP, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(herr));
+    pe_trainer* t = new pe_trainer;
+    t->device = device;
+    t->T = n_features; t->F = feature_size; t->H = H;
+    t->n_params = train_n_params(feature_size, H);
+    const size_t pb = (size_t)t->n_params * sizeof(float);
+    for (float** p : {&t->theta, &t->accum, &t->grads, &t->loss}) {
+        herr = hipMalloc(reinterpret_cast<void**>(p), pb);
+        if (herr != hipSuccess) {
+            *p = nullptr;
+            pe_trainer_destroy(t);
+            return tfail(nullptr, PE_ERR_NOMEM, "hipMalloc(%zu) failed: %s", pb, hipGetErrorString(herr));
+        }
+    }
+    std::vector<float> flat((size_t)t->n_params);
+    const int F = feature_size, H3 = 3 * H;
+    memcpy(flat.data(), init->layers[0].kernel, (size_t)F * H3 * sizeof(float));
+    memcpy(flat.data() + F * H3, init->layers[0].recurrent_kernel, (size_t)H * H3 * sizeof(float));
+    memcpy(flat.data() + (F + H) * H3, init->layers[0].bias, (size_t)H3 * sizeof(float));
+    memcpy(flat.data() + (F + H + 1) * H3, init->dense_kernel, (size_t)H * sizeof(float));
+    flat[(size_t)t->n_params - 1] = init->dense_bias;
+    int rc = pe_trainer_set_weights(t, flat.data());
+    if (!rc) rc = pe_trainer_reset_optimizer(t);
+    if (rc) {
+        g_global_error = t->err;
+        pe_trainer_destroy(t);
+        return rc;
+    }
+    *out = t;
+    return PE_OK;
+}
+
+int pe_trainer_n_params(const pe_trainer* t) { return t ? t->n_params : -1; }
+
+int pe_trainer_get_weights(pe_trainer* t, float* flat_out) {
+    if (!t) return PE_ERR_INVALID;
+    if (!flat_out) return tfail(t, PE_ERR_INVALID, "pe_trainer_get_weights: null pointer");
+    PE_THIP(t, hipSetDevice(t->device));
+    PE_THIP(t, hipMemcpy(flat_out, t->theta, (size_t)t->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_trainer_set_weights(pe_trainer* t, const float* flat) {
+    if (!t) return PE_ERR_INVALID;
+    if (!flat) return tfail(t, PE_ERR_INVALID, "pe_trainer_set_weights: null pointer");
+    PE_THIP(t, hipSetDevice(t->device));
+    PE_THIP(t, hipMemcpy(t->theta, flat, (size_t)t->n_params * sizeof(float), hipMemcpyHostToDevice));
+    return PE_OK;
+}
+
+int pe_trainer_get_accumulators(pe_trainer* t, float* flat_out) {
+    if (!t) return PE_ERR_INVALID;
+    if (!flat_out) return tfail(t, PE_ERR_INVALID, "pe_trainer_get_accumulators: null pointer");
+    PE_THIP(t, hipSetDevice(t->device));
+    PE_THIP(t, hipMemcpy(flat_out, t->accum, (size_t)t->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_trainer_reset_optimizer(pe_trainer* t) {
+    if (!t) return PE_ERR_INVALID;
+    PE_THIP(t, hipSetDevice(t->device));
+    PE_THIP(t, hipMemset(t->accum, 0, (size_t)t->n_params * sizeof(float)));
+    return PE_OK;
+}
+
+int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, const float* masks_host,
+                         float loss_bias, float* loss_out, float* grads_out, float* probs_out) {
+    if (!t) return PE_ERR_INVALID;
+    if (!feats_host || !targets_host || !loss_out || !grads_out) return tfail(t, PE_ERR_INVALID, "pe_trainer_loss_grad: null pointer");
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_loss_grad: n = %d", n);
+    int rc = train_check_targets(t, targets_host, n);
+    if (rc) return rc;
+    PE_THIP(t, hipSetDevice(t->device));
+    TrainArgs a{};
+    if ((rc = train_upload_batch(t, feats_host, targets_host, n, &a))) return rc;
+    if (masks_host) {
+        const size_t mb = (size_t)3 * n * t->F * sizeof(float);
+        if ((rc = train_reserve(t, 2, mb))) return rc;
+        PE_THIP(t, hipMemcpy(t->buf[2].p, masks_host, mb, hipMemcpyHostToDevice));
+        a.mask_mode = 1;
+        a.masks = static_cast<const float*>(t->buf[2].p);
+    }
+    if ((rc = train_run(t, a, true, loss_bias, nullptr))) return rc;
+    PE_THIP(t, hipMemcpy(loss_out, t->loss, sizeof(float), hipMemcpyDeviceToHost));
+    PE_THIP(t, hipMemcpy(grads_out, t->grads, (size_t)t->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    if (probs_out) PE_THIP(t, hipMemcpy(probs_out, t->buf[6].p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho, float eps, int32_t frozen_mask) {
+    if (!t) return PE_ERR_INVALID;
+    if (!grads_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_apply: null pointer");
+    PE_THIP(t, hipSetDevice(t->device));
+    PE_THIP(t, hipMemcpy(t->grads, grads_host, (size_t)t->n_params * sizeof(float), hipMemcpyHostToDevice));
+    TrainReduceArgs r{};
+    r.n_grad = t->n_params;
+    r.grads = t->grads;
+    r.theta = t->theta;
+    r.accum = t->accum;
+    r.lr = lr; r.rho = rho; r.eps = eps;
+    r.frozen_mask = frozen_mask;
+    r.n_gru = train_n_gru(t->F, t->H);
+    PE_THIP(t, launch_train_apply(r, nullptr));
+    PE_THIP(t, hipDeviceSynchronize());
+    return PE_OK;
+}
+
+int pe_trainer_set_data(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n) {
+    if (!t) return PE_ERR_INVALID;
+    if (!feats_host || !targets_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_set_data: null pointer");
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_set_data: n = %d", n);
+    int rc = train_check_targets(t, targets_host, n);
+    if (rc) return rc;
+    PE_THIP(t, hipSetDevice(t->device));
+    t->data_n = 0;
+    const size_t fb = (size_t)n * t->T * t->F * sizeof(float);
+    if ((rc = train_reserve(t, 7, fb)) || (rc = train_reserve(t, 8, (size_t)n * sizeof(float)))) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[7].p, feats_host, fb, hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(t->buf[8].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    t->data_feats = static_cast<const float*>(t->buf[7].p);
+    t->data_targets = static_cast<const float*>(t->buf[8].p);
+    t->data_n = n;
+    return PE_OK;
+}
+
+int pe_trainer_step(pe_trainer* t, const int32_t* indices_host, int32_t n, float dropout_rate, uint64_t seed, uint64_t step,
+                    float loss_bias, float lr, float rho, float eps, int32_t frozen_mask, float* loss_out) {
+    if (!t) return PE_ERR_INVALID;
+    if (!indices_host || !loss_out) return tfail(t, PE_ERR_INVALID, "pe_trainer_step: null pointer");
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_step: n = %d", n);
+    if (t->data_n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_step: no dataset (call pe_trainer_set_data first)");
+    if (!(dropout_rate >= 0.0f && dropout_rate < 1.0f)) return tfail(t, PE_ERR_INVALID, "dropout rate %g is outside [0, 1)", (double)dropout_rate);
+    for (int i = 0; i < n; ++i)
+        if (indices_host[i] < 0 || indices_host[i] >= t->data_n)
+            return tfail(t, PE_ERR_INVALID, "indices[%d] = %d is outside the dataset of %d samples", i, indices_host[i], t->data_n);
+    PE_THIP(t, hipSetDevice(t->device));
+    int rc = train_reserve(t, 3, (size_t)n * sizeof(int32_t));
+    if (rc) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[3].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    TrainArgs a{};
+    a.n = n;
+    a.feats = t->data_feats;
+    a.targets = t->data_targets;
+    a.indices = static_cast<const int32_t*>(t->buf[3].p);
+    if (dropout_rate > 0.0f) {
+        a.mask_mode = 2;
+        a.mask_key = train_mask_key(seed, step);
+        a.rate = dropout_rate;
+        a.keep_scale = train_keep_scale(dropout_rate);
+    }
+    TrainReduceArgs r{};
+    r.apply = 1;
+    r.lr = lr; r.rho = rho; r.eps = eps;
+    r.frozen_mask = frozen_mask;
+    if ((rc = train_run(t, a, true, loss_bias, &r))) return rc;
+    PE_THIP(t, hipMemcpy(loss_out, t->loss, sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_trainer_evaluate(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, float loss_bias,
+                        float* loss_out, float* acc_out, float* probs_out) {
+    if (!t) return PE_ERR_INVALID;
+    if (!feats_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_evaluate: null pointer");
+    if (!targets_host && (loss_out || acc_out)) return tfail(t, PE_ERR_INVALID, "pe_trainer_evaluate: loss and accuracy need targets");
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_evaluate: n = %d", n);
+    int rc = targets_host ? train_check_targets(t, targets_host, n) : PE_OK;
+    if (rc) return rc;
+    PE_THIP(t, hipSetDevice(t->device));
+    TrainArgs a{};
+    if ((rc = train_upload_batch(t, feats_host, targets_host, n, &a))) return rc;
+    if ((rc = train_run(t, a, false, loss_bias, nullptr))) return rc;
+    std::vector<float> probs((size_t)n);
+    PE_THIP(t, hipMemcpy(probs.data(), t->buf[6].p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (loss_out) PE_THIP(t, hipMemcpy(loss_out, t->loss, sizeof(float), hipMemcpyDeviceToHost));
+    if (acc_out) {                                     // Keras binary_accuracy: mean(round(p) == y), ties to even
+        int64_t hits = 0;
+        for (int i = 0; i < n; ++i) hits += nearbyintf(probs[i]) == targets_host[i] ? 1 : 0;
+        *acc_out = (float)((double)hits / n);
+    }
+    if (probs_out) memcpy(probs_out, probs.data(), (size_t)n * sizeof(float));
+    return PE_OK;
+}
+
+int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feature_size, float rate, float* out) {
+    if (!out) return tfail(nullptr, PE_ERR_INVALID, "pe_train_dropout_masks: null pointer");
+    if (n <= 0) return tfail(nullptr, PE_ERR_INVALID, "pe_train_dropout_masks: n = %d", n);
+    if (feature_size < 1 || feature_size > kTrainMaxFeat)
+        return tfail(nullptr, PE_ERR_INVALID, "pe_train_dropout_masks: feature_size = %d (1..%d)", feature_size, kTrainMaxFeat);
+    if (!(rate >= 0.0f && rate < 1.0f)) return tfail(nullptr, PE_ERR_INVALID, "dropout rate %g is outside [0, 1)", (double)rate);
+    const uint64_t key = train_mask_key(seed, step);
+    const float scale = train_keep_scale(rate);
+    for (int g = 0; g < 3; ++g)
+        for (int64_t i = 0; i < n; ++i)
+            for (int f = 0; f < feature_size; ++f)
+                out[((size_t)g * n + i) * feature_size + f] = train_mask_keep(key, g, i, f, rate) ? scale : 0.0f;
     return PE_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "gru_wide_device.h"
 #include "gru_wide_x3_device.h"
 #include "mfcc_general_device.h"
+#include "gru_train_device.h"
 
 namespace pe {
 
@@ -1107,6 +1108,41 @@ hipError_t launch_simulate(const SimArgs& a, int n_models, int n_cus, hipStream_
                            a.hist ? (size_t)(a.n_thresholds + 1) * sizeof(uint32_t) : 0, s, a);
     }
     if (a.metrics) hipLaunchKernelGGL(sim_fold_kernel, dim3((a.n_rec + 63) / 64, n_models), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- training (gru_train_device.h) -------------------------------------------------------------------------------------
+template <bool BACKWARD>
+__global__ __launch_bounds__(64 * 8) void train_tile_kernel(const TrainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float train_lds[];
+    train_tile<BACKWARD>(a, train_lds);
+}
+__global__ __launch_bounds__(256) void train_reduce_kernel(const TrainReduceArgs a) { train_reduce(a); }
+__global__ __launch_bounds__(256) void train_apply_kernel(const TrainReduceArgs a) { train_apply(a); }
+
+size_t train_lds_bytes(int F, int H) { return (size_t)TrainLds(F, H).total * sizeof(float); }
+
+template <bool BACKWARD>
+static hipError_t launch_train_t(const TrainArgs& a, hipStream_t s) {
+    const size_t lds = train_lds_bytes(a.F, a.H);
+    if (lds > 48 * 1024) {
+        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&train_tile_kernel<BACKWARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (err != hipSuccess) return err;
+    }
+    hipLaunchKernelGGL(train_tile_kernel<BACKWARD>, dim3((a.n + kTrainTile - 1) / kTrainTile), dim3(train_threads(a.H)), lds, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_train(const TrainArgs& a, bool backward, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    return backward ? launch_train_t<true>(a, s) : launch_train_t<false>(a, s);
+}
+hipError_t launch_train_reduce(const TrainReduceArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(train_reduce_kernel, dim3((a.n_grad + 1 + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_train_apply(const TrainReduceArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(train_apply_kernel, dim3((a.n_grad + 255) / 256), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -21,8 +21,11 @@ from .params import inject_params, pr
 
 
 class ModelParams:
-    """Same fields and defaults as the reference's attrs class (model.py:28-45); only
-    ``recurrent_units`` matters for inference."""
+    """Same fields and defaults as the reference's attrs class (model.py:28-45).  Inference reads only
+    ``recurrent_units``; training (``train.Trainer``) also reads ``dropout`` (the GRU's input dropout rate), ``loss_bias``
+    (weighted_log_loss: near 1 punishes false activations, near 0 missed ones; the reference passes ``1.0 - sensitivity``) and
+    ``freeze_till`` (the first ``freeze_till`` layers -- GRU, then Dense -- keep their weights).  ``extra_metrics`` and
+    ``skip_acc`` only select what Keras prints and are not used."""
 
     def __init__(self, recurrent_units=20, dropout=0.2, extra_metrics=False, skip_acc=False,
                  loss_bias=0.7, freeze_till=0):
