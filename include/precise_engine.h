@@ -456,12 +456,31 @@ int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms);
  *   kernel[F][3H] | recurrent_kernel[H][3H] | bias[3H] | dense_kernel[H] | dense_bias      = pe_trainer_n_params floats.
  * PE_ERR_INVALID, before any device work and with the outputs untouched: null pointers, n <= 0, indices outside the dataset,
  * targets outside [0, 1] (NaN included), a dropout rate outside [0, 1).
- * pe_trainer_last_error(NULL) returns the message of a failed pe_trainer_create / pe_train_dropout_masks. */
+ * Several networks: a trainer made by pe_trainer_create_models owns n_models (1..PE_TRAIN_MAX_MODELS) networks and trains all
+ * of them on the same batch in one launch.  SHARED by the networks of a trainer: n_features, feature_size, the device, the
+ * resident training set (pe_trainer_set_data), the resident validation set (pe_trainer_set_validation) and, per call, the
+ * batch: indices, n, step.  PER NETWORK: units (1..32), the parameters and accumulators, and every field of pe_train_hparams.
+ * The flat vector of such a trainer -- pe_trainer_get_weights / set_weights / get_accumulators -- is the concatenation of
+ * the networks' flat vectors in model order, pe_trainer_n_params its length and pe_trainer_n_params_model one network's
+ * share.  Bit for bit: a network trained or evaluated next to others gets the losses, probabilities, parameters and
+ * accumulators of the same network in a trainer of its own given the same calls -- whatever the other networks' widths,
+ * their order and their hyperparameters (every sum runs in an order that depends on neither the launch's width nor on the
+ * company).  A trainer of one network IS the n_models = 1 case: pe_trainer_create, pe_trainer_step and pe_trainer_evaluate
+ * call the *_models functions; on a trainer of several they, and the inspection calls pe_trainer_loss_grad and
+ * pe_trainer_apply, return PE_ERR_UNSUPPORTED.  A per-network complaint of a trainer of several starts "model <index>: ".
+ * pe_trainer_last_error(NULL) returns the message of a failed pe_trainer_create[_models] / pe_train_dropout_masks. */
+#define PE_TRAIN_MAX_MODELS 16
 typedef struct pe_trainer pe_trainer;
 int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t device, pe_trainer** out);
+/* init[n_models].  n_models < 1 and null weight arrays are PE_ERR_INVALID, n_models > PE_TRAIN_MAX_MODELS is
+ * PE_ERR_UNSUPPORTED naming n_models; every refusal happens before any device work. */
+int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
+                             pe_trainer** out);
 int pe_trainer_destroy(pe_trainer* t);
 const char* pe_trainer_last_error(const pe_trainer* t);
-int pe_trainer_n_params(const pe_trainer* t);          /* -1 for a null trainer */
+int pe_trainer_n_models(const pe_trainer* t);          /* -1 for a null trainer */
+int pe_trainer_n_params(const pe_trainer* t);          /* the total over the networks; -1 for a null trainer */
+int pe_trainer_n_params_model(const pe_trainer* t, int32_t m);     /* -1 for a null trainer or an m outside 0 .. n_models - 1 */
 
 /* The parameters / the RMSprop accumulators in the flat order.  pe_trainer_set_weights leaves the accumulators as they are;
  * pe_trainer_reset_optimizer zeroes them (a fresh keras.optimizers.RMSprop). */
@@ -493,10 +512,40 @@ int pe_trainer_set_data(pe_trainer* t, const float* feats_host, const float* tar
 int pe_trainer_step(pe_trainer* t, const int32_t* indices_host, int32_t n, float dropout_rate, uint64_t seed, uint64_t step,
                     float loss_bias, float lr, float rho, float eps, int32_t frozen_mask, float* loss_out);
 
+/* The same step for every network of the trainer: the indices are uploaded once, forward + backward of all networks is
+ * ONE launch over (tile, network), the reduction + RMSprop of all of them a second, and loss_out[n_models] comes back in one
+ * copy.  hp[n_models] holds each network's hyperparameters; network m's masks are those of (hp[m].seed, step).  A dropout
+ * rate outside [0, 1) is refused naming the network.  pe_trainer_step is this call on a trainer of one network. */
+typedef struct pe_train_hparams {
+    float dropout_rate;
+    uint64_t seed;
+    float loss_bias;
+    float lr, rho, eps;
+    int32_t frozen_mask;
+} pe_train_hparams;
+int pe_trainer_step_models(pe_trainer* t, const int32_t* indices_host, int32_t n, uint64_t step, const pe_train_hparams* hp,
+                           float* loss_out);
+
+/* A second resident set, for validation: like pe_trainer_set_data, with buffers of its own. */
+int pe_trainer_set_validation(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n);
+
 /* model.evaluate / model.predict: dropout off.  loss_out[1], acc_out[1] = mean(round(p) == y) (Keras binary_accuracy),
  * probs_out[n]; each may be NULL.  targets may be NULL when neither loss nor accuracy is asked for. */
 int pe_trainer_evaluate(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, float loss_bias,
                         float* loss_out, float* acc_out, float* probs_out);
+
+/* The same for every network in one launch: loss_bias[n_models] (may be NULL when loss_out is), loss_out[n_models],
+ * acc_out[n_models], probs_out[n_models][n]; each output may be NULL.  source says where the samples are: host data
+ * (feats_host / targets_host / n as in pe_trainer_evaluate, uploaded once for all networks), or one of the resident sets --
+ * then the host pointers and n are ignored, n is the set's, and nothing but the results crosses the bus: the hits
+ * round(p) == y (ties to even) are counted on the device as integers.  A resident set that was never uploaded is
+ * PE_ERR_INVALID. */
+#define PE_TRAIN_SOURCE_HOST 0
+#define PE_TRAIN_SOURCE_DATA 1             /* pe_trainer_set_data */
+#define PE_TRAIN_SOURCE_VALIDATION 2       /* pe_trainer_set_validation */
+int pe_trainer_n_samples(const pe_trainer* t, int32_t source);     /* of a resident set; 0 if never uploaded, -1 for a null trainer or another source */
+int pe_trainer_evaluate_models(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n,
+                               const float* loss_bias, float* loss_out, float* acc_out, float* probs_out);
 
 /* The dropout masks of one step, on the host (no GPU call; works on a machine without one): out[3][n][feature_size], gate
  * order z, r, h.  With mix(v) the splitmix64 finaliser (v ^= v >> 30; v *= 0xBF58476D1CE4E5B9; v ^= v >> 27;

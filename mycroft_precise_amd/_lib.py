@@ -35,6 +35,16 @@ class PeWeights(C.Structure):
                 ('dense_kernel', C.POINTER(C.c_float)), ('dense_bias', C.c_float)]
 
 
+class PeTrainHparams(C.Structure):
+    """pe_train_hparams: one network's hyperparameters of a training step"""
+    _fields_ = [('dropout_rate', C.c_float), ('seed', C.c_uint64), ('loss_bias', C.c_float), ('lr', C.c_float),
+                ('rho', C.c_float), ('eps', C.c_float), ('frozen_mask', C.c_int32)]
+
+
+TRAIN_MAX_MODELS = 16                                                  # PE_TRAIN_MAX_MODELS
+TRAIN_SOURCE_HOST, TRAIN_SOURCE_DATA, TRAIN_SOURCE_VALIDATION = 0, 1, 2     # PE_TRAIN_SOURCE_*
+
+
 class PeInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         'n_streams', 'n_features', 'n_mfcc', 'units', 'n_layers', 'ring_slots', 'carry_capacity',
@@ -119,6 +129,14 @@ EXPORTS = {
     'pe_trainer_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_int32, C.c_void_p]),
     'pe_trainer_evaluate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pe_trainer_create_models': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    'pe_trainer_n_models': (C.c_int, [C.c_void_p]),
+    'pe_trainer_n_params_model': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pe_trainer_step_models': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(PeTrainHparams), C.c_void_p]),
+    'pe_trainer_n_samples': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pe_trainer_set_validation': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    'pe_trainer_evaluate_models': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     'pe_train_dropout_masks': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
 }
 
@@ -688,36 +706,52 @@ class HipTrainer:
     One C-ABI trainer (pe_trainer): the parameters of Sequential[GRU(units), Dense(1, sigmoid)], their RMSprop accumulators
     and, after ``set_data``, a dataset on one MI355X.  Parameters, gradients and accumulators travel as ONE flat float32 vector
     (kernel | recurrent_kernel | bias | dense_kernel | dense_bias); ``train.py`` holds the reference-shaped ``Trainer``.
+
+    ``weights`` is one weights dict, or a list of them: then the trainer owns that many networks (their ``units`` may differ),
+    trains them on the same batches in one launch (``step_models``) and evaluates them together (``evaluate_models``); the
+    flat vector is the concatenation in model order, ``units`` and ``n_params`` are lists, ``n_params_total`` the length.
     """
 
     def __init__(self, weights, n_features, feature_size, device=0):
         self._lib = load()
         self._h = C.c_void_p()
-        layers = weights['gru']
-        arr = (PeGruLayer * len(layers))()
+        many = isinstance(weights, (list, tuple))
+        models = list(weights) if many else [weights]
+        ws = (PeWeights * max(1, len(models)))()
         keep = []
-        for i, (k, rk, b) in enumerate(layers):
-            k = np.ascontiguousarray(k, dtype=np.float32)
-            rk = np.ascontiguousarray(rk, dtype=np.float32)
-            b = np.ascontiguousarray(b, dtype=np.float32)
-            units = rk.shape[0]
-            if k.ndim != 2 or k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
-                raise ValueError('GRU layer %d has inconsistent shapes' % i)
-            keep += [k, rk, b]
-            arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
-        dk = np.ascontiguousarray(weights['dense_kernel'], dtype=np.float32).reshape(-1)
-        db = float(np.asarray(weights['dense_bias'], dtype=np.float32).reshape(-1)[0])
-        if dk.size != layers[-1][1].shape[0]:
-            raise ValueError('dense_kernel has %d entries for %d units' % (dk.size, layers[-1][1].shape[0]))
-        w = PeWeights(len(layers), arr, _fptr(dk), db)
-        rc = self._lib.pe_trainer_create(int(n_features), int(feature_size), C.byref(w), int(device), C.byref(self._h))
+        for m, wm in enumerate(models):
+            layers = wm['gru']
+            arr = (PeGruLayer * len(layers))()
+            for i, (k, rk, b) in enumerate(layers):
+                k = np.ascontiguousarray(k, dtype=np.float32)
+                rk = np.ascontiguousarray(rk, dtype=np.float32)
+                b = np.ascontiguousarray(b, dtype=np.float32)
+                units = rk.shape[0]
+                if k.ndim != 2 or k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
+                    raise ValueError('GRU layer %d has inconsistent shapes' % i)
+                keep += [k, rk, b]
+                arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
+            dk = np.ascontiguousarray(wm['dense_kernel'], dtype=np.float32).reshape(-1)
+            db = float(np.asarray(wm['dense_bias'], dtype=np.float32).reshape(-1)[0])
+            if dk.size != layers[-1][1].shape[0]:
+                raise ValueError('dense_kernel has %d entries for %d units' % (dk.size, layers[-1][1].shape[0]))
+            keep += [arr, dk]
+            ws[m] = PeWeights(len(layers), arr, _fptr(dk), db)
+        if many:
+            rc = self._lib.pe_trainer_create_models(int(n_features), int(feature_size), ws, len(models), int(device), C.byref(self._h))
+        else:
+            rc = self._lib.pe_trainer_create(int(n_features), int(feature_size), ws, int(device), C.byref(self._h))
         if rc != PE_OK:
             msg = self._lib.pe_trainer_last_error(None).decode()
             self._h = C.c_void_p()
             HipEngine._raise(rc, msg)
         self.n_features, self.feature_size = int(n_features), int(feature_size)
-        self.units = layers[0][1].shape[0]
-        self.n_params = int(self._lib.pe_trainer_n_params(self._h))
+        self.n_models = int(self._lib.pe_trainer_n_models(self._h))
+        self.n_params_total = int(self._lib.pe_trainer_n_params(self._h))
+        units = [wm['gru'][0][1].shape[0] for wm in models]
+        per_model = [int(self._lib.pe_trainer_n_params_model(self._h, m)) for m in range(self.n_models)]
+        self.units = units if many else units[0]
+        self.n_params = per_model if many else per_model[0]
 
     def _check(self, rc):
         if rc != PE_OK:
@@ -738,12 +772,12 @@ class HipTrainer:
 
     def _flat(self, v, what):
         v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
-        if v.size != self.n_params:
-            raise ValueError('%s must hold %d values, got %d' % (what, self.n_params, v.size))
+        if v.size != self.n_params_total:
+            raise ValueError('%s must hold %d values, got %d' % (what, self.n_params_total, v.size))
         return v
 
     def get_weights(self) -> np.ndarray:
-        out = np.empty(self.n_params, dtype=np.float32)
+        out = np.empty(self.n_params_total, dtype=np.float32)
         self._check(self._lib.pe_trainer_get_weights(self._h, out.ctypes.data))
         return out
 
@@ -752,7 +786,7 @@ class HipTrainer:
         self._check(self._lib.pe_trainer_set_weights(self._h, flat.ctypes.data))
 
     def get_accumulators(self) -> np.ndarray:
-        out = np.empty(self.n_params, dtype=np.float32)
+        out = np.empty(self.n_params_total, dtype=np.float32)
         self._check(self._lib.pe_trainer_get_accumulators(self._h, out.ctypes.data))
         return out
 
@@ -769,7 +803,7 @@ class HipTrainer:
             if masks.shape != (3, n, self.feature_size):
                 raise ValueError('masks must be [3, %d, %d], got %r' % (n, self.feature_size, masks.shape))
         loss = np.zeros(1, dtype=np.float32)
-        grads = np.zeros(self.n_params, dtype=np.float32)
+        grads = np.zeros(self.n_params_total, dtype=np.float32)
         probs = np.zeros(n, dtype=np.float32) if want_probs else None
         self._check(self._lib.pe_trainer_loss_grad(self._h, feats.ctypes.data if n else None, targets.ctypes.data if n else None, n,
                                                    masks.ctypes.data if masks is not None else None, float(loss_bias),
@@ -808,6 +842,70 @@ class HipTrainer:
         self._check(self._lib.pe_trainer_evaluate(self._h, feats.ctypes.data if n else None, targets.ctypes.data if n else None, n,
                                                   float(loss_bias), loss.ctypes.data, acc.ctypes.data, probs.ctypes.data))
         return float(loss[0]), float(acc[0]), probs
+
+    def split(self, flat):
+        """the concatenated flat vector -> one view per network, in model order"""
+        sizes = self.n_params if isinstance(self.n_params, list) else [self.n_params]
+        return np.split(np.asarray(flat), np.cumsum(sizes)[:-1])
+
+    def set_validation(self, feats, targets):
+        """a second resident set (``evaluate_models(source='validation')``), next to the one of ``set_data``"""
+        feats = self._feats(feats)
+        targets = self._targets(targets, feats.shape[0])
+        self._check(self._lib.pe_trainer_set_validation(self._h, feats.ctypes.data if feats.size else None,
+                                                        targets.ctypes.data if targets.size else None, feats.shape[0]))
+
+    def _per_model(self, v, what):
+        """one value for all networks, or a sequence of one per network -> a plain list (no numpy: a seed keeps all 64 bits)"""
+        v = [v] * self.n_models if np.ndim(v) == 0 else list(v)
+        if len(v) != self.n_models:
+            raise ValueError('%s must hold one value per network (%d), got %d' % (what, self.n_models, len(v)))
+        return v
+
+    def step_models(self, indices, step=0, dropout_rate=0.0, seed=0, loss_bias=0.7, lr=1e-3, rho=0.9, eps=1e-7,
+                    frozen_mask=0) -> np.ndarray:
+        """One optimizer step of every network on the same batch, in one launch.  Each hyperparameter is one value for all
+        networks or a sequence with one value per network.  -> the batch losses, float32 [n_models]."""
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        cols = [self._per_model(v, name) for v, name in ((dropout_rate, 'dropout_rate'), (seed, 'seed'), (loss_bias, 'loss_bias'),
+                                                         (lr, 'lr'), (rho, 'rho'), (eps, 'eps'), (frozen_mask, 'frozen_mask'))]
+        hp = (PeTrainHparams * self.n_models)()
+        for m in range(self.n_models):
+            hp[m] = PeTrainHparams(float(cols[0][m]), int(cols[1][m]), float(cols[2][m]), float(cols[3][m]), float(cols[4][m]),
+                                   float(cols[5][m]), int(cols[6][m]))
+        loss = np.zeros(self.n_models, dtype=np.float32)
+        self._check(self._lib.pe_trainer_step_models(self._h, idx.ctypes.data if idx.size else None, idx.size, int(step), hp,
+                                                     loss.ctypes.data))
+        return loss
+
+    def evaluate_models(self, feats=None, targets=None, loss_bias=0.7, source='host', want_probs=True):
+        """Every network on the same samples, dropout off.  ``source``: 'host' (``feats`` [N, n_features, feature_size] and
+        optional ``targets``, uploaded once), 'data' (the set of ``set_data``) or 'validation' (``set_validation``): nothing
+        but the results crosses the bus.  -> (losses float32 [n_models], accuracies float32 [n_models], probabilities float32
+        [n_models, N] or None); losses and accuracies are None without targets."""
+        code = {'host': TRAIN_SOURCE_HOST, 'data': TRAIN_SOURCE_DATA, 'validation': TRAIN_SOURCE_VALIDATION}.get(source)
+        if code is None:
+            raise ValueError("source must be 'host', 'data' or 'validation', got %r" % (source,))
+        K = self.n_models
+        bias = np.ascontiguousarray(self._per_model(loss_bias, 'loss_bias'), dtype=np.float32)
+        loss, acc = np.zeros(K, dtype=np.float32), np.zeros(K, dtype=np.float32)
+        if code == TRAIN_SOURCE_HOST:
+            feats = self._feats(feats)
+            n = feats.shape[0]
+            has_targets = targets is not None
+            targets = self._targets(targets, n) if has_targets else None
+            probs = np.zeros((K, n), dtype=np.float32)
+            self._check(self._lib.pe_trainer_evaluate_models(
+                self._h, code, feats.ctypes.data if n else None, targets.ctypes.data if has_targets and n else None, n,
+                bias.ctypes.data, loss.ctypes.data if has_targets else None, acc.ctypes.data if has_targets else None,
+                probs.ctypes.data))
+            return (loss, acc, probs) if has_targets else (None, None, probs)
+        probs = None
+        if want_probs:
+            probs = np.zeros((K, max(0, int(self._lib.pe_trainer_n_samples(self._h, code)))), dtype=np.float32)   # (no set: the call refuses)
+        self._check(self._lib.pe_trainer_evaluate_models(self._h, code, None, None, 0, bias.ctypes.data, loss.ctypes.data,
+                                                         acc.ctypes.data, probs.ctypes.data if want_probs and probs.size else None))
+        return loss, acc, probs
 
     def close(self):
         if getattr(self, '_h', None) and self._h.value:

@@ -2436,19 +2436,27 @@ int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms) {
 }  // extern "C"
 
 // ---- training (kernels: gru_train_device.h) ----------------------------------------------------------------
+static_assert(PE_TRAIN_MAX_MODELS == kTrainMaxModels, "the header's cap is the kernel table's length");
+
+struct TrainSet {                           // a resident set: pe_trainer_set_data / pe_trainer_set_validation
+    const float* feats = nullptr;
+    const float* targets = nullptr;
+    int n = 0;
+};
+
 struct pe_trainer {
     int device = 0;
-    int T = 0, F = 0, H = 0, n_params = 0;
+    int T = 0, F = 0, K = 0, n_params = 0;  // n_params: the total over the networks
+    int H[kTrainMaxModels] = {}, ofs[kTrainMaxModels + 1] = {};        // units; offset of a network's flat vector
     std::string err;
-    float* theta = nullptr;         // flat parameters
+    float* theta = nullptr;         // concatenated flat parameters
     float* accum = nullptr;         // RMSprop accumulators
     float* grads = nullptr;
-    float* loss = nullptr;
-    const float* data_feats = nullptr;      // pe_trainer_set_data
-    const float* data_targets = nullptr;
-    int data_n = 0;
-    // buffers that grow with the largest call: 0 feats, 1 targets, 2 masks, 3 indices, 4 tape, 5 partial, 6 probs, 7 / 8 dataset
-    DeviceBuf buf[9];
+    float* loss = nullptr;          // [K] losses, then [K] int32 accuracy counts: one copy brings both back
+    TrainSet data, validation;
+    // buffers that grow with the largest call: 0 feats, 1 targets, 2 masks, 3 indices, 4 tape, 5 partial, 6 probs,
+    // 7 / 8 dataset, 9 / 10 validation set
+    DeviceBuf buf[11];
 };
 
 namespace {
@@ -2488,35 +2496,44 @@ int train_check_targets(pe_trainer* t, const float* y, int n) {
     return PE_OK;
 }
 
-// forward (+ backward) over n samples and the reduction; the caller has filled a.feats / targets / indices / mask_*
-int train_run(pe_trainer* t, TrainArgs a, bool backward, float loss_bias, const TrainReduceArgs* apply) {
+// "model 2: " in front of a per-network complaint of a trainer of several
+std::string train_model_prefix(int n_models, int m) { return n_models > 1 ? "model " + std::to_string(m) + ": " : std::string(); }
+
+// Forward (+ backward) of every network over n samples, and the reduction.  The caller has filled a.n / feats / targets /
+// indices / masks / apply and, per network, mask_* / beta / lr / rho / eps / frozen_mask; the rest is set here.
+int train_run(pe_trainer* t, TrainArgs& a, bool backward) {
     const int blocks = (a.n + kTrainTile - 1) / kTrainTile;
-    a.T = t->T; a.F = t->F; a.H = t->H;
-    a.theta = t->theta;
-    a.beta = loss_bias;
+    int widest = 0;
+    for (int m = 0; m < t->K; ++m) widest = std::max(widest, t->H[m]);
+    a.T = t->T; a.F = t->F; a.n_models = t->K;
+    a.backward = backward ? 1 : 0;
+    a.n_blocks = blocks;
+    a.threads = train_threads(widest);
+    a.n_total = t->n_params;
     a.inv_n = 1.0f / (float)a.n;
-    a.n_grad = backward ? t->n_params : 0;
-    int rc = train_reserve(t, 5, (size_t)blocks * (a.n_grad + 2) * sizeof(float));
+    a.theta = t->theta;
+    a.accum = t->accum;
+    a.grads = backward ? t->grads : nullptr;
+    a.loss = t->loss;
+    size_t tape = 0, partial = 0;
+    for (int m = 0; m < t->K; ++m) {
+        TrainModel& r = a.model[m];
+        r.H = t->H[m];
+        r.ofs = t->ofs[m];
+        r.tape_ofs = tape;
+        r.partial_ofs = partial;
+        if (backward) tape += (size_t)blocks * t->T * 4 * a.threads;
+        partial += (size_t)blocks * ((backward ? t->ofs[m + 1] - t->ofs[m] : 0) + 2);
+    }
+    int rc = train_reserve(t, 5, partial * sizeof(float));
     if (rc) return rc;
-    if (backward && (rc = train_reserve(t, 4, (size_t)blocks * t->T * 4 * train_threads(t->H) * sizeof(float)))) return rc;
-    if ((rc = train_reserve(t, 6, (size_t)a.n * sizeof(float)))) return rc;
+    if (backward && (rc = train_reserve(t, 4, tape * sizeof(float)))) return rc;
+    if ((rc = train_reserve(t, 6, (size_t)t->K * a.n * sizeof(float)))) return rc;
     a.tape = static_cast<float*>(t->buf[4].p);
     a.partial = static_cast<float*>(t->buf[5].p);
     a.probs = static_cast<float*>(t->buf[6].p);
-    PE_THIP(t, launch_train(a, backward, nullptr));
-    TrainReduceArgs r{};
-    if (apply) r = *apply;
-    r.partial = a.partial;
-    r.n_blocks = blocks;
-    r.n_grad = a.n_grad;
-    r.grads = backward ? t->grads : nullptr;
-    r.loss = t->loss;
-    r.beta = loss_bias;
-    r.inv_n = a.inv_n;
-    r.theta = t->theta;
-    r.accum = t->accum;
-    r.n_gru = train_n_gru(t->F, t->H);
-    PE_THIP(t, launch_train_reduce(r, nullptr));
+    PE_THIP(t, launch_train(a, nullptr));
+    PE_THIP(t, launch_train_reduce(a, nullptr));
     return PE_OK;
 }
 
@@ -2536,6 +2553,116 @@ int train_upload_batch(pe_trainer* t, const float* feats_host, const float* targ
     return PE_OK;
 }
 
+int train_upload_set(pe_trainer* t, const char* who, TrainSet* set, int slot, const float* feats_host, const float* targets_host, int n) {
+    if (!feats_host || !targets_host) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: n = %d", who, n);
+    int rc = train_check_targets(t, targets_host, n);
+    if (rc) return rc;
+    PE_THIP(t, hipSetDevice(t->device));
+    set->n = 0;
+    const size_t fb = (size_t)n * t->T * t->F * sizeof(float);
+    if ((rc = train_reserve(t, slot, fb)) || (rc = train_reserve(t, slot + 1, (size_t)n * sizeof(float)))) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[slot].p, feats_host, fb, hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(t->buf[slot + 1].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    set->feats = static_cast<const float*>(t->buf[slot].p);
+    set->targets = static_cast<const float*>(t->buf[slot + 1].p);
+    set->n = n;
+    return PE_OK;
+}
+
+int train_step(pe_trainer* t, const char* who, const int32_t* indices_host, int n, uint64_t step, const pe_train_hparams* hp,
+               float* loss_out) {
+    if (!indices_host || !hp || !loss_out) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: n = %d", who, n);
+    if (t->data.n <= 0) return tfail(t, PE_ERR_INVALID, "%s: no dataset (call pe_trainer_set_data first)", who);
+    for (int m = 0; m < t->K; ++m)
+        if (!(hp[m].dropout_rate >= 0.0f && hp[m].dropout_rate < 1.0f))
+            return tfail(t, PE_ERR_INVALID, "%sdropout rate %g is outside [0, 1)", train_model_prefix(t->K, m).c_str(), (double)hp[m].dropout_rate);
+    for (int i = 0; i < n; ++i)
+        if (indices_host[i] < 0 || indices_host[i] >= t->data.n)
+            return tfail(t, PE_ERR_INVALID, "indices[%d] = %d is outside the dataset of %d samples", i, indices_host[i], t->data.n);
+    PE_THIP(t, hipSetDevice(t->device));
+    int rc = train_reserve(t, 3, (size_t)n * sizeof(int32_t));
+    if (rc) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[3].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    TrainArgs a{};
+    a.n = n;
+    a.feats = t->data.feats;
+    a.targets = t->data.targets;
+    a.indices = static_cast<const int32_t*>(t->buf[3].p);
+    a.apply = 1;
+    for (int m = 0; m < t->K; ++m) {
+        TrainModel& r = a.model[m];
+        if (hp[m].dropout_rate > 0.0f) {
+            r.mask_mode = 2;
+            r.mask_key = train_mask_key(hp[m].seed, step);
+            r.rate = hp[m].dropout_rate;
+            r.keep_scale = train_keep_scale(hp[m].dropout_rate);
+        }
+        r.beta = hp[m].loss_bias;
+        r.lr = hp[m].lr; r.rho = hp[m].rho; r.eps = hp[m].eps;
+        r.frozen_mask = hp[m].frozen_mask;
+    }
+    if ((rc = train_run(t, a, true))) return rc;
+    PE_THIP(t, hipMemcpy(loss_out, t->loss, (size_t)t->K * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int train_evaluate(pe_trainer* t, const char* who, int source, const float* feats_host, const float* targets_host, int n,
+                   const float* loss_bias, float* loss_out, float* acc_out, float* probs_out) {
+    const TrainSet* set = nullptr;
+    if (source == PE_TRAIN_SOURCE_HOST) {
+        if (!feats_host) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+        if (!targets_host && (loss_out || acc_out)) return tfail(t, PE_ERR_INVALID, "%s: loss and accuracy need targets", who);
+        if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: n = %d", who, n);
+    } else if (source == PE_TRAIN_SOURCE_DATA || source == PE_TRAIN_SOURCE_VALIDATION) {
+        set = source == PE_TRAIN_SOURCE_DATA ? &t->data : &t->validation;
+        if (set->n <= 0)
+            return tfail(t, PE_ERR_INVALID, "%s: no resident %s set (call %s first)", who, source == PE_TRAIN_SOURCE_DATA ? "training" : "validation",
+                         source == PE_TRAIN_SOURCE_DATA ? "pe_trainer_set_data" : "pe_trainer_set_validation");
+        n = set->n;
+    } else {
+        return tfail(t, PE_ERR_INVALID, "%s: source = %d", who, source);
+    }
+    if (loss_out && !loss_bias) return tfail(t, PE_ERR_INVALID, "%s: a loss needs loss_bias", who);
+    int rc = (!set && targets_host) ? train_check_targets(t, targets_host, n) : PE_OK;
+    if (rc) return rc;
+    PE_THIP(t, hipSetDevice(t->device));
+    TrainArgs a{};
+    if (set) {
+        a.n = n;
+        a.feats = set->feats;
+        a.targets = set->targets;
+    } else if ((rc = train_upload_batch(t, feats_host, targets_host, n, &a))) {
+        return rc;
+    }
+    for (int m = 0; m < t->K; ++m) a.model[m].beta = loss_bias ? loss_bias[m] : 0.0f;
+    if ((rc = train_run(t, a, false))) return rc;
+    const int K = t->K;
+    int32_t* const hits = reinterpret_cast<int32_t*>(t->loss + K);
+    if (acc_out) {
+        TrainAccuracyArgs c{a.probs, a.targets, n, hits};
+        PE_THIP(t, launch_train_accuracy(c, K, nullptr));
+    }
+    float back[2 * kTrainMaxModels];
+    PE_THIP(t, hipMemcpy(back, t->loss, (size_t)(acc_out ? 2 : 1) * K * sizeof(float), hipMemcpyDeviceToHost));
+    if (probs_out) PE_THIP(t, hipMemcpy(probs_out, t->buf[6].p, (size_t)K * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (loss_out) memcpy(loss_out, back, (size_t)K * sizeof(float));
+    if (acc_out)                                       // Keras binary_accuracy: mean(round(p) == y), ties to even
+        for (int m = 0; m < K; ++m) {
+            int32_t h;
+            memcpy(&h, back + K + m, sizeof h);
+            acc_out[m] = (float)((double)h / n);
+        }
+    return PE_OK;
+}
+
+int train_one_model_only(pe_trainer* t, const char* who, const char* instead) {
+    if (t->K == 1) return PE_OK;
+    return tfail(t, PE_ERR_UNSUPPORTED, "%s: this trainer holds n_models = %d networks%s%s", who, t->K, instead ? "; call " : " (one-network entry point)",
+                 instead ? instead : "");
+}
+
 }  // namespace
 
 extern "C" {
@@ -2552,43 +2679,60 @@ int pe_trainer_destroy(pe_trainer* t) {
     return PE_OK;
 }
 
-int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t device, pe_trainer** out) {
+int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
+                             pe_trainer** out) {
     if (!init || !out) return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: null argument");
     *out = nullptr;
-    if (init->n_layers != 1)
-        return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: n_layers = %d (one GRU layer has a training kernel)", init->n_layers);
-    if (!init->layers || !init->layers[0].kernel || !init->layers[0].recurrent_kernel || !init->layers[0].bias || !init->dense_kernel)
-        return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: null weight array");
-    const int H = init->layers[0].units;
-    if (H < 1 || H > kTrainMaxUnits) return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: units = %d (1..%d)", H, kTrainMaxUnits);
+    if (n_models < 1) return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: n_models = %d", n_models);
+    if (n_models > PE_TRAIN_MAX_MODELS)
+        return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: n_models = %d (1..%d)", n_models, PE_TRAIN_MAX_MODELS);
     if (feature_size < 1 || feature_size > kTrainMaxFeat)
         return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: feature_size = %d (1..%d)", feature_size, kTrainMaxFeat);
     if (n_features < 1 || n_features > kTrainMaxSteps)
         return tfail(nullptr, PE_ERR_UNSUPPORTED, "training: n_features = %d (1..%d)", n_features, kTrainMaxSteps);
-    if (init->layers[0].n_in != feature_size)
-        return tfail(nullptr, PE_ERR_INVALID, "the GRU layer takes %d inputs, feature_size is %d", init->layers[0].n_in, feature_size);
+    for (int m = 0; m < n_models; ++m) {
+        const pe_weights& w = init[m];
+        const std::string pre = train_model_prefix(n_models, m);
+        if (w.n_layers != 1)
+            return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: n_layers = %d (one GRU layer has a training kernel)", pre.c_str(), w.n_layers);
+        if (!w.layers || !w.layers[0].kernel || !w.layers[0].recurrent_kernel || !w.layers[0].bias || !w.dense_kernel)
+            return tfail(nullptr, PE_ERR_INVALID, "%spe_trainer_create: null weight array", pre.c_str());
+        const int H = w.layers[0].units;
+        if (H < 1 || H > kTrainMaxUnits) return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: units = %d (1..%d)", pre.c_str(), H, kTrainMaxUnits);
+        if (w.layers[0].n_in != feature_size)
+            return tfail(nullptr, PE_ERR_INVALID, "%sthe GRU layer takes %d inputs, feature_size is %d", pre.c_str(), w.layers[0].n_in, feature_size);
+    }
     hipError_t herr = hipSetDevice(device);
     if (herr != hipSuccess) return tfail(nullptr, PE_ERR_HIP, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(herr));
     pe_trainer* t = new pe_trainer;
     t->device = device;
-    t->T = n_features; t->F = feature_size; t->H = H;
-    t->n_params = train_n_params(feature_size, H);
+    t->T = n_features; t->F = feature_size; t->K = n_models;
+    for (int m = 0; m < n_models; ++m) {
+        t->H[m] = init[m].layers[0].units;
+        t->ofs[m + 1] = t->ofs[m] + train_n_params(feature_size, t->H[m]);
+    }
+    t->n_params = t->ofs[n_models];
     const size_t pb = (size_t)t->n_params * sizeof(float);
     for (float** p : {&t->theta, &t->accum, &t->grads, &t->loss}) {
-        herr = hipMalloc(reinterpret_cast<void**>(p), pb);
+        const size_t bytes = p == &t->loss ? (size_t)2 * kTrainMaxModels * sizeof(float) : pb;
+        herr = hipMalloc(reinterpret_cast<void**>(p), bytes);
         if (herr != hipSuccess) {
             *p = nullptr;
             pe_trainer_destroy(t);
-            return tfail(nullptr, PE_ERR_NOMEM, "hipMalloc(%zu) failed: %s", pb, hipGetErrorString(herr));
+            return tfail(nullptr, PE_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(herr));
         }
     }
     std::vector<float> flat((size_t)t->n_params);
-    const int F = feature_size, H3 = 3 * H;
-    memcpy(flat.data(), init->layers[0].kernel, (size_t)F * H3 * sizeof(float));
-    memcpy(flat.data() + F * H3, init->layers[0].recurrent_kernel, (size_t)H * H3 * sizeof(float));
-    memcpy(flat.data() + (F + H) * H3, init->layers[0].bias, (size_t)H3 * sizeof(float));
-    memcpy(flat.data() + (F + H + 1) * H3, init->dense_kernel, (size_t)H * sizeof(float));
-    flat[(size_t)t->n_params - 1] = init->dense_bias;
+    const int F = feature_size;
+    for (int m = 0; m < n_models; ++m) {
+        const int H = t->H[m], H3 = 3 * H;
+        float* f = flat.data() + t->ofs[m];
+        memcpy(f, init[m].layers[0].kernel, (size_t)F * H3 * sizeof(float));
+        memcpy(f + F * H3, init[m].layers[0].recurrent_kernel, (size_t)H * H3 * sizeof(float));
+        memcpy(f + (F + H) * H3, init[m].layers[0].bias, (size_t)H3 * sizeof(float));
+        memcpy(f + (F + H + 1) * H3, init[m].dense_kernel, (size_t)H * sizeof(float));
+        f[(F + H + 1) * H3 + H] = init[m].dense_bias;
+    }
     int rc = pe_trainer_set_weights(t, flat.data());
     if (!rc) rc = pe_trainer_reset_optimizer(t);
     if (rc) {
@@ -2600,7 +2744,17 @@ int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights
     return PE_OK;
 }
 
+int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t device, pe_trainer** out) {
+    return pe_trainer_create_models(n_features, feature_size, init, 1, device, out);
+}
+
+int pe_trainer_n_models(const pe_trainer* t) { return t ? t->K : -1; }
 int pe_trainer_n_params(const pe_trainer* t) { return t ? t->n_params : -1; }
+int pe_trainer_n_samples(const pe_trainer* t, int32_t source) {
+    if (!t || (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION)) return -1;
+    return source == PE_TRAIN_SOURCE_DATA ? t->data.n : t->validation.n;
+}
+int pe_trainer_n_params_model(const pe_trainer* t, int32_t m) { return t && m >= 0 && m < t->K ? t->ofs[m + 1] - t->ofs[m] : -1; }
 
 int pe_trainer_get_weights(pe_trainer* t, float* flat_out) {
     if (!t) return PE_ERR_INVALID;
@@ -2636,10 +2790,11 @@ int pe_trainer_reset_optimizer(pe_trainer* t) {
 int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, const float* masks_host,
                          float loss_bias, float* loss_out, float* grads_out, float* probs_out) {
     if (!t) return PE_ERR_INVALID;
+    int rc = train_one_model_only(t, "pe_trainer_loss_grad", nullptr);
+    if (rc) return rc;
     if (!feats_host || !targets_host || !loss_out || !grads_out) return tfail(t, PE_ERR_INVALID, "pe_trainer_loss_grad: null pointer");
     if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_loss_grad: n = %d", n);
-    int rc = train_check_targets(t, targets_host, n);
-    if (rc) return rc;
+    if ((rc = train_check_targets(t, targets_host, n))) return rc;
     PE_THIP(t, hipSetDevice(t->device));
     TrainArgs a{};
     if ((rc = train_upload_batch(t, feats_host, targets_host, n, &a))) return rc;
@@ -2647,10 +2802,11 @@ int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* ta
         const size_t mb = (size_t)3 * n * t->F * sizeof(float);
         if ((rc = train_reserve(t, 2, mb))) return rc;
         PE_THIP(t, hipMemcpy(t->buf[2].p, masks_host, mb, hipMemcpyHostToDevice));
-        a.mask_mode = 1;
+        a.model[0].mask_mode = 1;
         a.masks = static_cast<const float*>(t->buf[2].p);
     }
-    if ((rc = train_run(t, a, true, loss_bias, nullptr))) return rc;
+    a.model[0].beta = loss_bias;
+    if ((rc = train_run(t, a, true))) return rc;
     PE_THIP(t, hipMemcpy(loss_out, t->loss, sizeof(float), hipMemcpyDeviceToHost));
     PE_THIP(t, hipMemcpy(grads_out, t->grads, (size_t)t->n_params * sizeof(float), hipMemcpyDeviceToHost));
     if (probs_out) PE_THIP(t, hipMemcpy(probs_out, t->buf[6].p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
@@ -2659,96 +2815,63 @@ int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* ta
 
 int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho, float eps, int32_t frozen_mask) {
     if (!t) return PE_ERR_INVALID;
+    int rc = train_one_model_only(t, "pe_trainer_apply", nullptr);
+    if (rc) return rc;
     if (!grads_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_apply: null pointer");
     PE_THIP(t, hipSetDevice(t->device));
     PE_THIP(t, hipMemcpy(t->grads, grads_host, (size_t)t->n_params * sizeof(float), hipMemcpyHostToDevice));
-    TrainReduceArgs r{};
-    r.n_grad = t->n_params;
-    r.grads = t->grads;
-    r.theta = t->theta;
-    r.accum = t->accum;
+    TrainArgs a{};
+    a.F = t->F; a.n_models = 1;
+    a.n_total = t->n_params;
+    a.grads = t->grads;
+    a.theta = t->theta;
+    a.accum = t->accum;
+    TrainModel& r = a.model[0];
+    r.H = t->H[0];
     r.lr = lr; r.rho = rho; r.eps = eps;
     r.frozen_mask = frozen_mask;
-    r.n_gru = train_n_gru(t->F, t->H);
-    PE_THIP(t, launch_train_apply(r, nullptr));
+    PE_THIP(t, launch_train_apply(a, nullptr));
     PE_THIP(t, hipDeviceSynchronize());
     return PE_OK;
 }
 
 int pe_trainer_set_data(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n) {
     if (!t) return PE_ERR_INVALID;
-    if (!feats_host || !targets_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_set_data: null pointer");
-    if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_set_data: n = %d", n);
-    int rc = train_check_targets(t, targets_host, n);
-    if (rc) return rc;
-    PE_THIP(t, hipSetDevice(t->device));
-    t->data_n = 0;
-    const size_t fb = (size_t)n * t->T * t->F * sizeof(float);
-    if ((rc = train_reserve(t, 7, fb)) || (rc = train_reserve(t, 8, (size_t)n * sizeof(float)))) return rc;
-    PE_THIP(t, hipMemcpy(t->buf[7].p, feats_host, fb, hipMemcpyHostToDevice));
-    PE_THIP(t, hipMemcpy(t->buf[8].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    t->data_feats = static_cast<const float*>(t->buf[7].p);
-    t->data_targets = static_cast<const float*>(t->buf[8].p);
-    t->data_n = n;
-    return PE_OK;
+    return train_upload_set(t, "pe_trainer_set_data", &t->data, 7, feats_host, targets_host, n);
+}
+
+int pe_trainer_set_validation(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n) {
+    if (!t) return PE_ERR_INVALID;
+    return train_upload_set(t, "pe_trainer_set_validation", &t->validation, 9, feats_host, targets_host, n);
+}
+
+int pe_trainer_step_models(pe_trainer* t, const int32_t* indices_host, int32_t n, uint64_t step, const pe_train_hparams* hp,
+                           float* loss_out) {
+    if (!t) return PE_ERR_INVALID;
+    return train_step(t, "pe_trainer_step_models", indices_host, n, step, hp, loss_out);
 }
 
 int pe_trainer_step(pe_trainer* t, const int32_t* indices_host, int32_t n, float dropout_rate, uint64_t seed, uint64_t step,
                     float loss_bias, float lr, float rho, float eps, int32_t frozen_mask, float* loss_out) {
     if (!t) return PE_ERR_INVALID;
-    if (!indices_host || !loss_out) return tfail(t, PE_ERR_INVALID, "pe_trainer_step: null pointer");
-    if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_step: n = %d", n);
-    if (t->data_n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_step: no dataset (call pe_trainer_set_data first)");
-    if (!(dropout_rate >= 0.0f && dropout_rate < 1.0f)) return tfail(t, PE_ERR_INVALID, "dropout rate %g is outside [0, 1)", (double)dropout_rate);
-    for (int i = 0; i < n; ++i)
-        if (indices_host[i] < 0 || indices_host[i] >= t->data_n)
-            return tfail(t, PE_ERR_INVALID, "indices[%d] = %d is outside the dataset of %d samples", i, indices_host[i], t->data_n);
-    PE_THIP(t, hipSetDevice(t->device));
-    int rc = train_reserve(t, 3, (size_t)n * sizeof(int32_t));
+    int rc = train_one_model_only(t, "pe_trainer_step", "pe_trainer_step_models");
     if (rc) return rc;
-    PE_THIP(t, hipMemcpy(t->buf[3].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-    TrainArgs a{};
-    a.n = n;
-    a.feats = t->data_feats;
-    a.targets = t->data_targets;
-    a.indices = static_cast<const int32_t*>(t->buf[3].p);
-    if (dropout_rate > 0.0f) {
-        a.mask_mode = 2;
-        a.mask_key = train_mask_key(seed, step);
-        a.rate = dropout_rate;
-        a.keep_scale = train_keep_scale(dropout_rate);
-    }
-    TrainReduceArgs r{};
-    r.apply = 1;
-    r.lr = lr; r.rho = rho; r.eps = eps;
-    r.frozen_mask = frozen_mask;
-    if ((rc = train_run(t, a, true, loss_bias, &r))) return rc;
-    PE_THIP(t, hipMemcpy(loss_out, t->loss, sizeof(float), hipMemcpyDeviceToHost));
-    return PE_OK;
+    const pe_train_hparams hp{dropout_rate, seed, loss_bias, lr, rho, eps, frozen_mask};
+    return train_step(t, "pe_trainer_step", indices_host, n, step, &hp, loss_out);
+}
+
+int pe_trainer_evaluate_models(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n,
+                               const float* loss_bias, float* loss_out, float* acc_out, float* probs_out) {
+    if (!t) return PE_ERR_INVALID;
+    return train_evaluate(t, "pe_trainer_evaluate_models", source, feats_host, targets_host, n, loss_bias, loss_out, acc_out, probs_out);
 }
 
 int pe_trainer_evaluate(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, float loss_bias,
                         float* loss_out, float* acc_out, float* probs_out) {
     if (!t) return PE_ERR_INVALID;
-    if (!feats_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_evaluate: null pointer");
-    if (!targets_host && (loss_out || acc_out)) return tfail(t, PE_ERR_INVALID, "pe_trainer_evaluate: loss and accuracy need targets");
-    if (n <= 0) return tfail(t, PE_ERR_INVALID, "pe_trainer_evaluate: n = %d", n);
-    int rc = targets_host ? train_check_targets(t, targets_host, n) : PE_OK;
+    int rc = train_one_model_only(t, "pe_trainer_evaluate", "pe_trainer_evaluate_models");
     if (rc) return rc;
-    PE_THIP(t, hipSetDevice(t->device));
-    TrainArgs a{};
-    if ((rc = train_upload_batch(t, feats_host, targets_host, n, &a))) return rc;
-    if ((rc = train_run(t, a, false, loss_bias, nullptr))) return rc;
-    std::vector<float> probs((size_t)n);
-    PE_THIP(t, hipMemcpy(probs.data(), t->buf[6].p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    if (loss_out) PE_THIP(t, hipMemcpy(loss_out, t->loss, sizeof(float), hipMemcpyDeviceToHost));
-    if (acc_out) {                                     // Keras binary_accuracy: mean(round(p) == y), ties to even
-        int64_t hits = 0;
-        for (int i = 0; i < n; ++i) hits += nearbyintf(probs[i]) == targets_host[i] ? 1 : 0;
-        *acc_out = (float)((double)hits / n);
-    }
-    if (probs_out) memcpy(probs_out, probs.data(), (size_t)n * sizeof(float));
-    return PE_OK;
+    return train_evaluate(t, "pe_trainer_evaluate", PE_TRAIN_SOURCE_HOST, feats_host, targets_host, n, &loss_bias, loss_out, acc_out, probs_out);
 }
 
 int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feature_size, float rate, float* out) {

@@ -10,6 +10,13 @@
 // fixed set of (row, col) sums in registers over all steps, in a fixed order, and the workgroup writes one partial
 // gradient vector.  train_reduce_kernel adds the partials in workgroup order (no floating-point atomic anywhere) and may
 // apply RMSprop in the same pass.
+//
+// Several networks (widths 1..32, their own hyperparameters) train on the same batch in ONE launch over (tile, network),
+// network fastest, so the workgroups that gather the same rows run next to each other.  The block is as wide as the widest
+// network needs and the LDS is the widest network's layout; a narrower network leaves threads idle (`active`) and strides
+// its staging loops, its tape and its gradient elements by the launch's width.  None of that enters a sum: every sum runs
+// over samples and timesteps in an order fixed by (F, H) alone, so a network's bits do not depend on its company.  The
+// per-network record (TrainModel) is read once per workgroup, outside the timestep loops.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,9 +51,12 @@ __host__ __device__ inline int train_n_gru(int F, int H) { return (F + H + 1) * 
 __host__ __device__ inline int train_n_params(int F, int H) { return train_n_gru(F, H) + H + 1; }
 inline int train_threads(int H) { return (kTrainTile * H + 63) / 64 * 64; }
 
-struct TrainArgs {
+constexpr int kTrainMaxModels = 16;     // PE_TRAIN_MAX_MODELS: 16 records of 64 bytes travel by value in the kernel arguments
+
+// What one workgroup of train_tile works on: the shared batch and ONE network.
+struct TrainView {
     int n, T, F, H;
-    const float* theta;         // flat parameters
+    const float* theta;         // flat parameters of the network
     const float* feats;         // [rows][T][F]
     const float* targets;       // [rows], or null (forward only: read as 0)
     const int32_t* indices;     // [n] rows of feats / targets, or null: row i
@@ -55,28 +65,64 @@ struct TrainArgs {
     uint64_t mask_key;
     float rate, keep_scale;     // keep_scale = 1 / (1 - rate), formed once on the host
     float beta, inv_n;
-    float* tape;                // [blocks][T][4][threads]   (training only)
+    float* tape;                // [blocks][T][4][threads of the launch]   (training only)
     float* partial;             // [blocks][n_grad + 2]: the gradient, then the two loss sums
     int n_grad;                 // train_n_params, or 0 for a forward-only launch
     float* probs;               // [n] or null
 };
 
-struct TrainReduceArgs {
-    const float* partial;
-    int n_blocks, n_grad;
-    float* grads;               // [n_grad] or null
-    float* loss;                // [1]
-    float beta, inv_n;
-    int apply;                  // 1: RMSprop on theta / accum with the summed gradient
-    float* theta;
-    float* accum;
+// The per-network record of a launch (64 bytes).  Everything not in here is shared by the networks of the launch.
+struct TrainModel {
+    int H;                      // units
+    int ofs;                    // of this network's flat vector in the concatenation (theta, accum, grads alike)
+    int mask_mode;
+    int frozen_mask;            // bit 0 freezes [0, n_gru), bit 1 the rest
+    float rate, keep_scale, beta;
     float lr, rho, eps;
-    int frozen_mask, n_gru;     // bit 0 freezes [0, n_gru), bit 1 the rest
+    uint64_t mask_key;
+    uint64_t tape_ofs;          // in floats from TrainArgs::tape: [blocks][T][4][threads]
+    uint64_t partial_ofs;       // in floats from TrainArgs::partial: [blocks][n_grad + 2]
 };
 
-hipError_t launch_train(const TrainArgs& a, bool backward, hipStream_t s);
-hipError_t launch_train_reduce(const TrainReduceArgs& a, hipStream_t s);
-hipError_t launch_train_apply(const TrainReduceArgs& a, hipStream_t s);      // a.grads is read
+static_assert(sizeof(TrainModel) == 64, "kTrainMaxModels records of 64 bytes are what the kernel arguments are sized for");
+
+// One launch over (tile, network), network fastest: workgroup b works on tile b / n_models for network b % n_models.
+// train_tile_kernel and train_reduce_kernel / train_apply_kernel take the same arguments.
+struct TrainArgs {
+    int n, T, F, n_models;
+    int backward;               // 1: gradients (n_grad = train_n_params per network); 0: forward only (n_grad = 0)
+    int n_blocks;               // tiles
+    int threads;                // of the tile launch: train_threads(widest network)
+    int apply;                  // reduction: 1 = RMSprop on theta / accum with the summed gradient
+    int n_total;                // floats of the concatenated flat vector
+    float inv_n;
+    float* theta;               // concatenated flat parameters
+    float* accum;
+    float* grads;               // [n_total] or null
+    float* loss;                // [n_models]
+    const float* feats;
+    const float* targets;
+    const int32_t* indices;
+    const float* masks;         // mask_mode 1 (one network only)
+    float* tape;
+    float* partial;
+    float* probs;               // [n_models][n] or null
+    TrainModel model[kTrainMaxModels];
+};
+
+static_assert(sizeof(TrainArgs) <= 1280, "the kernel arguments stay well below the 4 KB a launch may carry");
+
+struct TrainAccuracyArgs {
+    const float* probs;         // [n_models][n]
+    const float* targets;       // [n]
+    int n;
+    int32_t* hits;              // [n_models]: samples with rintf(p) == y
+};
+
+hipError_t launch_train(const TrainArgs& a, hipStream_t s);                  // a.threads must be train_threads(widest H)
+hipError_t launch_train_reduce(const TrainArgs& a, hipStream_t s);
+hipError_t launch_train_apply(const TrainArgs& a, hipStream_t s);           // a.grads is read
+hipError_t launch_train_accuracy(const TrainAccuracyArgs& a, int n_models, hipStream_t s);
 size_t train_lds_bytes(int F, int H);
 
 #if defined(__HIPCC__)
@@ -119,9 +165,9 @@ struct TrainLds {
 };
 
 template <bool BACKWARD>
-__device__ inline void train_tile(const TrainArgs& a, float* lds) {
+__device__ inline void train_tile(const TrainView& a, float* lds, const int blk) {
     const int T = a.T, F = a.F, H = a.H, H3 = 3 * H, R = F + H + 1;
-    const int tid = threadIdx.x, nt = blockDim.x, blk = blockIdx.x;
+    const int tid = threadIdx.x, nt = blockDim.x;
     const TrainLds o(F, H);
     float* const W = lds + o.W;   float* const U = lds + o.U;   float* const UT = lds + o.UT;
     float* const B = lds + o.B;   float* const WD = lds + o.WD; float* const MS = lds + o.MS;
@@ -308,24 +354,78 @@ __device__ inline void train_tile(const TrainArgs& a, float* lds) {
         if (lo[i] >= 0) part[tid + i * nt] = acc[i];
 }
 
-__device__ inline void train_reduce(const TrainReduceArgs& a) {
+// The view of workgroup blockIdx.x: the per-network record is read here, once, and nowhere inside the timestep loops.
+__device__ inline TrainView train_view(const TrainArgs& g, const int m) {
+    const TrainModel& r = g.model[m];
+    TrainView a;
+    a.n = g.n; a.T = g.T; a.F = g.F; a.H = r.H;
+    a.theta = g.theta + r.ofs;
+    a.feats = g.feats; a.targets = g.targets; a.indices = g.indices;
+    a.mask_mode = r.mask_mode; a.masks = g.masks; a.mask_key = r.mask_key;
+    a.rate = r.rate; a.keep_scale = r.keep_scale;
+    a.beta = r.beta; a.inv_n = g.inv_n;
+    a.tape = g.tape + r.tape_ofs;
+    a.partial = g.partial + r.partial_ofs;
+    a.n_grad = g.backward ? train_n_params(g.F, r.H) : 0;
+    a.probs = g.probs ? g.probs + (size_t)m * g.n : nullptr;
+    return a;
+}
+
+// element e of the concatenated flat vector -> its network
+__device__ inline int train_model_of(const TrainArgs& a, const int e) {
+    int m = 0;
+    while (m + 1 < a.n_models && e >= a.model[m + 1].ofs) ++m;
+    return m;
+}
+
+// One thread per element of the concatenated gradient vector (backward launches), then one per network for its loss.
+__device__ inline void train_reduce(const TrainArgs& a) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)a.n_grad + 2;
-    if (e < a.n_grad) {
+    const int n_elem = a.backward ? a.n_total : 0;
+    if (e < n_elem) {
+        const int m = train_model_of(a, e);
+        const TrainModel& r = a.model[m];
+        const int le = e - r.ofs;
+        const size_t stride = (size_t)train_n_params(a.F, r.H) + 2;
+        const float* part = a.partial + r.partial_ofs + le;
         float sum = 0.0f;
-        for (int b = 0; b < a.n_blocks; ++b) sum += a.partial[b * stride + e];
+        for (int b = 0; b < a.n_blocks; ++b) sum += part[b * stride];
         if (a.grads) a.grads[e] = sum;
-        if (a.apply && !((a.frozen_mask >> (e < a.n_gru ? 0 : 1)) & 1)) train_rmsprop(a.theta[e], a.accum[e], sum, a.lr, a.rho, a.eps);
-    } else if (e == a.n_grad) {
+        if (a.apply && !((r.frozen_mask >> (le < train_n_gru(a.F, r.H) ? 0 : 1)) & 1))
+            train_rmsprop(a.theta[e], a.accum[e], sum, r.lr, r.rho, r.eps);
+    } else if (e < n_elem + a.n_models) {
+        const int m = e - n_elem;
+        const TrainModel& r = a.model[m];
+        const int n_grad = a.backward ? train_n_params(a.F, r.H) : 0;
+        const size_t stride = (size_t)n_grad + 2;
+        const float* part = a.partial + r.partial_ofs + n_grad;
         float la = 0.0f, lb = 0.0f;
-        for (int b = 0; b < a.n_blocks; ++b) { la += a.partial[b * stride + e]; lb += a.partial[b * stride + e + 1]; }
-        a.loss[0] = a.beta * (la * a.inv_n) + (1.0f - a.beta) * (lb * a.inv_n);
+        for (int b = 0; b < a.n_blocks; ++b) { la += part[b * stride]; lb += part[b * stride + 1]; }
+        a.loss[m] = r.beta * (la * a.inv_n) + (1.0f - r.beta) * (lb * a.inv_n);
     }
 }
 
-__device__ inline void train_apply(const TrainReduceArgs& a) {
+__device__ inline void train_apply(const TrainArgs& a) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < a.n_grad && !((a.frozen_mask >> (e < a.n_gru ? 0 : 1)) & 1)) train_rmsprop(a.theta[e], a.accum[e], a.grads[e], a.lr, a.rho, a.eps);
+    if (e >= a.n_total) return;
+    const TrainModel& r = a.model[train_model_of(a, e)];
+    if (!((r.frozen_mask >> (e - r.ofs < train_n_gru(a.F, r.H) ? 0 : 1)) & 1))
+        train_rmsprop(a.theta[e], a.accum[e], a.grads[e], r.lr, r.rho, r.eps);
+}
+
+// Keras binary_accuracy's numerator: one workgroup per network counts round-half-even(p) == y over the n samples, as integers.
+constexpr int kTrainAccThreads = 256;
+__device__ inline void train_accuracy(const TrainAccuracyArgs& a, int32_t* lds) {
+    const float* p = a.probs + (size_t)blockIdx.x * a.n;
+    int32_t hits = 0;
+    for (int i = threadIdx.x; i < a.n; i += kTrainAccThreads) hits += rintf(p[i]) == a.targets[i] ? 1 : 0;
+    lds[threadIdx.x] = hits;
+    __syncthreads();
+    for (int w = kTrainAccThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) lds[threadIdx.x] += lds[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.hits[blockIdx.x] = lds[0];
 }
 
 #endif  // __HIPCC__

@@ -1115,34 +1115,48 @@ hipError_t launch_simulate(const SimArgs& a, int n_models, int n_cus, hipStream_
 template <bool BACKWARD>
 __global__ __launch_bounds__(64 * 8) void train_tile_kernel(const TrainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float train_lds[];
-    train_tile<BACKWARD>(a, train_lds);
+    const int m = blockIdx.x % a.n_models;
+    train_tile<BACKWARD>(train_view(a, m), train_lds, blockIdx.x / a.n_models);
 }
-__global__ __launch_bounds__(256) void train_reduce_kernel(const TrainReduceArgs a) { train_reduce(a); }
-__global__ __launch_bounds__(256) void train_apply_kernel(const TrainReduceArgs a) { train_apply(a); }
+__global__ __launch_bounds__(256) void train_reduce_kernel(const TrainArgs a) { train_reduce(a); }
+__global__ __launch_bounds__(256) void train_apply_kernel(const TrainArgs a) { train_apply(a); }
+__global__ __launch_bounds__(kTrainAccThreads) void train_accuracy_kernel(const TrainAccuracyArgs a) {
+    __shared__ int32_t hits[kTrainAccThreads];
+    train_accuracy(a, hits);
+}
 
 size_t train_lds_bytes(int F, int H) { return (size_t)TrainLds(F, H).total * sizeof(float); }
 
 template <bool BACKWARD>
 static hipError_t launch_train_t(const TrainArgs& a, hipStream_t s) {
-    const size_t lds = train_lds_bytes(a.F, a.H);
+    int widest = 0;
+    for (int m = 0; m < a.n_models; ++m) widest = a.model[m].H > widest ? a.model[m].H : widest;
+    if (a.threads != train_threads(widest) || a.threads > 64 * 8) return hipErrorInvalidValue;
+    const size_t lds = train_lds_bytes(a.F, widest);                 // TrainLds grows with H: the widest network's layout
     if (lds > 48 * 1024) {
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&train_tile_kernel<BACKWARD>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) return err;
     }
-    hipLaunchKernelGGL(train_tile_kernel<BACKWARD>, dim3((a.n + kTrainTile - 1) / kTrainTile), dim3(train_threads(a.H)), lds, s, a);
+    hipLaunchKernelGGL(train_tile_kernel<BACKWARD>, dim3((unsigned)a.n_blocks * a.n_models), dim3(a.threads), lds, s, a);
     return hipGetLastError();
 }
-hipError_t launch_train(const TrainArgs& a, bool backward, hipStream_t s) {
-    if (a.n <= 0) return hipSuccess;
-    return backward ? launch_train_t<true>(a, s) : launch_train_t<false>(a, s);
+hipError_t launch_train(const TrainArgs& a, hipStream_t s) {
+    if (a.n <= 0 || a.n_models < 1 || a.n_models > kTrainMaxModels) return hipErrorInvalidValue;
+    if (a.n_blocks != (a.n + kTrainTile - 1) / kTrainTile) return hipErrorInvalidValue;
+    return a.backward ? launch_train_t<true>(a, s) : launch_train_t<false>(a, s);
 }
-hipError_t launch_train_reduce(const TrainReduceArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(train_reduce_kernel, dim3((a.n_grad + 1 + 255) / 256), dim3(256), 0, s, a);
+hipError_t launch_train_reduce(const TrainArgs& a, hipStream_t s) {
+    const int threads = (a.backward ? a.n_total : 0) + a.n_models;
+    hipLaunchKernelGGL(train_reduce_kernel, dim3((threads + 255) / 256), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_train_apply(const TrainReduceArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(train_apply_kernel, dim3((a.n_grad + 255) / 256), dim3(256), 0, s, a);
+hipError_t launch_train_apply(const TrainArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(train_apply_kernel, dim3((a.n_total + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_train_accuracy(const TrainAccuracyArgs& a, int n_models, hipStream_t s) {
+    hipLaunchKernelGGL(train_accuracy_kernel, dim3(n_models), dim3(kTrainAccThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -11,6 +11,14 @@ DESIGN.md 4.9); this module only shuffles indices and keeps the history.
     history = trainer.fit(inputs, outputs, batch_size=5000, epochs=10, validation_data=(val_in, val_out))
     trainer.save('hey-computer.npz')            # then HipRunner('hey-computer.npz') / Listener serve it
 
+``TrainerGroup`` trains several candidate networks -- other widths, dropout rates, ``loss_bias`` values, seeds -- on the same
+data at once: one resident dataset, one launch per batch for all of them, and each candidate ends with exactly the bits that a
+``Trainer`` of its own would have given it.
+
+    group = TrainerGroup([ModelParams(recurrent_units=u, loss_bias=b) for u in (12, 20, 32) for b in (0.5, 0.7)])
+    histories = group.fit(inputs, outputs, validation_data=(val_in, val_out))
+    group.save(group.best('val_loss'), 'hey-computer.npz')
+
 There is no CPU fallback: without the HIP library or a GPU the constructor raises.
 """
 import numpy as np
@@ -122,6 +130,123 @@ class Trainer:
             if callback is not None:
                 callback(epoch, logs)
         return history
+
+    def close(self):
+        self._t.close()
+
+
+class TrainerGroup:
+    """K candidate networks trained together on ONE resident dataset (``pe_trainer_create_models``).
+
+    ``candidates``: a list of ``ModelParams``; ``recurrent_units``, ``dropout``, ``loss_bias`` and ``freeze_till`` mean what
+    they mean to ``Trainer``.  ``seeds[m]`` (default: ``seed`` for every candidate) drives candidate m's initial network and its
+    dropout masks; ``weights[m]`` (a weights dict or None) continues candidate m from a given network.  The group shuffles
+    ONCE per epoch for all candidates, with the generator ``Trainer(seed=seed)`` uses.  Candidate m gets, bit for bit, what
+    ``Trainer(weights[m], candidates[m], seed=seeds[m])`` gets from the same batches."""
+
+    def __init__(self, candidates, seeds=None, weights=None, seed: int = 42, device: int = 0, n_features: int = None):
+        self.candidates = list(candidates)
+        K = len(self.candidates)
+        if K < 1:
+            raise ValueError('TrainerGroup needs at least one candidate')
+        self.seed = int(seed)
+        self.seeds = [self.seed] * K if seeds is None else [int(v) for v in seeds]
+        if len(self.seeds) != K:
+            raise ValueError('%d seeds for %d candidates' % (len(self.seeds), K))
+        weights = [None] * K if weights is None else list(weights)
+        if len(weights) != K:
+            raise ValueError('%d weights for %d candidates' % (len(weights), K))
+        weights = [create_model(None, p, seed=s) if w is None else w for w, p, s in zip(weights, self.candidates, self.seeds)]
+        for w in weights:
+            if len(w['gru']) != 1:
+                raise NotImplementedError('training: n_layers = %d (one GRU layer has a training kernel)' % len(w['gru']))
+        sizes = {int(np.shape(w['gru'][0][0])[0]) for w in weights}
+        if len(sizes) != 1:
+            raise ValueError('the candidates of a group share feature_size, got %s' % sorted(sizes))
+        self.feature_size = sizes.pop()
+        self.units = [int(np.shape(w['gru'][0][1])[0]) for w in weights]
+        self.n_features = int(pr.n_features if n_features is None else n_features)
+        self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device)
+        self._rng = np.random.default_rng(self.seed)
+        self._step = 0
+        self.frozen_masks = [((1 << max(0, int(p.freeze_till))) - 1) & 3 for p in self.candidates]
+
+    def __len__(self):
+        return len(self.candidates)
+
+    def _biases(self):
+        return [p.loss_bias for p in self.candidates]
+
+    # -- the networks -------------------------------------------------------------------------------------------------
+    @property
+    def weights(self) -> list:
+        return [unflatten_weights(flat, self.feature_size, units)
+                for flat, units in zip(self._t.split(self._t.get_weights()), self.units)]
+
+    def save(self, m: int, model_name: str):
+        """candidate m as ``Trainer.save`` writes it"""
+        save_weights(model_name, self.weights[m])
+        save_params(model_name)
+
+    # -- evaluation -----------------------------------------------------------------------------------------------------
+    def predict(self, inputs) -> np.ndarray:
+        """[N, n_features, feature_size] -> raw network outputs float32 [K, N, 1] (dropout off)"""
+        return self._t.evaluate_models(inputs)[2][:, :, None]
+
+    def evaluate(self, inputs, outputs) -> list:
+        """-> K pairs (loss, acc), each candidate with its own ``loss_bias``"""
+        loss, acc, _ = self._t.evaluate_models(inputs, outputs, loss_bias=self._biases())
+        return [(float(a), float(b)) for a, b in zip(loss, acc)]
+
+    def _evaluate_resident(self, source):
+        loss, acc, _ = self._t.evaluate_models(loss_bias=self._biases(), source=source, want_probs=False)
+        return [float(v) for v in loss], [float(v) for v in acc]
+
+    # -- model.fit ------------------------------------------------------------------------------------------------------
+    def fit(self, inputs, outputs, batch_size=5000, epochs=10, validation_data=None, shuffle=True, callback=None) -> list:
+        """``Trainer.fit`` for every candidate on the same batches: one upload of the training set, one of the validation
+        set, one step call per batch; ``acc`` / ``val_loss`` / ``val_acc`` are measured on the resident sets.
+        ``callback(epoch, logs_list)`` runs once per epoch.  -> K history dicts with ``Trainer.fit``'s keys."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.float32)
+        n, K = inputs.shape[0], len(self)
+        if n == 0 or int(batch_size) < 1:
+            raise ValueError('fit needs at least one sample and batch_size >= 1')
+        self._t.set_data(inputs, outputs)
+        if validation_data is not None:
+            self._t.set_validation(*validation_data)
+        histories = [{'loss': [], 'acc': []} for _ in range(K)]
+        if validation_data is not None:
+            for h in histories:
+                h.update(val_loss=[], val_acc=[])
+        rates = [p.dropout for p in self.candidates]
+        for epoch in range(int(epochs)):
+            order = self._rng.permutation(n) if shuffle else np.arange(n)
+            losses = []
+            for a in range(0, n, int(batch_size)):
+                losses.append(self._t.step_models(order[a:a + int(batch_size)], step=self._step, dropout_rate=rates, seed=self.seeds,
+                                                  loss_bias=self._biases(), lr=RMSPROP_LR, rho=RMSPROP_RHO, eps=RMSPROP_EPS,
+                                                  frozen_mask=self.frozen_masks))
+                self._step += 1
+            acc = self._evaluate_resident('data')[1]
+            logs_list = [{'loss': float(np.mean([float(batch[m]) for batch in losses])), 'acc': acc[m]} for m in range(K)]
+            if validation_data is not None:
+                val_loss, val_acc = self._evaluate_resident('validation')
+                for m, logs in enumerate(logs_list):
+                    logs['val_loss'], logs['val_acc'] = val_loss[m], val_acc[m]
+            for h, logs in zip(histories, logs_list):
+                for k, v in logs.items():
+                    h[k].append(v)
+            if callback is not None:
+                callback(epoch, logs_list)
+        self.histories = histories
+        return histories
+
+    def best(self, key: str = 'val_loss') -> int:
+        """the candidate whose last-epoch ``key`` is smallest (largest for the accuracies)"""
+        if not getattr(self, 'histories', None) or key not in self.histories[0] or not self.histories[0][key]:
+            raise ValueError('no %r in the histories of this group (call fit first)' % key)
+        last = [h[key][-1] for h in self.histories]
+        return int(np.argmax(last) if key.endswith('acc') else np.argmin(last))
 
     def close(self):
         self._t.close()
