@@ -144,6 +144,18 @@ int pe_create_models(const pe_params* params, const double* mel_filters, const p
                      int32_t n_models, int32_t n_streams, int32_t device, pe_engine** out);
 int pe_get_n_models(const pe_engine* e);
 
+/* Replace the network of model `model` in a live engine: what scripts/train_incremental.py:86-88,106 gets by training the very
+ * model object its Listener predicts with -- the next chunk is judged by the retrained network, the stream goes on.  Additive to
+ * ABI 8.  The weights are packed by the routines pe_create used, into the buffers pe_create made: afterwards every entry
+ * point gives, bit for bit, what an engine created with these weights gives (the form, pe_get_gru_tiling, does not change).
+ * The stream state -- leftover samples, feature windows, triggers -- is untouched.  Work in flight (pe_update_async, the
+ * *_device entry points on any stream) is drained first.
+ * PE_ERR_INVALID, before any device work and with the old network still serving: null pointers, a model outside
+ * 0 .. n_models - 1, n_layers / units / n_in other than the engine was created with.  The input-projection rows
+ * (pe_set_input_projection) are rebuilt from the new network, and with the option on the projections of the frames already in
+ * the feature windows are computed again. */
+int pe_set_weights(pe_engine* e, const pe_weights* weights, int32_t model);
+
 /* Listener.clear (network_runner.py:121-123).  mask: n_streams bytes, non-zero = clear that
  * stream; NULL = clear all.  Runs on the NULL stream and synchronises: a caller that drives the
  * *_device entry points on a non-blocking stream must synchronise that stream first (the same holds for
@@ -556,6 +568,66 @@ int pe_trainer_evaluate_models(pe_trainer* t, int32_t source, const float* feats
  * and element (gate, i, f) is kept iff (float)(bits >> 40) / 2^24 >= rate (both float32; the quotient is exact).  A kept
  * element is 1 / (1 - rate) evaluated in float32, a dropped one 0. */
 int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feature_size, float rate, float* out);
+
+/* A resident set that grows (TrainData.merge of scripts/train_incremental.py:101-102 without a new upload of what is already
+ * there).  source = PE_TRAIN_SOURCE_DATA or PE_TRAIN_SOURCE_VALIDATION.
+ * pe_trainer_append: n more samples behind the set's own (an empty / never uploaded set becomes these n samples); the samples
+ * already resident keep their bits and their indices.  Checks as pe_trainer_set_data makes them.
+ * pe_trainer_get_data: samples [first, first + n) of the set, feats_out[n][n_features][feature_size] and targets_out[n] (each
+ * may be NULL); a range outside the set is PE_ERR_INVALID. */
+int pe_trainer_append(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n);
+int pe_trainer_get_data(pe_trainer* t, int32_t source, int32_t first, int32_t n, float* feats_out, float* targets_out);
+
+/* Incremental training: precise-train-incremental (scripts/train_incremental.py:113-137) plays hours of not-wake-word audio
+ * through a Listener chunk by chunk, saves the last buffer_t seconds whenever the model fires, and retrains.  A pe_miner is
+ * that scan as a session over ONE engine: the recordings are uploaded once and every frame of every recording is computed
+ * once, when the session is created (frames do not depend on the model); a scan then scores ALL chunks from a position on in
+ * a few launches, and the saved samples go from the resident audio into a trainer's resident set without crossing the bus.
+ * Additive to ABI 8.  The session is not thread-safe, uses the engine's device and leaves the engine's streams untouched;
+ * destroy it before its engine.
+ *
+ * Chunks (util.py:30-32): chunk i of a recording is samples [i C, (i + 1) C) for (i + 1) C < len -- a recording of len samples
+ * has (len - 1) / C chunks (0 for len = 0), the tail and a last chunk that would end exactly at len are never seen.  The chunks
+ * of all recordings in order have GLOBAL ids 0 .. total - 1; pe_miner_layout gives the exclusive prefix sum of the counts.
+ * Prediction of a chunk (network_runner.py:125-152 on a listener cleared at the start of the recording, :119): after
+ * n = (i + 1) C samples 1 + (n - window) / hop frames have been emitted (0 below one window; one fewer with vectorizer = 3);
+ * the network input is the last n_features rows of n_features zero rows followed by those frames (use_delta: with the row
+ * differences the engine's streaming path forms).  Frames are float32 rows as the engine's feature window holds them, and the
+ * batch goes through pe_predict_device: a scan is bit for bit pe_predict of those windows on this engine.
+ * Hit (:125): decode(p) > threshold in float64, strict; decode is model's pe_set_decoder table through pe_decode's kernel when
+ * one is set, else (double)p.
+ * Saved sample (:79,:123,:130 and util.py:65,71): the float64 ring of buffer_samples samples starts as zeros, takes every chunk
+ * and is never cleared -- at a hit it holds the last buffer_samples samples of ALL chunks so far, earlier recordings included
+ * (carry_audio = 1; 0: zeros before the hit's own recording).  It is written as int16, q = (int16) trunc(x * 32767.0), and read
+ * back as (float32) q / 32767.0f, then vectorized: exactly pe_vectorize_clips of that float32 clip (and its launch).
+ *
+ * pe_miner_create: audio_host / sample_format / offsets / n_rec as pe_evaluate_clips takes them (zero-length recordings
+ *   allowed), checked as it checks them; chunk_size >= 1; buffer_samples >= 1 (ListenerParams.buffer_samples, params.py:74).
+ *   PRECONDITION: buffer_samples <= ListenerParams.max_samples (params.py:95; true of every ListenerParams, whose
+ *   buffer_samples is max_samples rounded down to whole hops): the saved clip is vectorized WITHOUT vectorize()'s crop, which
+ *   pe_params does not carry.  mining.Miner refuses a larger value;
+ *   at most 2^31 - 1 chunks and frames per session (PE_ERR_INVALID); PE_ERR_NOMEM when the device cannot hold the session.
+ * pe_miner_layout: chunk_offsets_out[n_rec + 1].
+ * pe_miner_scan: chunks first_chunk .. total - 1 (first_chunk = total: nothing) of model `model`: scores_out[total -
+ *   first_chunk] raw predictions (may be NULL), hits_out[capacity] the ascending global ids of the first `capacity` hits (NULL
+ *   with capacity 0), *n_hits = min(capacity, hits), *n_above = all hits of the range.  Runs in passes of
+ *   pe_set_clip_pass_bytes bytes of network input (at least one chunk); no result depends on the pass size.  A NaN threshold
+ *   is PE_ERR_INVALID.
+ * pe_miner_vectorize: feats_out[n][n_features][n_mfcc] float64, the saved sample of every hit as vectorize() returns it
+ *   (vectorization.py:62-84).  hits: global ids in any order, repeats allowed; an id outside 0 .. total - 1 is PE_ERR_INVALID.
+ * pe_miner_append: the same rows as float32 (use_delta: with the delta columns pe_score_clips forms, vectorization.py:87-89)
+ *   appended to the trainer's resident set `source`, device to device, every target = `target` (the script saves under
+ *   not-wake-word: 0).  The trainer must live on the engine's device with the engine's n_features and feature_size
+ *   (PE_ERR_INVALID); the trainer's own failures are reported on the engine with the trainer's message. */
+typedef struct pe_miner pe_miner;
+int pe_miner_create(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_rec,
+                    int32_t chunk_size, int32_t buffer_samples, int32_t carry_audio, pe_miner** out);
+int pe_miner_destroy(pe_miner* m);
+int pe_miner_layout(const pe_miner* m, int64_t* chunk_offsets_out);
+int pe_miner_scan(pe_miner* m, int32_t model, int64_t first_chunk, double threshold, float* scores_out, int32_t* hits_out,
+                  int32_t capacity, int32_t* n_hits, int64_t* n_above);
+int pe_miner_vectorize(pe_miner* m, const int32_t* hits, int32_t n, double* feats_out_host);
+int pe_miner_append(pe_miner* m, pe_trainer* trainer, int32_t source, const int32_t* hits, int32_t n, float target);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,7 @@ EXPORTS = {
     'pe_create_models': (C.c_int, [C.POINTER(PeParams), C.POINTER(C.c_double), C.POINTER(PeWeights), C.c_int32, C.c_int32,
                                    C.c_int32, C.POINTER(C.c_void_p)]),
     'pe_get_n_models': (C.c_int, [C.c_void_p]),
+    'pe_set_weights': (C.c_int, [C.c_void_p, C.POINTER(PeWeights), C.c_int32]),
     'pe_destroy': (C.c_int, [C.c_void_p]),
     'pe_last_error': (C.c_char_p, [C.c_void_p]),
     'pe_clear': (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -138,6 +139,17 @@ EXPORTS = {
     'pe_trainer_evaluate_models': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
     'pe_train_dropout_masks': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    'pe_trainer_append': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    'pe_trainer_get_data': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    # mining false activations (pe_miner)
+    'pe_miner_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(C.c_void_p)]),
+    'pe_miner_destroy': (C.c_int, [C.c_void_p]),
+    'pe_miner_layout': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'pe_miner_scan': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    'pe_miner_vectorize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    'pe_miner_append': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float]),
 }
 
 # pe_sim_metric: one (model, recording) of pe_simulate_scores / pe_simulate_clips
@@ -199,6 +211,28 @@ def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _pe_weights(wm, check_dense=True):
+    """one weights dict -> (PeWeights, the numpy / ctypes objects its pointers refer to: keep them alive across the call)"""
+    layers = wm['gru']
+    arr = (PeGruLayer * len(layers))()
+    keep = [arr]
+    for i, (k, rk, b) in enumerate(layers):
+        k = np.ascontiguousarray(k, dtype=np.float32)
+        rk = np.ascontiguousarray(rk, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        units = rk.shape[0]
+        if k.ndim != 2 or k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
+            raise ValueError('GRU layer %d has inconsistent shapes' % i)
+        keep += [k, rk, b]
+        arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
+    dk = np.ascontiguousarray(wm['dense_kernel'], dtype=np.float32).reshape(-1)
+    if check_dense and dk.size != np.shape(layers[-1][1])[0]:
+        raise ValueError('dense_kernel has %d entries for %d units' % (dk.size, np.shape(layers[-1][1])[0]))
+    db = float(np.asarray(wm['dense_bias'], dtype=np.float32).reshape(-1)[0])
+    keep.append(dk)
+    return PeWeights(len(layers), arr, _fptr(dk), db), keep
+
+
 class HipEngine:
     """
     One C-ABI engine: the streaming state of ``n_streams`` audio streams plus one network on one
@@ -216,6 +250,7 @@ class HipEngine:
         self._lib = load()
         self._h = C.c_void_p()
         self._async_keep = []
+        self._miners = weakref.WeakSet()   # HipMiner sessions over this engine: closed before the engine is destroyed
         self._views = 0                # host_array() buffers still referenced by numpy arrays (their memory dies with the engine)
         self._close_pending = False
         self.n_streams = int(n_streams)
@@ -243,21 +278,8 @@ class HipEngine:
         keep = []                      # keep numpy buffers alive across the call
         ws = (PeWeights * len(models))()
         for m, wm in enumerate(models):
-            layers = wm['gru']
-            arr = (PeGruLayer * len(layers))()
-            for i, (k, rk, b) in enumerate(layers):
-                k = np.ascontiguousarray(k, dtype=np.float32)
-                rk = np.ascontiguousarray(rk, dtype=np.float32)
-                b = np.ascontiguousarray(b, dtype=np.float32)
-                units = rk.shape[0]
-                if k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
-                    raise ValueError('GRU layer %d has inconsistent shapes' % i)
-                keep += [k, rk, b]
-                arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
-            dk = np.ascontiguousarray(wm['dense_kernel'], dtype=np.float32).reshape(-1)
-            db = float(np.asarray(wm['dense_bias'], dtype=np.float32).reshape(-1)[0])
-            keep += [arr, dk]
-            ws[m] = PeWeights(len(layers), arr, _fptr(dk), db)
+            ws[m], held = _pe_weights(wm, check_dense=False)
+            keep.append(held)
         if self._multi:
             rc = self._lib.pe_create_models(C.byref(p), mel.ctypes.data_as(C.POINTER(C.c_double)), ws, len(models),
                                             self.n_streams, int(device), C.byref(self._h))
@@ -275,6 +297,14 @@ class HipEngine:
     def _lead(self, *shape):
         """shape of a network output: a leading model axis on a K-model engine"""
         return ((self.n_models,) if self._multi else ()) + shape
+
+    def set_weights(self, weights, model: int = 0):
+        """Replace the network of ``model`` in the live engine (pe_set_weights): same widths as the engine was created
+        with (else ValueError, the old network keeps serving); the streams' state stays, and every entry point then gives the
+        bits of an engine created with ``weights``."""
+        w, keep = _pe_weights(weights)
+        self._check(self._lib.pe_set_weights(self._h, C.byref(w), int(model)))
+        del keep
 
     # -- errors -------------------------------------------------------------------------
     @staticmethod
@@ -680,6 +710,8 @@ class HipEngine:
                 except Exception:
                     pass
                 return
+            for miner in list(getattr(self, '_miners', ())):
+                miner.close()
             self._lib.pe_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -720,23 +752,8 @@ class HipTrainer:
         ws = (PeWeights * max(1, len(models)))()
         keep = []
         for m, wm in enumerate(models):
-            layers = wm['gru']
-            arr = (PeGruLayer * len(layers))()
-            for i, (k, rk, b) in enumerate(layers):
-                k = np.ascontiguousarray(k, dtype=np.float32)
-                rk = np.ascontiguousarray(rk, dtype=np.float32)
-                b = np.ascontiguousarray(b, dtype=np.float32)
-                units = rk.shape[0]
-                if k.ndim != 2 or k.shape[1] != 3 * units or rk.shape != (units, 3 * units) or b.shape != (3 * units,):
-                    raise ValueError('GRU layer %d has inconsistent shapes' % i)
-                keep += [k, rk, b]
-                arr[i] = PeGruLayer(k.shape[0], units, _fptr(k), _fptr(rk), _fptr(b))
-            dk = np.ascontiguousarray(wm['dense_kernel'], dtype=np.float32).reshape(-1)
-            db = float(np.asarray(wm['dense_bias'], dtype=np.float32).reshape(-1)[0])
-            if dk.size != layers[-1][1].shape[0]:
-                raise ValueError('dense_kernel has %d entries for %d units' % (dk.size, layers[-1][1].shape[0]))
-            keep += [arr, dk]
-            ws[m] = PeWeights(len(layers), arr, _fptr(dk), db)
+            ws[m], held = _pe_weights(wm)
+            keep.append(held)
         if many:
             rc = self._lib.pe_trainer_create_models(int(n_features), int(feature_size), ws, len(models), int(device), C.byref(self._h))
         else:
@@ -843,6 +860,31 @@ class HipTrainer:
                                                   float(loss_bias), loss.ctypes.data, acc.ctypes.data, probs.ctypes.data))
         return float(loss[0]), float(acc[0]), probs
 
+    @staticmethod
+    def _source(validation):
+        return TRAIN_SOURCE_VALIDATION if validation else TRAIN_SOURCE_DATA
+
+    def n_samples(self, validation=False) -> int:
+        """samples of the resident training (validation) set; 0 if never uploaded"""
+        return int(self._lib.pe_trainer_n_samples(self._h, self._source(validation)))
+
+    def append(self, feats, targets, validation=False):
+        """more samples behind the resident training (validation) set, whose own samples stay where they are (pe_trainer_append)"""
+        feats = self._feats(feats)
+        targets = self._targets(targets, feats.shape[0])
+        if feats.shape[0]:
+            self._check(self._lib.pe_trainer_append(self._h, self._source(validation), feats.ctypes.data, targets.ctypes.data, feats.shape[0]))
+
+    def get_data(self, first=0, n=None, validation=False):
+        """-> (inputs float32 [n, n_features, feature_size], targets float32 [n]): samples first .. first + n of a resident set
+        (n None: to its end), read back from the device (pe_trainer_get_data)"""
+        n = self.n_samples(validation) - int(first) if n is None else int(n)
+        feats = np.empty((max(n, 0), self.n_features, self.feature_size), dtype=np.float32)
+        targets = np.empty(max(n, 0), dtype=np.float32)
+        self._check(self._lib.pe_trainer_get_data(self._h, self._source(validation), int(first), n, feats.ctypes.data if n > 0 else None,
+                                                  targets.ctypes.data if n > 0 else None))
+        return feats, targets
+
     def split(self, flat):
         """the concatenated flat vector -> one view per network, in model order"""
         sizes = self.n_params if isinstance(self.n_params, list) else [self.n_params]
@@ -910,6 +952,78 @@ class HipTrainer:
     def close(self):
         if getattr(self, '_h', None) and self._h.value:
             self._lib.pe_trainer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipMiner:
+    """
+    One C-ABI mining session (pe_miner) over one ``HipEngine``: the recordings resident on the device, every frame computed once;
+    ``mining.Miner`` is the reference-shaped class.  Chunks carry GLOBAL ids: recording r's chunk i is ``chunk_offsets[r] + i``.
+    The session keeps its engine alive; close it before the engine.
+    """
+
+    def __init__(self, engine: HipEngine, audios, chunk_size: int, buffer_samples: int, carry_audio: bool = True):
+        self._lib = load()
+        self._h = C.c_void_p()
+        self.engine = engine
+        audio, offsets, fmt = HipEngine._clips(audios)
+        self.n_recordings = offsets.size - 1
+        self.chunk_size, self.buffer_samples = int(chunk_size), int(buffer_samples)
+        engine._check(self._lib.pe_miner_create(engine._h, audio.ctypes.data if audio.size else None, fmt, offsets.ctypes.data,
+                                                self.n_recordings, self.chunk_size, self.buffer_samples, int(bool(carry_audio)),
+                                                C.byref(self._h)))
+        engine._miners.add(self)
+        self.chunk_offsets = np.zeros(self.n_recordings + 1, dtype=np.int64)
+        engine._check(self._lib.pe_miner_layout(self._h, self.chunk_offsets.ctypes.data))
+        self.n_chunks = int(self.chunk_offsets[-1])
+
+    def _hits(self, hits):
+        hits = np.ascontiguousarray(hits, dtype=np.int64).reshape(-1)
+        if hits.size and (hits.min() < 0 or hits.max() >= self.n_chunks):
+            raise ValueError('chunk ids must be in 0..%d' % (self.n_chunks - 1))
+        return hits.astype(np.int32)
+
+    def scan(self, first=0, threshold=0.5, capacity=None, return_scores=False, model=0):
+        """-> (hits int32 [<= capacity] ascending global ids, n_above, scores float32 [n_chunks - first] or None)"""
+        first = int(first)
+        n = self.n_chunks - first
+        capacity = max(n, 0) if capacity is None else int(capacity)
+        hits = np.empty(max(capacity, 0), dtype=np.int32)
+        scores = np.empty(max(n, 0), dtype=np.float32) if return_scores else None
+        n_hits, n_above = C.c_int32(0), C.c_int64(0)
+        self.engine._check(self._lib.pe_miner_scan(self._handle(), int(model), first, float(threshold),
+                                                   scores.ctypes.data if return_scores and n > 0 else None,
+                                                   hits.ctypes.data if capacity > 0 else None, capacity, C.byref(n_hits), C.byref(n_above)))
+        return hits[:n_hits.value], int(n_above.value), scores
+
+    def vectorize(self, hits) -> np.ndarray:
+        hits = self._hits(hits)
+        out = np.empty((hits.size, self.engine.n_features, self.engine.n_mfcc), dtype=np.float64)
+        if hits.size:
+            self.engine._check(self._lib.pe_miner_vectorize(self._handle(), hits.ctypes.data, hits.size, out.ctypes.data))
+        return out
+
+    def append(self, trainer: HipTrainer, hits, validation=False, target=0.0):
+        hits = self._hits(hits)
+        if hits.size:
+            self.engine._check(self._lib.pe_miner_append(self._handle(), trainer._h, HipTrainer._source(validation), hits.ctypes.data,
+                                                         hits.size, float(target)))
+
+    def _handle(self):
+        if not self._h.value:
+            raise ValueError('the mining session is closed (close(), or its engine was closed)')
+        return self._h
+
+    def close(self):
+        """pe_miner_destroy; the engine calls it for every session it still has when it is closed itself"""
+        if getattr(self, '_h', None) and self._h.value:
+            self._lib.pe_miner_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

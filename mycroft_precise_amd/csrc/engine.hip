@@ -7,6 +7,7 @@
 #include "gru_cw_pack.h"
 #include "mfcc_general_device.h"
 #include "gru_train_device.h"
+#include "mine_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -67,6 +68,7 @@ struct pe_engine {
     int mel_nnz = 0;
     std::string err;
     std::vector<void*> allocs;
+    std::vector<size_t> alloc_bytes;         // bytes behind allocs[i] (dev_upload into an existing buffer checks them)
     int64_t device_bytes = 0;
     // streaming state: per stream two sides of (16-byte record, leftover PCM); a call that advances a stream reads its
     // current side and writes the other (pe_common.h: StreamRec) -- streams that take no part in a call are not touched
@@ -107,6 +109,10 @@ struct pe_engine {
     std::vector<DecState> dec;
     bool wide = false;      // wide / stacked network (units 64..256, 1-2 layers)
     int wide_kx4[2] = {1, 1};
+    // the architecture as pe_create was given it (pe_set_weights takes the same widths only) and the width the streamed-weight
+    // kernel runs at
+    int layer_units[2] = {0, 0}, layer_n_in[2] = {0, 0}, wide_units = 0;
+    std::vector<double> mel_host;            // the filterbank pe_create was given: pe_set_weights rebuilds the table blob's projection rows
     int32_t* activation = nullptr;
     // staging for the host entry points (grown on demand)
     DeviceBuf st_pcm, st_out, st_feats, st_mask, st_audio, st_mfcc, st_conf, st_fired, st_ids;
@@ -174,15 +180,26 @@ int dev_alloc(pe_engine* e, T** out, size_t count) {
     hipError_t err = hipMalloc(&p, bytes);
     if (err != hipSuccess) return fail(e, PE_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(err));
     e->allocs.push_back(p);
+    e->alloc_bytes.push_back(bytes);
     e->device_bytes += (int64_t)bytes;
     *out = static_cast<T*>(p);
     return PE_OK;
 }
 
+// *out null: allocate, then copy.  *out set (pe_set_weights packing a network of the same widths again): the buffer
+// pe_create made for this very vector is written in place -- it must be one of the engine's and hold exactly this many bytes.
 template <class T>
 int dev_upload(pe_engine* e, T** out, const std::vector<T>& host) {
-    int rc = dev_alloc(e, out, host.size());
-    if (rc) return rc;
+    if (!*out) {
+        int rc = dev_alloc(e, out, host.size());
+        if (rc) return rc;
+    } else {
+        const size_t bytes = (host.size() ? host.size() : 1) * sizeof(T);
+        size_t i = 0;
+        while (i < e->allocs.size() && e->allocs[i] != static_cast<void*>(*out)) ++i;
+        if (i == e->allocs.size() || e->alloc_bytes[i] != bytes)
+            return fail(e, PE_ERR_INVALID, "repacking %zu bytes into a buffer of %zu", bytes, i == e->allocs.size() ? (size_t)0 : e->alloc_bytes[i]);
+    }
     if (!host.empty()) PE_HIP(e, hipMemcpy(*out, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     return PE_OK;
 }
@@ -190,8 +207,8 @@ int dev_upload(pe_engine* e, T** out, const std::vector<T>& host) {
 // release one dev_alloc'ed buffer before pe_destroy (tables that are replaced: decoder LUT, ring, ke_hist)
 void dev_free(pe_engine* e, void* p, size_t bytes) {
     if (!p) return;
-    for (auto it = e->allocs.begin(); it != e->allocs.end(); ++it)
-        if (*it == p) { e->allocs.erase(it); break; }
+    for (size_t i = 0; i < e->allocs.size(); ++i)
+        if (e->allocs[i] == p) { e->allocs.erase(e->allocs.begin() + i); e->alloc_bytes.erase(e->alloc_bytes.begin() + i); break; }
     (void)hipFree(p);
     e->device_bytes -= (int64_t)bytes;
 }
@@ -1074,6 +1091,48 @@ const char* pe_last_global_error(void) { return g_global_error.c_str(); }
 const char* pe_last_error(const pe_engine* e) { return e ? e->err.c_str() : g_global_error.c_str(); }
 
 namespace {
+// One model's network in every layout the engine's forms read: pe_create fills a fresh NetPack (dev_upload allocates), pe_set_weights
+// runs the same routines again over the buffers that exist (same widths: same sizes).
+int pack_model(pe_engine* e, NetPack& n, const pe_weights* w, const bool wide, const int wide_units) {
+    const pe_gru_layer& L = w->layers[0];
+    int rc = PE_OK;
+    n.dense_bias = w->dense_bias;
+    do {
+        if (wide) {
+            // Any width 33..256 (and stacked layers of different widths) runs on the streamed-weight kernel at the next
+            // multiple of 64: a padded unit has zero weights and zero bias everywhere, so z = r = 1/2, candidate = 0 and
+            // its state stays exactly 0 -- it neither receives nor contributes anything.
+            const int Hp = wide_units;
+            std::vector<std::vector<float>> kp(w->n_layers), rp(w->n_layers), bp(w->n_layers);
+            std::vector<pe_gru_layer> lp(w->n_layers);
+            for (int l = 0; l < w->n_layers; ++l) {
+                const pe_gru_layer& Ls = w->layers[l];
+                const int Hs = Ls.units, Fin = Ls.n_in, Fp = l == 0 ? Fin : Hp;
+                kp[l].assign((size_t)Fp * 3 * Hp, 0.f); rp[l].assign((size_t)Hp * 3 * Hp, 0.f); bp[l].assign((size_t)3 * Hp, 0.f);
+                for (int gate = 0; gate < 3; ++gate)
+                    for (int u = 0; u < Hs; ++u) {
+                        for (int k = 0; k < Fin; ++k) kp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.kernel[(size_t)k * 3 * Hs + gate * Hs + u];
+                        for (int k = 0; k < Hs; ++k) rp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.recurrent_kernel[(size_t)k * 3 * Hs + gate * Hs + u];
+                        bp[l][(size_t)gate * Hp + u] = Ls.bias[gate * Hs + u];
+                    }
+                lp[l] = pe_gru_layer{Fp, Hp, kp[l].data(), rp[l].data(), bp[l].data()};
+            }
+            std::vector<float> dp(Hp, 0.f);
+            const int Hlast = w->layers[w->n_layers - 1].units;
+            for (int u = 0; u < Hlast; ++u) dp[u] = w->dense_kernel[u];
+            pe_weights wp{w->n_layers, lp.data(), dp.data(), w->dense_bias};
+            e->units = Hp;
+            if ((rc = pack_gru_weights_wide(e, n, &wp))) break;
+            if ((rc = pack_gru_weights_wide_x3(e, n, &wp))) break;
+        }
+        else if ((rc = pack_gru_weights(e, n, L, w->dense_kernel))) break;
+        if (e->prm.gru_precision == 1 && (rc = pack_gru_weights_bf16(e, n, L, w->dense_kernel))) break;
+        if (!wide && b20_eligible(e->prm, L) && (rc = pack_gru_weights_b20(e, n, L, w->dense_kernel))) break;
+        if (!wide && x3_eligible(e->prm, L) && (rc = pack_gru_weights_x3(e, n, L, w->dense_kernel))) break;
+    } while (false);
+    return rc;
+}
+
 // pe_create / pe_create_models: w[0 .. n_models) (checked against w[0] by pe_create_models before it comes here)
 int create_engine(const pe_params* p, const double* mel_filters, const pe_weights* w, int32_t n_models, int32_t n_streams,
                   int32_t device, pe_engine** out) {
@@ -1176,6 +1235,9 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
     e->n_padded = e->n_tiles * kTileStreams;
     e->units = L.units; e->n_in = p->n_mfcc; e->n_layers = w->n_layers; e->wide = wide;
     e->n_models = n_models;
+    e->wide_units = wide_units;
+    e->mel_host.assign(mel_filters, mel_filters + (size_t)p->n_filt * (p->n_fft / 2 + 1));
+    for (int l = 0; l < w->n_layers; ++l) { e->layer_units[l] = w->layers[l].units; e->layer_n_in[l] = w->layers[l].n_in; }
     e->nets.assign((size_t)n_models, NetPack{});
     e->dec.assign((size_t)n_models, DecState{});
     if (e->prm.vectorizer == 0) e->prm.vectorizer = 2;
@@ -1188,47 +1250,7 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
         if ((rc = dev_alloc(e, &e->carry, (size_t)2 * e->n_padded * e->carry_cap))) break;
         if ((rc = dev_alloc(e, &e->rec, (size_t)2 * e->n_padded))) break;
         if ((rc = dev_alloc(e, &e->ring, ring_floats(e)))) break;
-        // one model's network in every layout the engine's forms read
-        auto pack_model = [&](NetPack& n, const pe_weights* w) -> int {
-            const pe_gru_layer& L = w->layers[0];
-            int rc = PE_OK;
-            n.dense_bias = w->dense_bias;
-            do {
-                if (wide) {
-                    // Any width 33..256 (and stacked layers of different widths) runs on the streamed-weight kernel at the next
-                    // multiple of 64: a padded unit has zero weights and zero bias everywhere, so z = r = 1/2, candidate = 0 and
-                    // its state stays exactly 0 -- it neither receives nor contributes anything.
-                    const int Hp = wide_units;
-                    std::vector<std::vector<float>> kp(w->n_layers), rp(w->n_layers), bp(w->n_layers);
-                    std::vector<pe_gru_layer> lp(w->n_layers);
-                    for (int l = 0; l < w->n_layers; ++l) {
-                        const pe_gru_layer& Ls = w->layers[l];
-                        const int Hs = Ls.units, Fin = Ls.n_in, Fp = l == 0 ? Fin : Hp;
-                        kp[l].assign((size_t)Fp * 3 * Hp, 0.f); rp[l].assign((size_t)Hp * 3 * Hp, 0.f); bp[l].assign((size_t)3 * Hp, 0.f);
-                        for (int gate = 0; gate < 3; ++gate)
-                            for (int u = 0; u < Hs; ++u) {
-                                for (int k = 0; k < Fin; ++k) kp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.kernel[(size_t)k * 3 * Hs + gate * Hs + u];
-                                for (int k = 0; k < Hs; ++k) rp[l][(size_t)k * 3 * Hp + gate * Hp + u] = Ls.recurrent_kernel[(size_t)k * 3 * Hs + gate * Hs + u];
-                                bp[l][(size_t)gate * Hp + u] = Ls.bias[gate * Hs + u];
-                            }
-                        lp[l] = pe_gru_layer{Fp, Hp, kp[l].data(), rp[l].data(), bp[l].data()};
-                    }
-                    std::vector<float> dp(Hp, 0.f);
-                    const int Hlast = w->layers[w->n_layers - 1].units;
-                    for (int u = 0; u < Hlast; ++u) dp[u] = w->dense_kernel[u];
-                    pe_weights wp{w->n_layers, lp.data(), dp.data(), w->dense_bias};
-                    e->units = Hp;
-                    if ((rc = pack_gru_weights_wide(e, n, &wp))) break;
-                    if ((rc = pack_gru_weights_wide_x3(e, n, &wp))) break;
-                }
-                else if ((rc = pack_gru_weights(e, n, L, w->dense_kernel))) break;
-                if (p->gru_precision == 1 && (rc = pack_gru_weights_bf16(e, n, L, w->dense_kernel))) break;
-                if (!wide && b20_eligible(*p, L) && (rc = pack_gru_weights_b20(e, n, L, w->dense_kernel))) break;
-                if (!wide && x3_eligible(*p, L) && (rc = pack_gru_weights_x3(e, n, L, w->dense_kernel))) break;
-            } while (false);
-            return rc;
-        };
-        for (int m = 0; m < n_models && !rc; ++m) rc = pack_model(e->nets[m], &w[m]);
+        for (int m = 0; m < n_models && !rc; ++m) rc = pack_model(e, e->nets[m], &w[m], wide, wide_units);
         if (rc) break;
         if (!wide) pack_projection_rows(e, L);
         // the projection rows exist for the stock-width float32 network (3 R <= 16 slots: 4 output tiles, R = 5) fed
@@ -1273,6 +1295,38 @@ int pe_create_models(const pe_params* p, const double* mel_filters, const pe_wei
 }
 
 int pe_get_n_models(const pe_engine* e) { return e ? e->n_models : -1; }
+
+int pe_set_weights(pe_engine* e, const pe_weights* w, int32_t model) {
+    if (!e) return PE_ERR_INVALID;
+    if (!w || !w->layers || !w->dense_kernel) return fail(e, PE_ERR_INVALID, "null argument to pe_set_weights");
+    if (model < 0 || model >= e->n_models) return fail(e, PE_ERR_INVALID, "model %d outside 0..%d", model, e->n_models - 1);
+    if (w->n_layers != e->n_layers) return fail(e, PE_ERR_INVALID, "pe_set_weights: n_layers=%d, the engine's network has %d", w->n_layers, e->n_layers);
+    for (int l = 0; l < e->n_layers; ++l) {
+        const pe_gru_layer& L = w->layers[l];
+        if (!L.kernel || !L.recurrent_kernel || !L.bias) return fail(e, PE_ERR_INVALID, "pe_set_weights: null weight pointer");
+        if (L.units != e->layer_units[l] || L.n_in != e->layer_n_in[l])
+            return fail(e, PE_ERR_INVALID, "pe_set_weights: layer %d is n_in=%d units=%d, the engine's is n_in=%d units=%d (a live engine takes the widths it was created with)",
+                        l, L.n_in, L.units, e->layer_n_in[l], e->layer_units[l]);
+    }
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    PE_HIP(e, hipDeviceSynchronize());                    // no launch may still read the buffers that are rewritten
+    int rc = pack_model(e, e->nets[(size_t)model], w, e->wide, e->wide_units);
+    if (rc) return rc;
+    if (e->proj_ok && model == 0 && !e->general) {
+        // the input-projection rows (pe_set_input_projection) live in the front end's table blob: built again from the new
+        // network, written over the old blob; rows already in the feature ring get their projections again
+        pack_projection_rows(e, w->layers[0]);
+        rc = e->prm.mfcc_precision == 0 ? build_tables<double>(e, e->mel_host.data()) : build_tables<float>(e, e->mel_host.data());
+        if (rc) return rc;
+        if (e->proj_on)
+            PE_HIP(e, launch_project_rows(e->ring, e->proj_ring, reinterpret_cast<const float*>(e->table_blob + e->table_layout.proj_w),
+                                          reinterpret_cast<const float*>(e->table_blob + e->table_layout.proj_b), e->prm.n_mfcc,
+                                          (long long)e->n_tiles * e->ring_slots * kTileStreams, nullptr));
+        PE_HIP(e, hipStreamSynchronize(nullptr));
+    }
+    return PE_OK;
+}
 
 int pe_destroy(pe_engine* e) {
     if (!e) return PE_OK;
@@ -1694,6 +1748,45 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
 }
 
 namespace {
+// the front-end launch over a clip table that is on the device (pe_vectorize_clips / pe_score_clips; pe_miner_vectorize / _append)
+int launch_clip_front_end(pe_engine* e, const ClipTable& ct, double* dev_out, float* dev_rows, double* dev_mels) {
+    if (e->general) {
+        if (e->prm.mfcc_precision == 0) {
+            GeneralClipArgs<double> a{geom(e), e->gtab, ct, dev_out, dev_rows, dev_mels, e->row_floats};
+            PE_HIP(e, launch_general_clips_f64(a, e->n_cus, nullptr));
+        } else {
+            GeneralClipArgs<float> a{geom(e), e->gtab, ct, dev_out, dev_rows, dev_mels, e->row_floats};
+            PE_HIP(e, launch_general_clips_f32(a, e->n_cus, nullptr));
+        }
+    } else if (e->prm.mfcc_precision == 0) {
+        MfccClipArgs<double> a{geom(e), ct, dev_out, dev_rows, dev_mels};
+        PE_HIP(e, launch_mfcc_clips_f64(a, tables<double>(e), e->n_cus, nullptr));
+    } else {
+        MfccClipArgs<float> a{geom(e), ct, dev_out, dev_rows, dev_mels};
+        PE_HIP(e, launch_mfcc_clips_f32(a, tables<float>(e), e->n_cus, nullptr));
+    }
+    return PE_OK;
+}
+// ... and over a recording table (pe_evaluate_clips / pe_simulate_clips; pe_miner_create)
+int launch_rec_front_end(pe_engine* e, const RecTable& rt, float* dev_rows) {
+    if (e->general) {
+        if (e->prm.mfcc_precision == 0) {
+            GeneralRecArgs<double> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
+            PE_HIP(e, launch_general_recs_f64(a, e->n_cus, nullptr));
+        } else {
+            GeneralRecArgs<float> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
+            PE_HIP(e, launch_general_recs_f32(a, e->n_cus, nullptr));
+        }
+    } else if (e->prm.mfcc_precision == 0) {
+        MfccRecArgs<double> a{geom(e), rt, dev_rows};
+        PE_HIP(e, launch_mfcc_recs_f64(a, tables<double>(e), e->n_cus, nullptr));
+    } else {
+        MfccRecArgs<float> a{geom(e), rt, dev_rows};
+        PE_HIP(e, launch_mfcc_recs_f32(a, tables<float>(e), e->n_cus, nullptr));
+    }
+    return PE_OK;
+}
+
 // pe_vectorize_clips (feats_out_host) / pe_score_clips (score_out_host): validation, then pass by pass one copy in, the
 // front-end launch, the network launch (scores), one copy out
 int run_clips(pe_engine* e, const char* who, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_clips,
@@ -1750,21 +1843,7 @@ int run_clips(pe_engine* e, const char* who, const void* audio_host, int32_t sam
         if (feats_out_host) { if ((rc = ensure(e, e->st_mfcc, fb))) return rc; dev_out = static_cast<double*>(e->st_mfcc.p); }
         else { if ((rc = ensure(e, e->st_feats, rb))) return rc; dev_rows = static_cast<float*>(e->st_feats.p); }
         if (t) PE_HIP(e, hipEventRecord(e->ev[0], nullptr));
-        if (e->general) {
-            if (e->prm.mfcc_precision == 0) {
-                GeneralClipArgs<double> a{geom(e), e->gtab, ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr, e->row_floats};
-                PE_HIP(e, launch_general_clips_f64(a, e->n_cus, nullptr));
-            } else {
-                GeneralClipArgs<float> a{geom(e), e->gtab, ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr, e->row_floats};
-                PE_HIP(e, launch_general_clips_f32(a, e->n_cus, nullptr));
-            }
-        } else if (e->prm.mfcc_precision == 0) {
-            MfccClipArgs<double> a{geom(e), ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr};
-            PE_HIP(e, launch_mfcc_clips_f64(a, tables<double>(e), e->n_cus, nullptr));
-        } else {
-            MfccClipArgs<float> a{geom(e), ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr};
-            PE_HIP(e, launch_mfcc_clips_f32(a, tables<float>(e), e->n_cus, nullptr));
-        }
+        if ((rc = launch_clip_front_end(e, ct, mels ? nullptr : dev_out, dev_rows, mels ? dev_out : nullptr))) return rc;
         if (t) PE_HIP(e, hipEventRecord(e->ev[1], nullptr));
         if (feats_out_host) {
             PE_HIP(e, hipMemcpy(feats_out_host + (size_t)c0 * T * width, dev_out, fb, hipMemcpyDeviceToHost));
@@ -1976,21 +2055,7 @@ int run_recordings(pe_engine* e, const char* who, const void* audio_host, int32_
                               n, (uint32_t)tasks, e->st_audio.p, sample_format == 1 ? 1 : 0};
             float* dev_rows = static_cast<float*>(e->st_feats.p);
             if (t) PE_HIP(e, hipEventRecord(e->ev[0], nullptr));
-            if (e->general) {
-                if (e->prm.mfcc_precision == 0) {
-                    GeneralRecArgs<double> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
-                    PE_HIP(e, launch_general_recs_f64(a, e->n_cus, nullptr));
-                } else {
-                    GeneralRecArgs<float> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
-                    PE_HIP(e, launch_general_recs_f32(a, e->n_cus, nullptr));
-                }
-            } else if (e->prm.mfcc_precision == 0) {
-                MfccRecArgs<double> a{geom(e), rt, dev_rows};
-                PE_HIP(e, launch_mfcc_recs_f64(a, tables<double>(e), e->n_cus, nullptr));
-            } else {
-                MfccRecArgs<float> a{geom(e), rt, dev_rows};
-                PE_HIP(e, launch_mfcc_recs_f32(a, tables<float>(e), e->n_cus, nullptr));
-            }
+            if ((rc = launch_rec_front_end(e, rt, dev_rows))) return rc;
             if (t) PE_HIP(e, hipEventRecord(e->ev[1], nullptr));
             // pe_evaluate's network launch: window w = rows [w hop_frames, + T) -- recording i's window j is window src0 + j
             GruArgs g = gru_args(e);
@@ -2887,6 +2952,367 @@ int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feat
             for (int f = 0; f < feature_size; ++f)
                 out[((size_t)g * n + i) * feature_size + f] = train_mask_keep(key, g, i, f, rate) ? scale : 0.0f;
     return PE_OK;
+}
+
+}  // extern "C"
+
+// ---- resident sets that grow (pe_trainer_append / pe_trainer_get_data; pe_miner_append below) ---------------------------------
+namespace {
+
+// buf[slot] holds at least `bytes`, its first `keep` bytes kept (device to device) when it has to move; grows by doubling
+int train_grow(pe_trainer* t, int slot, size_t keep, size_t bytes) {
+    DeviceBuf& b = t->buf[slot];
+    if (b.p && b.bytes >= bytes) return PE_OK;
+    const size_t want = std::max(bytes, 2 * b.bytes);
+    void* p = nullptr;
+    hipError_t err = hipMalloc(&p, want ? want : 1);
+    if (err != hipSuccess) return tfail(t, PE_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(err));
+    if (b.p && keep) {
+        err = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
+        if (err != hipSuccess) { (void)hipFree(p); return tfail(t, PE_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(err)); }
+    }
+    if (b.p) (void)hipFree(b.p);
+    b.p = p; b.bytes = want;
+    return PE_OK;
+}
+
+// room for n more samples behind the resident set `source`: *set / *slot name it, its pointers follow the buffers
+int train_set_room(pe_trainer* t, const char* who, int source, int n, TrainSet** set, int* slot) {
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return tfail(t, PE_ERR_INVALID, "%s: source = %d", who, source);
+    *set = source == PE_TRAIN_SOURCE_DATA ? &t->data : &t->validation;
+    *slot = source == PE_TRAIN_SOURCE_DATA ? 7 : 9;
+    const int have = (*set)->n;
+    if (n > 0x7fffffff - have) return tfail(t, PE_ERR_INVALID, "%s: %d + %d samples are more than a set holds", who, have, n);
+    const size_t row = (size_t)t->T * t->F * sizeof(float);
+    int rc;
+    // (the set follows each buffer as soon as it has moved: a failure of the second leaves a valid set of `have` samples)
+    if ((rc = train_grow(t, *slot, (size_t)have * row, (size_t)(have + n) * row))) return rc;
+    (*set)->feats = static_cast<const float*>(t->buf[*slot].p);
+    if ((rc = train_grow(t, *slot + 1, (size_t)have * sizeof(float), (size_t)(have + n) * sizeof(float)))) return rc;
+    (*set)->targets = static_cast<const float*>(t->buf[*slot + 1].p);
+    return PE_OK;
+}
+
+// n samples whose rows are on the trainer's device already, every target = `target`
+int train_append_device(pe_trainer* t, const char* who, int source, const float* feats_dev, int n, float target) {
+    if (!(target >= 0.0f && target <= 1.0f)) return tfail(t, PE_ERR_INVALID, "%s: target %g is outside [0, 1]", who, (double)target);
+    TrainSet* set; int slot;
+    PE_THIP(t, hipSetDevice(t->device));
+    int rc = train_set_room(t, who, source, n, &set, &slot);
+    if (rc) return rc;
+    const size_t row = (size_t)t->T * t->F;
+    const std::vector<float> y((size_t)n, target);
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot].p) + (size_t)set->n * row, feats_dev, (size_t)n * row * sizeof(float), hipMemcpyDeviceToDevice));
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot + 1].p) + set->n, y.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    set->n += n;
+    return PE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pe_trainer_append(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n) {
+    const char* who = "pe_trainer_append";
+    if (!t) return PE_ERR_INVALID;
+    if (!feats_host || !targets_host) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: n = %d", who, n);
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return tfail(t, PE_ERR_INVALID, "%s: source = %d", who, source);
+    int rc = train_check_targets(t, targets_host, n);
+    if (rc) return rc;
+    PE_THIP(t, hipSetDevice(t->device));
+    TrainSet* set; int slot;
+    if ((rc = train_set_room(t, who, source, n, &set, &slot))) return rc;
+    const size_t row = (size_t)t->T * t->F;
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot].p) + (size_t)set->n * row, feats_host, (size_t)n * row * sizeof(float), hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot + 1].p) + set->n, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    set->n += n;
+    return PE_OK;
+}
+
+int pe_trainer_get_data(pe_trainer* t, int32_t source, int32_t first, int32_t n, float* feats_out, float* targets_out) {
+    const char* who = "pe_trainer_get_data";
+    if (!t) return PE_ERR_INVALID;
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return tfail(t, PE_ERR_INVALID, "%s: source = %d", who, source);
+    const TrainSet& set = source == PE_TRAIN_SOURCE_DATA ? t->data : t->validation;
+    if (first < 0 || n < 0 || first > set.n || n > set.n - first)
+        return tfail(t, PE_ERR_INVALID, "%s: samples %d .. %d + %d are outside the set of %d", who, first, first, n, set.n);
+    if (n == 0) return PE_OK;
+    PE_THIP(t, hipSetDevice(t->device));
+    const size_t row = (size_t)t->T * t->F;
+    if (feats_out) PE_THIP(t, hipMemcpy(feats_out, set.feats + (size_t)first * row, (size_t)n * row * sizeof(float), hipMemcpyDeviceToHost));
+    if (targets_out) PE_THIP(t, hipMemcpy(targets_out, set.targets + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+}  // extern "C"
+
+// ---- mining false activations (pe_miner; kernels: mine_device.h) ----------------------------------------------
+struct pe_miner {
+    pe_engine* e = nullptr;
+    int n_rec = 0, chunk = 0, buffer_samples = 0, carry_audio = 1, audio_f32 = 0;
+    int64_t total_chunks = 0, total_frames = 0;
+    std::vector<int64_t> chunk_prefix;                  // [n_rec + 1]
+    // resident: the samples as given, the three prefix sums [n_rec + 1] each (chunks, frames, samples), every frame's float32 row
+    DeviceBuf audio, tables, rows;
+    // grown on demand: a pass's network input and its predictions [n_models][pass]; a scan's predictions, decoded values, block
+    // counts and hit ids; a pass's hit ids, saved clips, clip table, float64 rows / float32 rows and packed trainer rows
+    DeviceBuf batch, pred, scores, conf, counts, hits, ids, ring, clips, feats64, clip_rows, packed;
+    const long long* d_chunk_prefix() const { return static_cast<const long long*>(tables.p); }
+    const long long* d_frame_base() const { return d_chunk_prefix() + n_rec + 1; }
+    const long long* d_rec_start() const { return d_chunk_prefix() + 2 * (n_rec + 1); }
+};
+
+namespace {
+
+void miner_free(pe_miner* m) {
+    pe_engine* e = m->e;
+    (void)hipSetDevice(e->device);
+    (void)hipDeviceSynchronize();
+    for (DeviceBuf* b : {&m->audio, &m->tables, &m->rows, &m->batch, &m->pred, &m->scores, &m->conf, &m->counts, &m->hits, &m->ids, &m->ring,
+                         &m->clips, &m->feats64, &m->clip_rows, &m->packed})
+        if (b->p) { (void)hipFree(b->p); e->device_bytes -= (int64_t)b->bytes; }
+    delete m;
+}
+
+MineGatherArgs miner_gather_args(const pe_miner* m) {
+    const pe_engine* e = m->e;
+    MineGatherArgs g{};
+    g.chunk = m->chunk; g.emit_window = emit_window(e->prm); g.hop = e->prm.hop_samples;
+    g.T = e->prm.n_features; g.F = e->n_in; g.use_delta = e->prm.use_delta ? 1 : 0; g.row_floats = e->row_floats;
+    return g;
+}
+
+int miner_check_hits(pe_miner* m, const char* who, const int32_t* hits, int32_t n) {
+    pe_engine* e = m->e;
+    if (n < 0) return fail(e, PE_ERR_INVALID, "%s: n=%d", who, n);
+    if (n > 0 && !hits) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    for (int32_t i = 0; i < n; ++i)
+        if (hits[i] < 0 || hits[i] >= m->total_chunks)
+            return fail(e, PE_ERR_INVALID, "%s: hits[%d] = %d is outside the session's %lld chunks", who, i, hits[i], (long long)m->total_chunks);
+    return PE_OK;
+}
+
+// The saved samples of hits[0 .. n) in passes: per pass the ids go up, mine_ring builds the clips, the clip front end writes
+// their windows -- float64 rows to feats_out_host, or float32 rows that mine_gather packs for the trainer
+int miner_rows(pe_miner* m, const char* who, const int32_t* hits, int32_t n, double* feats_out_host, pe_trainer* trainer, int source, float target) {
+    pe_engine* e = m->e;
+    int rc = miner_check_hits(m, who, hits, n);
+    if (rc) return rc;
+    if (n == 0) return PE_OK;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    const int T = e->prm.n_features, B = m->buffer_samples;
+    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    // vectorize() of a clip of B samples (no crop: buffer_samples <= max_samples, params.py:74,95): the same for every hit
+    const int64_t frames = frames_of_buffer(e->prm, B);
+    const int kept = (int)(frames < T ? frames : T);
+    int64_t per_pass = e->clip_pass_bytes / ((int64_t)B * (int64_t)sizeof(float));
+    per_pass = std::max<int64_t>(1, std::min<int64_t>(per_pass, 32768));
+    std::vector<ClipDesc> desc;
+    std::vector<uint32_t> prefix;
+    for (int32_t h0 = 0; h0 < n; h0 += (int32_t)per_pass) {
+        const int k = (int)std::min<int64_t>(per_pass, n - h0);
+        desc.resize((size_t)k); prefix.resize((size_t)k + 1);
+        for (int i = 0; i < k; ++i) {
+            desc[(size_t)i] = ClipDesc{(long long)i * B, (int)(frames - kept), kept, T - kept, 0};
+            prefix[(size_t)i] = (uint32_t)i * (uint32_t)kept;
+        }
+        prefix[(size_t)k] = (uint32_t)k * (uint32_t)kept;
+        const size_t db = (size_t)k * sizeof(ClipDesc), pb = ((size_t)k + 1) * sizeof(uint32_t);
+        if ((rc = ensure(e, m->ids, (size_t)k * sizeof(int32_t)))) return rc;
+        if ((rc = ensure(e, m->ring, (size_t)k * B * sizeof(float)))) return rc;
+        if ((rc = ensure(e, m->clips, db + pb))) return rc;
+        PE_HIP(e, hipMemcpy(m->ids.p, hits + h0, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice));
+        PE_HIP(e, hipMemcpy(m->clips.p, desc.data(), db, hipMemcpyHostToDevice));
+        PE_HIP(e, hipMemcpy(static_cast<char*>(m->clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
+        MineRingArgs r{static_cast<const int32_t*>(m->ids.p), k, m->d_chunk_prefix(), m->d_rec_start(), m->n_rec, m->chunk, B, m->carry_audio,
+                       m->audio.p, m->audio_f32, static_cast<float*>(m->ring.p)};
+        PE_HIP(e, launch_mine_ring(r, nullptr));
+        const ClipTable ct{static_cast<const ClipDesc*>(m->clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(m->clips.p) + db),
+                           k, (uint32_t)k * (uint32_t)kept, m->ring.p, 1};
+        if (feats_out_host) {
+            const size_t fb = (size_t)k * T * e->prm.n_mfcc * sizeof(double);
+            if ((rc = ensure(e, m->feats64, fb))) return rc;
+            if ((rc = launch_clip_front_end(e, ct, static_cast<double*>(m->feats64.p), nullptr, nullptr))) return rc;
+            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)h0 * T * e->prm.n_mfcc, m->feats64.p, fb, hipMemcpyDeviceToHost));
+        } else {
+            if ((rc = ensure(e, m->clip_rows, (size_t)k * T * e->row_floats * sizeof(float)))) return rc;
+            if ((rc = ensure(e, m->packed, (size_t)k * T * width * sizeof(float)))) return rc;
+            if ((rc = launch_clip_front_end(e, ct, nullptr, static_cast<float*>(m->clip_rows.p), nullptr))) return rc;
+            MineGatherArgs g = miner_gather_args(m);
+            g.rows = static_cast<const float*>(m->clip_rows.p);
+            g.n = k;
+            g.out = static_cast<float*>(m->packed.p);
+            PE_HIP(e, launch_mine_gather(g, nullptr));
+            PE_HIP(e, hipStreamSynchronize(nullptr));
+            const int trc = train_append_device(trainer, who, source, static_cast<const float*>(m->packed.p), k, target);
+            if (trc) return fail(e, trc, "%s", trainer->err.c_str());
+        }
+    }
+    return PE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pe_miner_create(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_rec,
+                    int32_t chunk_size, int32_t buffer_samples, int32_t carry_audio, pe_miner** out) {
+    const char* who = "pe_miner_create";
+    if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
+    if (!out) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    *out = nullptr;
+    if (n_rec < 0) return fail(e, PE_ERR_INVALID, "%s: n_rec=%d", who, n_rec);
+    if (n_rec > 0 && !offsets_host) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (sample_format != 0 && sample_format != 1) return fail(e, PE_ERR_INVALID, "%s: sample_format must be 0 (float64) or 1 (float32), got %d", who, sample_format);
+    if (chunk_size < 1) return fail(e, PE_ERR_INVALID, "%s: chunk_size must be >= 1, got %d", who, chunk_size);
+    if (buffer_samples < 1) return fail(e, PE_ERR_INVALID, "%s: buffer_samples must be >= 1, got %d", who, buffer_samples);
+    if (n_rec > 0 && offsets_host[0] != 0) return fail(e, PE_ERR_INVALID, "%s: offsets[0] must be 0, got %lld", who, (long long)offsets_host[0]);
+    std::vector<int64_t> tab((size_t)3 * (n_rec + 1), 0);       // chunk prefix | frame base | first sample
+    int64_t* cp = tab.data(); int64_t* fb = cp + n_rec + 1; int64_t* rs = fb + n_rec + 1;
+    for (int32_t r = 0; r < n_rec; ++r) {
+        const int64_t len = offsets_host[r + 1] - offsets_host[r];
+        if (len < 0) return fail(e, PE_ERR_INVALID, "%s: offsets decrease at recording %d (%lld after %lld)", who, r, (long long)offsets_host[r + 1], (long long)offsets_host[r]);
+        cp[r + 1] = cp[r] + (len > 0 ? (len - 1) / chunk_size : 0);        // util.py:30-32
+        fb[r + 1] = fb[r] + frames_of_buffer(e->prm, len);
+        rs[r] = offsets_host[r];
+        if (cp[r + 1] > 0x7fffffff || fb[r + 1] > 0x7fffffff)
+            return fail(e, PE_ERR_INVALID, "%s: more than 2^31 - 1 chunks or frames in one session (at recording %d)", who, r);
+    }
+    const int64_t n_samples = n_rec > 0 ? offsets_host[n_rec] : 0;
+    rs[n_rec] = n_samples;
+    if (n_samples > 0 && !audio_host) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    pe_miner* m = new pe_miner;
+    m->e = e; m->n_rec = n_rec; m->chunk = chunk_size; m->buffer_samples = buffer_samples; m->carry_audio = carry_audio ? 1 : 0;
+    m->audio_f32 = sample_format == 1 ? 1 : 0;
+    m->total_chunks = cp[n_rec]; m->total_frames = fb[n_rec];
+    m->chunk_prefix.assign(cp, cp + n_rec + 1);
+    const size_t elem = sample_format == 1 ? sizeof(float) : sizeof(double);
+    int rc = PE_OK;
+    hipError_t herr = hipSuccess;
+    do {
+        if ((rc = ensure(e, m->audio, (size_t)std::max<int64_t>(n_samples, 1) * elem))) break;
+        if ((rc = ensure(e, m->tables, tab.size() * sizeof(int64_t)))) break;
+        if ((rc = ensure(e, m->rows, (size_t)std::max<int64_t>(m->total_frames, 1) * e->row_floats * sizeof(float)))) break;
+        if (n_samples > 0 && (herr = hipMemcpy(m->audio.p, audio_host, (size_t)n_samples * elem, hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((herr = hipMemcpy(m->tables.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if (m->total_frames > 0) {
+            // every frame of every recording, once: pe_evaluate_clips' front-end launch with the rows back to back
+            std::vector<RecDesc> desc((size_t)n_rec);
+            std::vector<uint32_t> prefix((size_t)n_rec + 1);
+            for (int32_t r = 0; r < n_rec; ++r) { desc[(size_t)r] = RecDesc{rs[r], fb[r]}; prefix[(size_t)r] = (uint32_t)fb[r]; }
+            prefix[(size_t)n_rec] = (uint32_t)fb[n_rec];
+            const size_t db = (size_t)n_rec * sizeof(RecDesc), pb = ((size_t)n_rec + 1) * sizeof(uint32_t);
+            if ((rc = ensure(e, m->clips, db + pb))) break;
+            if ((herr = hipMemcpy(m->clips.p, desc.data(), db, hipMemcpyHostToDevice)) != hipSuccess) break;
+            if ((herr = hipMemcpy(static_cast<char*>(m->clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice)) != hipSuccess) break;
+            const RecTable rt{static_cast<const RecDesc*>(m->clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(m->clips.p) + db),
+                              n_rec, (uint32_t)m->total_frames, m->audio.p, m->audio_f32};
+            if ((rc = launch_rec_front_end(e, rt, static_cast<float*>(m->rows.p)))) break;
+        }
+        herr = hipStreamSynchronize(nullptr);
+    } while (false);
+    if (!rc && herr != hipSuccess) rc = fail(e, PE_ERR_HIP, "%s: %s", who, hipGetErrorString(herr));
+    if (rc) { miner_free(m); return rc; }
+    *out = m;
+    return PE_OK;
+}
+
+int pe_miner_destroy(pe_miner* m) {
+    if (m) miner_free(m);
+    return PE_OK;
+}
+
+int pe_miner_layout(const pe_miner* m, int64_t* chunk_offsets_out) {
+    if (!m || !chunk_offsets_out) return PE_ERR_INVALID;
+    std::copy(m->chunk_prefix.begin(), m->chunk_prefix.end(), chunk_offsets_out);
+    return PE_OK;
+}
+
+int pe_miner_scan(pe_miner* m, int32_t model, int64_t first_chunk, double threshold, float* scores_out, int32_t* hits_out,
+                  int32_t capacity, int32_t* n_hits, int64_t* n_above) {
+    const char* who = "pe_miner_scan";
+    if (!m) return PE_ERR_INVALID;
+    pe_engine* e = m->e;
+    if (!n_hits || !n_above) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (model < 0 || model >= e->n_models) return fail(e, PE_ERR_INVALID, "%s: model %d outside 0..%d", who, model, e->n_models - 1);
+    if (first_chunk < 0 || first_chunk > m->total_chunks) return fail(e, PE_ERR_INVALID, "%s: first_chunk %lld outside 0..%lld", who, (long long)first_chunk, (long long)m->total_chunks);
+    if (threshold != threshold) return fail(e, PE_ERR_INVALID, "%s: threshold is NaN", who);
+    if (capacity < 0 || (capacity > 0 && !hits_out)) return fail(e, PE_ERR_INVALID, "%s: capacity=%d without hits_out", who, capacity);
+    *n_hits = 0; *n_above = 0;
+    const int64_t n = m->total_chunks - first_chunk;
+    if (n == 0) return PE_OK;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    const int T = e->prm.n_features, width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    const int64_t window_bytes = (int64_t)T * width * (int64_t)sizeof(float);
+    const int64_t per_pass = std::max<int64_t>(1, std::min<int64_t>(e->clip_pass_bytes / window_bytes, 1 << 24));
+    int rc;
+    if ((rc = ensure(e, m->scores, (size_t)n * sizeof(float)))) return rc;
+    float* const scores = static_cast<float*>(m->scores.p);
+    MineGatherArgs g = miner_gather_args(m);
+    g.rows = static_cast<const float*>(m->rows.p);
+    g.chunk_prefix = m->d_chunk_prefix(); g.frame_base = m->d_frame_base(); g.n_rec = m->n_rec;
+    for (int64_t c0 = 0; c0 < n; c0 += per_pass) {
+        const int k = (int)std::min<int64_t>(per_pass, n - c0);
+        if ((rc = ensure(e, m->batch, (size_t)k * (size_t)window_bytes))) return rc;
+        g.first = first_chunk + c0; g.n = k; g.out = static_cast<float*>(m->batch.p);
+        PE_HIP(e, launch_mine_gather(g, nullptr));
+        if (e->n_models == 1) {
+            if ((rc = pe_predict_device(e, g.out, k, scores + c0, nullptr))) return rc;
+        } else {                // a K-model engine predicts all of its models: [K][k]; the scan keeps block `model`
+            if ((rc = ensure(e, m->pred, (size_t)e->n_models * k * sizeof(float)))) return rc;
+            if ((rc = pe_predict_device(e, g.out, k, static_cast<float*>(m->pred.p), nullptr))) return rc;
+            PE_HIP(e, hipMemcpyAsync(scores + c0, static_cast<const float*>(m->pred.p) + (size_t)model * k, (size_t)k * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+        }
+    }
+    // decode (pe_decode's kernel, when model has a table), then the ordered compaction over the whole range
+    const DecState& d = e->dec[(size_t)model];
+    const double* conf = nullptr;
+    if (d.cd) {
+        if ((rc = ensure(e, m->conf, (size_t)n * sizeof(double)))) return rc;
+        DecodeArgs a{};
+        a.n_streams = (int)n; a.raw = scores; a.cd = d.cd; a.cd_len = d.cd_len; a.min_out = d.min_out; a.out_range = d.out_range; a.center = d.center;
+        a.conf_out = static_cast<double*>(m->conf.p);
+        PE_HIP(e, launch_decode(a, nullptr));
+        conf = a.conf_out;
+    }
+    const int n_blocks = mine_blocks(n);
+    if ((rc = ensure(e, m->counts, ((size_t)n_blocks + 1) * sizeof(uint32_t)))) return rc;
+    if (capacity > 0 && (rc = ensure(e, m->hits, (size_t)capacity * sizeof(int32_t)))) return rc;
+    MineCompactArgs c{scores, conf, n, threshold, first_chunk, static_cast<uint32_t*>(m->counts.p), n_blocks,
+                      capacity > 0 ? static_cast<int32_t*>(m->hits.p) : nullptr, capacity};
+    PE_HIP(e, launch_mine_compact(c, nullptr));
+    uint32_t total = 0;
+    PE_HIP(e, hipMemcpy(&total, c.block_counts + n_blocks, sizeof total, hipMemcpyDeviceToHost));
+    const int32_t got = (int32_t)std::min<int64_t>(total, capacity);
+    if (got > 0) PE_HIP(e, hipMemcpy(hits_out, m->hits.p, (size_t)got * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (scores_out) PE_HIP(e, hipMemcpy(scores_out, scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    *n_hits = got; *n_above = (int64_t)total;
+    return PE_OK;
+}
+
+int pe_miner_vectorize(pe_miner* m, const int32_t* hits, int32_t n, double* feats_out_host) {
+    if (!m) return PE_ERR_INVALID;
+    if (n > 0 && !feats_out_host) return fail(m->e, PE_ERR_INVALID, "null argument to pe_miner_vectorize");
+    return miner_rows(m, "pe_miner_vectorize", hits, n, feats_out_host, nullptr, 0, 0.0f);
+}
+
+int pe_miner_append(pe_miner* m, pe_trainer* trainer, int32_t source, const int32_t* hits, int32_t n, float target) {
+    const char* who = "pe_miner_append";
+    if (!m) return PE_ERR_INVALID;
+    pe_engine* e = m->e;
+    if (!trainer) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    if (trainer->device != e->device) return fail(e, PE_ERR_INVALID, "%s: the trainer lives on device %d, the engine on %d", who, trainer->device, e->device);
+    if (trainer->F != width || trainer->T != e->prm.n_features)
+        return fail(e, PE_ERR_INVALID, "%s: the trainer takes [%d][%d] inputs, the engine's windows are [%d][%d]", who, trainer->T, trainer->F, e->prm.n_features, width);
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
+    if (!(target >= 0.0f && target <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: target %g is outside [0, 1]", who, (double)target);
+    return miner_rows(m, who, hits, n, nullptr, trainer, source, target);
 }
 
 }  // extern "C"

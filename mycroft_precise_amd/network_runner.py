@@ -76,6 +76,12 @@ class HipRunner(Runner):
     def run(self, inp: np.ndarray) -> float:
         return self.predict(np.asarray(inp)[np.newaxis])[0][0]
 
+    def set_weights(self, weights: dict):
+        """Serve another network of the same widths from the next call on, streams in progress included: what training the
+        Listener's own model object does in the reference (scripts/train_incremental.py:86-88,106)."""
+        self.engine.set_weights(weights)
+        self.weights = weights
+
     def predict_clips(self, audios) -> np.ndarray:
         """``predict(np.array([vectorize(a) for a in audios]))`` (``vectorize_delta`` for use_delta models) without the
         per-clip loop: every clip goes through the front end and the network in one device call each (the dataset tools'

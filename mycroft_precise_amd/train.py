@@ -110,9 +110,14 @@ class Trainer:
         if n == 0 or int(batch_size) < 1:
             raise ValueError('fit needs at least one sample and batch_size >= 1')
         self._t.set_data(inputs, outputs)
+        return self._fit(n, batch_size, epochs, shuffle, callback, lambda: self.evaluate(inputs, outputs),
+                         None if validation_data is None else lambda: self.evaluate(*validation_data))
+
+    def _fit(self, n, batch_size, epochs, shuffle, callback, measure, measure_validation) -> dict:
+        """the epochs of ``fit`` over the resident training set of ``n`` samples; ``measure()`` -> (loss, acc) after an epoch"""
         p = self.params
         history = {'loss': [], 'acc': []}
-        if validation_data is not None:
+        if measure_validation is not None:
             history.update(val_loss=[], val_acc=[])
         for epoch in range(int(epochs)):
             order = self._rng.permutation(n) if shuffle else np.arange(n)
@@ -122,14 +127,43 @@ class Trainer:
                                            loss_bias=p.loss_bias, lr=RMSPROP_LR, rho=RMSPROP_RHO, eps=RMSPROP_EPS,
                                            frozen_mask=self.frozen_mask))
                 self._step += 1
-            logs = {'loss': float(np.mean(losses)), 'acc': self.evaluate(inputs, outputs)[1]}
-            if validation_data is not None:
-                logs['val_loss'], logs['val_acc'] = self.evaluate(*validation_data)
+            logs = {'loss': float(np.mean(losses)), 'acc': measure()[1]}
+            if measure_validation is not None:
+                logs['val_loss'], logs['val_acc'] = measure_validation()
             for k, v in logs.items():
                 history[k].append(v)
             if callback is not None:
                 callback(epoch, logs)
         return history
+
+    # -- a training set that stays on the device and grows (scripts/train_incremental.py:96-111) ----------------------
+    def set_data(self, inputs, outputs, validation=False):
+        """Upload the training (``validation``: the validation) set once; ``append`` / ``Miner.append_to`` add to it and
+        ``fit_resident`` trains on it."""
+        (self._t.set_validation if validation else self._t.set_data)(inputs, outputs)
+
+    def append(self, inputs, outputs, validation=False):
+        """More samples behind the resident training (validation) set; what is there stays (``TrainData.merge``,
+        train_incremental.py:101-102, without a new upload)."""
+        self._t.append(inputs, outputs, validation=validation)
+
+    def n_samples(self, validation=False) -> int:
+        return self._t.n_samples(validation)
+
+    def _evaluate_resident(self, source):
+        loss, acc, _ = self._t.evaluate_models(loss_bias=self.params.loss_bias, source=source, want_probs=False)
+        return float(loss[0]), float(acc[0])
+
+    def fit_resident(self, batch_size=5000, epochs=1, shuffle=True, callback=None) -> dict:
+        """``fit`` on the resident training set, without an upload: the same steps -- the same weights, bit for bit, as ``fit``
+        on the same samples from the same state -- with ``acc`` (and ``val_loss`` / ``val_acc`` when a validation set is
+        resident) measured on the resident sets.  The optimizer state carries over from call to call, as it does when the
+        reference calls ``model.fit`` again on the model it keeps (train_incremental.py:106-109)."""
+        n = self._t.n_samples()
+        if n == 0 or int(batch_size) < 1:
+            raise ValueError('fit_resident needs a resident training set (set_data / append) and batch_size >= 1')
+        return self._fit(n, batch_size, epochs, shuffle, callback, lambda: self._evaluate_resident('data'),
+                         (lambda: self._evaluate_resident('validation')) if self._t.n_samples(True) else None)
 
     def close(self):
         self._t.close()
@@ -250,3 +284,116 @@ class TrainerGroup:
 
     def close(self):
         self._t.close()
+
+
+class IncrementalTrainer:
+    """The policy of ``precise-train-incremental`` (scripts/train_incremental.py:113-137) over a ``mining.Miner``.
+
+    Per recording the script draws ``save_test = random() > 0.8``; every chunk whose prediction exceeds ``threshold`` is saved
+    -- into the validation folder for a test recording -- and counted; after every chunk, ``not save_test and count >=
+    delay_samples and epochs > 0`` retrains for ``epochs`` epochs and resets the count, and the next chunk is judged by the
+    retrained model.  Hits of test recordings count but never trigger.  Here the chunks of all recordings are scored in one
+    scan; the host walks the ordered hits to the first chunk at which the script would retrain (the cut), appends the hits up
+    to it to the trainer's resident sets, runs ``fit_resident``, hands ``trainer.weights`` to the runner and scans again from
+    the chunk after the cut.
+
+        trainer.set_data(train_inputs, train_outputs)               # what retrain() loads from the data folder
+        inc = IncrementalTrainer(trainer, runner, delay_samples=10, epochs=1)
+        hits, retrains = inc.run(audios)
+
+    ``run`` -> (``[(recording, chunk, went_to_test), ...]`` in the order the script saves them, ``[(recording, chunk), ...]``
+    the chunks after which it retrained).  ``test_flags``: one bool per recording; None draws them as the script does, from
+    ``rng`` (``numpy.random.Generator``; default: a fresh one).  wav files stay with the caller."""
+
+    def __init__(self, trainer, runner, delay_samples: int = 10, epochs: int = 1, batch_size: int = 5000, threshold: float = 0.5,
+                 chunk_size: int = 2048, capacity: int = 4096, shuffle: bool = True, miner_cls=None):
+        self.trainer, self.runner = trainer, runner
+        self.delay_samples, self.epochs, self.batch_size = int(delay_samples), int(epochs), int(batch_size)
+        self.threshold, self.chunk_size, self.capacity, self.shuffle = float(threshold), int(chunk_size), max(1, int(capacity)), shuffle
+        self.miner_cls = miner_cls
+        self.samples_since_train = 0
+
+    def _make_miner(self, audios):
+        if self.miner_cls is not None:
+            return self.miner_cls(self.runner, audios, chunk_size=self.chunk_size, carry_audio=True)
+        from .mining import Miner
+        return Miner(self.runner, audios, chunk_size=self.chunk_size, carry_audio=True)
+
+    def run(self, audios, test_flags=None, rng=None):
+        audios = list(audios)
+        if test_flags is None:
+            rng = np.random.default_rng() if rng is None else rng
+            test_flags = [bool(rng.random() > 0.8) for _ in audios]                 # train_incremental.py:115
+        test_flags = [bool(f) for f in test_flags]
+        if len(test_flags) != len(audios):
+            raise ValueError('%d test flags for %d recordings' % (len(test_flags), len(audios)))
+        miner = self._make_miner(audios)
+        offsets = np.asarray(miner.chunk_offsets, dtype=np.int64)
+        total = int(offsets[-1])
+        flags = np.asarray(test_flags, dtype=bool)
+        saved, retrains = [], []
+        pos = 0
+        try:
+            while pos < total:
+                hits, n_above, _ = miner.scan(first=pos, threshold=self.threshold, capacity=self.capacity)
+                hits = np.asarray(hits, dtype=np.int64)
+                rec, chunk = miner.locate(hits)
+                # the cut: the first hit in a training recording at which the count reaches delay_samples.  A count that a test
+                # recording pushed past it fires at the FIRST chunk of the next training recording, hit or not (:134).
+                cut = self._cut(pos, hits, rec, offsets, flags, total, complete=len(hits) == n_above)
+                upto = total if cut is None else cut + 1
+                take = hits[hits < upto]
+                r_take, c_take = rec[:take.size], chunk[:take.size]
+                for validation in (False, True):
+                    part = take[flags[r_take] == validation]
+                    if part.size:
+                        miner.append_to(self.trainer, part, validation=validation)
+                saved += [(int(r), int(c), bool(flags[r])) for r, c in zip(r_take, c_take)]
+                if cut is None and len(hits) < n_above:
+                    # capacity ran out before a cut: the count so far stands, go on behind the last hit taken
+                    self.samples_since_train += int(take.size)
+                    pos = int(take[-1]) + 1
+                    continue
+                if cut is None:
+                    self.samples_since_train += int(take.size)
+                    break
+                self.samples_since_train = 0
+                r_cut = int(np.searchsorted(offsets, cut, side='right') - 1)
+                retrains.append((r_cut, int(cut - offsets[r_cut])))
+                self.trainer.fit_resident(self.batch_size, self.epochs, shuffle=self.shuffle)
+                self.runner.set_weights(self.trainer.weights)
+                pos = cut + 1
+        finally:
+            miner.close()
+        return saved, retrains
+
+    def _cut(self, pos, hits, rec, offsets, flags, total, complete):
+        """global id of the first chunk >= pos after which the script retrains, given the hits from pos on (all of them when
+        ``complete``, else a prefix: then nothing behind the last one is known) -- or None if there is none in what is known"""
+        if self.epochs <= 0:
+            return None
+        horizon = total if complete else (int(hits[-1]) + 1 if len(hits) else pos)
+        count = self.samples_since_train
+        i = 0
+        g = pos
+        while g < horizon:
+            r = int(np.searchsorted(offsets, g, side='right') - 1)
+            end = min(int(offsets[r + 1]), horizon)
+            if flags[r]:                                    # a test recording: its hits count, nothing fires
+                while i < len(hits) and hits[i] < end:
+                    count += 1
+                    i += 1
+                g = end
+                continue
+            if count >= self.delay_samples:                 # pushed past by a test recording: fires after this very chunk
+                return g                                    # (a hit in it is saved first, and trained on)
+            if i < len(hits) and hits[i] < end:
+                nxt = int(hits[i])
+                count += 1
+                i += 1
+                if count >= self.delay_samples:
+                    return nxt
+                g = nxt + 1
+            else:
+                g = end
+        return None

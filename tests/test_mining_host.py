@@ -1,0 +1,149 @@
+"""No GPU: the mining session's ABI surface, its chunk arithmetic, and the policy of ``IncrementalTrainer`` against the numpy
+restatement of scripts/train_incremental.py:113-137 (incremental_reference.py)."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import incremental_reference as ref
+from mycroft_precise_amd import _lib, synth
+from mycroft_precise_amd.train import IncrementalTrainer
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ['pe_set_weights', 'pe_trainer_append', 'pe_trainer_get_data', 'pe_miner_create', 'pe_miner_destroy', 'pe_miner_layout',
+               'pe_miner_scan', 'pe_miner_vectorize', 'pe_miner_append']
+
+
+def test_symbols_declared_and_bound():
+    header = open(os.path.join(REPO, 'include', 'precise_engine.h')).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(r'\bint %s\(' % name, header), name
+        assert name in _lib.EXPORTS, name
+    assert '#define PE_ABI_VERSION 8' in header and _lib.ABI_VERSION == 8
+
+
+@pytest.mark.parametrize('C', [512, 2048])
+def test_chunk_offsets_follow_chunk_audio(C):
+    lengths = [0, 1, C - 1, C, C + 1, 2 * C, 2 * C + 1]
+    counts = [len(list(ref.chunks(np.zeros(n), C))) for n in lengths]
+    assert counts == [0, 0, 0, 0, 1, 1, 2]
+    assert ref.chunk_offsets(lengths, C).tolist() == np.concatenate(([0], np.cumsum(counts))).tolist()
+    # (pe_miner_layout itself is held to ref.chunk_offsets on the same lengths in tests/test_mining.py: it needs an engine)
+
+
+def test_round_trip_is_not_the_identity():
+    """load_audio output is k / 32767 in float32; times 32767.0 that lands below k for many k and truncates to k - 1: a ring
+    kernel that skipped the round trip would produce other samples."""
+    audio = synth.stream_pcm(3, 16000).astype(np.float32) / np.float32(32767.0)
+    back = ref.round_trip(audio.astype(np.float64))
+    assert back.dtype == np.float32
+    changed = np.count_nonzero(back != audio)
+    assert 0 < changed < audio.size
+    one = np.float32(1.0) / np.float32(32767.0)
+    assert ref.round_trip(np.array([float(one)]))[0] == 0.0
+
+
+# ---- the policy, with everything that touches a device replaced ------------------------------------------------------------
+def fake_score(g, n_retrains):
+    """a prediction in [0, 1) that depends on (global chunk id, retrains so far) alone"""
+    return ((int(g) * 2654435761 + int(n_retrains) * 40503 + 12345) % 1000) / 1000.0
+
+
+class FakeRunner:
+    def __init__(self):
+        self.n_retrains = 0
+
+    def set_weights(self, weights):
+        self.n_retrains = weights
+
+
+class FakeTrainer:
+    def __init__(self):
+        self.fits, self.appended = 0, {False: [], True: []}
+
+    def fit_resident(self, batch_size, epochs, shuffle=True):
+        self.fits += 1
+        self.snapshots = getattr(self, 'snapshots', []) + [(list(self.appended[False]), list(self.appended[True]))]
+
+    @property
+    def weights(self):
+        return self.fits
+
+
+class FakeMiner:
+    scans = 0
+
+    def __init__(self, runner, audios, chunk_size=2048, carry_audio=True):
+        self.runner = runner
+        self.chunk_offsets = ref.chunk_offsets([len(a) for a in audios], chunk_size)
+        self.n_chunks = int(self.chunk_offsets[-1])
+
+    def scan(self, first=0, threshold=0.5, capacity=None, return_scores=False):
+        FakeMiner.scans += 1
+        scores = np.array([fake_score(g, self.runner.n_retrains) for g in range(first, self.n_chunks)])
+        hits = first + np.flatnonzero(scores > threshold)
+        return hits[:capacity].astype(np.int32), int(hits.size), None
+
+    def locate(self, hits):
+        hits = np.asarray(hits, dtype=np.int64)
+        rec = np.searchsorted(self.chunk_offsets, hits, side='right') - 1
+        return rec, hits - self.chunk_offsets[rec]
+
+    def append_to(self, trainer, hits, validation=False):
+        trainer.appended[bool(validation)] += [int(h) for h in hits]
+
+    def close(self):
+        pass
+
+
+LENGTHS = [5 * 100 + 1, 0, 12 * 100 + 7, 100, 30 * 100 + 1, 9 * 100 + 50, 17 * 100 + 1, 1, 25 * 100 + 3]
+CASES = {
+    # a test recording (index 4, 30 chunks) pushes the count far past delay_samples; the retrain comes at the next training chunk
+    'test_recording_pushes_past': dict(flags=[0, 0, 0, 0, 1, 0, 0, 1, 0], delay=4, epochs=1, capacity=4096, threshold=0.7),
+    'epochs_zero': dict(flags=[0, 0, 1, 0, 0, 0, 1, 0, 0], delay=3, epochs=0, capacity=4096, threshold=0.6),
+    'capacity_below_a_cut': dict(flags=[0, 0, 0, 0, 1, 0, 0, 0, 0], delay=7, epochs=2, capacity=2, threshold=0.5),
+    'capacity_one': dict(flags=[1, 0, 0, 0, 0, 0, 1, 0, 0], delay=3, epochs=1, capacity=1, threshold=0.8),
+    'all_training': dict(flags=[0] * 9, delay=1, epochs=1, capacity=4096, threshold=0.9),
+}
+
+
+@pytest.mark.parametrize('case', sorted(CASES))
+def test_incremental_policy_equals_the_scripts_loop(case):
+    c = CASES[case]
+    C = 100
+    audios = [np.zeros(n, np.float32) for n in LENGTHS]
+    offsets = ref.chunk_offsets(LENGTHS, C)
+    runner, trainer = FakeRunner(), FakeTrainer()
+    inc = IncrementalTrainer(trainer, runner, delay_samples=c['delay'], epochs=c['epochs'], threshold=c['threshold'], chunk_size=C,
+                             capacity=c['capacity'], miner_cls=FakeMiner)
+    got_hits, got_retrains = inc.run(audios, test_flags=c['flags'])
+
+    state = {'retrains': 0, 'snapshots': []}
+
+    def retrain(saved):
+        state['retrains'] += 1
+        state['snapshots'].append(len(saved))
+
+    hits, retrains, saved, count = ref.policy_loop(
+        audios, c['flags'], C, 300, c['delay'], c['epochs'], c['threshold'], lambda r: None,
+        lambda r, i, chunk: fake_score(offsets[r] + i, state['retrains']), retrain)
+    assert len(hits) > 3
+    assert got_hits == hits
+    assert got_retrains == retrains
+    assert trainer.fits == len(retrains) and runner.n_retrains == len(retrains)
+    assert inc.samples_since_train == count
+    # routing: training hits in the training set, test hits in the validation set, each in the script's order ...
+    for test in (False, True):
+        assert trainer.appended[test] == [int(offsets[r] + i) for r, i, t in hits if t == test]
+    # ... and at every retrain exactly the samples the script had saved by then
+    assert [len(a) + len(b) for a, b in getattr(trainer, 'snapshots', [])] == state['snapshots']
+    if case == 'test_recording_pushes_past':
+        first_after = (5, 0)            # the first chunk of the first training recording behind the test recording
+        assert first_after in retrains
+        in_test = sum(1 for r, i, t in hits if r == 4)
+        assert in_test > c['delay']
+    if case == 'epochs_zero':
+        assert retrains == [] and trainer.fits == 0
+    if case.startswith('capacity'):
+        assert len(retrains) >= 1
