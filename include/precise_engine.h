@@ -629,6 +629,66 @@ int pe_miner_scan(pe_miner* m, int32_t model, int64_t first_chunk, double thresh
 int pe_miner_vectorize(pe_miner* m, const int32_t* hits, int32_t n, double* feats_out_host);
 int pe_miner_append(pe_miner* m, pe_trainer* trainer, int32_t source, const int32_t* hits, int32_t n, float target);
 
+/* Generated training data: precise-train-generated (scripts/train_generated.py:118-237) streams every background recording
+ * chunk by chunk through a Listener, overlays volume-normalised wake-word / not-wake-word clips with random gaps on it, and
+ * feeds (window, target) pairs to fit_generator.  A pe_generator is that stream as a session over ONE engine: both audio pools
+ * are uploaded once; a PLAN -- the script's random draws and its piece stream, flattened by the host (generated.py) into
+ * segments -- is mixed on the device and every frame of every planned file is computed once; windows then go to the host or
+ * straight behind a trainer's resident set.  Additive to ABI 8.  The session is not thread-safe, uses the engine's device and
+ * leaves the engine's streams untouched; destroy it before its engine.
+ *
+ * Plan: file f overlays background `background` (a background may be planned any number of times); its output is the
+ * (len - 1) / C whole chunks of that background (util.py:30-32), and its segments first_segment .. + n_segments -- the files'
+ * ranges follow one another without gaps from segment 0 -- tile exactly those n_chunks * C samples in order.  Segment: `length`
+ * (>= 1) output samples under which lie samples first .. first + length of clip `clip`, or silence (clip = -1: first, rms
+ * ignored).  `target` is the host's business (labels come from run lengths over the segments) and is not read.
+ * Arithmetic of an output sample, numpy's to the bit (:149-155, with s the background and c the clip sample, all float32):
+ *   b = fl32(fl32(fl32(audio_volume) * s) / fl32(file rms));  w = (double) fl32(fl32(fl32(volume) * c) / fl32(segment rms)), 0.0
+ *   in silence;  out = (double) fl32(fl32(1.0 - 0.6) * b) + 0.6 * w, the last product and the sum in float64.
+ * The planner sets a segment's volume to its file's audio_volume (:182); the device reads the file's.
+ * Chunks of all files in order have GLOBAL ids 0 .. total - 1, as pe_miner's.  The network input after chunk i of a file is what
+ * a Listener cleared at the start of the file (:180) holds after i + 1 chunks of the mixed samples: pe_miner's window, zero rows
+ * before the file's first frame.  With use_delta the delta columns are formed as pe_miner_scan forms them; the reference yields
+ * the bare window (:188,202) and so cannot train a use_delta model this way at all.
+ *
+ * pe_generator_create: float32 pools (what load_audio returns) with offsets[n + 1] each, checked as pe_miner_create checks its
+ *   offsets (empty entries allowed); chunk_size >= 1.
+ * pe_generator_set_plan: replaces the resident plan.  Everything is checked on the host first -- a background or clip index out
+ *   of range, a segment outside its clip, a length < 1, a file rms that is not > 0 (files with chunks) or a segment rms that is
+ *   not > 0, segment ranges that do not follow one another, a file whose segment lengths do not sum to n_chunks * chunk_size,
+ *   more than 2^31 - 1 chunks, frames or segments: PE_ERR_INVALID naming the file or segment, and the plan that was resident
+ *   stays.  Then the files are mixed and their frames computed in passes of pe_set_clip_pass_bytes bytes of mixed float64
+ *   samples over whole files (a larger file runs alone); no result depends on the pass size.
+ * pe_generator_audio: out_host[n] = mixed samples first .. first + n of planned file `file` (the mix is run again for them).
+ * pe_generator_vectorize: feats_out_host[n][n_features][width] float32, width = feature_size (n_mfcc, doubled by use_delta).
+ *   ids: global chunk ids in any order, repeats allowed; one outside the plan is PE_ERR_INVALID.
+ * pe_generator_append: the same rows behind the trainer's resident set `source`, device to device, sample i with targets[i];
+ *   trainer, device and shape checks as pe_miner_append's, every target in [0, 1] (PE_ERR_INVALID naming the index). */
+typedef struct pe_generator pe_generator;
+typedef struct pe_gen_file {
+    int32_t background;
+    int32_t reserved;
+    double audio_volume;    /* rms * (0.4 + 0.5 u) */
+    double rms;             /* of the background */
+    int64_t first_segment;
+    int64_t n_segments;
+} pe_gen_file;
+typedef struct pe_gen_segment {
+    int32_t clip;           /* -1: silence */
+    int32_t target;
+    int64_t first;
+    int64_t length;
+    double volume;
+    double rms;             /* of the clip */
+} pe_gen_segment;
+int pe_generator_create(pe_engine* e, const float* bg_audio, const int64_t* bg_offsets, int32_t n_bg, const float* clip_audio,
+                        const int64_t* clip_offsets, int32_t n_clips, int32_t chunk_size, pe_generator** out);
+int pe_generator_destroy(pe_generator* g);
+int pe_generator_set_plan(pe_generator* g, const pe_gen_file* files, int32_t n_files, const pe_gen_segment* segments, int64_t n_segments);
+int pe_generator_audio(pe_generator* g, int32_t file, int64_t first, int64_t n, double* out_host);
+int pe_generator_vectorize(pe_generator* g, const int32_t* ids, int32_t n, float* feats_out_host);
+int pe_generator_append(pe_generator* g, pe_trainer* trainer, int32_t source, const int32_t* ids, const float* targets, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

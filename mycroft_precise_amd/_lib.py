@@ -150,7 +150,20 @@ EXPORTS = {
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     'pe_miner_vectorize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'pe_miner_append': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float]),
+    # generated training data (pe_generator)
+    'pe_generator_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_void_p)]),
+    'pe_generator_destroy': (C.c_int, [C.c_void_p]),
+    'pe_generator_set_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
+    'pe_generator_audio': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
+    'pe_generator_vectorize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    'pe_generator_append': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
 }
+
+# pe_gen_file / pe_gen_segment: the tables of pe_generator_set_plan
+GEN_FILE = np.dtype([('background', '<i4'), ('reserved', '<i4'), ('audio_volume', '<f8'), ('rms', '<f8'), ('first_segment', '<i8'),
+                     ('n_segments', '<i8')])
+GEN_SEGMENT = np.dtype([('clip', '<i4'), ('target', '<i4'), ('first', '<i8'), ('length', '<i8'), ('volume', '<f8'), ('rms', '<f8')])
 
 # pe_sim_metric: one (model, recording) of pe_simulate_scores / pe_simulate_clips
 SIM_METRIC = np.dtype([('n_windows', '<i8'), ('activated_chunks', '<i8'), ('activations', '<i8'), ('activation_sum', '<f8')])
@@ -250,7 +263,7 @@ class HipEngine:
         self._lib = load()
         self._h = C.c_void_p()
         self._async_keep = []
-        self._miners = weakref.WeakSet()   # HipMiner sessions over this engine: closed before the engine is destroyed
+        self._miners = weakref.WeakSet()   # HipMiner / HipGenerator sessions over this engine: closed before the engine is destroyed
         self._views = 0                # host_array() buffers still referenced by numpy arrays (their memory dies with the engine)
         self._close_pending = False
         self.n_streams = int(n_streams)
@@ -1024,6 +1037,101 @@ class HipMiner:
         """pe_miner_destroy; the engine calls it for every session it still has when it is closed itself"""
         if getattr(self, '_h', None) and self._h.value:
             self._lib.pe_miner_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipGenerator:
+    """
+    One C-ABI generating session (pe_generator) over one ``HipEngine``: the background and clip pools resident on the device, one
+    plan at a time mixed and vectorized there; ``generated.Generator`` is the reference-shaped class and the planner.  Chunks
+    carry GLOBAL ids over the files of the resident plan.  The session keeps its engine alive; close it before the engine.
+    """
+
+    def __init__(self, engine: HipEngine, backgrounds, clips, chunk_size: int):
+        self._lib = load()
+        self._h = C.c_void_p()
+        self.engine = engine
+        self.chunk_size = int(chunk_size)
+        bg, bg_off = self._pool(backgrounds)
+        cl, cl_off = self._pool(clips)
+        self.background_chunks = np.maximum(np.diff(bg_off) - 1, 0) // max(self.chunk_size, 1)
+        engine._check(self._lib.pe_generator_create(engine._h, bg.ctypes.data if bg.size else None, bg_off.ctypes.data, bg_off.size - 1,
+                                                    cl.ctypes.data if cl.size else None, cl_off.ctypes.data, cl_off.size - 1,
+                                                    self.chunk_size, C.byref(self._h)))
+        engine._miners.add(self)
+        self.chunk_offsets = np.zeros(1, dtype=np.int64)
+
+    @staticmethod
+    def _pool(audios):
+        audios = [np.asarray(a) for a in audios]
+        for a in audios:
+            if a.ndim != 1 or a.dtype != np.float32:
+                raise ValueError('every recording must be a 1-D float32 array (load_audio), got %s %r' % (a.dtype, a.shape))
+        offsets = np.zeros(len(audios) + 1, dtype=np.int64)
+        np.cumsum([a.size for a in audios], out=offsets[1:])
+        return (np.concatenate(audios) if audios else np.empty(0, np.float32)), offsets
+
+    def set_plan(self, files, segments):
+        """``files`` / ``segments``: structured arrays of ``GEN_FILE`` / ``GEN_SEGMENT``; mixes and vectorizes every file"""
+        files = np.ascontiguousarray(files, dtype=GEN_FILE)
+        segments = np.ascontiguousarray(segments, dtype=GEN_SEGMENT)
+        self.engine._check(self._lib.pe_generator_set_plan(self._handle(), files.ctypes.data if files.size else None, files.size,
+                                                           segments.ctypes.data if segments.size else None, segments.size))
+        self.chunk_offsets = np.zeros(files.size + 1, dtype=np.int64)
+        np.cumsum(self.background_chunks[files['background']], out=self.chunk_offsets[1:])
+
+    @property
+    def n_chunks(self):
+        return int(self.chunk_offsets[-1])
+
+    def audio(self, file: int, first: int = 0, n: int = None) -> np.ndarray:
+        """float64 mixed samples ``first .. first + n`` (default: to the end) of planned file ``file``"""
+        file = int(file)
+        if not 0 <= file < self.chunk_offsets.size - 1:
+            raise ValueError('file %d is outside the plan of %d files' % (file, self.chunk_offsets.size - 1))
+        total = int(self.chunk_offsets[file + 1] - self.chunk_offsets[file]) * self.chunk_size
+        n = total - int(first) if n is None else int(n)
+        out = np.empty(max(n, 0), dtype=np.float64)
+        self.engine._check(self._lib.pe_generator_audio(self._handle(), file, int(first), n, out.ctypes.data if out.size else None))
+        return out
+
+    def _ids(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.n_chunks):
+            raise ValueError('chunk ids must be in 0..%d' % (self.n_chunks - 1))
+        return ids.astype(np.int32)
+
+    def vectorize(self, ids) -> np.ndarray:
+        ids = self._ids(ids)
+        out = np.empty((ids.size, self.engine.n_features, self.engine.feature_size), dtype=np.float32)
+        if ids.size:
+            self.engine._check(self._lib.pe_generator_vectorize(self._handle(), ids.ctypes.data, ids.size, out.ctypes.data))
+        return out
+
+    def append(self, trainer: HipTrainer, ids, targets, validation=False):
+        ids = self._ids(ids)
+        targets = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
+        if targets.size != ids.size:
+            raise ValueError('%d targets for %d ids' % (targets.size, ids.size))
+        if ids.size:
+            self.engine._check(self._lib.pe_generator_append(self._handle(), trainer._h, HipTrainer._source(validation), ids.ctypes.data,
+                                                             targets.ctypes.data, ids.size))
+
+    def _handle(self):
+        if not self._h.value:
+            raise ValueError('the generating session is closed (close(), or its engine was closed)')
+        return self._h
+
+    def close(self):
+        """pe_generator_destroy; the engine calls it for every session it still has when it is closed itself"""
+        if getattr(self, '_h', None) and self._h.value:
+            self._lib.pe_generator_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

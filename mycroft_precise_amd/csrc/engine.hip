@@ -8,6 +8,7 @@
 #include "mfcc_general_device.h"
 #include "gru_train_device.h"
 #include "mine_device.h"
+#include "generate_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -3008,6 +3009,19 @@ int train_append_device(pe_trainer* t, const char* who, int source, const float*
     return PE_OK;
 }
 
+// ... one target per sample, on the device as well (the caller has checked that each lies in [0, 1])
+int train_append_device_targets(pe_trainer* t, const char* who, int source, const float* feats_dev, const float* targets_dev, int n) {
+    TrainSet* set; int slot;
+    PE_THIP(t, hipSetDevice(t->device));
+    int rc = train_set_room(t, who, source, n, &set, &slot);
+    if (rc) return rc;
+    const size_t row = (size_t)t->T * t->F;
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot].p) + (size_t)set->n * row, feats_dev, (size_t)n * row * sizeof(float), hipMemcpyDeviceToDevice));
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot + 1].p) + set->n, targets_dev, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice));
+    set->n += n;
+    return PE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3313,6 +3327,292 @@ int pe_miner_append(pe_miner* m, pe_trainer* trainer, int32_t source, const int3
     if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
     if (!(target >= 0.0f && target <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: target %g is outside [0, 1]", who, (double)target);
     return miner_rows(m, who, hits, n, nullptr, trainer, source, target);
+}
+
+}  // extern "C"
+
+// ---- generating training audio (pe_generator; kernel: generate_device.h) --------------------------------------
+struct pe_generator {
+    pe_engine* e = nullptr;
+    int n_bg = 0, n_clips = 0, chunk = 0;
+    std::vector<int64_t> bg_offsets, clip_offsets;      // [n_bg + 1], [n_clips + 1]
+    // the plan: per file its chunk / frame / sample prefix sums [n_files + 1] and its segment range; per segment its start
+    int n_files = 0;
+    int64_t n_segments = 0, total_chunks = 0, total_frames = 0;
+    std::vector<int64_t> chunk_prefix, frame_base, sample_base, seg_first;
+    // resident: the two pools as given; of the plan: chunk prefix | frame base, the segments, their prefix sum, every frame's row
+    DeviceBuf bg, clips, tables, segs, seg_prefix, rows;
+    // grown on demand: a pass's mixed samples and recording table; a pass's ids, targets and network input; pe_generator_audio's samples
+    DeviceBuf mixed, recs, ids, targets, batch, audio_out;
+    const long long* d_chunk_prefix() const { return static_cast<const long long*>(tables.p); }
+    const long long* d_frame_base() const { return d_chunk_prefix() + n_files + 1; }
+};
+
+namespace {
+
+void generator_free(pe_generator* g) {
+    pe_engine* e = g->e;
+    (void)hipSetDevice(e->device);
+    (void)hipDeviceSynchronize();
+    for (DeviceBuf* b : {&g->bg, &g->clips, &g->tables, &g->segs, &g->seg_prefix, &g->rows, &g->mixed, &g->recs, &g->ids, &g->targets, &g->batch, &g->audio_out})
+        if (b->p) { (void)hipFree(b->p); e->device_bytes -= (int64_t)b->bytes; }
+    delete g;
+}
+
+int generator_check_offsets(pe_engine* e, const char* who, const char* what, const int64_t* offsets, int32_t n) {
+    if (n < 0) return fail(e, PE_ERR_INVALID, "%s: %d %ss", who, n, what);
+    if (n > 0 && !offsets) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (n > 0 && offsets[0] != 0) return fail(e, PE_ERR_INVALID, "%s: %s offsets[0] must be 0, got %lld", who, what, (long long)offsets[0]);
+    for (int32_t r = 0; r < n; ++r)
+        if (offsets[r + 1] < offsets[r])
+            return fail(e, PE_ERR_INVALID, "%s: offsets decrease at %s %d (%lld after %lld)", who, what, r, (long long)offsets[r + 1], (long long)offsets[r]);
+    return PE_OK;
+}
+
+GenMixArgs generator_mix_args(const pe_generator* g) {
+    GenMixArgs a{};
+    a.bg = static_cast<const float*>(g->bg.p); a.clips = static_cast<const float*>(g->clips.p);
+    a.segs = static_cast<const GenSeg*>(g->segs.p); a.seg_prefix = static_cast<const long long*>(g->seg_prefix.p);
+    a.keep = (float)(1.0 - 0.6);                                // train_generated.py:155,185
+    return a;
+}
+
+void generator_drop_plan(pe_generator* g) {
+    g->n_files = 0; g->n_segments = 0; g->total_chunks = 0; g->total_frames = 0;
+    g->chunk_prefix.assign(1, 0); g->frame_base.assign(1, 0); g->sample_base.assign(1, 0); g->seg_first.assign(1, 0);
+}
+
+// the windows after chunks ids[0 .. n) in passes: the ids (and targets) go up, mine_gather packs the rows, which go to the
+// host or behind the trainer's set
+int generator_rows(pe_generator* g, const char* who, const int32_t* ids, const float* targets, int32_t n, float* feats_out_host, pe_trainer* trainer, int source) {
+    pe_engine* e = g->e;
+    if (n < 0) return fail(e, PE_ERR_INVALID, "%s: n=%d", who, n);
+    if (n > 0 && !ids) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    for (int32_t i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= g->total_chunks)
+            return fail(e, PE_ERR_INVALID, "%s: ids[%d] = %d is outside the plan's %lld chunks", who, i, ids[i], (long long)g->total_chunks);
+    if (n == 0) return PE_OK;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    const int T = e->prm.n_features, width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    const int64_t window_bytes = (int64_t)T * width * (int64_t)sizeof(float);
+    const int64_t per_pass = std::max<int64_t>(1, std::min<int64_t>(e->clip_pass_bytes / window_bytes, 1 << 24));
+    MineGatherArgs a{};
+    a.chunk = g->chunk; a.emit_window = emit_window(e->prm); a.hop = e->prm.hop_samples;
+    a.T = T; a.F = e->n_in; a.use_delta = e->prm.use_delta ? 1 : 0; a.row_floats = e->row_floats;
+    a.rows = static_cast<const float*>(g->rows.p);
+    a.chunk_prefix = g->d_chunk_prefix(); a.frame_base = g->d_frame_base(); a.n_rec = g->n_files;
+    int rc;
+    for (int32_t i0 = 0; i0 < n; i0 += (int32_t)per_pass) {
+        const int k = (int)std::min<int64_t>(per_pass, n - i0);
+        if ((rc = ensure(e, g->ids, (size_t)k * sizeof(int32_t)))) return rc;
+        if ((rc = ensure(e, g->batch, (size_t)k * (size_t)window_bytes))) return rc;
+        PE_HIP(e, hipMemcpy(g->ids.p, ids + i0, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice));
+        a.ids = static_cast<const int32_t*>(g->ids.p); a.n = k; a.out = static_cast<float*>(g->batch.p);
+        PE_HIP(e, launch_mine_gather(a, nullptr));
+        if (feats_out_host) {
+            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)i0 * T * width, g->batch.p, (size_t)k * (size_t)window_bytes, hipMemcpyDeviceToHost));
+        } else {
+            if ((rc = ensure(e, g->targets, (size_t)k * sizeof(float)))) return rc;
+            PE_HIP(e, hipMemcpy(g->targets.p, targets + i0, (size_t)k * sizeof(float), hipMemcpyHostToDevice));
+            PE_HIP(e, hipStreamSynchronize(nullptr));
+            const int trc = train_append_device_targets(trainer, who, source, a.out, static_cast<const float*>(g->targets.p), k);
+            if (trc) return fail(e, trc, "%s", trainer->err.c_str());
+        }
+    }
+    return PE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pe_generator_create(pe_engine* e, const float* bg_audio, const int64_t* bg_offsets, int32_t n_bg, const float* clip_audio,
+                        const int64_t* clip_offsets, int32_t n_clips, int32_t chunk_size, pe_generator** out) {
+    const char* who = "pe_generator_create";
+    if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
+    if (!out) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    *out = nullptr;
+    if (chunk_size < 1) return fail(e, PE_ERR_INVALID, "%s: chunk_size must be >= 1, got %d", who, chunk_size);
+    int rc;
+    if ((rc = generator_check_offsets(e, who, "background", bg_offsets, n_bg))) return rc;
+    if ((rc = generator_check_offsets(e, who, "clip", clip_offsets, n_clips))) return rc;
+    const int64_t bg_samples = n_bg > 0 ? bg_offsets[n_bg] : 0, clip_samples = n_clips > 0 ? clip_offsets[n_clips] : 0;
+    if ((bg_samples > 0 && !bg_audio) || (clip_samples > 0 && !clip_audio)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    pe_generator* g = new pe_generator;
+    g->e = e; g->n_bg = n_bg; g->n_clips = n_clips; g->chunk = chunk_size;
+    g->bg_offsets.assign(1, 0); g->clip_offsets.assign(1, 0);
+    if (n_bg > 0) g->bg_offsets.assign(bg_offsets, bg_offsets + n_bg + 1);
+    if (n_clips > 0) g->clip_offsets.assign(clip_offsets, clip_offsets + n_clips + 1);
+    generator_drop_plan(g);
+    hipError_t herr = hipSuccess;
+    do {
+        if ((rc = ensure(e, g->bg, (size_t)std::max<int64_t>(bg_samples, 1) * sizeof(float)))) break;
+        if ((rc = ensure(e, g->clips, (size_t)std::max<int64_t>(clip_samples, 1) * sizeof(float)))) break;
+        if (bg_samples > 0 && (herr = hipMemcpy(g->bg.p, bg_audio, (size_t)bg_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if (clip_samples > 0 && (herr = hipMemcpy(g->clips.p, clip_audio, (size_t)clip_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+    } while (false);
+    if (!rc && herr != hipSuccess) rc = fail(e, PE_ERR_HIP, "%s: %s", who, hipGetErrorString(herr));
+    if (rc) { generator_free(g); return rc; }
+    *out = g;
+    return PE_OK;
+}
+
+int pe_generator_destroy(pe_generator* g) {
+    if (g) generator_free(g);
+    return PE_OK;
+}
+
+int pe_generator_set_plan(pe_generator* g, const pe_gen_file* files, int32_t n_files, const pe_gen_segment* segments, int64_t n_segments) {
+    const char* who = "pe_generator_set_plan";
+    if (!g) return PE_ERR_INVALID;
+    pe_engine* e = g->e;
+    if (n_files < 0 || n_segments < 0 || n_segments > 0x7fffffff) return fail(e, PE_ERR_INVALID, "%s: %d files, %lld segments", who, n_files, (long long)n_segments);
+    if ((n_files > 0 && !files) || (n_segments > 0 && !segments)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    // everything is checked on the host before any device work; the resident plan stays as it is when a check fails
+    const int64_t C = g->chunk;
+    std::vector<int64_t> cp((size_t)n_files + 1, 0), fb((size_t)n_files + 1, 0), sb((size_t)n_files + 1, 0), sf((size_t)n_files + 1, 0);
+    std::vector<GenSeg> segs((size_t)n_segments);
+    std::vector<int64_t> prefix((size_t)n_segments + 1, 0);
+    int64_t next_segment = 0;
+    for (int32_t f = 0; f < n_files; ++f) {
+        const pe_gen_file& pf = files[f];
+        if (pf.background < 0 || pf.background >= g->n_bg) return fail(e, PE_ERR_INVALID, "%s: file %d names background %d of %d", who, f, pf.background, g->n_bg);
+        if (pf.first_segment != next_segment || pf.n_segments < 0 || pf.n_segments > n_segments - next_segment)
+            return fail(e, PE_ERR_INVALID, "%s: file %d takes segments %lld + %lld, expected them to start at %lld of %lld", who, f,
+                        (long long)pf.first_segment, (long long)pf.n_segments, (long long)next_segment, (long long)n_segments);
+        const int64_t bg0 = g->bg_offsets[(size_t)pf.background], len = g->bg_offsets[(size_t)pf.background + 1] - bg0;
+        const int64_t chunks = len > 0 ? (len - 1) / C : 0;                    // util.py:30-32
+        const float volume = (float)pf.audio_volume, rms_bg = (float)pf.rms;
+        if (chunks > 0 && !(pf.rms > 0.0 && pf.audio_volume == pf.audio_volume))
+            return fail(e, PE_ERR_INVALID, "%s: file %d has rms %g, audio_volume %g", who, f, pf.rms, pf.audio_volume);
+        int64_t filled = 0;
+        for (int64_t s = next_segment; s < next_segment + pf.n_segments; ++s) {
+            const pe_gen_segment& ps = segments[s];
+            if (ps.length < 1) return fail(e, PE_ERR_INVALID, "%s: segment %lld has length %lld", who, (long long)s, (long long)ps.length);
+            if (ps.clip < -1 || ps.clip >= g->n_clips) return fail(e, PE_ERR_INVALID, "%s: segment %lld names clip %d of %d", who, (long long)s, ps.clip, g->n_clips);
+            if (ps.length > chunks * C - filled)
+                return fail(e, PE_ERR_INVALID, "%s: the segments of file %d overrun its %lld chunks of %lld samples at segment %lld", who, f, (long long)chunks, (long long)C, (long long)s);
+            GenSeg d{-1, bg0 + filled, volume, rms_bg, 1.0f, 0.0f};
+            if (ps.clip >= 0) {
+                const int64_t c0 = g->clip_offsets[(size_t)ps.clip], clen = g->clip_offsets[(size_t)ps.clip + 1] - c0;
+                if (ps.first < 0 || ps.first > clen || ps.length > clen - ps.first)
+                    return fail(e, PE_ERR_INVALID, "%s: segment %lld takes samples %lld + %lld of clip %d, which has %lld", who, (long long)s,
+                                (long long)ps.first, (long long)ps.length, ps.clip, (long long)clen);
+                if (!(ps.rms > 0.0)) return fail(e, PE_ERR_INVALID, "%s: segment %lld (clip %d) has rms %g", who, (long long)s, ps.clip, ps.rms);
+                d.clip = c0 + ps.first; d.rms_clip = (float)ps.rms;
+            }
+            segs[(size_t)s] = d;
+            prefix[(size_t)s + 1] = prefix[(size_t)s] + ps.length;
+            filled += ps.length;
+        }
+        if (filled != chunks * C)
+            return fail(e, PE_ERR_INVALID, "%s: the segments of file %d hold %lld samples, its %lld chunks of %lld need %lld", who, f,
+                        (long long)filled, (long long)chunks, (long long)C, (long long)(chunks * C));
+        next_segment += pf.n_segments;
+        sf[(size_t)f + 1] = next_segment;
+        cp[(size_t)f + 1] = cp[(size_t)f] + chunks;
+        fb[(size_t)f + 1] = fb[(size_t)f] + frames_of_buffer(e->prm, chunks * C);
+        sb[(size_t)f + 1] = sb[(size_t)f] + chunks * C;
+        if (cp[(size_t)f + 1] > 0x7fffffff || fb[(size_t)f + 1] > 0x7fffffff)
+            return fail(e, PE_ERR_INVALID, "%s: more than 2^31 - 1 chunks or frames in one plan (at file %d)", who, f);
+    }
+    if (next_segment != n_segments) return fail(e, PE_ERR_INVALID, "%s: the files take %lld of %lld segments", who, (long long)next_segment, (long long)n_segments);
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    generator_drop_plan(g);                     // from here on the old plan is gone, whatever happens
+    int rc;
+    std::vector<int64_t> tab(cp);
+    tab.insert(tab.end(), fb.begin(), fb.end());
+    if ((rc = ensure(e, g->tables, tab.size() * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(e, g->segs, std::max<size_t>(segs.size(), 1) * sizeof(GenSeg)))) return rc;
+    if ((rc = ensure(e, g->seg_prefix, prefix.size() * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(e, g->rows, (size_t)std::max<int64_t>(fb[(size_t)n_files], 1) * e->row_floats * sizeof(float)))) return rc;
+    PE_HIP(e, hipMemcpy(g->tables.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!segs.empty()) PE_HIP(e, hipMemcpy(g->segs.p, segs.data(), segs.size() * sizeof(GenSeg), hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(g->seg_prefix.p, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    // passes over whole files: mix, then every frame of the pass's files once (pe_evaluate_clips' front-end launch, rows back to back)
+    std::vector<RecDesc> desc;
+    std::vector<uint32_t> rprefix;
+    for (int32_t f0 = 0; f0 < n_files;) {
+        int32_t f1 = f0 + 1;
+        while (f1 < n_files && (sb[(size_t)f1 + 1] - sb[(size_t)f0]) * (int64_t)sizeof(double) <= e->clip_pass_bytes) ++f1;
+        const int64_t n_samples = sb[(size_t)f1] - sb[(size_t)f0], n_frames = fb[(size_t)f1] - fb[(size_t)f0];
+        if (n_samples > 0) {
+            if ((rc = ensure(e, g->mixed, (size_t)n_samples * sizeof(double)))) return rc;
+            GenMixArgs a = generator_mix_args(g);
+            a.seg_lo = (int)sf[(size_t)f0]; a.seg_hi = (int)sf[(size_t)f1];
+            a.first = sb[(size_t)f0]; a.n = n_samples; a.out = static_cast<double*>(g->mixed.p);
+            PE_HIP(e, launch_gen_mix(a, nullptr));
+        }
+        if (n_frames > 0) {
+            const int n = f1 - f0;
+            desc.resize((size_t)n); rprefix.resize((size_t)n + 1);
+            for (int i = 0; i < n; ++i) {
+                desc[(size_t)i] = RecDesc{sb[(size_t)f0 + i] - sb[(size_t)f0], fb[(size_t)f0 + i]};
+                rprefix[(size_t)i] = (uint32_t)(fb[(size_t)f0 + i] - fb[(size_t)f0]);
+            }
+            rprefix[(size_t)n] = (uint32_t)n_frames;
+            const size_t db = (size_t)n * sizeof(RecDesc), pb = ((size_t)n + 1) * sizeof(uint32_t);
+            if ((rc = ensure(e, g->recs, db + pb))) return rc;
+            PE_HIP(e, hipMemcpy(g->recs.p, desc.data(), db, hipMemcpyHostToDevice));
+            PE_HIP(e, hipMemcpy(static_cast<char*>(g->recs.p) + db, rprefix.data(), pb, hipMemcpyHostToDevice));
+            const RecTable rt{static_cast<const RecDesc*>(g->recs.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(g->recs.p) + db),
+                              n, (uint32_t)n_frames, g->mixed.p, 0};
+            if ((rc = launch_rec_front_end(e, rt, static_cast<float*>(g->rows.p)))) return rc;
+        }
+        PE_HIP(e, hipStreamSynchronize(nullptr));               // the next pass reuses the mixed samples and the table
+        f0 = f1;
+    }
+    g->n_files = n_files; g->n_segments = n_segments;
+    g->total_chunks = cp[(size_t)n_files]; g->total_frames = fb[(size_t)n_files];
+    g->chunk_prefix.swap(cp); g->frame_base.swap(fb); g->sample_base.swap(sb); g->seg_first.swap(sf);
+    return PE_OK;
+}
+
+int pe_generator_audio(pe_generator* g, int32_t file, int64_t first, int64_t n, double* out_host) {
+    const char* who = "pe_generator_audio";
+    if (!g) return PE_ERR_INVALID;
+    pe_engine* e = g->e;
+    if (file < 0 || file >= g->n_files) return fail(e, PE_ERR_INVALID, "%s: file %d is outside the plan's %d files", who, file, g->n_files);
+    const int64_t len = g->sample_base[(size_t)file + 1] - g->sample_base[(size_t)file];
+    if (first < 0 || n < 0 || first > len || n > len - first)
+        return fail(e, PE_ERR_INVALID, "%s: samples %lld + %lld are outside file %d, which has %lld", who, (long long)first, (long long)n, file, (long long)len);
+    if (n == 0) return PE_OK;
+    if (!out_host) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    int rc;
+    if ((rc = ensure(e, g->audio_out, (size_t)n * sizeof(double)))) return rc;
+    GenMixArgs a = generator_mix_args(g);
+    a.seg_lo = (int)g->seg_first[(size_t)file]; a.seg_hi = (int)g->seg_first[(size_t)file + 1];
+    a.first = g->sample_base[(size_t)file] + first; a.n = n; a.out = static_cast<double*>(g->audio_out.p);
+    PE_HIP(e, launch_gen_mix(a, nullptr));
+    PE_HIP(e, hipMemcpy(out_host, g->audio_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_generator_vectorize(pe_generator* g, const int32_t* ids, int32_t n, float* feats_out_host) {
+    if (!g) return PE_ERR_INVALID;
+    if (n > 0 && !feats_out_host) return fail(g->e, PE_ERR_INVALID, "null argument to pe_generator_vectorize");
+    return generator_rows(g, "pe_generator_vectorize", ids, nullptr, n, feats_out_host, nullptr, 0);
+}
+
+int pe_generator_append(pe_generator* g, pe_trainer* trainer, int32_t source, const int32_t* ids, const float* targets, int32_t n) {
+    const char* who = "pe_generator_append";
+    if (!g) return PE_ERR_INVALID;
+    pe_engine* e = g->e;
+    if (!trainer || (n > 0 && !targets)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    if (trainer->device != e->device) return fail(e, PE_ERR_INVALID, "%s: the trainer lives on device %d, the engine on %d", who, trainer->device, e->device);
+    if (trainer->F != width || trainer->T != e->prm.n_features)
+        return fail(e, PE_ERR_INVALID, "%s: the trainer takes [%d][%d] inputs, the engine's windows are [%d][%d]", who, trainer->T, trainer->F, e->prm.n_features, width);
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
+    for (int32_t i = 0; i < n; ++i)
+        if (!(targets[i] >= 0.0f && targets[i] <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: targets[%d] = %g is outside [0, 1]", who, i, (double)targets[i]);
+    return generator_rows(g, who, ids, targets, n, nullptr, trainer, source);
 }
 
 }  // extern "C"

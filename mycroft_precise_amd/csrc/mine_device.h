@@ -37,6 +37,7 @@ struct MineGatherArgs {
     int chunk, emit_window, hop;    // emit_window: samples behind the first frame (window; + hop with speechpy)
     int T, F, use_delta, row_floats;
     float* out;                     // [n][T][F], with use_delta [n][T][2 F]: x_t, x_t - x_(t-1) (0 in the first row)
+    const int32_t* ids;             // [n] global id of every window (any order, repeats allowed), or null: first + v
 };
 
 struct MineCompactArgs {
@@ -92,7 +93,7 @@ __device__ __forceinline__ void mine_gather(const MineGatherArgs& a) {
     long long base;             // row of the window's first timestep (may lie before row0)
     long long row0;             // first row that exists
     if (a.chunk_prefix) {
-        const long long g = a.first + v;
+        const long long g = a.ids ? (long long)a.ids[v] : a.first + v;
         const int r = mine_recording_of(a.chunk_prefix, a.n_rec, g);
         const long long n = (g - a.chunk_prefix[r] + 1) * (long long)a.chunk;
         const long long emitted = n >= a.emit_window ? 1 + (n - a.emit_window) / a.hop : 0;

@@ -11,6 +11,9 @@ DESIGN.md 4.9); this module only shuffles indices and keeps the history.
     history = trainer.fit(inputs, outputs, batch_size=5000, epochs=10, validation_data=(val_in, val_out))
     trainer.save('hey-computer.npz')            # then HipRunner('hey-computer.npz') / Listener serve it
 
+``GeneratedTrainer`` is the ``fit_generator`` loop of ``precise-train-generated`` over a ``generated.Generator``; ``IncrementalTrainer``
+the policy of ``precise-train-incremental`` over a ``mining.Miner``.
+
 ``TrainerGroup`` trains several candidate networks -- other widths, dropout rates, ``loss_bias`` values, seeds -- on the same
 data at once: one resident dataset, one launch per batch for all of them, and each candidate ends with exactly the bits that a
 ``Trainer`` of its own would have given it.
@@ -397,3 +400,79 @@ class IncrementalTrainer:
             else:
                 g = end
         return None
+
+
+class GeneratedTrainer:
+    """The ``fit_generator`` call of ``precise-train-generated`` (scripts/train_generated.py:204-237) over a
+    ``generated.Generator``.
+
+    The script's sample stream runs over the background files again and again (the caller shuffles ``files`` once, as the
+    script does before its loop); ``samples_to_batches`` cuts it into consecutive batches of ``batch_size`` -- no shuffling,
+    across file borders -- and every batch is one optimizer step.  Here the stream is planned ``files_per_plan`` files at a
+    time, only when the next batch needs more samples; a plan is mixed and vectorized on the device and its samples go behind
+    the trainer's resident training set, where the steps read them by index.  Samples a plan has left over are used before
+    the next plan is drawn.  The resident set keeps every sample trained on (n_features x feature_size floats each).
+
+        gen = Generator(runner, backgrounds, positives, negatives)
+        history = GeneratedTrainer(trainer, gen).fit(epochs=100, steps_per_epoch=100, batch_size=200, rng=random.Random(1),
+                                                     validation_data=(val_in, val_out))
+
+    ``fit`` -> history dict of lists: ``loss`` (the mean of the epoch's batch losses) and, with a validation set (given, or
+    already resident), ``val_loss`` / ``val_acc`` measured on the resident validation set after the epoch.  The step counter
+    -- and with it the dropout masks -- and the position in the stream run on across epochs and calls."""
+
+    def __init__(self, trainer, generator, replay: str = 'reference', files_per_plan: int = 1):
+        self.trainer, self.generator = trainer, generator
+        self.replay, self.files_per_plan = replay, max(1, int(files_per_plan))
+        self._cursor = 0                # files planned so far: the next one is files[_cursor % len(files)]
+        self._next = self._end = 0      # resident samples [_next, _end) are drawn and not yet trained on
+
+    def _more(self, rng, files):
+        """plan, load and append the next files of the stream.  A plan may bring no sample (every chunk between the two
+        thresholds); sixteen rounds over the files without one end the wait the script would sit out forever"""
+        barren = 0
+        while True:
+            take = [files[(self._cursor + k) % len(files)] for k in range(self.files_per_plan)]
+            self._cursor += len(take)
+            plan = self.generator.plan(rng, files=take, replay=self.replay)
+            if plan.ids.size:
+                break
+            barren += len(take)
+            if barren >= 16 * len(files):
+                raise ValueError('%d rounds over the %d background files brought no training sample' % (barren // len(files), len(files)))
+        self.generator.load(plan)
+        if self._next == self._end:
+            self._next = self._end = self.trainer.n_samples()
+        self.generator.append_to(self.trainer, plan.ids, plan.targets)
+        self._end += int(plan.ids.size)
+
+    def fit(self, epochs, steps_per_epoch, batch_size, rng, validation_data=None, files=None, callback=None) -> dict:
+        t, p = self.trainer, self.trainer.params
+        batch_size = int(batch_size)
+        files = list(range(len(self.generator.backgrounds))) if files is None else [int(f) for f in files]
+        if not files or batch_size < 1:
+            raise ValueError('fit needs at least one background file and batch_size >= 1')
+        if validation_data is not None:
+            t.set_data(*validation_data, validation=True)
+        validate = t.n_samples(True) > 0
+        history = {'loss': []}
+        if validate:
+            history.update(val_loss=[], val_acc=[])
+        for epoch in range(int(epochs)):
+            losses = []
+            for _ in range(int(steps_per_epoch)):
+                while self._end - self._next < batch_size:
+                    self._more(rng, files)
+                indices = np.arange(self._next, self._next + batch_size)
+                self._next += batch_size
+                losses.append(t._t.step(indices, dropout_rate=p.dropout, seed=t.seed, step=t._step, loss_bias=p.loss_bias, lr=RMSPROP_LR,
+                                        rho=RMSPROP_RHO, eps=RMSPROP_EPS, frozen_mask=t.frozen_mask))
+                t._step += 1
+            logs = {'loss': float(np.mean(losses))}
+            if validate:
+                logs['val_loss'], logs['val_acc'] = t._evaluate_resident('validation')
+            for k, v in logs.items():
+                history[k].append(v)
+            if callback is not None:
+                callback(epoch, logs)
+        return history
