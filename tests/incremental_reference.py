@@ -31,8 +31,9 @@ def round_trip(ring) -> np.ndarray:
     return q.astype(np.float32) / np.float32(32767.0)
 
 
-def rings(audios, chunk_size: int, buffer_samples: int, carry_audio: bool = True) -> list:
-    """the float64 ring after every chunk of every recording, in global chunk order (before the int16 round trip)"""
+def rings(audios, chunk_size: int, buffer_samples: int, carry_audio: bool = True, only=None) -> list:
+    """the float64 ring after every chunk of every recording, in global chunk order (before the int16 round trip); with
+    ``only`` (a set of global chunk ids) the other entries are None: a session of many chunks keeps the rings it compares"""
     out = []
     ring = np.zeros(buffer_samples, dtype=np.float64)
     for audio in audios:
@@ -40,8 +41,20 @@ def rings(audios, chunk_size: int, buffer_samples: int, carry_audio: bool = True
             ring = np.zeros(buffer_samples, dtype=np.float64)
         for chunk in chunks(np.asarray(audio), chunk_size):
             ring = np.concatenate((ring[len(chunk):], chunk))[-buffer_samples:]
-            out.append(ring)
+            out.append(ring if only is None or len(out) in only else None)
     return out
+
+
+def locate(lengths, chunk_size: int) -> list:
+    """(recording, chunk within the recording) of every global chunk id, by the loop the script runs"""
+    return [(r, i) for r, n in enumerate(lengths) for i in range(n_chunks(int(n), chunk_size))]
+
+
+def emitted_frames(n_samples, window_samples: int, hop_samples: int) -> np.ndarray:
+    """frames a Listener cleared at the recording's start has emitted once n samples have arrived (network_runner.py:137-144:
+    vectorize_raw of everything buffered returns 1 + (len - window) // hop frames and leaves the rest; nothing below one window)"""
+    n = np.asarray(n_samples, dtype=np.int64)
+    return np.where(n >= window_samples, 1 + (n - window_samples) // hop_samples, 0)
 
 
 def policy_loop(audios, test_flags, chunk_size, buffer_samples, delay_samples, epochs, threshold, start_recording, predict, retrain,

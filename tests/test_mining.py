@@ -2,7 +2,8 @@
 
 Every comparison is equality: a scan is pe_predict's arithmetic over the frames the offline front end computes, which is what a
 float-mode ``Listener`` runs per chunk; a hit's rows are pe_vectorize_clips' launch over the saved ring; the trainer sees the
-same float32 rows in the same order.  The expected rings, chunk counts and the policy come from incremental_reference.py.
+same float32 rows in the same order.  The expected rings, chunk counts and the policy come from incremental_reference.py; the
+hit ids of a session too large for a Listener (66 compaction blocks) come from numpy's comparison over the scores it returned.
 """
 import functools
 from types import SimpleNamespace
@@ -111,6 +112,166 @@ def test_hits_are_the_strict_float64_comparison_in_order(decoder):
     miner.close()
 
 
+# ---- hits past one compaction block ------------------------------------------------------------------------------------------
+BLOCK = 4096                            # kMineThreads * kMineItems (csrc/mine_device.h): the predictions one compaction block owns
+N_BLOCKS_SESSION = 65 * BLOCK + 1       # 66 blocks, one prediction in the last: past the 64 counts mine_scan_counts sums at a time
+
+
+def mine_blocks(n):
+    return -(-n // BLOCK)
+
+
+@functools.lru_cache(maxsize=None)
+def block_session_audios():
+    """Recordings with N_BLOCKS_SESSION chunks of ONE sample (a recording of n samples has n - 1 of them), so that the hits of
+    a threshold between the scores lie in every block and on both kinds of block boundary whatever the network's last bits:
+
+      * the first window_samples - 1 chunks of every recording see the all-zero window of a cleared Listener and share one
+        score, p0; with ``weights()`` the tones of streams 50 .. 59 (mod 97: synth.stream_pcm) score below p0 and those of
+        streams 100 .. 139 above it.  Most recordings are of the first kind and between 3600 and 5599 samples long: more than
+        half of all chunks score below p0, so the median threshold lies among them, the p0 chunks at the head of every
+        recording are hits, and no 4096 consecutive ids are without one;
+      * after every third recording a filler of fewer than 4096 chunks makes the next recording start on a multiple of 4096:
+        ids 4096 b - 1 (the end of a recording) and 4096 b (p0) are judged independently, where otherwise a run of one hop of
+        equal scores straddles the boundary;
+      * an empty recording, one below an analysis window and one of a single sample at the head, three chunkless ones in
+        the middle.
+    The test asserts these properties of the reference hit set; the lengths are drawn with a fixed seed."""
+    rng = np.random.default_rng(1)
+    specs, total, k = [(50, 0), (51, 700), (52, 1)], 699, 0
+    while N_BLOCKS_SESSION - total > 5599:
+        n = int(rng.integers(3600, 5600))
+        specs.append((100 + k % 40 if k % 9 == 3 else 50 + k % 10 + 97 * (k // 10 % 3), n))
+        total += n - 1
+        k += 1
+        filler = -total % BLOCK
+        if k % 3 == 0 and filler and N_BLOCKS_SESSION - total - filler > 5599:
+            specs.append((50 + k % 10 + 97 * 3, filler + 1))
+            total += filler
+        if k == 20:
+            specs += [(53, 0), (54, 1), (55, 0)]
+    if N_BLOCKS_SESSION - total:
+        specs.append((59, N_BLOCKS_SESSION - total + 1))
+    audios = [recording(s, n) for s, n in specs]
+    for a in audios:
+        a.setflags(write=False)
+    return tuple(audios)
+
+
+def quantile_value(conf, q):
+    """the exact float64 value of one prediction near the q-quantile"""
+    return float(np.sort(conf)[int(q * conf.size)])
+
+
+@pytest.mark.parametrize('decoder', [False, True])
+def test_hits_in_order_across_compaction_blocks(decoder):
+    audios = block_session_audios()
+    lengths = [len(a) for a in audios]
+    assert 0 in lengths and any(0 < n < P.pr.window_samples for n in lengths)
+    runner = HipRunner(weights=weights())
+    conf_of = lambda s: s.astype(np.float64)
+    if decoder:
+        dec = ThresholdDecoder(P.pr.threshold_config, P.pr.threshold_center)
+        runner.engine.set_decoder(dec)
+
+        def conf_of(s):                 # decode_many is element-wise: every distinct prediction once
+            values, inverse = np.unique(s, return_inverse=True)
+            return dec.decode_many(values)[inverse]
+    miner = Miner(runner, audios, chunk_size=1)
+    n = miner.n_chunks
+    assert n == int(ref.chunk_offsets(lengths, 1)[-1]) == N_BLOCKS_SESSION
+    assert miner.chunk_offsets.tolist() == ref.chunk_offsets(lengths, 1).tolist()
+    none, n_above, scores = miner.scan(threshold=2.0, return_scores=True)
+    assert none.size == 0 and n_above == 0 and scores.size == n
+    conf = conf_of(scores)
+    assert conf.dtype == np.float64 and conf.shape == (n,)
+
+    def check(thr, first=0, capacity=None, return_scores=False):
+        want = first + np.flatnonzero(conf[first:] > thr)
+        hits, n_above, got_scores = miner.scan(first=first, threshold=thr, capacity=capacity, return_scores=return_scores)
+        assert n_above == want.size
+        assert hits.dtype == np.int32 and np.array_equal(hits, want if capacity is None else want[:capacity])
+        if return_scores:
+            assert got_scores.tobytes() == scores[first:].tobytes()
+        return want
+
+    # thresholds: every chunk, none, and the exact values of predictions, so that `>` is strict in every block at once
+    everything = check(float('-inf'))
+    assert np.array_equal(everything, np.arange(n))
+    assert check(float(conf.max())).size == 0
+    for q in (0.25, 0.9):
+        thr = quantile_value(conf, q)
+        want = check(thr)
+        print('%d chunks, %d distinct predictions, q = %.2f: %d hits above %r' % (n, np.unique(scores).size, q, want.size, thr))
+        assert 0 < want.size < n
+    thr = quantile_value(conf, 0.5)
+    want = np.flatnonzero(conf > thr)
+    total = want.size
+    # what the reference hit set must be like for the scans below to leave the first block, before the device is asked
+    hit = np.zeros(n, bool)
+    hit[want] = True
+    edges = BLOCK * np.arange(1, mine_blocks(n))
+    both, one = hit[edges - 1] & hit[edges], hit[edges - 1] ^ hit[edges]
+    print('median %r: %d hits in %d blocks; boundaries with hits on both sides %d, on one side %d; %d hits from id %d on'
+          % (thr, total, np.unique(want // BLOCK).size, both.sum(), one.sum(), np.count_nonzero(want >= 64 * BLOCK), 64 * BLOCK))
+    assert np.unique(want // BLOCK).size >= 65
+    assert both.any() and one.any()
+    assert want[-1] >= 64 * BLOCK
+    assert np.array_equal(check(thr), want)
+    # capacity: around the total, and cuts inside block 1 and inside a block behind the first 64
+    in_block = lambda b: np.count_nonzero(want // BLOCK == b)
+    late = max([b for b in range(64, mine_blocks(n)) if in_block(b) >= 2], default=None)
+    assert in_block(1) >= 2 and late is not None
+    cut_early = np.count_nonzero(want < BLOCK) + in_block(1) // 2
+    cut_late = np.count_nonzero(want < late * BLOCK) + in_block(late) // 2
+    assert want[cut_early - 1] // BLOCK == 1 == want[cut_early] // BLOCK and want[cut_late - 1] // BLOCK == late == want[cut_late] // BLOCK
+    for capacity in (1, total - 1, total, total + 5, cut_early, cut_late):
+        check(thr, capacity=capacity)
+    # first: 64 full blocks; 65 with one prediction in the last; ids that are odd against the blocks
+    for first, blocks, in_last in ((n - 64 * BLOCK, 64, BLOCK), (n - 64 * BLOCK - 1, 65, 1), (BLOCK + 1 + 123, 64, BLOCK - 123)):
+        assert mine_blocks(n - first) == blocks and n - first - (blocks - 1) * BLOCK == in_last
+        tail = check(thr, first=first, return_scores=True)
+        assert np.array_equal(tail, want[want >= first]) and tail.size > 0
+    # the same scan twice: the same bytes
+    a, b = miner.scan(threshold=thr, return_scores=True), miner.scan(threshold=thr, return_scores=True)
+    assert a[0].tobytes() == b[0].tobytes() and a[1] == b[1] and a[2].tobytes() == b[2].tobytes()
+    miner.close()
+
+
+def test_one_sample_chunks_agree_with_listener_sized_chunks(model_file):
+    """Nothing can replay 266 241 chunks through a Listener.  The prediction of a chunk depends on the samples that have arrived
+    alone, so chunk j of a recording at C = 512 -- which a Listener does verify -- is chunk 512 (j + 1) - 1 of it at C = 1."""
+    C = 512
+    audios = block_session_audios()
+    lengths = [len(a) for a in audios]
+    runner = HipRunner(weights=weights())
+    fine, coarse = Miner(runner, audios, chunk_size=1), Miner(runner, audios, chunk_size=C)
+    _, _, fine_scores = fine.scan(threshold=2.0, return_scores=True)
+    _, _, coarse_scores = coarse.scan(threshold=2.0, return_scores=True)
+    off1, offc = ref.chunk_offsets(lengths, 1), ref.chunk_offsets(lengths, C)
+    assert fine.chunk_offsets.tolist() == off1.tolist() and coarse.chunk_offsets.tolist() == offc.tolist()
+    want = listener_scores(Listener(model_file, C), audios, C)
+    assert want.size == coarse.n_chunks >= 400
+    assert coarse_scores.tobytes() == want.tobytes()
+    same_samples = np.concatenate([off1[r] + C * (np.arange(offc[r + 1] - offc[r]) + 1) - 1 for r in range(len(audios))])
+    assert same_samples.size == coarse.n_chunks and np.all(np.diff(same_samples) > 0) and same_samples[-1] < fine.n_chunks
+    assert fine_scores[same_samples].tobytes() == coarse_scores.tobytes()
+    # between those: a prediction changes only where a frame has been emitted (window and hop from params, not from the kernel)
+    bits = fine_scores.view(np.uint32)
+    steps = changes = 0
+    for r, n in enumerate(lengths):
+        mine = bits[off1[r]:off1[r + 1]]
+        emitted = ref.emitted_frames(np.arange(1, mine.size + 1), P.pr.window_samples, P.pr.hop_samples)
+        assert emitted.size == max(n - 1, 0)
+        no_frame = emitted[1:] == emitted[:-1]
+        assert np.array_equal(mine[1:][no_frame], mine[:-1][no_frame]), r
+        steps += np.count_nonzero(~no_frame)
+        changes += np.count_nonzero(mine[1:] != mine[:-1])
+    print('%d chunks at C = 1, %d at C = %d; %d frames emitted, %d changes of the prediction' % (fine.n_chunks, coarse.n_chunks, C, steps, changes))
+    assert 0 < changes <= steps
+    fine.close(); coarse.close()
+
+
 # ---- the saved rings ------------------------------------------------------------------------------------------------------
 def ring_audios():
     """three recordings shorter than the ring (24000 samples) in a row, so that a ring spans them, behind a long first one whose
@@ -141,6 +302,95 @@ def test_vectorize_equals_vectorize_clips_of_the_saved_rings(carry):
     assert miner.vectorize(ids[::-1].copy()).tobytes() == back.tobytes() == want[::-1].tobytes()
     with pytest.raises(ValueError):
         miner.vectorize([miner.n_chunks])
+    miner.close()
+
+
+def chunkless_audios():
+    """300 recordings of 0 .. 50 samples at C = 7: lengths 0, 1 and 7 have no chunk, so the prefix table mine_recording_of
+    searches holds long runs of equal entries -- at its head, at its tail and in between"""
+    rng = np.random.default_rng(17)
+    lengths = [0, 1, 7, 0, 1, 7] + rng.choice([0, 1, 7, 8, 15, 50], 289).tolist() + [7, 0, 0, 1, 0]
+    return [recording(200 + s, n) for s, n in enumerate(lengths)]
+
+
+def longest_chunkless_run(lengths, C):
+    best = run = 0
+    for n in lengths:
+        run = run + 1 if ref.n_chunks(n, C) == 0 else 0
+        best = max(best, run)
+    return best
+
+
+RING_CASES = {
+    # name: (C, B, recordings): B <= max_samples, the ring the script saves
+    'chunk_is_the_ring': (24000, 24000, lambda: [recording(60, 2 * 24000 + 1), recording(61, 3 * 24000 + 5)]),
+    'chunk_longer_than_the_ring': (30001, 24000, lambda: [recording(62, 2 * 30001 + 1), recording(63, 3 * 30001 + 5)]),
+    'one_sample_chunks': (1, 2000, lambda: [recording(64 + s, n) for s, n in enumerate([300, 0, 1, 2, 150, 400])]),
+    'ring_below_a_window': (256, 1000, lambda: ring_audios()),
+    'many_chunkless_recordings': (7, 24000, chunkless_audios),
+}
+
+
+@pytest.mark.parametrize('carry', [True, False])
+@pytest.mark.parametrize('case', sorted(RING_CASES))
+def test_saved_rings_at_other_geometries(model_file, case, carry):
+    C, B, make = RING_CASES[case]
+    audios = make()
+    lengths = [len(a) for a in audios]
+    runner = HipRunner(weights=weights())
+    miner = Miner(runner, audios, chunk_size=C, carry_audio=carry, buffer_samples=B)
+    off = ref.chunk_offsets(lengths, C)
+    n = miner.n_chunks
+    assert miner.chunk_offsets.tolist() == off.tolist() and 0 < n <= 900
+    ids = np.arange(n)
+    if case == 'many_chunkless_recordings':         # a shuffled subset, repeats included
+        ids = np.random.default_rng(23).integers(0, n, 200)
+        assert longest_chunkless_run(lengths, C) >= 5 and longest_chunkless_run(lengths[:6], C) == 6 and longest_chunkless_run(lengths[-5:], C) == 5
+        assert len(audios) == 300 and set(lengths) == {0, 1, 7, 8, 15, 50}
+        want_where = ref.locate(lengths, C)
+        rec, chunk = miner.locate(np.arange(n))
+        assert list(zip(rec.tolist(), chunk.tolist())) == want_where
+    rings = ref.rings(audios, C, B, carry, only=set(ids.tolist()))
+    assert len(rings) == n and all(len(rings[i]) == B for i in ids)
+    if case in ('chunk_is_the_ring', 'chunk_longer_than_the_ring'):     # the ring is the tail of one chunk, of any recording
+        for r, audio in enumerate(audios):
+            for i in range(int(off[r + 1] - off[r])):
+                assert np.array_equal(rings[int(off[r]) + i], audio[(i + 1) * C - B:(i + 1) * C].astype(np.float64))
+    if case == 'one_sample_chunks':
+        g = int(off[4]) + 10                        # 11 samples of recording 4 behind recordings 3 (one chunk) and 0 (299)
+        assert lengths[1:3] == [0, 1] and off[1] == off[2] == off[3]
+        head = rings[g][:B - 11]
+        assert np.array_equal(rings[g][B - 11:], audios[4][:11].astype(np.float64))
+        if carry:
+            assert head[-1] == audios[3][0] and np.array_equal(head[-300:-1], audios[0][:299].astype(np.float64)) and not np.any(head[:-300])
+        else:
+            assert not np.any(head)
+    clips = [ref.round_trip(rings[i]) for i in ids]
+    want = runner.engine.vectorize_clips(clips, P.pr.max_samples)
+    got = miner.vectorize(ids)
+    assert got.shape == want.shape == (ids.size, P.pr.n_features, P.pr.n_mfcc)
+    assert got.tobytes() == want.tobytes()
+    if case == 'ring_below_a_window':               # no frame fits into the ring: every row of every hit is padding
+        assert B < P.pr.window_samples and any(np.any(c) for c in clips)
+        assert want.tobytes() == np.zeros_like(want).tobytes()
+        T, F = P.pr.n_features, P.pr.n_mfcc
+        rng = np.random.default_rng(5)
+        X = rng.normal(0, 1, (7, T, F)).astype(np.float32)
+        y = (rng.random(7) < 0.5).astype(np.float32)
+        trainer = Trainer(weights(), ModelParams(recurrent_units=20), n_features=T)
+        some = np.array([0, n - 1, int(off[3]) + 1, 5, 5])
+        for validation in (False, True):
+            trainer.set_data(X, y, validation=validation)
+            miner.append_to(trainer, some, validation=validation)
+            feats, targets = trainer._t.get_data(validation=validation)
+            assert feats[:7].tobytes() == X.tobytes() and targets[:7].tobytes() == y.tobytes()
+            assert feats[7:].tobytes() == np.zeros((some.size, T, F), np.float32).tobytes() and np.all(targets[7:] == 0.0)
+        trainer.close()
+    else:
+        assert np.any(want)
+    if case == 'many_chunkless_recordings' and carry:       # the same table in mine_gather: under a thousand Listener updates
+        _, _, scores = miner.scan(threshold=2.0, return_scores=True)
+        assert scores.tobytes() == listener_scores(Listener(model_file, C), audios, C).tobytes()
     miner.close()
 
 
@@ -259,6 +509,42 @@ def test_set_weights_gives_the_bits_of_an_engine_created_with_them(form):
         live.set_weights(w1, model=5)
     assert live.predict(x).tobytes() == fresh.predict(x).tobytes()
     assert live.predict(x).tobytes() != old.predict(x).tobytes()
+
+
+def test_scan_of_a_k_model_engine_is_each_model_alone():
+    """pe_predict_device of a K-model engine writes [K][k] per pass; the scan keeps block `model` of it.  The reference is an
+    engine that holds that model alone (the bit equality tests/test_multi_model.py establishes for predict)."""
+    C, B = 2048, P.pr.buffer_samples
+    T, F = P.pr.n_features, P.pr.n_mfcc
+    networks = [weights(1), weights(2), weights(3)]
+    audios = recordings(C) + [recording(9, 40000)]
+    alone = []
+    for w in networks:
+        miner = HipMiner(HipEngine(P.pr, w), audios, C, B)
+        _, _, scores = miner.scan(threshold=2.0, return_scores=True)
+        conf = scores.astype(np.float64)
+        thr = quantile_value(conf, 0.5)
+        hits, n_above, _ = miner.scan(threshold=thr)
+        assert hits.tolist() == np.flatnonzero(conf > thr).tolist() and 0 < hits.size == n_above < conf.size
+        alone.append((scores, thr, hits))
+        miner.close()
+    n = alone[0][0].size
+    assert n >= 40
+    for a in range(3):
+        for b in range(a):
+            assert np.any(alone[a][0] != alone[b][0])
+    engine = HipEngine(P.pr, networks)
+    miner = HipMiner(engine, audios, C, B)
+    assert miner.n_chunks == n
+    for per in (None, 16):
+        if per:                                     # at least three passes, the last shorter than the others: k changes
+            assert n > 2 * per and n % per
+            engine.set_clip_pass_bytes(per * T * F * 4)
+        for model, (scores, thr, hits) in enumerate(alone):
+            got_hits, n_above, got_scores = miner.scan(threshold=thr, return_scores=True, model=model)
+            assert got_scores.tobytes() == scores.tobytes(), (per, model)
+            assert got_hits.tolist() == hits.tolist() and n_above == hits.size, (per, model)
+    miner.close()
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------

@@ -32,6 +32,27 @@ def test_chunk_offsets_follow_chunk_audio(C):
     # (pe_miner_layout itself is held to ref.chunk_offsets on the same lengths in tests/test_mining.py: it needs an engine)
 
 
+@pytest.mark.parametrize('C', [1, 7, 100])
+def test_locate_skips_recordings_without_a_chunk(C):
+    """Miner.locate is host arithmetic over chunk_offsets: a recording without a chunk repeats its neighbour's entry, at the
+    head, in the middle and at the tail of the table, and is never the answer"""
+    from types import SimpleNamespace
+    from mycroft_precise_amd.mining import Miner
+    lengths = [0, 1, C, 0, 3 * C + 1, 1, 0, 0, C, 1, C + 1, 2 * C, 2 * C + 1, 0, 0, 0, 0, 0, 5 * C + 1, C, 0, 1]
+    want = ref.locate(lengths, C)
+    offsets = ref.chunk_offsets(lengths, C)
+    assert len(want) == offsets[-1] == 3 + 1 + 1 + 2 + 5 and offsets[0] == offsets[4] == 0 and offsets[-1] == offsets[-4]
+    session = SimpleNamespace(chunk_offsets=offsets)
+    ids = np.arange(len(want))
+    for order in (ids, ids[::-1], np.array([4, 4, 0, 11])):
+        rec, chunk = Miner.locate(session, order)
+        assert rec.dtype == chunk.dtype == np.int64
+        assert list(zip(rec.tolist(), chunk.tolist())) == [want[i] for i in order]
+        assert all(ref.n_chunks(lengths[r], C) > i for r, i in zip(rec.tolist(), chunk.tolist()))
+    rec, chunk = Miner.locate(session, [])
+    assert rec.size == chunk.size == 0
+
+
 def test_round_trip_is_not_the_identity():
     """load_audio output is k / 32767 in float32; times 32767.0 that lands below k for many k and truncates to k - 1: a ring
     kernel that skipped the round trip would produce other samples."""
