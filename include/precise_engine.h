@@ -689,6 +689,80 @@ int pe_generator_audio(pe_generator* g, int32_t file, int64_t first, int64_t n, 
 int pe_generator_vectorize(pe_generator* g, const int32_t* ids, int32_t n, float* feats_out_host);
 int pe_generator_append(pe_generator* g, pe_trainer* trainer, int32_t source, const int32_t* ids, const float* targets, int32_t n);
 
+/* Noise augmentation: precise-add-noise (scripts/add_noise.py:56-90) makes inflation_factor noisy copies of every clip of a
+ * dataset -- a cursor walks through a pool of noise recordings, the noise under a copy is scaled to the clip's energy and mixed
+ * in at a random ratio, the result is saved as an int16 wav -- and training reads the copies back through load_audio and
+ * vectorize.  A pe_augmenter is that loop as a session over ONE engine: the clip pool and the noise pool are uploaded once; a
+ * PLAN -- the cursor and the draws, replayed by the host (augment.py) into copies and pieces -- is mixed on the device, and the
+ * reloaded copies go through pe_vectorize_clips' front-end launch to the host or straight behind a trainer's resident set.
+ * Additive to ABI 8.  The session is not thread-safe, uses the engine's device and leaves the engine's streams untouched;
+ * destroy it before its engine.
+ *
+ * Plan: copy o is a noisy version of clip `clip` at ratio `ratio`; its pieces first_piece .. + n_pieces -- the copies' ranges
+ * follow one another without gaps from piece 0 -- tile the clip's samples in order: piece = `length` (>= 1) consecutive output
+ * samples under which lie samples first .. first + length of noise recording `noise`.
+ * Arithmetic (add_noise.py:66-90, util.py:65,71), every product and sum rounded exactly once.  a[i]: the clip's float32 samples;
+ * n[i]: the noise samples under the copy, float32 widened to double (get_fresh_noise concatenates onto np.empty(0): float64);
+ * r: the ratio, a double.
+ *   S_a = sum(audio ** 2), Python's sum over a float32 array: the float32 left-to-right chain s = fl32(s + fl32(a[i] a[i])), i
+ *         ascending, from 0;  va = sqrt((double) S_a).
+ *   S_n = sum(noise_data ** 2): the float64 left-to-right chain over the copy's noise samples in piece order (the square of a
+ *         float32 is exact in double);  vn = sqrt(S_n).
+ *   adj    = (va * n[i]) / vn, two float64 roundings in that order;
+ *   out[i] = r * adj + (double) fl32(fl32(1.0 - r) * a[i]): 1.0 - r is formed in double and rounded to float32 when it meets the
+ *            float32 array; the first product and the sum are float64;
+ *   saved and reloaded: q = (int16_t)(int)(out[i] * 32767.0), training sample fl32(q) / 32767.0f.
+ * Both sums are sequential chains on the device too, one lane per chain: the scale va / vn feeds a truncation to int16, and
+ * another summation order would flip isolated samples by one step.
+ * Where the reference is undefined: vn == 0 (all-zero noise under a copy; NaN in the reference) is flagged by the device and
+ * refused by pe_augmenter_set_plan; |out[i] * 32767| >= 32768 is an out-of-range cast (undefined in C, the device gives what
+ * (int16_t)(int) gives) and is counted per copy (`overflowed`), so a caller can reject those copies; an empty clip (the reference
+ * writes an empty wav) or an empty noise recording (the reference loops forever on an all-empty pool) is refused at creation.
+ *
+ * pe_augmenter_create: float32 pools (what load_audio returns) with offsets[n + 1] each; at least one clip and one noise
+ *   recording, none of them empty: PE_ERR_INVALID naming the clip or the recording.  S_a of every clip is computed here.
+ *   A NULL engine makes a session without a device that checks plans only: pe_augmenter_set_plan runs its host checks and keeps
+ *   the plan's shape, every other entry point is PE_ERR_INVALID, and messages go to pe_last_global_error.
+ * pe_augmenter_set_plan: replaces the resident plan.  Everything is checked on the host first -- a clip, noise or piece index out
+ *   of range, a piece outside its recording, a length < 1, a copy whose piece lengths do not sum to its clip's length, piece
+ *   ranges that do not follow one another, a ratio that is NaN, more than 2^31 - 1 copies or pieces: PE_ERR_INVALID naming the
+ *   copy or piece.  Then S_n of every copy is computed; a copy with vn == 0 is PE_ERR_INVALID naming the copy.  Either way the
+ *   plan that was resident stays.
+ * pe_augmenter_volumes: clip_volume[n_clips] = va, noise_volume[n_copies] = vn, overflowed[n_copies] = samples of the copy with
+ *   |out * 32767| >= 32768 (the mix is run once over the plan to count them); each may be NULL.
+ * pe_augmenter_audio: mixed_out[len] = out, pcm_out[len] = q of copy `copy` (len: its clip's length); each may be NULL.
+ * pe_augmenter_vectorize: feats_out_host[n][n_features][width] float32, width = feature_size (n_mfcc, doubled by use_delta):
+ *   vectorize() (vectorization.py:62-84: the last max_samples samples, max_samples <= 0 = no crop) of the reloaded copy ids[i]
+ *   -- pe_vectorize_clips' rows, rounded to float32 as the trainer holds them, with use_delta the delta columns as
+ *   pe_miner_append forms them.  ids: copies in any order, repeats allowed; one outside the plan is PE_ERR_INVALID.
+ * pe_augmenter_append: the same rows behind the trainer's resident set `source`, device to device, sample i with targets[i];
+ *   trainer, device and shape checks as pe_miner_append's, every target in [0, 1] (PE_ERR_INVALID naming the index).
+ * The mix, the front end and the append run in passes of pe_set_clip_pass_bytes bytes of mixed samples over whole copies (at
+ * least one copy per pass); no result depends on the pass size, and nothing per sample stays resident but the two pools. */
+typedef struct pe_augmenter pe_augmenter;
+typedef struct pe_aug_copy {
+    int32_t clip;
+    int32_t reserved;
+    double ratio;           /* low + (high - low) u */
+    int64_t first_piece;
+    int64_t n_pieces;
+} pe_aug_copy;
+typedef struct pe_aug_piece {
+    int32_t noise;
+    int32_t reserved;
+    int64_t first;
+    int64_t length;
+} pe_aug_piece;
+int pe_augmenter_create(pe_engine* e, const float* clip_audio, const int64_t* clip_offsets, int32_t n_clips, const float* noise_audio,
+                        const int64_t* noise_offsets, int32_t n_noise, pe_augmenter** out);
+int pe_augmenter_destroy(pe_augmenter* g);
+int pe_augmenter_set_plan(pe_augmenter* g, const pe_aug_copy* copies, int32_t n_copies, const pe_aug_piece* pieces, int64_t n_pieces);
+int pe_augmenter_volumes(pe_augmenter* g, double* clip_volume, double* noise_volume, int64_t* overflowed);
+int pe_augmenter_audio(pe_augmenter* g, int32_t copy, double* mixed_out, int16_t* pcm_out);
+int pe_augmenter_vectorize(pe_augmenter* g, const int32_t* ids, int32_t n, int64_t max_samples, float* feats_out_host);
+int pe_augmenter_append(pe_augmenter* g, pe_trainer* trainer, int32_t source, const int32_t* ids, const float* targets, int32_t n,
+                        int64_t max_samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,12 +158,24 @@ EXPORTS = {
     'pe_generator_audio': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     'pe_generator_vectorize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'pe_generator_append': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    # noise augmentation (pe_augmenter)
+    'pe_augmenter_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    'pe_augmenter_destroy': (C.c_int, [C.c_void_p]),
+    'pe_augmenter_set_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
+    'pe_augmenter_volumes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pe_augmenter_audio': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'pe_augmenter_vectorize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    'pe_augmenter_append': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
 }
 
 # pe_gen_file / pe_gen_segment: the tables of pe_generator_set_plan
 GEN_FILE = np.dtype([('background', '<i4'), ('reserved', '<i4'), ('audio_volume', '<f8'), ('rms', '<f8'), ('first_segment', '<i8'),
                      ('n_segments', '<i8')])
 GEN_SEGMENT = np.dtype([('clip', '<i4'), ('target', '<i4'), ('first', '<i8'), ('length', '<i8'), ('volume', '<f8'), ('rms', '<f8')])
+
+# pe_aug_copy / pe_aug_piece: the tables of pe_augmenter_set_plan
+AUG_COPY = np.dtype([('clip', '<i4'), ('reserved', '<i4'), ('ratio', '<f8'), ('first_piece', '<i8'), ('n_pieces', '<i8')])
+AUG_PIECE = np.dtype([('noise', '<i4'), ('reserved', '<i4'), ('first', '<i8'), ('length', '<i8')])
 
 # pe_sim_metric: one (model, recording) of pe_simulate_scores / pe_simulate_clips
 SIM_METRIC = np.dtype([('n_windows', '<i8'), ('activated_chunks', '<i8'), ('activations', '<i8'), ('activation_sum', '<f8')])
@@ -263,7 +275,7 @@ class HipEngine:
         self._lib = load()
         self._h = C.c_void_p()
         self._async_keep = []
-        self._miners = weakref.WeakSet()   # HipMiner / HipGenerator sessions over this engine: closed before the engine is destroyed
+        self._miners = weakref.WeakSet()   # HipMiner / HipGenerator / HipAugmenter sessions over this engine: closed before the engine is destroyed
         self._views = 0                # host_array() buffers still referenced by numpy arrays (their memory dies with the engine)
         self._close_pending = False
         self.n_streams = int(n_streams)
@@ -1132,6 +1144,114 @@ class HipGenerator:
         """pe_generator_destroy; the engine calls it for every session it still has when it is closed itself"""
         if getattr(self, '_h', None) and self._h.value:
             self._lib.pe_generator_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipAugmenter:
+    """
+    One C-ABI augmenting session (pe_augmenter) over one ``HipEngine``: the clip and noise pools resident on the device, one plan
+    at a time mixed and vectorized there; ``augment.NoiseAugmenter`` is the reference-shaped class and the planner.  The session
+    keeps its engine alive; close it before the engine.  ``engine=None`` makes a session without a device that only checks the
+    plans handed to ``set_plan``.
+    """
+
+    def __init__(self, engine, clips, noises):
+        self._lib = load()
+        self._h = C.c_void_p()
+        self.engine = engine
+        cl, cl_off = HipGenerator._pool(clips)
+        no, no_off = HipGenerator._pool(noises)
+        self.clip_lengths = np.diff(cl_off)
+        self.n_copies = 0
+        self._copy_clip = np.zeros(0, dtype=np.int64)
+        self._check(self._lib.pe_augmenter_create(engine._h if engine is not None else None, cl.ctypes.data if cl.size else None,
+                                                  cl_off.ctypes.data, cl_off.size - 1, no.ctypes.data if no.size else None,
+                                                  no_off.ctypes.data, no_off.size - 1, C.byref(self._h)))
+        if engine is not None:
+            engine._miners.add(self)
+
+    def _check(self, rc):
+        if self.engine is not None:
+            self.engine._check(rc)
+        elif rc != PE_OK:
+            HipEngine._raise(rc, self._lib.pe_last_global_error().decode())
+
+    def set_plan(self, copies, pieces):
+        """``copies`` / ``pieces``: structured arrays of ``AUG_COPY`` / ``AUG_PIECE``; computes every copy's noise volume"""
+        copies = np.ascontiguousarray(copies, dtype=AUG_COPY)
+        pieces = np.ascontiguousarray(pieces, dtype=AUG_PIECE)
+        self._check(self._lib.pe_augmenter_set_plan(self._handle(), copies.ctypes.data if copies.size else None, copies.size,
+                                                    pieces.ctypes.data if pieces.size else None, pieces.size))
+        self.n_copies = int(copies.size)
+        self._copy_clip = copies['clip'].astype(np.int64)
+
+    def volumes(self, overflowed=True):
+        """-> (clip volume float64 [n_clips], noise volume float64 [n_copies], overflowed int64 [n_copies] or None)"""
+        va = np.empty(self.clip_lengths.size, dtype=np.float64)
+        vn = np.empty(self.n_copies, dtype=np.float64)
+        over = np.zeros(self.n_copies, dtype=np.int64) if overflowed else None
+        self._check(self._lib.pe_augmenter_volumes(self._handle(), va.ctypes.data, vn.ctypes.data if vn.size else None,
+                                                   over.ctypes.data if overflowed and over.size else None))
+        return va, vn, over
+
+    def _copy(self, copy):
+        copy = int(copy)
+        if not 0 <= copy < self.n_copies:
+            raise ValueError('copy %d is outside the plan of %d copies' % (copy, self.n_copies))
+        return copy, int(self.clip_lengths[self._copy_clip[copy]])
+
+    def audio(self, copy: int) -> np.ndarray:
+        """float64: the mix of copy ``copy``, what ``noised_audio`` returns"""
+        copy, n = self._copy(copy)
+        out = np.empty(n, dtype=np.float64)
+        self._check(self._lib.pe_augmenter_audio(self._handle(), copy, out.ctypes.data, None))
+        return out
+
+    def pcm(self, copy: int) -> np.ndarray:
+        """int16: what ``save_audio`` writes for copy ``copy``"""
+        copy, n = self._copy(copy)
+        out = np.empty(n, dtype=np.int16)
+        self._check(self._lib.pe_augmenter_audio(self._handle(), copy, None, out.ctypes.data))
+        return out
+
+    def _ids(self, ids):
+        ids = np.arange(self.n_copies) if ids is None else ids
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.n_copies):
+            raise ValueError('copy ids must be in 0..%d' % (self.n_copies - 1))
+        return ids.astype(np.int32)
+
+    def vectorize(self, ids=None, max_samples: int = 0) -> np.ndarray:
+        ids = self._ids(ids)
+        out = np.empty((ids.size, self.engine.n_features, self.engine.feature_size), dtype=np.float32)
+        if ids.size:
+            self._check(self._lib.pe_augmenter_vectorize(self._handle(), ids.ctypes.data, ids.size, int(max_samples), out.ctypes.data))
+        return out
+
+    def append(self, trainer: HipTrainer, ids, targets, validation=False, max_samples: int = 0):
+        ids = self._ids(ids)
+        targets = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
+        if targets.size != ids.size:
+            raise ValueError('%d targets for %d ids' % (targets.size, ids.size))
+        if ids.size:
+            self._check(self._lib.pe_augmenter_append(self._handle(), trainer._h, HipTrainer._source(validation), ids.ctypes.data,
+                                                      targets.ctypes.data, ids.size, int(max_samples)))
+
+    def _handle(self):
+        if not self._h.value:
+            raise ValueError('the augmenting session is closed (close(), or its engine was closed)')
+        return self._h
+
+    def close(self):
+        """pe_augmenter_destroy; the engine calls it for every session it still has when it is closed itself"""
+        if getattr(self, '_h', None) and self._h.value:
+            self._lib.pe_augmenter_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -9,6 +9,7 @@
 #include "gru_train_device.h"
 #include "mine_device.h"
 #include "generate_device.h"
+#include "augment_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -3613,6 +3614,369 @@ int pe_generator_append(pe_generator* g, pe_trainer* trainer, int32_t source, co
     for (int32_t i = 0; i < n; ++i)
         if (!(targets[i] >= 0.0f && targets[i] <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: targets[%d] = %g is outside [0, 1]", who, i, (double)targets[i]);
     return generator_rows(g, who, ids, targets, n, nullptr, trainer, source);
+}
+
+}  // extern "C"
+
+// ---- noise augmentation (pe_augmenter; kernels: augment_device.h) ---------------------------------------------
+struct pe_augmenter {
+    pe_engine* e = nullptr;                             // null: a session that checks plans only
+    int n_clips = 0, n_noise = 0;
+    std::vector<int64_t> clip_offsets, noise_offsets;   // [n_clips + 1], [n_noise + 1]
+    std::vector<double> clip_volume;                    // [n_clips] va = sqrt((double) S_a)
+    // the plan, as given, and vn = sqrt(S_n) of every copy
+    std::vector<pe_aug_copy> copies;
+    std::vector<pe_aug_piece> pieces;
+    std::vector<double> noise_volume;
+    // resident: the two pools as given
+    DeviceBuf clips, noise;
+    // grown on demand: the chains' tables and sums; of a pass: its copies, pieces and piece prefix, the reloaded samples, the clip
+    // table, the front end's rows, the trainer's rows and targets; pe_augmenter_audio's samples; the plan's overflow counts
+    DeviceBuf tables, sums, slots, pass_pieces, reloaded, desc, rows, packed, targets, mixed, pcm, overflow;
+    int64_t copy_length(int32_t o) const { const int32_t c = copies[(size_t)o].clip; return clip_offsets[(size_t)c + 1] - clip_offsets[(size_t)c]; }
+};
+
+namespace {
+
+void augmenter_free(pe_augmenter* g) {
+    if (pe_engine* e = g->e) {
+        (void)hipSetDevice(e->device);
+        (void)hipDeviceSynchronize();
+        for (DeviceBuf* b : {&g->clips, &g->noise, &g->tables, &g->sums, &g->slots, &g->pass_pieces, &g->reloaded, &g->desc, &g->rows, &g->packed,
+                             &g->targets, &g->mixed, &g->pcm, &g->overflow})
+            if (b->p) { (void)hipFree(b->p); e->device_bytes -= (int64_t)b->bytes; }
+    }
+    delete g;
+}
+
+// offsets[n + 1] of a pool whose entries must all hold samples
+int augmenter_check_pool(pe_engine* e, const char* who, const char* what, const int64_t* offsets, int32_t n) {
+    if (n < 1) return fail(e, PE_ERR_INVALID, "%s: %d %ss (at least one is needed)", who, n, what);
+    if (!offsets) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (offsets[0] != 0) return fail(e, PE_ERR_INVALID, "%s: %s offsets[0] must be 0, got %lld", who, what, (long long)offsets[0]);
+    for (int32_t r = 0; r < n; ++r) {
+        if (offsets[r + 1] < offsets[r])
+            return fail(e, PE_ERR_INVALID, "%s: offsets decrease at %s %d (%lld after %lld)", who, what, r, (long long)offsets[r + 1], (long long)offsets[r]);
+        if (offsets[r + 1] == offsets[r]) return fail(e, PE_ERR_INVALID, "%s: %s %d is empty", who, what, r);
+    }
+    return PE_OK;
+}
+
+// Copies ids[0 .. k) as one pass: their slots, pieces and piece prefix go up, aug_mix writes what the caller asks for.
+// slot_begin[k + 1]: where every copy starts among the pass's samples.
+int augmenter_mix(pe_augmenter* g, const int32_t* ids, int k, std::vector<int64_t>& slot_begin, float* reloaded, double* mixed, int16_t* pcm,
+                  unsigned long long* overflowed) {
+    pe_engine* e = g->e;
+    std::vector<AugSlot> slots((size_t)k);
+    std::vector<AugPiece> pieces;
+    std::vector<int64_t> prefix(1, 0);
+    slot_begin.assign((size_t)k + 1, 0);
+    for (int i = 0; i < k; ++i) {
+        const pe_aug_copy& c = g->copies[(size_t)ids[i]];
+        slots[(size_t)i] = AugSlot{g->clip_volume[(size_t)c.clip], g->noise_volume[(size_t)ids[i]], c.ratio, (float)(1.0 - c.ratio), ids[i]};
+        int64_t at = g->clip_offsets[(size_t)c.clip];
+        for (int64_t q = c.first_piece; q < c.first_piece + c.n_pieces; ++q) {
+            const pe_aug_piece& p = g->pieces[(size_t)q];
+            pieces.push_back(AugPiece{g->noise_offsets[(size_t)p.noise] + p.first, at, i, 0});
+            prefix.push_back(prefix.back() + p.length);
+            at += p.length;
+        }
+        slot_begin[(size_t)i + 1] = prefix.back();
+    }
+    if (pieces.size() > 0x7fffffffu) return fail(e, PE_ERR_INVALID, "pe_augmenter: a pass of %d copies holds more than 2^31 - 1 pieces", k);
+    int rc;
+    const size_t pb = pieces.size() * sizeof(AugPiece), xb = prefix.size() * sizeof(int64_t);
+    if ((rc = ensure(e, g->slots, slots.size() * sizeof(AugSlot)))) return rc;
+    if ((rc = ensure(e, g->pass_pieces, pb + xb))) return rc;
+    PE_HIP(e, hipMemcpy(g->slots.p, slots.data(), slots.size() * sizeof(AugSlot), hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(g->pass_pieces.p, pieces.data(), pb, hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(static_cast<char*>(g->pass_pieces.p) + pb, prefix.data(), xb, hipMemcpyHostToDevice));
+    AugMixArgs a{};
+    a.clips = static_cast<const float*>(g->clips.p); a.noise = static_cast<const float*>(g->noise.p);
+    a.slots = static_cast<const AugSlot*>(g->slots.p); a.pieces = static_cast<const AugPiece*>(g->pass_pieces.p);
+    a.prefix = reinterpret_cast<const long long*>(static_cast<const char*>(g->pass_pieces.p) + pb);
+    a.n_pieces = (int)pieces.size(); a.n = prefix.back();
+    a.reloaded = reloaded; a.mixed = mixed; a.pcm = pcm; a.overflowed = overflowed;
+    PE_HIP(e, launch_aug_mix(a, nullptr));
+    return PE_OK;
+}
+
+// the copies of the pass that starts at ids[i0]: at least one, then as many as stay within the byte target (and the bounds
+// that keep a pass's tables and row buffers small)
+int32_t augmenter_pass_end(const pe_augmenter* g, const int32_t* ids, int32_t i0, int32_t n) {
+    const int64_t T = g->e->prm.n_features;
+    int64_t samples = g->copy_length(ids[i0]), pieces = g->copies[(size_t)ids[i0]].n_pieces;
+    int32_t i1 = i0 + 1;
+    while (i1 < n) {
+        const int64_t len = g->copy_length(ids[i1]), np = g->copies[(size_t)ids[i1]].n_pieces;
+        if ((samples + len) * (int64_t)sizeof(float) > g->e->clip_pass_bytes || (int64_t)(i1 + 1 - i0) * T > kClipPassRows || pieces + np > (1ll << 26)) break;
+        samples += len; pieces += np; ++i1;
+    }
+    return i1;
+}
+
+int augmenter_check_ids(pe_augmenter* g, const char* who, const int32_t* ids, int32_t n) {
+    pe_engine* e = g->e;
+    if (!e) return fail(e, PE_ERR_INVALID, "%s: the session was created without an engine: it checks plans only", who);
+    if (n < 0) return fail(e, PE_ERR_INVALID, "%s: n=%d", who, n);
+    if (n > 0 && !ids) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    for (int32_t i = 0; i < n; ++i)
+        if (ids[i] < 0 || (size_t)ids[i] >= g->copies.size())
+            return fail(e, PE_ERR_INVALID, "%s: ids[%d] = %d is outside the plan's %zu copies", who, i, ids[i], g->copies.size());
+    return PE_OK;
+}
+
+// vectorize() of the reloaded copies ids[0 .. n) in passes: aug_mix writes the float32 clips, the clip front end their windows,
+// mine_gather packs them for the trainer; the rows go to the host or behind the trainer's set
+int augmenter_rows(pe_augmenter* g, const char* who, const int32_t* ids, const float* targets, int32_t n, int64_t max_samples, float* feats_out_host,
+                   pe_trainer* trainer, int source) {
+    pe_engine* e = g->e;
+    int rc = augmenter_check_ids(g, who, ids, n);
+    if (rc) return rc;
+    if (n == 0) return PE_OK;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    const int T = e->prm.n_features, width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    std::vector<int64_t> begin;
+    std::vector<ClipDesc> desc;
+    std::vector<uint32_t> prefix;
+    for (int32_t i0 = 0; i0 < n;) {
+        const int32_t i1 = augmenter_pass_end(g, ids, i0, n);
+        const int k = i1 - i0;
+        int64_t n_samples = 0;
+        for (int32_t i = i0; i < i1; ++i) n_samples += g->copy_length(ids[i]);
+        if ((rc = ensure(e, g->reloaded, (size_t)n_samples * sizeof(float)))) return rc;
+        if ((rc = augmenter_mix(g, ids + i0, k, begin, static_cast<float*>(g->reloaded.p), nullptr, nullptr, nullptr))) return rc;
+        desc.resize((size_t)k); prefix.resize((size_t)k + 1);
+        uint32_t tasks = 0;
+        for (int i = 0; i < k; ++i) {
+            const int64_t len = begin[(size_t)i + 1] - begin[(size_t)i];
+            const int64_t cut = max_samples > 0 && len > max_samples ? max_samples : len;          // vectorize: audio[-max_samples:]
+            const int64_t frames = frames_of_buffer(e->prm, cut);
+            const int64_t kept = frames < T ? frames : T;                                          // ... feats[-n_features:]
+            desc[(size_t)i] = ClipDesc{begin[(size_t)i + 1] - cut, (int)(frames - kept), (int)kept, (int)(T - kept), 0};
+            prefix[(size_t)i] = tasks;
+            tasks += (uint32_t)kept;
+        }
+        prefix[(size_t)k] = tasks;
+        const size_t db = (size_t)k * sizeof(ClipDesc), pb = ((size_t)k + 1) * sizeof(uint32_t);
+        if ((rc = ensure(e, g->desc, db + pb))) return rc;
+        if ((rc = ensure(e, g->rows, (size_t)k * T * e->row_floats * sizeof(float)))) return rc;
+        if ((rc = ensure(e, g->packed, (size_t)k * T * width * sizeof(float)))) return rc;
+        PE_HIP(e, hipMemcpy(g->desc.p, desc.data(), db, hipMemcpyHostToDevice));
+        PE_HIP(e, hipMemcpy(static_cast<char*>(g->desc.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
+        const ClipTable ct{static_cast<const ClipDesc*>(g->desc.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(g->desc.p) + db),
+                           k, tasks, g->reloaded.p, 1};
+        if ((rc = launch_clip_front_end(e, ct, nullptr, static_cast<float*>(g->rows.p), nullptr))) return rc;
+        MineGatherArgs a{};
+        a.T = T; a.F = e->n_in; a.use_delta = e->prm.use_delta ? 1 : 0; a.row_floats = e->row_floats;
+        a.rows = static_cast<const float*>(g->rows.p); a.n = k; a.out = static_cast<float*>(g->packed.p);
+        PE_HIP(e, launch_mine_gather(a, nullptr));
+        if (feats_out_host) {
+            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)i0 * T * width, g->packed.p, (size_t)k * T * width * sizeof(float), hipMemcpyDeviceToHost));
+        } else {
+            if ((rc = ensure(e, g->targets, (size_t)k * sizeof(float)))) return rc;
+            PE_HIP(e, hipMemcpy(g->targets.p, targets + i0, (size_t)k * sizeof(float), hipMemcpyHostToDevice));
+            PE_HIP(e, hipStreamSynchronize(nullptr));
+            const int trc = train_append_device_targets(trainer, who, source, a.out, static_cast<const float*>(g->targets.p), k);
+            if (trc) return fail(e, trc, "%s", trainer->err.c_str());
+        }
+        PE_HIP(e, hipStreamSynchronize(nullptr));               // the next pass reuses the samples and the tables
+        i0 = i1;
+    }
+    return PE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pe_augmenter_create(pe_engine* e, const float* clip_audio, const int64_t* clip_offsets, int32_t n_clips, const float* noise_audio,
+                        const int64_t* noise_offsets, int32_t n_noise, pe_augmenter** out) {
+    const char* who = "pe_augmenter_create";
+    if (!out) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    *out = nullptr;
+    int rc;
+    if ((rc = augmenter_check_pool(e, who, "clip", clip_offsets, n_clips))) return rc;
+    if ((rc = augmenter_check_pool(e, who, "noise recording", noise_offsets, n_noise))) return rc;
+    if (e && (!clip_audio || !noise_audio)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    pe_augmenter* g = new pe_augmenter;
+    g->e = e; g->n_clips = n_clips; g->n_noise = n_noise;
+    g->clip_offsets.assign(clip_offsets, clip_offsets + n_clips + 1);
+    g->noise_offsets.assign(noise_offsets, noise_offsets + n_noise + 1);
+    g->clip_volume.assign((size_t)n_clips, 0.0);
+    if (!e) { *out = g; return PE_OK; }
+    const int64_t clip_samples = clip_offsets[n_clips], noise_samples = noise_offsets[n_noise];
+    std::vector<float> sums((size_t)n_clips);
+    hipError_t herr = hipSuccess;
+    do {
+        if ((herr = hipSetDevice(e->device)) != hipSuccess) break;
+        if ((rc = drain_async(e))) break;
+        if ((rc = ensure(e, g->clips, (size_t)clip_samples * sizeof(float)))) break;
+        if ((rc = ensure(e, g->noise, (size_t)noise_samples * sizeof(float)))) break;
+        if ((rc = ensure(e, g->tables, ((size_t)n_clips + 1) * sizeof(int64_t)))) break;
+        if ((rc = ensure(e, g->sums, (size_t)n_clips * sizeof(float)))) break;
+        if ((herr = hipMemcpy(g->clips.p, clip_audio, (size_t)clip_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((herr = hipMemcpy(g->noise.p, noise_audio, (size_t)noise_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((herr = hipMemcpy(g->tables.p, clip_offsets, ((size_t)n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
+        AugEnergyArgs a{};                                      // S_a of every clip: it does not depend on the plan
+        a.pool = static_cast<const float*>(g->clips.p); a.offsets = static_cast<const long long*>(g->tables.p);
+        a.n = n_clips; a.sum_f32 = static_cast<float*>(g->sums.p);
+        if ((herr = launch_aug_energy_clips(a, nullptr)) != hipSuccess) break;
+        herr = hipMemcpy(sums.data(), g->sums.p, (size_t)n_clips * sizeof(float), hipMemcpyDeviceToHost);
+    } while (false);
+    if (!rc && herr != hipSuccess) rc = fail(e, PE_ERR_HIP, "%s: %s", who, hipGetErrorString(herr));
+    if (rc) { augmenter_free(g); return rc; }
+    for (int32_t c = 0; c < n_clips; ++c) g->clip_volume[(size_t)c] = std::sqrt((double)sums[(size_t)c]);     // sqrt(sum(audio ** 2))
+    *out = g;
+    return PE_OK;
+}
+
+int pe_augmenter_destroy(pe_augmenter* g) {
+    if (g) augmenter_free(g);
+    return PE_OK;
+}
+
+int pe_augmenter_set_plan(pe_augmenter* g, const pe_aug_copy* copies, int32_t n_copies, const pe_aug_piece* pieces, int64_t n_pieces) {
+    const char* who = "pe_augmenter_set_plan";
+    if (!g) return PE_ERR_INVALID;
+    pe_engine* e = g->e;
+    if (n_copies < 0 || n_pieces < 0) return fail(e, PE_ERR_INVALID, "%s: %d copies, %lld pieces", who, n_copies, (long long)n_pieces);
+    if (n_pieces > 0x7fffffff) return fail(e, PE_ERR_INVALID, "%s: %lld pieces are more than 2^31 - 1", who, (long long)n_pieces);
+    if ((n_copies > 0 && !copies) || (n_pieces > 0 && !pieces)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    // everything is checked on the host before any device work; the resident plan stays as it is when a check fails
+    std::vector<int64_t> tab((size_t)n_copies + 1 + (size_t)n_pieces + 1 + (size_t)n_pieces, 0);     // first piece | piece prefix | piece source
+    int64_t* const fp = tab.data(); int64_t* const pp = fp + n_copies + 1; int64_t* const ps = pp + n_pieces + 1;
+    int64_t next_piece = 0;
+    for (int32_t o = 0; o < n_copies; ++o) {
+        const pe_aug_copy& c = copies[o];
+        if (c.clip < 0 || c.clip >= g->n_clips) return fail(e, PE_ERR_INVALID, "%s: copy %d names clip %d of %d", who, o, c.clip, g->n_clips);
+        if (c.ratio != c.ratio) return fail(e, PE_ERR_INVALID, "%s: copy %d has ratio NaN", who, o);
+        if (c.first_piece != next_piece || c.n_pieces < 0 || c.n_pieces > n_pieces - next_piece)
+            return fail(e, PE_ERR_INVALID, "%s: copy %d takes pieces %lld + %lld, expected them to start at %lld of %lld", who, o,
+                        (long long)c.first_piece, (long long)c.n_pieces, (long long)next_piece, (long long)n_pieces);
+        const int64_t len = g->clip_offsets[(size_t)c.clip + 1] - g->clip_offsets[(size_t)c.clip];
+        int64_t filled = 0;
+        for (int64_t q = next_piece; q < next_piece + c.n_pieces; ++q) {
+            const pe_aug_piece& p = pieces[q];
+            if (p.noise < 0 || p.noise >= g->n_noise) return fail(e, PE_ERR_INVALID, "%s: piece %lld names noise recording %d of %d", who, (long long)q, p.noise, g->n_noise);
+            if (p.length < 1) return fail(e, PE_ERR_INVALID, "%s: piece %lld has length %lld", who, (long long)q, (long long)p.length);
+            const int64_t n0 = g->noise_offsets[(size_t)p.noise], nlen = g->noise_offsets[(size_t)p.noise + 1] - n0;
+            if (p.first < 0 || p.first > nlen || p.length > nlen - p.first)
+                return fail(e, PE_ERR_INVALID, "%s: piece %lld takes samples %lld + %lld of noise recording %d, which has %lld", who, (long long)q,
+                            (long long)p.first, (long long)p.length, p.noise, (long long)nlen);
+            if (p.length > len - filled)
+                return fail(e, PE_ERR_INVALID, "%s: the pieces of copy %d overrun the %lld samples of its clip %d at piece %lld", who, o, (long long)len, c.clip, (long long)q);
+            ps[q] = n0 + p.first;
+            pp[q + 1] = pp[q] + p.length;
+            filled += p.length;
+        }
+        if (filled != len)
+            return fail(e, PE_ERR_INVALID, "%s: the pieces of copy %d hold %lld samples, its clip %d has %lld", who, o, (long long)filled, c.clip, (long long)len);
+        next_piece += c.n_pieces;
+        fp[o + 1] = next_piece;
+    }
+    if (next_piece != n_pieces) return fail(e, PE_ERR_INVALID, "%s: the copies take %lld of %lld pieces", who, (long long)next_piece, (long long)n_pieces);
+    std::vector<double> vn((size_t)n_copies, 0.0);
+    if (e && n_copies > 0) {
+        // S_n of every copy, and the flags of those whose noise is all zero
+        PE_HIP(e, hipSetDevice(e->device));
+        PE_DRAIN(e);
+        int rc;
+        const size_t sb = (size_t)n_copies * sizeof(double), zb = (size_t)n_copies * sizeof(int32_t);
+        if ((rc = ensure(e, g->tables, tab.size() * sizeof(int64_t)))) return rc;
+        if ((rc = ensure(e, g->sums, sb + zb))) return rc;
+        PE_HIP(e, hipMemcpy(g->tables.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        AugEnergyArgs a{};
+        a.pool = static_cast<const float*>(g->noise.p);
+        a.first_piece = static_cast<const long long*>(g->tables.p); a.piece_prefix = a.first_piece + n_copies + 1; a.piece_src = a.piece_prefix + n_pieces + 1;
+        a.n = n_copies; a.sum_f64 = static_cast<double*>(g->sums.p);
+        a.zero = reinterpret_cast<int32_t*>(static_cast<char*>(g->sums.p) + sb);
+        PE_HIP(e, launch_aug_energy_copies(a, nullptr));
+        std::vector<int32_t> zero((size_t)n_copies);
+        PE_HIP(e, hipMemcpy(vn.data(), a.sum_f64, sb, hipMemcpyDeviceToHost));
+        PE_HIP(e, hipMemcpy(zero.data(), a.zero, zb, hipMemcpyDeviceToHost));
+        for (int32_t o = 0; o < n_copies; ++o) {
+            if (zero[(size_t)o])
+                return fail(e, PE_ERR_INVALID, "%s: the noise under copy %d is all zero: its volume is 0 and the reference divides by it", who, o);
+            vn[(size_t)o] = std::sqrt(vn[(size_t)o]);           // sqrt(sum(noise_data ** 2))
+        }
+    }
+    g->copies.assign(copies, copies + n_copies);
+    g->pieces.assign(pieces, pieces + n_pieces);
+    g->noise_volume.swap(vn);
+    return PE_OK;
+}
+
+int pe_augmenter_volumes(pe_augmenter* g, double* clip_volume, double* noise_volume, int64_t* overflowed) {
+    const char* who = "pe_augmenter_volumes";
+    if (!g) return PE_ERR_INVALID;
+    pe_engine* e = g->e;
+    if (!e) return fail(e, PE_ERR_INVALID, "%s: the session was created without an engine: it checks plans only", who);
+    if (clip_volume) std::copy(g->clip_volume.begin(), g->clip_volume.end(), clip_volume);
+    if (noise_volume) std::copy(g->noise_volume.begin(), g->noise_volume.end(), noise_volume);
+    const int32_t n = (int32_t)g->copies.size();
+    if (!overflowed || n == 0) return PE_OK;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    int rc;
+    if ((rc = ensure(e, g->overflow, (size_t)n * sizeof(unsigned long long)))) return rc;
+    PE_HIP(e, hipMemsetAsync(g->overflow.p, 0, (size_t)n * sizeof(unsigned long long), nullptr));
+    std::vector<int32_t> ids((size_t)n);
+    for (int32_t o = 0; o < n; ++o) ids[(size_t)o] = o;
+    std::vector<int64_t> begin;
+    for (int32_t i0 = 0; i0 < n;) {             // the mix of every copy, nothing written but the counts
+        const int32_t i1 = augmenter_pass_end(g, ids.data(), i0, n);
+        if ((rc = augmenter_mix(g, ids.data() + i0, i1 - i0, begin, nullptr, nullptr, nullptr, static_cast<unsigned long long*>(g->overflow.p)))) return rc;
+        PE_HIP(e, hipStreamSynchronize(nullptr));
+        i0 = i1;
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied out as they are");
+    PE_HIP(e, hipMemcpy(overflowed, g->overflow.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_augmenter_audio(pe_augmenter* g, int32_t copy, double* mixed_out, int16_t* pcm_out) {
+    const char* who = "pe_augmenter_audio";
+    if (!g) return PE_ERR_INVALID;
+    pe_engine* e = g->e;
+    int rc = augmenter_check_ids(g, who, &copy, 1);
+    if (rc) return rc;
+    if (!mixed_out && !pcm_out) return PE_OK;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    const int64_t len = g->copy_length(copy);
+    if (mixed_out && (rc = ensure(e, g->mixed, (size_t)len * sizeof(double)))) return rc;
+    if (pcm_out && (rc = ensure(e, g->pcm, (size_t)len * sizeof(int16_t)))) return rc;
+    std::vector<int64_t> begin;
+    if ((rc = augmenter_mix(g, &copy, 1, begin, nullptr, mixed_out ? static_cast<double*>(g->mixed.p) : nullptr,
+                            pcm_out ? static_cast<int16_t*>(g->pcm.p) : nullptr, nullptr))) return rc;
+    if (mixed_out) PE_HIP(e, hipMemcpy(mixed_out, g->mixed.p, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    if (pcm_out) PE_HIP(e, hipMemcpy(pcm_out, g->pcm.p, (size_t)len * sizeof(int16_t), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_augmenter_vectorize(pe_augmenter* g, const int32_t* ids, int32_t n, int64_t max_samples, float* feats_out_host) {
+    if (!g) return PE_ERR_INVALID;
+    if (n > 0 && !feats_out_host) return fail(g->e, PE_ERR_INVALID, "null argument to pe_augmenter_vectorize");
+    return augmenter_rows(g, "pe_augmenter_vectorize", ids, nullptr, n, max_samples, feats_out_host, nullptr, 0);
+}
+
+int pe_augmenter_append(pe_augmenter* g, pe_trainer* trainer, int32_t source, const int32_t* ids, const float* targets, int32_t n,
+                        int64_t max_samples) {
+    const char* who = "pe_augmenter_append";
+    if (!g) return PE_ERR_INVALID;
+    pe_engine* e = g->e;
+    if (!e) return fail(e, PE_ERR_INVALID, "%s: the session was created without an engine: it checks plans only", who);
+    if (!trainer || (n > 0 && !targets)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    if (trainer->device != e->device) return fail(e, PE_ERR_INVALID, "%s: the trainer lives on device %d, the engine on %d", who, trainer->device, e->device);
+    if (trainer->F != width || trainer->T != e->prm.n_features)
+        return fail(e, PE_ERR_INVALID, "%s: the trainer takes [%d][%d] inputs, the engine's windows are [%d][%d]", who, trainer->T, trainer->F, e->prm.n_features, width);
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
+    for (int32_t i = 0; i < n; ++i)
+        if (!(targets[i] >= 0.0f && targets[i] <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: targets[%d] = %g is outside [0, 1]", who, i, (double)targets[i]);
+    return augmenter_rows(g, who, ids, targets, n, max_samples, nullptr, trainer, source);
 }
 
 }  // extern "C"

@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Compact per-kernel resource table (VGPRs, AGPRs, SGPRs, spills, LDS, occupancy) of kernels.hip for gfx950.
-    python tools/kernel_resources.py [filter-regex] [extra hipcc flags...]"""
+    python tools/kernel_resources.py [filter-regex] [extra hipcc flags...]
+    python tools/kernel_resources.py --source augment.hip [filter-regex] ...      another source of csrc/"""
 import re, subprocess, sys, os
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pat = sys.argv[1] if len(sys.argv) > 1 else '.'
-flags = sys.argv[2:]
+argv = sys.argv[1:]
+source = 'kernels.hip'
+if argv[:1] == ['--source']:
+    source, argv = argv[1], argv[2:]
+pat = argv[0] if argv else '.'
+flags = argv[1:]
 cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c',
-       os.path.join(REPO, 'mycroft_precise_amd/csrc/kernels.hip'), '-o', '/tmp/kernels_res.o',
+       os.path.join(REPO, 'mycroft_precise_amd/csrc', source), '-o', '/tmp/kernels_res.o',
        '-Rpass-analysis=kernel-resource-usage'] + flags
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
