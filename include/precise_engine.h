@@ -365,6 +365,58 @@ int pe_simulate_clips(pe_engine* e, const void* audio_host, int32_t sample_forma
                       const double* thresholds, int32_t n_thresholds, pe_sim_metric* metrics_out, int64_t* buckets_out,
                       float* out_host, int64_t max_windows);
 
+/* precise-test, precise-graph and precise-calc-threshold (stats.py:46-58,102-107; scripts/graph.py:147-151;
+ * scripts/calc_threshold.py:66-77) and the wake-word buckets of the annoyance estimate (annoyance_estimator.py:83-84) for
+ * several rows of predictions -- one per network -- against one row of targets and a whole table of thresholds in one call.
+ * Targets, shared by the rows: positive is y > 0.5, negative is y == 0; a target in (0, 0.5], which a trainer's resident
+ * sets may hold and on which the reference's own definitions disagree (astype(bool) against > 0.5 / < 0.5), is counted in
+ * n_other and enters no other count.
+ * thresholds: non-decreasing, no NaN, n_thresholds in 0..4096 (duplicates allowed); n_thresholds = 0: counts_out is NULL.
+ * compare: PE_STATS_COMPARE_F32 makes every comparison p > (float)t / p >= (float)t, what numpy does when a float32 array
+ * meets a Python float (Stats, with the floats ThresholdDecoder.encode returns); PE_STATS_COMPARE_F64 makes it
+ * (double)p > t, what numpy does when it meets a float64 array (annoyance_estimator.py:83).  The two differ where a
+ * prediction equals the float32 rounding of a threshold: float32(0.1) is above 0.1 in F64 and not in F32.
+ * counts_out[n_rows][n_thresholds], per (row, threshold) the samples with p > t (Stats.calc_metric) and with p >= t
+ * (Stats.num_correct), by target class: true_pos = pos_gt, false_pos = neg_gt, false_neg = n_pos - pos_gt, true_neg =
+ * n_neg - neg_gt, num_correct = pos_ge + n_neg - neg_ge.  A NaN prediction is above no threshold.
+ * summary_out[n_rows]: n and the class counts; n_nan, the NaN predictions; n_unsaturated, the predictions that are neither 0,
+ * 1 nor NaN (save_spots, calc_threshold.py:66); n_fit, those of them with y > 0.5; and over these n_fit samples
+ *   x = -log((double)u), u = fl32(fl32(1 / p) - 1)        (numpy's float32 `1 / outputs - 1`, then the logarithm in float64;
+ *                                                          the reference takes it in float32, which is not the same bits on
+ *                                                          every host)
+ *   logit_mean = sum(x) / n_fit, logit_std = sqrt(sum((x - logit_mean)^2) / n_fit)    (two passes, calc_threshold.py:76-77,
+ *                                                          without the smoothing factor; n_fit = 0: NaN for both)
+ * with every sum in float64 in an order that depends on n alone: the same bits in every run, for a row alone or among
+ * others, whatever the threshold table.
+ * pe_stats_scores: predictions the caller holds, raw[n_rows][stride] with n valid per row, 1 <= n_rows <= 16.
+ * pe_test_clips: pe_score_clips and pe_stats_scores in one call, the predictions staying on the device: every pass writes
+ * its scores into one buffer [n_models][n_clips] and the statistics run once after the last pass, so no result depends on
+ * pe_set_clip_pass_bytes.  targets_host[n_clips]; out_host [n_models][n_clips] (may be NULL) is bit for bit what
+ * pe_score_clips returns.  n_clips = 0 does nothing.
+ * pe_trainer_stats_models: every network of a trainer over host data or a resident set (source, feats_host, targets_host
+ * and n as pe_trainer_evaluate_models takes them; host data needs targets); probs_out [n_models][n] (may be NULL) is bit for
+ * bit what pe_trainer_evaluate_models returns.  Rows are the networks in model order.
+ * PE_ERR_INVALID, checked before any device work and with the outputs untouched: null pointers, n < 1 (but n_clips = 0),
+ * n > 2^31 - 1, n_rows outside 1..16, stride < n, thresholds out of order or NaN, n_thresholds outside 0..4096, compare other
+ * than 0 or 1, a target outside [0, 1] or NaN, a resident set never uploaded, and whatever pe_score_clips /
+ * pe_trainer_evaluate_models refuse.  The engine's streams are untouched; updates of pe_update_async still in flight finish
+ * first. */
+#define PE_STATS_COMPARE_F32 0
+#define PE_STATS_COMPARE_F64 1
+typedef struct pe_stats_count {     /* one (row, threshold) */
+    int64_t pos_gt, neg_gt, pos_ge, neg_ge;
+} pe_stats_count;
+typedef struct pe_stats_summary {   /* one row */
+    int64_t n, n_pos, n_neg, n_other, n_nan, n_unsaturated, n_fit;
+    double logit_mean, logit_std;
+} pe_stats_summary;
+int pe_stats_scores(pe_engine* e, const float* raw_host, int32_t n_rows, int64_t stride, const float* targets_host, int64_t n,
+                    const double* thresholds, int32_t n_thresholds, int32_t compare,
+                    pe_stats_count* counts_out, pe_stats_summary* summary_out);
+int pe_test_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_clips,
+                  int64_t max_samples, const float* targets_host, const double* thresholds, int32_t n_thresholds, int32_t compare,
+                  pe_stats_count* counts_out, pe_stats_summary* summary_out, float* out_host);
+
 /* ThresholdDecoder.decode (threshold_decoder.py:45-57) and TriggerDetector.update
  * (runner/precise_runner/runner.py:127-142) for every stream, on the device.
  * pe_set_decoder: cd = the decoder's cumulative table (np.cumsum of the summed normal pdfs,
@@ -558,6 +610,11 @@ int pe_trainer_evaluate(pe_trainer* t, const float* feats_host, const float* tar
 int pe_trainer_n_samples(const pe_trainer* t, int32_t source);     /* of a resident set; 0 if never uploaded, -1 for a null trainer or another source */
 int pe_trainer_evaluate_models(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n,
                                const float* loss_bias, float* loss_out, float* acc_out, float* probs_out);
+/* pe_stats_scores (above) over the predictions of every network, which stay on the device: counts_out[n_models][n_thresholds],
+ * summary_out[n_models]; the contract is written out at pe_stats_scores. */
+int pe_trainer_stats_models(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n,
+                            const double* thresholds, int32_t n_thresholds, int32_t compare,
+                            pe_stats_count* counts_out, pe_stats_summary* summary_out, float* probs_out);
 
 /* The dropout masks of one step, on the host (no GPU call; works on a machine without one): out[3][n][feature_size], gate
  * order z, r, h.  With mix(v) the splitmix64 finaliser (v ^= v >> 30; v *= 0xBF58476D1CE4E5B9; v ^= v >> 27;

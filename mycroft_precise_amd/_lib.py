@@ -99,6 +99,10 @@ EXPORTS = {
                                      C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'pe_simulate_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    'pe_stats_scores': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                  C.c_void_p, C.c_void_p]),
+    'pe_test_clips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_set_decoder': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
     'pe_set_trigger': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     'pe_set_decoder_model': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
@@ -138,6 +142,8 @@ EXPORTS = {
     'pe_trainer_set_validation': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     'pe_trainer_evaluate_models': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    'pe_trainer_stats_models': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_train_dropout_masks': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     'pe_trainer_append': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     'pe_trainer_get_data': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -179,6 +185,47 @@ AUG_PIECE = np.dtype([('noise', '<i4'), ('reserved', '<i4'), ('first', '<i8'), (
 
 # pe_sim_metric: one (model, recording) of pe_simulate_scores / pe_simulate_clips
 SIM_METRIC = np.dtype([('n_windows', '<i8'), ('activated_chunks', '<i8'), ('activations', '<i8'), ('activation_sum', '<f8')])
+
+
+
+class PeStatsCount(C.Structure):
+    """pe_stats_count: one (row, threshold) of pe_stats_scores / pe_test_clips / pe_trainer_stats_models"""
+    _fields_ = [(n, C.c_int64) for n in ('pos_gt', 'neg_gt', 'pos_ge', 'neg_ge')]
+
+
+class PeStatsSummary(C.Structure):
+    """pe_stats_summary: one row of those calls"""
+    _fields_ = [(n, C.c_int64) for n in ('n', 'n_pos', 'n_neg', 'n_other', 'n_nan', 'n_unsaturated', 'n_fit')] + \
+        [('logit_mean', C.c_double), ('logit_std', C.c_double)]
+
+
+STATS_COUNT, STATS_SUMMARY = np.dtype(PeStatsCount), np.dtype(PeStatsSummary)
+STATS_MAX_ROWS, STATS_MAX_THRESHOLDS = 16, 4096
+STATS_COMPARE = {'f32': 0, 'f64': 1}                                   # PE_STATS_COMPARE_*
+
+
+def stats_request(thresholds, compare):
+    """-> (float64 thresholds [T], compare code) of a statistics call, refused here -- before any call into the library --
+    with ValueError when the table is not 1-D, holds a NaN, decreases or is longer than 4096, or ``compare`` is neither
+    'f32' nor 'f64'."""
+    if compare not in STATS_COMPARE:
+        raise ValueError("compare must be 'f32' or 'f64', got %r" % (compare,))
+    thr = np.zeros(0) if thresholds is None else np.array(thresholds, dtype=np.float64, ndmin=1)
+    if thr.ndim != 1:
+        raise ValueError('thresholds must be a 1-D table, got shape %r' % (thr.shape,))
+    if thr.size > STATS_MAX_THRESHOLDS:
+        raise ValueError('at most %d thresholds per call, got %d' % (STATS_MAX_THRESHOLDS, thr.size))
+    if np.isnan(thr).any():
+        raise ValueError('thresholds[%d] is NaN' % int(np.flatnonzero(np.isnan(thr))[0]))
+    if thr.size > 1 and (np.diff(thr) < 0).any():
+        raise ValueError('thresholds decrease at %d' % (int(np.flatnonzero(np.diff(thr) < 0)[0]) + 1))
+    return np.ascontiguousarray(thr), STATS_COMPARE[compare]
+
+
+def _stats_out(rows, n_thresholds):
+    """zeroed outputs of a statistics call: (counts STATS_COUNT [rows, T], summary STATS_SUMMARY [rows])"""
+    return np.zeros((rows, n_thresholds), dtype=STATS_COUNT), np.zeros(rows, dtype=STATS_SUMMARY)
+
 
 _lib = None
 
@@ -630,6 +677,44 @@ class HipEngine:
                                                     out.ctypes.data if return_scores else None, out.shape[-1] if return_scores else 0))
         return metrics, buckets, (self._split(out[..., :total], woff) if return_scores else None)
 
+    def stats_scores(self, scores, targets, thresholds=(0.5,), compare='f32'):
+        """Confusion counts for a whole table of thresholds and the calibration summary over predictions the caller holds
+        (pe_stats_scores): ``scores`` float32 [rows, n] (or [n]: one row), 1 <= rows <= 16, ``targets`` [n] shared by the rows,
+        ``thresholds`` non-decreasing, ``compare`` 'f32' (numpy's float32-against-Python-float comparison, what ``Stats``
+        makes) or 'f64' (float32 against a float64 array, the annoyance estimate's).  -> (counts STATS_COUNT [rows, T],
+        summary STATS_SUMMARY [rows])."""
+        thr, code = stats_request(thresholds, compare)
+        raw = np.ascontiguousarray(scores, dtype=np.float32)
+        raw = raw.reshape(1, -1) if raw.ndim == 1 else raw.reshape(raw.shape[0], -1)
+        rows, n = raw.shape
+        y = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
+        if y.size != n:
+            raise ValueError('%d targets for %d predictions per row' % (y.size, n))
+        counts, summary = _stats_out(rows, thr.size)
+        self._check(self._lib.pe_stats_scores(self._h, raw.ctypes.data if raw.size else None, rows, n, y.ctypes.data if n else None, n,
+                                              thr.ctypes.data if thr.size else None, thr.size, code,
+                                              counts.ctypes.data if thr.size else None, summary.ctypes.data))
+        return counts, summary
+
+    def test_clips(self, clips, max_samples, targets, thresholds=(0.5,), compare='f32', return_scores=False):
+        """``score_clips`` and ``stats_scores`` in one call, the predictions staying on the device (pe_test_clips).
+        -> (counts STATS_COUNT [K, T], summary STATS_SUMMARY [K], scores float32 [K, n] or None); K = 1 on a one-model
+        engine."""
+        thr, code = stats_request(thresholds, compare)
+        audio, offsets, fmt = self._clips(clips)
+        n = offsets.size - 1
+        y = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
+        if y.size != n:
+            raise ValueError('%d targets for %d clips' % (y.size, n))
+        counts, summary = _stats_out(self.n_models, thr.size)
+        out = np.zeros((self.n_models, n), dtype=np.float32) if return_scores else None
+        if n:
+            self._check(self._lib.pe_test_clips(self._h, audio.ctypes.data, fmt, offsets.ctypes.data, n, int(max_samples), y.ctypes.data,
+                                                thr.ctypes.data if thr.size else None, thr.size, code,
+                                                counts.ctypes.data if thr.size else None, summary.ctypes.data,
+                                                out.ctypes.data if return_scores else None))
+        return counts, summary, out
+
     def set_decoder(self, decoder, model=None):
         """Upload a ThresholdDecoder (its cumulative table and scalars) for pe_decode*: for every model, or for ``model``."""
         cd = np.ascontiguousarray(decoder.cd, dtype=np.float64)
@@ -973,6 +1058,31 @@ class HipTrainer:
         self._check(self._lib.pe_trainer_evaluate_models(self._h, code, None, None, 0, bias.ctypes.data, loss.ctypes.data,
                                                          acc.ctypes.data, probs.ctypes.data if want_probs and probs.size else None))
         return loss, acc, probs
+
+    def stats_models(self, feats=None, targets=None, thresholds=(0.5,), compare='f32', source='host', want_probs=False):
+        """``evaluate_models``' forward pass and ``HipEngine.stats_scores`` over its probabilities, which stay on the device
+        (pe_trainer_stats_models); ``source`` as ``evaluate_models`` takes it, host data with targets.  -> (counts
+        STATS_COUNT [n_models, T], summary STATS_SUMMARY [n_models], probabilities float32 [n_models, N] or None)."""
+        code = {'host': TRAIN_SOURCE_HOST, 'data': TRAIN_SOURCE_DATA, 'validation': TRAIN_SOURCE_VALIDATION}.get(source)
+        if code is None:
+            raise ValueError("source must be 'host', 'data' or 'validation', got %r" % (source,))
+        thr, cmp_code = stats_request(thresholds, compare)
+        counts, summary = _stats_out(self.n_models, thr.size)
+        feats_p = targets_p = None
+        if code == TRAIN_SOURCE_HOST:
+            feats = self._feats(feats)
+            n = feats.shape[0]
+            if targets is None:
+                raise ValueError('statistics over host data need targets')
+            targets = self._targets(targets, n)
+            feats_p, targets_p = (feats.ctypes.data, targets.ctypes.data) if n else (None, None)
+        else:
+            n = max(0, int(self._lib.pe_trainer_n_samples(self._h, code)))        # (no set: the call refuses)
+        probs = np.zeros((self.n_models, n), dtype=np.float32) if want_probs else None
+        self._check(self._lib.pe_trainer_stats_models(self._h, code, feats_p, targets_p, n, thr.ctypes.data if thr.size else None, thr.size,
+                                                      cmp_code, counts.ctypes.data if thr.size else None, summary.ctypes.data,
+                                                      probs.ctypes.data if want_probs and probs.size else None))
+        return counts, summary, probs
 
     def close(self):
         if getattr(self, '_h', None) and self._h.value:

@@ -10,6 +10,7 @@
 #include "mine_device.h"
 #include "generate_device.h"
 #include "augment_device.h"
+#include "stats_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -122,6 +123,7 @@ struct pe_engine {
     // pe_evaluate_clips / pe_simulate_*: the tables of a pass, its padded predictions, the call's thresholds + histogram +
     // metrics, a pass's mask words + partial sums
     DeviceBuf st_recs, st_pred, st_sim, st_simw;
+    DeviceBuf st_stats;                     // pe_stats_scores / pe_test_clips: the scratch of a call (StatsScratch)
     int64_t clip_pass_bytes = kClipPassBytes;  // audio bytes a pass of those entry points stages (pe_set_clip_pass_bytes: tests)
     std::vector<uint8_t> seen_ids;          // pe_update_subset: duplicate check of the host entry point
     // timing
@@ -1335,7 +1337,7 @@ int pe_destroy(pe_engine* e) {
     (void)hipSetDevice(e->device);
     (void)drain_async(e);
     for (void* p : e->allocs) (void)hipFree(p);
-    for (DeviceBuf* b : {&e->st_pcm, &e->st_out, &e->st_feats, &e->st_mask, &e->st_audio, &e->st_mfcc, &e->st_conf, &e->st_fired, &e->st_ids, &e->st_clips, &e->st_recs, &e->st_pred, &e->st_sim, &e->st_simw})
+    for (DeviceBuf* b : {&e->st_pcm, &e->st_out, &e->st_feats, &e->st_mask, &e->st_audio, &e->st_mfcc, &e->st_conf, &e->st_fired, &e->st_ids, &e->st_clips, &e->st_recs, &e->st_pred, &e->st_sim, &e->st_simw, &e->st_stats})
         if (b->p) (void)hipFree(b->p);
     for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->s_compute) (void)hipStreamSynchronize(e->s_compute);
@@ -1750,6 +1752,87 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
 }
 
 namespace {
+// ---- statistics (kernels: stats_device.h) -------------------------------------------------------------
+static_assert(sizeof(pe_stats_summary) == sizeof(StatsSummary) && sizeof(StatsSummary) == 72, "pe_stats_summary is what the device writes");
+static_assert(sizeof(pe_stats_count) == 32, "four counts per (row, threshold)");
+
+struct StatsRequest {
+    const double* thresholds; int32_t n_thresholds, compare;
+    pe_stats_count* counts_out; pe_stats_summary* summary_out;
+};
+// what is wrong with a request over n samples, or nothing; targets_host null: a resident set, checked when it was uploaded
+bool stats_request_wrong(std::string& why, const char* who, const StatsRequest& q, const float* targets_host, int64_t n) {
+    char buf[256] = "";
+    const auto say = [&](const char* fmt, auto... v) { snprintf(buf, sizeof buf, fmt, who, v...); why = buf; return true; };
+    if (!q.summary_out) return say("null argument to %s (summary_out)");
+    if (n < 1 || n > 0x7fffffffll) return say("%s: n must lie in 1..2^31 - 1, got %lld", (long long)n);
+    if (q.compare != PE_STATS_COMPARE_F32 && q.compare != PE_STATS_COMPARE_F64) return say("%s: compare must be 0 (float32) or 1 (float64), got %d", q.compare);
+    if (q.n_thresholds < 0 || q.n_thresholds > kStatsMaxThresholds) return say("%s: n_thresholds must lie in 0..4096, got %d", q.n_thresholds);
+    if (q.n_thresholds > 0 && (!q.thresholds || !q.counts_out)) return say("null argument to %s (thresholds / counts_out with n_thresholds = %d)", q.n_thresholds);
+    for (int32_t j = 0; j < q.n_thresholds; ++j) {
+        if (q.thresholds[j] != q.thresholds[j]) return say("%s: thresholds[%d] is NaN", j);
+        if (j && q.thresholds[j] < q.thresholds[j - 1]) return say("%s: thresholds decrease at %d (%g after %g)", j, q.thresholds[j], q.thresholds[j - 1]);
+    }
+    if (targets_host)
+        for (int64_t i = 0; i < n; ++i)
+            if (!(targets_host[i] >= 0.0f && targets_host[i] <= 1.0f)) return say("%s: targets[%lld] = %g is outside [0, 1]", (long long)i, (double)targets_host[i]);
+    return false;
+}
+// one call's device scratch, as byte offsets: thresholds | histogram | counters | word sums x, d | summaries | the caller's
+// targets and predictions where they are not on the device yet
+struct StatsScratch {
+    size_t thresholds, hist, counters, word_x, word_d, summary, targets, probs, total;
+    uint32_t n_words;
+};
+StatsScratch stats_scratch(int rows, int64_t n, int n_thresholds, bool with_targets, bool with_probs) {
+    StatsScratch s{};
+    s.n_words = (uint32_t)((n + 63) / 64);
+    const size_t words = (size_t)rows * s.n_words * sizeof(double);
+    s.thresholds = 0;
+    s.hist = s.thresholds + (size_t)n_thresholds * sizeof(double);
+    s.counters = s.hist + (n_thresholds ? (size_t)rows * 4 * ((size_t)n_thresholds + 1) * sizeof(unsigned long long) : 0);
+    s.word_x = s.counters + (size_t)rows * kStatsCounters * sizeof(unsigned long long);
+    s.word_d = s.word_x + words;
+    s.summary = s.word_d + words;
+    s.targets = s.summary + (size_t)rows * sizeof(StatsSummary);
+    s.probs = s.targets + (with_targets ? ((size_t)n * sizeof(float) + 7) / 8 * 8 : 0);
+    s.total = s.probs + (with_probs ? (size_t)rows * (size_t)n * sizeof(float) : 0);
+    return s;
+}
+// the kernels over predictions and targets that are on the device, and the results back: the summaries as they are, the
+// counts as the histogram's sums from the top (a sample lies above thresholds[j] when its bin is > j)
+hipError_t stats_run(char* scratch, const StatsScratch& s, const float* probs_dev, int64_t stride, const float* targets_dev, int64_t n,
+                     int rows, const StatsRequest& q) {
+    const int T = q.n_thresholds;
+    const size_t nb = (size_t)T + 1;
+    hipError_t err;
+    if (T && (err = hipMemcpy(scratch + s.thresholds, q.thresholds, (size_t)T * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return err;
+    if ((err = hipMemsetAsync(scratch + s.hist, 0, s.word_x - s.hist, nullptr)) != hipSuccess) return err;       // histogram and counters
+    StatsArgs a{};
+    a.probs = probs_dev; a.stride = stride; a.targets = targets_dev; a.n = n; a.n_words = s.n_words;
+    a.thresholds = T ? reinterpret_cast<const double*>(scratch + s.thresholds) : nullptr; a.n_thresholds = T;
+    a.hist = T ? reinterpret_cast<unsigned long long*>(scratch + s.hist) : nullptr;
+    a.counters = reinterpret_cast<unsigned long long*>(scratch + s.counters);
+    a.word_x = reinterpret_cast<double*>(scratch + s.word_x);
+    a.word_d = reinterpret_cast<double*>(scratch + s.word_d);
+    a.summary = reinterpret_cast<StatsSummary*>(scratch + s.summary);
+    if ((err = launch_stats(a, rows, q.compare, nullptr)) != hipSuccess) return err;
+    std::vector<unsigned long long> hist(T ? (size_t)rows * 4 * nb : 0);
+    if (T && (err = hipMemcpy(hist.data(), a.hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost)) != hipSuccess) return err;
+    if ((err = hipMemcpy(q.summary_out, a.summary, (size_t)rows * sizeof(StatsSummary), hipMemcpyDeviceToHost)) != hipSuccess) return err;
+    for (int r = 0; r < rows && T; ++r) {
+        const unsigned long long* h = hist.data() + (size_t)r * 4 * nb;        // [> / >=][positive / negative][nb]
+        int64_t above[4] = {0, 0, 0, 0};
+        for (size_t j = nb - 1; j-- > 0;) {
+            for (int k = 0; k < 4; ++k) above[k] += (int64_t)h[(size_t)k * nb + j + 1];
+            q.counts_out[(size_t)r * T + j] = pe_stats_count{above[0], above[1], above[2], above[3]};
+        }
+    }
+    return hipSuccess;
+}
+}  // namespace
+
+namespace {
 // the front-end launch over a clip table that is on the device (pe_vectorize_clips / pe_score_clips; pe_miner_vectorize / _append)
 int launch_clip_front_end(pe_engine* e, const ClipTable& ct, double* dev_out, float* dev_rows, double* dev_mels) {
     if (e->general) {
@@ -1789,27 +1872,35 @@ int launch_rec_front_end(pe_engine* e, const RecTable& rt, float* dev_rows) {
     return PE_OK;
 }
 
-// pe_vectorize_clips (feats_out_host) / pe_score_clips (score_out_host): validation, then pass by pass one copy in, the
-// front-end launch, the network launch (scores), one copy out
+// pe_vectorize_clips (feats_out_host) / pe_score_clips (score_out_host) / pe_test_clips (stats; score_out_host may be null):
+// validation, then pass by pass one copy in, the front-end launch, the network launch (scores), one copy out -- and, for
+// pe_test_clips, the statistics kernels once over the scores of all passes
 int run_clips(pe_engine* e, const char* who, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_clips,
-              int64_t max_samples, bool mels, double* feats_out_host, float* score_out_host) {
+              int64_t max_samples, bool mels, double* feats_out_host, float* score_out_host, const StatsRequest* stats = nullptr,
+              const float* targets_host = nullptr) {
     if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
     if (n_clips < 0) return fail(e, PE_ERR_INVALID, "%s: n_clips=%d", who, n_clips);
     if (n_clips == 0) return PE_OK;
-    if (!audio_host || !offsets_host || !(feats_out_host || score_out_host)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (!audio_host || !offsets_host || !(feats_out_host || score_out_host || stats)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
     if (sample_format != 0 && sample_format != 1) return fail(e, PE_ERR_INVALID, "%s: sample_format must be 0 (float64) or 1 (float32), got %d", who, sample_format);
     if (offsets_host[0] != 0) return fail(e, PE_ERR_INVALID, "%s: offsets[0] must be 0, got %lld", who, (long long)offsets_host[0]);
     for (int32_t c = 0; c < n_clips; ++c) {
         if (offsets_host[c + 1] < offsets_host[c]) return fail(e, PE_ERR_INVALID, "%s: offsets decrease at clip %d (%lld after %lld)", who, c, (long long)offsets_host[c + 1], (long long)offsets_host[c]);
         if (offsets_host[c + 1] == offsets_host[c]) return fail(e, PE_ERR_INVALID, "%s: clip %d is empty (the reference raises InvalidAudio: cannot vectorize empty audio)", who, c);
     }
+    if (stats) {            // pe_test_clips: targets_host[n_clips]
+        if (!targets_host) return fail(e, PE_ERR_INVALID, "null argument to %s (targets)", who);
+        std::string wrong;
+        if (stats_request_wrong(wrong, who, *stats, targets_host, n_clips)) return fail(e, PE_ERR_INVALID, "%s", wrong.c_str());
+    }
+    const bool score = score_out_host || stats;
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
     int rc;
     const int T = e->prm.n_features;
     const int width = mels ? e->prm.n_filt : e->prm.n_mfcc;
     const size_t elem = sample_format == 1 ? sizeof(float) : sizeof(double);
-    if (score_out_host && (rc = ensure(e, e->st_out, (size_t)e->n_models * n_clips * sizeof(float)))) return rc;
+    if (score && (rc = ensure(e, e->st_out, (size_t)e->n_models * n_clips * sizeof(float)))) return rc;
     std::vector<ClipDesc> desc;
     std::vector<uint32_t> prefix;
     const bool t = e->timing;
@@ -1860,10 +1951,18 @@ int run_clips(pe_engine* e, const char* who, const void* audio_host, int32_t sam
             g.waves_per_tile = 1;
             if ((rc = launch_networks(e, g, 2, nullptr, n_clips))) return rc;
         }
-        if (t) { PE_HIP(e, hipEventRecord(e->ev[2], nullptr)); e->ev_valid = true; e->ev_has_gru = score_out_host != nullptr; }
+        if (t) { PE_HIP(e, hipEventRecord(e->ev[2], nullptr)); e->ev_valid = true; e->ev_has_gru = score; }
         c0 = c1;
     }
     if (score_out_host) PE_HIP(e, hipMemcpy(score_out_host, e->st_out.p, (size_t)e->n_models * n_clips * sizeof(float), hipMemcpyDeviceToHost));
+    if (stats) {            // once, over the scores of every pass
+        const StatsScratch s = stats_scratch(e->n_models, n_clips, stats->n_thresholds, true, false);
+        if ((rc = ensure(e, e->st_stats, s.total))) return rc;
+        char* const scratch = static_cast<char*>(e->st_stats.p);
+        PE_HIP(e, hipMemcpy(scratch + s.targets, targets_host, (size_t)n_clips * sizeof(float), hipMemcpyHostToDevice));
+        PE_HIP(e, stats_run(scratch, s, static_cast<const float*>(e->st_out.p), n_clips, reinterpret_cast<const float*>(scratch + s.targets), n_clips,
+                            e->n_models, *stats));
+    }
     return PE_OK;
 }
 }  // namespace
@@ -2143,6 +2242,38 @@ int pe_simulate_scores(pe_engine* e, const float* raw_host, int64_t stride, cons
     word_prefix[(size_t)n_rec] = (uint32_t)words;
     if ((rc = sim_launch(e, &q, &dev, sim, word_prefix, static_cast<const float*>(e->st_pred.p), total, nullptr, 0, 0, n_rec))) return rc;
     return sim_end(e, q, n_rec, dev);
+}
+
+int pe_test_clips(pe_engine* e, const void* audio_host, int32_t sample_format, const int64_t* offsets_host, int32_t n_clips,
+                  int64_t max_samples, const float* targets_host, const double* thresholds, int32_t n_thresholds, int32_t compare,
+                  pe_stats_count* counts_out, pe_stats_summary* summary_out, float* out_host) {
+    const StatsRequest q{thresholds, n_thresholds, compare, counts_out, summary_out};
+    return run_clips(e, "pe_test_clips", audio_host, sample_format, offsets_host, n_clips, max_samples, false, nullptr, out_host, &q, targets_host);
+}
+
+int pe_stats_scores(pe_engine* e, const float* raw_host, int32_t n_rows, int64_t stride, const float* targets_host, int64_t n,
+                    const double* thresholds, int32_t n_thresholds, int32_t compare,
+                    pe_stats_count* counts_out, pe_stats_summary* summary_out) {
+    const char* who = "pe_stats_scores";
+    if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
+    if (!raw_host || !targets_host) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (n_rows < 1 || n_rows > kStatsMaxRows) return fail(e, PE_ERR_INVALID, "%s: n_rows must lie in 1..%d, got %d", who, kStatsMaxRows, n_rows);
+    const StatsRequest q{thresholds, n_thresholds, compare, counts_out, summary_out};
+    std::string wrong;
+    if (stats_request_wrong(wrong, who, q, targets_host, n)) return fail(e, PE_ERR_INVALID, "%s", wrong.c_str());
+    if (stride < n) return fail(e, PE_ERR_INVALID, "%s: stride %lld is less than the %lld samples of a row", who, (long long)stride, (long long)n);
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    const StatsScratch s = stats_scratch(n_rows, n, n_thresholds, true, true);
+    int rc;
+    if ((rc = ensure(e, e->st_stats, s.total))) return rc;
+    char* const scratch = static_cast<char*>(e->st_stats.p);
+    float* const probs = reinterpret_cast<float*>(scratch + s.probs);
+    PE_HIP(e, hipMemcpy(scratch + s.targets, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    for (int32_t r = 0; r < n_rows; ++r)
+        PE_HIP(e, hipMemcpy(probs + (size_t)r * n, raw_host + (size_t)r * stride, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    PE_HIP(e, stats_run(scratch, s, probs, n, reinterpret_cast<const float*>(scratch + s.targets), n, n_rows, q));
+    return PE_OK;
 }
 
 int pe_set_clip_pass_bytes(pe_engine* e, int64_t bytes) {
@@ -2522,8 +2653,8 @@ struct pe_trainer {
     float* loss = nullptr;          // [K] losses, then [K] int32 accuracy counts: one copy brings both back
     TrainSet data, validation;
     // buffers that grow with the largest call: 0 feats, 1 targets, 2 masks, 3 indices, 4 tape, 5 partial, 6 probs,
-    // 7 / 8 dataset, 9 / 10 validation set
-    DeviceBuf buf[11];
+    // 7 / 8 dataset, 9 / 10 validation set, 11 the scratch of pe_trainer_stats_models (StatsScratch)
+    DeviceBuf buf[12];
 };
 
 namespace {
@@ -2931,6 +3062,36 @@ int pe_trainer_evaluate_models(pe_trainer* t, int32_t source, const float* feats
                                const float* loss_bias, float* loss_out, float* acc_out, float* probs_out) {
     if (!t) return PE_ERR_INVALID;
     return train_evaluate(t, "pe_trainer_evaluate_models", source, feats_host, targets_host, n, loss_bias, loss_out, acc_out, probs_out);
+}
+
+int pe_trainer_stats_models(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n,
+                            const double* thresholds, int32_t n_thresholds, int32_t compare,
+                            pe_stats_count* counts_out, pe_stats_summary* summary_out, float* probs_out) {
+    const char* who = "pe_trainer_stats_models";
+    if (!t) return PE_ERR_INVALID;
+    const TrainSet* set = nullptr;
+    if (source == PE_TRAIN_SOURCE_HOST) {
+        if (!feats_host || !targets_host) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+    } else if (source == PE_TRAIN_SOURCE_DATA || source == PE_TRAIN_SOURCE_VALIDATION) {
+        set = source == PE_TRAIN_SOURCE_DATA ? &t->data : &t->validation;
+        if (set->n <= 0)
+            return tfail(t, PE_ERR_INVALID, "%s: no resident %s set (call %s first)", who, source == PE_TRAIN_SOURCE_DATA ? "training" : "validation",
+                         source == PE_TRAIN_SOURCE_DATA ? "pe_trainer_set_data" : "pe_trainer_set_validation");
+        n = set->n;
+    } else {
+        return tfail(t, PE_ERR_INVALID, "%s: source = %d", who, source);
+    }
+    const StatsRequest q{thresholds, n_thresholds, compare, counts_out, summary_out};
+    std::string wrong;
+    if (stats_request_wrong(wrong, who, q, set ? nullptr : targets_host, n)) return tfail(t, PE_ERR_INVALID, "%s", wrong.c_str());
+    // the forward pass of pe_trainer_evaluate_models: its probabilities stay in buffer 6, host targets arrive in buffer 1
+    int rc = train_evaluate(t, who, source, feats_host, targets_host, n, nullptr, nullptr, nullptr, probs_out);
+    if (rc) return rc;
+    const StatsScratch s = stats_scratch(t->K, n, n_thresholds, false, false);
+    if ((rc = train_reserve(t, 11, s.total))) return rc;
+    PE_THIP(t, stats_run(static_cast<char*>(t->buf[11].p), s, static_cast<const float*>(t->buf[6].p), n,
+                         set ? set->targets : static_cast<const float*>(t->buf[1].p), n, t->K, q));
+    return PE_OK;
 }
 
 int pe_trainer_evaluate(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n, float loss_bias,

@@ -121,6 +121,23 @@ class HipRunner(Runner):
         return self.engine.simulate_clips(audios, self._hops(chunk_size), threshold, threshold, 0, chunk_size, thresholds, return_scores)
 
 
+    def test_clips(self, audios, targets, thresholds=(0.5,), compare='f32', return_scores=False):
+        """precise-test's arithmetic (scripts/test.py:48-53 with stats.py) without the per-clip loop and for a whole table of
+        thresholds: every clip through the front end and the network as ``predict_clips`` does it, then -- the predictions
+        staying on the device -- the confusion counts per threshold and the calibration summary.  -> a ``stats.Sweep`` (a list
+        of K on a K-model runner); with ``return_scores`` the pair (sweeps, raw outputs as ``predict_clips`` returns them),
+        from which ``stats.Stats`` lists the failing files."""
+        from .stats import sweeps_of
+        audios = _require_clips(audios)
+        counts, summary, scores = self.engine.test_clips(audios, pr.max_samples, targets, thresholds, compare, return_scores)
+        sweeps = sweeps_of(np.array(thresholds, dtype=np.float64, ndmin=1), counts, summary, compare)
+        multi = self.engine._multi
+        result = sweeps if multi else sweeps[0]
+        if not return_scores:
+            return result
+        return result, (scores[:, :, None] if multi else scores[0][:, None])
+
+
 # The reference's two runner names (network_runner.py:45-95): `from precise.network_runner import Listener, KerasRunner`
 # (scripts/train_incremental.py:45) and `TensorFlowRunner` resolve to the one implementation here, whatever the file format.
 KerasRunner = TensorFlowRunner = HipRunner

@@ -24,6 +24,8 @@ data at once: one resident dataset, one launch per batch for all of them, and ea
 
 There is no CPU fallback: without the HIP library or a GPU the constructor raises.
 """
+from math import exp
+
 import numpy as np
 
 from ._lib import HipTrainer, dropout_masks            # noqa: F401  (dropout_masks: the kernel's mask function on the host)
@@ -157,6 +159,14 @@ class Trainer:
         loss, acc, _ = self._t.evaluate_models(loss_bias=self.params.loss_bias, source=source, want_probs=False)
         return float(loss[0]), float(acc[0])
 
+    def stats(self, thresholds=(0.5,), validation=True, compare='f32'):
+        """The network over the resident validation (training) set and, next to the predictions on the device, its confusion
+        counts at every threshold plus the calibration summary: -> a ``stats.Sweep``.  Targets in (0, 0.5] are refused by
+        name (ValueError naming ``n_other``)."""
+        from .stats import sweeps_of
+        counts, summary, _ = self._t.stats_models(thresholds=thresholds, compare=compare, source='validation' if validation else 'data')
+        return sweeps_of(np.array(thresholds, dtype=np.float64, ndmin=1), counts, summary, compare)[0]
+
     def fit_resident(self, batch_size=5000, epochs=1, shuffle=True, callback=None) -> dict:
         """``fit`` on the resident training set, without an upload: the same steps -- the same weights, bit for bit, as ``fit``
         on the same samples from the same state -- with ``acc`` (and ``val_loss`` / ``val_acc`` when a validation set is
@@ -278,8 +288,19 @@ class TrainerGroup:
         self.histories = histories
         return histories
 
+    def stats(self, thresholds=(0.5,), validation=True, compare='f32') -> list:
+        """``Trainer.stats`` for every candidate in one device call: -> K sweeps over the same thresholds"""
+        from .stats import sweeps_of
+        counts, summary, _ = self._t.stats_models(thresholds=thresholds, compare=compare, source='validation' if validation else 'data')
+        return sweeps_of(np.array(thresholds, dtype=np.float64, ndmin=1), counts, summary, compare)
+
     def best(self, key: str = 'val_loss') -> int:
-        """the candidate whose last-epoch ``key`` is smallest (largest for the accuracies)"""
+        """the candidate whose last-epoch ``key`` is smallest (largest for the accuracies); ``'cost'``: the candidate whose
+        trial report (``trial_reports``) has the smallest cost"""
+        if key == 'cost':
+            if not getattr(self, 'reports', None):
+                raise ValueError("no 'cost' for this group yet (call trial_reports first)")
+            return int(np.argmin([r['cost'] for r in self.reports]))
         if not getattr(self, 'histories', None) or key not in self.histories[0] or not self.histories[0][key]:
             raise ValueError('no %r in the histories of this group (call fit first)' % key)
         last = [h[key][-1] for h in self.histories]
@@ -287,6 +308,46 @@ class TrainerGroup:
 
     def close(self):
         self._t.close()
+
+
+def params_cost(n_params: int) -> float:
+    """what a network's size costs (train_optimize.py:64-77): flat up to about 11000 parameters, exponential beyond"""
+    return 1.0 + exp((n_params - 11000) / 10000)
+
+
+def trial_reports(group, runner, noise_audios, interaction_estimate=100, ambient_annoyance=1.0, chunk_size: int = 4096) -> list:
+    """What a trial of ``precise-train-optimize`` remembers (scripts/train_optimize.py:98-127), for every candidate of a
+    ``TrainerGroup`` at once: -> K dicts ``test_stats`` (the confusion counts at 0.5), ``best_threshold``, ``cost`` and
+    ``cost_info`` (``params_cost``, ``annoyance``, ``ww_annoyance``, ``nww_annoyance``).
+
+    The wake-word side is counted on the group's resident validation set (``TrainerGroup.stats``, two device calls for all
+    candidates); the noise side on ``runner``, a K-model ``HipRunner`` that holds ``group.weights``, over ``noise_audios``
+    (``simulate.nww_buckets``, one call).  The reports are kept as ``group.reports`` for ``group.best('cost')``."""
+    from . import annoyance, simulate
+    K = len(group)
+    engine = runner.engine
+    if not getattr(engine, '_multi', False) or engine.n_models != K:
+        raise ValueError('trial_reports needs a multi-model HipRunner holding the %d networks of the group (HipRunner(weights=group.weights)), '
+                         'got one of %d model%s' % (K, engine.n_models, '' if getattr(engine, '_multi', False) else ' (single-model form)'))
+    if len(set(group.units)) != 1:
+        raise ValueError('trial_reports: a multi-model engine holds networks of one width, the group has units = %r' % (group.units,))
+    thresholds = simulate.default_thresholds()
+    at_half = group.stats((0.5,), validation=True, compare='f32')
+    ww = group.stats(thresholds, validation=True, compare='f64')
+    recordings = [np.asarray(a) for a in noise_audios]
+    seconds = 0.0
+    for a in recordings:                          # (annoyance_estimator.py:67 adds file by file; an empty file adds 0)
+        seconds += len(a) / pr.sample_rate
+    nww = simulate.nww_buckets(runner, recordings, thresholds, chunk_size).reshape(K, -1)
+    reports = []
+    for m in range(K):
+        est = annoyance.estimate(ww[m].counts['pos_gt'], ww[m].n_pos, nww[m], seconds, interaction_estimate, ambient_annoyance, thresholds)
+        size = params_cost(int(group._t.n_params[m]))
+        reports.append({'test_stats': at_half[m].to_dict(0), 'best_threshold': est.threshold, 'cost': est.annoyance + size,
+                        'cost_info': {'params_cost': size, 'annoyance': est.annoyance, 'ww_annoyance': est.ww_annoyance,
+                                      'nww_annoyance': est.nww_annoyance}})
+    group.reports = reports
+    return reports
 
 
 class IncrementalTrainer:
