@@ -635,6 +635,62 @@ int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feat
 int pe_trainer_append(pe_trainer* t, int32_t source, const float* feats_host, const float* targets_host, int32_t n);
 int pe_trainer_get_data(pe_trainer* t, int32_t source, int32_t first, int32_t n, float* feats_out, float* targets_out);
 
+/* Sampled training: precise-train-sampled (scripts/train_sampled.py:54-90) predicts its WHOLE training set every cycle, adds at
+ * most num_sample_chunk samples the model still gets wrong to a growing selection and fits on the selection only; precise-train
+ * -sf FILE [-is] (scripts/train.py:146-157) then trains on that selection or on its complement.  Here the set is resident, the
+ * choice is made next to the predictions and a fit reads the chosen rows by index: a cycle uploads nothing.  Additive to ABI 8.
+ *
+ * pe_trainer_evaluate_indices: pe_trainer_evaluate_models' outputs (loss_out[n_models], acc_out[n_models], probs_out[n_models][n];
+ *   each may be NULL) for rows indices_host[0 .. n) of the resident set `source` (PE_TRAIN_SOURCE_DATA or _VALIDATION), in that
+ *   order; repeats allowed.  Bit for bit pe_trainer_evaluate_models(PE_TRAIN_SOURCE_HOST) on host copies of those rows.  An index
+ *   outside the set is PE_ERR_INVALID before any device work; the outputs are then untouched.
+ *
+ * The selection state belongs to the training set: per row `eligible` and `selected`, and the list of the selected rows in the
+ * order they were chosen.  pe_trainer_set_data empties it (nothing selected, every row eligible); rows that pe_trainer_append
+ * (or a miner / generator / augmenter) adds are eligible and unselected.
+ * pe_trainer_sample_reset replaces it: eligible_host[n] (non-zero = eligible; NULL = all) and selected_host[n_selected], the
+ *   selection in order.  An index outside the set, a repeated index or an ineligible selected row is PE_ERR_INVALID and leaves
+ *   the state as it was.  `eligible` is how duplicated samples are handled: the reference keys samples by an md5 of their bytes
+ *   and its hash_to_ind keeps the LAST row of every hash, so the caller marks exactly those rows eligible (hashing stays on the
+ *   host); identical rows predict identical bits, so a duplicate fails exactly when its eligible twin does.
+ * pe_trainer_sample_choose: ONE device call.  (1) the evaluate launch over the whole training set, dropout off; the predictions
+ *   p of network `model` stay on the device.  (2) per row fail = (p > 0.5f) != (y > 0.5f) (a NaN p compares false, as numpy's
+ *   does), candidate = fail && eligible && !selected; the counts are integers.  (3) the first max_new candidates in `order`:
+ *     PE_SAMPLE_ORDER_INDEX   lowest row first -- the reference's loop with sorted(remaining, key=hash_to_ind.get) in front of
+ *                             its islice (which otherwise follows Python's set order: it has no reproducible order to match);
+ *     PE_SAMPLE_ORDER_ERROR   largest float32 |p - y| first (fabsf of one correctly rounded subtraction; a NaN counts as
+ *                             +infinity), ties to the lower row -- "the highest loss" of the script's docstring.
+ *   The order is a unique 64-bit key per row and the choice its max_new smallest keys, found by sorting (no atomics decide a
+ *   position): the same call on the same state gives the same ids in the same order.  (4) the chosen rows are marked selected
+ *   and appended to the selection list; *report and added_out[n_added] (may be NULL) come back in one copy, probs_out[n] (may
+ *   be NULL) in a second.  max_new = 0 reports only.  max_new > PE_SAMPLE_MAX_NEW is PE_ERR_UNSUPPORTED (the message names
+ *   max_new); model outside the trainer, an unknown order, a negative max_new or no resident training set PE_ERR_INVALID; all
+ *   checks happen before any device work.
+ * pe_trainer_sample_selected: out[pe_trainer_n_selected(t)], the selection in the order chosen.
+ * The samples file itself (hashes, one per selected row) is the host's business: train.py writes a JSON array of hash strings;
+ * that the reference's fitipy writer produces exactly that was not verified. */
+#define PE_SAMPLE_ORDER_INDEX 0
+#define PE_SAMPLE_ORDER_ERROR 1
+#define PE_SAMPLE_MAX_NEW 1024
+#define PE_SAMPLE_BLOCK_ROWS 2048           /* rows one selection block owns (tests place failing rows at its borders) */
+typedef struct pe_sample_report {
+    int64_t n;            /* rows of the resident training set */
+    int64_t n_correct;    /* rows with (p > 0.5) == (y > 0.5), over ALL rows */
+    int64_t n_failed;     /* eligible rows that fail */
+    int64_t n_remaining;  /* of those, not selected before this call (the script's "Remaining failed samples") */
+    int64_t n_added;      /* min(max_new, n_remaining) */
+    int64_t n_selected;   /* size of the selection after this call */
+} pe_sample_report;
+int pe_trainer_evaluate_indices(pe_trainer* t, int32_t source, const int32_t* indices_host, int32_t n,
+                                const float* loss_bias, float* loss_out, float* acc_out, float* probs_out);
+int pe_trainer_sample_reset(pe_trainer* t, const uint8_t* eligible_host /* [n] or NULL = all */,
+                            const int32_t* selected_host, int32_t n_selected);
+int pe_trainer_sample_choose(pe_trainer* t, int32_t model, int32_t max_new, int32_t order,
+                             pe_sample_report* report, int32_t* added_out /* [max_new] or NULL */,
+                             float* probs_out /* [n] or NULL */);
+int pe_trainer_sample_selected(pe_trainer* t, int32_t* out /* [n_selected], in order of selection */);
+int pe_trainer_n_selected(const pe_trainer* t);                    /* -1 for a null trainer */
+
 /* Incremental training: precise-train-incremental (scripts/train_incremental.py:113-137) plays hours of not-wake-word audio
  * through a Listener chunk by chunk, saves the last buffer_t seconds whenever the model fires, and retrains.  A pe_miner is
  * that scan as a session over ONE engine: the recordings are uploaded once and every frame of every recording is computed

@@ -45,6 +45,15 @@ TRAIN_MAX_MODELS = 16                                                  # PE_TRAI
 TRAIN_SOURCE_HOST, TRAIN_SOURCE_DATA, TRAIN_SOURCE_VALIDATION = 0, 1, 2     # PE_TRAIN_SOURCE_*
 
 
+class PeSampleReport(C.Structure):
+    """pe_sample_report: what pe_trainer_sample_choose counted and did"""
+    _fields_ = [(n, C.c_int64) for n in ('n', 'n_correct', 'n_failed', 'n_remaining', 'n_added', 'n_selected')]
+
+
+SAMPLE_ORDER = {'index': 0, 'error': 1}                                # PE_SAMPLE_ORDER_*
+SAMPLE_MAX_NEW, SAMPLE_BLOCK_ROWS = 1024, 2048                         # PE_SAMPLE_MAX_NEW, PE_SAMPLE_BLOCK_ROWS
+
+
 class PeInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         'n_streams', 'n_features', 'n_mfcc', 'units', 'n_layers', 'ring_slots', 'carry_capacity',
@@ -147,6 +156,14 @@ EXPORTS = {
     'pe_train_dropout_masks': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     'pe_trainer_append': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     'pe_trainer_get_data': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    # sampled training (pe_trainer_sample_*)
+    'pe_trainer_evaluate_indices': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    'pe_trainer_sample_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    'pe_trainer_sample_choose': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PeSampleReport), C.c_void_p,
+                                           C.c_void_p]),
+    'pe_trainer_sample_selected': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'pe_trainer_n_selected': (C.c_int, [C.c_void_p]),
     # mining false activations (pe_miner)
     'pe_miner_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.POINTER(C.c_void_p)]),
@@ -1083,6 +1100,56 @@ class HipTrainer:
                                                       cmp_code, counts.ctypes.data if thr.size else None, summary.ctypes.data,
                                                       probs.ctypes.data if want_probs and probs.size else None))
         return counts, summary, probs
+
+    # -- sampled training (pe_trainer_sample_*) -----------------------------------------------------------------------------
+    def evaluate_indices(self, indices, loss_bias=0.7, validation=False, want_probs=True):
+        """``evaluate_models`` over rows ``indices`` (any order, repeats allowed) of a resident set, without an upload: ->
+        (losses [n_models], accuracies [n_models], probabilities [n_models, len(indices)] or None), bit for bit what
+        ``evaluate_models`` gives for host copies of those rows (pe_trainer_evaluate_indices)."""
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        K = self.n_models
+        bias = np.ascontiguousarray(self._per_model(loss_bias, 'loss_bias'), dtype=np.float32)
+        loss, acc = np.zeros(K, dtype=np.float32), np.zeros(K, dtype=np.float32)
+        probs = np.zeros((K, idx.size), dtype=np.float32) if want_probs else None
+        self._check(self._lib.pe_trainer_evaluate_indices(self._h, self._source(validation), idx.ctypes.data if idx.size else None, idx.size,
+                                                          bias.ctypes.data, loss.ctypes.data, acc.ctypes.data,
+                                                          probs.ctypes.data if want_probs and idx.size else None))
+        return loss, acc, probs
+
+    def sample_reset(self, eligible=None, selected=()):
+        """Replace the selection state of the training set: ``eligible`` bool [n] (None: every row), ``selected`` the rows
+        selected so far, in order (pe_trainer_sample_reset)."""
+        n = self.n_samples()
+        if eligible is not None:
+            eligible = np.ascontiguousarray(np.asarray(eligible).reshape(-1) != 0, dtype=np.uint8)
+            if eligible.size != n:
+                raise ValueError('eligible must hold one flag per row (%d), got %d' % (n, eligible.size))
+        sel = np.ascontiguousarray(selected, dtype=np.int32).reshape(-1)
+        self._check(self._lib.pe_trainer_sample_reset(self._h, eligible.ctypes.data if eligible is not None and n else None,
+                                                      sel.ctypes.data if sel.size else None, sel.size))
+
+    def sample_choose(self, max_new, order='index', model=0, want_probs=False):
+        """Predict the whole training set with network ``model`` and select the first ``max_new`` failing, eligible, not yet
+        selected rows in ``order`` ('index': lowest row first; 'error': largest float32 |p - y| first, ties to the lower row),
+        all on the device (pe_trainer_sample_choose).  -> (report dict ``n``, ``n_correct``, ``n_failed``, ``n_remaining``,
+        ``n_added``, ``n_selected``; the added rows int32 in order; probabilities float32 [n] or None)."""
+        code = SAMPLE_ORDER.get(order)
+        if code is None:
+            raise ValueError("order must be 'index' or 'error', got %r" % (order,))
+        max_new = int(max_new)
+        report = PeSampleReport()
+        added = np.zeros(min(max(max_new, 0), SAMPLE_MAX_NEW), dtype=np.int32)
+        probs = np.zeros(max(0, self.n_samples()), dtype=np.float32) if want_probs else None
+        self._check(self._lib.pe_trainer_sample_choose(self._h, int(model), max_new, code, C.byref(report),
+                                                       added.ctypes.data if added.size else None,
+                                                       probs.ctypes.data if want_probs and probs.size else None))
+        return {name: int(getattr(report, name)) for name, _ in PeSampleReport._fields_}, added[:int(report.n_added)].copy(), probs
+
+    def sample_selected(self) -> np.ndarray:
+        """the selected rows int32, in the order they were selected (pe_trainer_sample_selected)"""
+        out = np.zeros(max(0, int(self._lib.pe_trainer_n_selected(self._h))), dtype=np.int32)
+        self._check(self._lib.pe_trainer_sample_selected(self._h, out.ctypes.data if out.size else None))
+        return out
 
     def close(self):
         if getattr(self, '_h', None) and self._h.value:

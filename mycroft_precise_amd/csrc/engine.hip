@@ -8,6 +8,7 @@
 #include "mfcc_general_device.h"
 #include "gru_train_device.h"
 #include "mine_device.h"
+#include "sample_device.h"
 #include "generate_device.h"
 #include "augment_device.h"
 #include "stats_device.h"
@@ -2652,9 +2653,13 @@ struct pe_trainer {
     float* grads = nullptr;
     float* loss = nullptr;          // [K] losses, then [K] int32 accuracy counts: one copy brings both back
     TrainSet data, validation;
+    // the selection state of the training set (pe_trainer_sample_*): rows [0, sample_n) have their state byte; rows behind
+    // them (a fresh or grown set) are eligible and unselected, and get theirs when a sample call next needs it
+    int sample_n = 0, n_selected = 0;
     // buffers that grow with the largest call: 0 feats, 1 targets, 2 masks, 3 indices, 4 tape, 5 partial, 6 probs,
-    // 7 / 8 dataset, 9 / 10 validation set, 11 the scratch of pe_trainer_stats_models (StatsScratch)
-    DeviceBuf buf[12];
+    // 7 / 8 dataset, 9 / 10 validation set, 11 the scratch of pe_trainer_stats_models (StatsScratch),
+    // 12 selection state bytes, 13 selection list, 14 the scratch of pe_trainer_sample_choose
+    DeviceBuf buf[15];
 };
 
 namespace {
@@ -2806,6 +2811,8 @@ int train_step(pe_trainer* t, const char* who, const int32_t* indices_host, int 
     return PE_OK;
 }
 
+int train_results(pe_trainer* t, const float* probs_dev, const float* targets_dev, int n, float* loss_out, float* acc_out, float* probs_out);
+
 int train_evaluate(pe_trainer* t, const char* who, int source, const float* feats_host, const float* targets_host, int n,
                    const float* loss_bias, float* loss_out, float* acc_out, float* probs_out) {
     const TrainSet* set = nullptr;
@@ -2836,15 +2843,20 @@ int train_evaluate(pe_trainer* t, const char* who, int source, const float* feat
     }
     for (int m = 0; m < t->K; ++m) a.model[m].beta = loss_bias ? loss_bias[m] : 0.0f;
     if ((rc = train_run(t, a, false))) return rc;
+    return train_results(t, a.probs, a.targets, n, loss_out, acc_out, probs_out);
+}
+
+// what an evaluation brings back after train_run(forward): targets_dev[n] are the targets of the n samples in launch order
+int train_results(pe_trainer* t, const float* probs_dev, const float* targets_dev, int n, float* loss_out, float* acc_out, float* probs_out) {
     const int K = t->K;
     int32_t* const hits = reinterpret_cast<int32_t*>(t->loss + K);
     if (acc_out) {
-        TrainAccuracyArgs c{a.probs, a.targets, n, hits};
+        TrainAccuracyArgs c{probs_dev, targets_dev, n, hits};
         PE_THIP(t, launch_train_accuracy(c, K, nullptr));
     }
     float back[2 * kTrainMaxModels];
     PE_THIP(t, hipMemcpy(back, t->loss, (size_t)(acc_out ? 2 : 1) * K * sizeof(float), hipMemcpyDeviceToHost));
-    if (probs_out) PE_THIP(t, hipMemcpy(probs_out, t->buf[6].p, (size_t)K * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (probs_out) PE_THIP(t, hipMemcpy(probs_out, probs_dev, (size_t)K * n * sizeof(float), hipMemcpyDeviceToHost));
     if (loss_out) memcpy(loss_out, back, (size_t)K * sizeof(float));
     if (acc_out)                                       // Keras binary_accuracy: mean(round(p) == y), ties to even
         for (int m = 0; m < K; ++m) {
@@ -3035,7 +3047,9 @@ int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho
 
 int pe_trainer_set_data(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n) {
     if (!t) return PE_ERR_INVALID;
-    return train_upload_set(t, "pe_trainer_set_data", &t->data, 7, feats_host, targets_host, n);
+    const int rc = train_upload_set(t, "pe_trainer_set_data", &t->data, 7, feats_host, targets_host, n);
+    if (rc == PE_OK || t->data.n == 0) t->sample_n = t->n_selected = 0;      // a new set: nothing selected, every row eligible
+    return rc;
 }
 
 int pe_trainer_set_validation(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n) {
@@ -3220,6 +3234,152 @@ int pe_trainer_get_data(pe_trainer* t, int32_t source, int32_t first, int32_t n,
     if (targets_out) PE_THIP(t, hipMemcpy(targets_out, set.targets + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return PE_OK;
 }
+
+}  // extern "C"
+
+// ---- sampled training (pe_trainer_evaluate_indices / pe_trainer_sample_*; kernels: sample_device.h) ------------
+static_assert(sizeof(pe_sample_report) == sizeof(SampleReport) && sizeof(SampleReport) == 48, "pe_sample_report is what the device writes");
+static_assert(PE_SAMPLE_BLOCK_ROWS == kSampleBlock && PE_SAMPLE_MAX_NEW == kSampleBlock / 2, "a selection round halves the keys at least");
+
+namespace {
+
+// every row of the training set has its state byte, and the selection list has room for all of them
+int sample_state_room(pe_trainer* t) {
+    const int n = t->data.n;
+    int rc;
+    if ((rc = train_grow(t, 12, (size_t)t->sample_n, (size_t)n))) return rc;
+    if ((rc = train_grow(t, 13, (size_t)t->n_selected * sizeof(int32_t), (size_t)n * sizeof(int32_t)))) return rc;
+    if (t->sample_n < n) {
+        PE_THIP(t, hipMemset(static_cast<uint8_t*>(t->buf[12].p) + t->sample_n, kSampleEligible, (size_t)(n - t->sample_n)));
+        t->sample_n = n;
+    }
+    return PE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pe_trainer_evaluate_indices(pe_trainer* t, int32_t source, const int32_t* indices_host, int32_t n, const float* loss_bias,
+                                float* loss_out, float* acc_out, float* probs_out) {
+    const char* who = "pe_trainer_evaluate_indices";
+    if (!t) return PE_ERR_INVALID;
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return tfail(t, PE_ERR_INVALID, "%s: source = %d", who, source);
+    const TrainSet& set = source == PE_TRAIN_SOURCE_DATA ? t->data : t->validation;
+    if (set.n <= 0)
+        return tfail(t, PE_ERR_INVALID, "%s: no resident %s set (call %s first)", who, source == PE_TRAIN_SOURCE_DATA ? "training" : "validation",
+                     source == PE_TRAIN_SOURCE_DATA ? "pe_trainer_set_data" : "pe_trainer_set_validation");
+    if (!indices_host) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: n = %d", who, n);
+    if (loss_out && !loss_bias) return tfail(t, PE_ERR_INVALID, "%s: a loss needs loss_bias", who);
+    for (int i = 0; i < n; ++i)
+        if (indices_host[i] < 0 || indices_host[i] >= set.n)
+            return tfail(t, PE_ERR_INVALID, "%s: indices[%d] = %d is outside the set of %d samples", who, i, indices_host[i], set.n);
+    PE_THIP(t, hipSetDevice(t->device));
+    int rc = train_reserve(t, 3, (size_t)n * sizeof(int32_t));
+    if (rc) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[3].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    TrainArgs a{};
+    a.n = n;
+    a.feats = set.feats;
+    a.targets = set.targets;
+    a.indices = static_cast<const int32_t*>(t->buf[3].p);
+    for (int m = 0; m < t->K; ++m) a.model[m].beta = loss_bias ? loss_bias[m] : 0.0f;
+    if ((rc = train_run(t, a, false))) return rc;
+    const float* targets = nullptr;
+    if (acc_out) {                                      // the accuracy count reads targets in launch order
+        if ((rc = train_reserve(t, 1, (size_t)n * sizeof(float)))) return rc;
+        SampleGatherArgs g{set.targets, a.indices, n, static_cast<float*>(t->buf[1].p)};
+        PE_THIP(t, launch_sample_gather_targets(g, nullptr));
+        targets = g.out;
+    }
+    return train_results(t, a.probs, targets, n, loss_out, acc_out, probs_out);
+}
+
+int pe_trainer_sample_reset(pe_trainer* t, const uint8_t* eligible_host, const int32_t* selected_host, int32_t n_selected) {
+    const char* who = "pe_trainer_sample_reset";
+    if (!t) return PE_ERR_INVALID;
+    const int n = t->data.n;
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: no resident training set (call pe_trainer_set_data first)", who);
+    if (n_selected < 0 || n_selected > n) return tfail(t, PE_ERR_INVALID, "%s: n_selected = %d for a set of %d samples", who, n_selected, n);
+    if (n_selected > 0 && !selected_host) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+    std::vector<uint8_t> state((size_t)n);
+    for (int i = 0; i < n; ++i) state[i] = (!eligible_host || eligible_host[i]) ? kSampleEligible : 0;
+    for (int i = 0; i < n_selected; ++i) {
+        const int32_t r = selected_host[i];
+        if (r < 0 || r >= n) return tfail(t, PE_ERR_INVALID, "%s: selected[%d] = %d is outside the set of %d samples", who, i, r, n);
+        if (state[r] & kSampleSelected) return tfail(t, PE_ERR_INVALID, "%s: selected[%d] = %d is repeated", who, i, r);
+        if (!(state[r] & kSampleEligible)) return tfail(t, PE_ERR_INVALID, "%s: selected[%d] = %d is not an eligible row", who, i, r);
+        state[r] |= kSampleSelected;
+    }
+    PE_THIP(t, hipSetDevice(t->device));
+    int rc;
+    if ((rc = train_grow(t, 12, 0, (size_t)n)) || (rc = train_grow(t, 13, 0, (size_t)n * sizeof(int32_t)))) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[12].p, state.data(), (size_t)n, hipMemcpyHostToDevice));
+    if (n_selected) PE_THIP(t, hipMemcpy(t->buf[13].p, selected_host, (size_t)n_selected * sizeof(int32_t), hipMemcpyHostToDevice));
+    t->sample_n = n;
+    t->n_selected = n_selected;
+    return PE_OK;
+}
+
+int pe_trainer_sample_choose(pe_trainer* t, int32_t model, int32_t max_new, int32_t order, pe_sample_report* report, int32_t* added_out,
+                             float* probs_out) {
+    const char* who = "pe_trainer_sample_choose";
+    if (!t) return PE_ERR_INVALID;
+    if (!report) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
+    if (model < 0 || model >= t->K) return tfail(t, PE_ERR_INVALID, "%s: model = %d of %d", who, model, t->K);
+    if (order != PE_SAMPLE_ORDER_INDEX && order != PE_SAMPLE_ORDER_ERROR) return tfail(t, PE_ERR_INVALID, "%s: order = %d", who, order);
+    if (max_new < 0) return tfail(t, PE_ERR_INVALID, "%s: max_new = %d", who, max_new);
+    if (max_new > PE_SAMPLE_MAX_NEW) return tfail(t, PE_ERR_UNSUPPORTED, "%s: max_new = %d (at most %d per call)", who, max_new, PE_SAMPLE_MAX_NEW);
+    const int n = t->data.n;
+    if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: no resident training set (call pe_trainer_set_data first)", who);
+    PE_THIP(t, hipSetDevice(t->device));
+    int rc = sample_state_room(t);
+    if (rc) return rc;
+    // scratch: counters[4] | report | added[PE_SAMPLE_MAX_NEW] | keys_a | keys_b
+    const size_t head = 4 * sizeof(unsigned long long), tail = sizeof(SampleReport) + (size_t)PE_SAMPLE_MAX_NEW * sizeof(int32_t);
+    const size_t keys = (size_t)sample_blocks(n) * max_new;
+    if ((rc = train_reserve(t, 14, head + tail + 2 * keys * sizeof(unsigned long long)))) return rc;
+    char* const scratch = static_cast<char*>(t->buf[14].p);
+    TrainArgs f{};
+    f.n = n;
+    f.feats = t->data.feats;
+    f.targets = t->data.targets;
+    if ((rc = train_run(t, f, false))) return rc;
+    SampleArgs a{};
+    a.probs = f.probs + (size_t)model * n;
+    a.targets = t->data.targets;
+    a.state = static_cast<uint8_t*>(t->buf[12].p);
+    a.n = n;
+    a.k = max_new;
+    a.order = order;
+    a.counters = reinterpret_cast<unsigned long long*>(scratch);
+    a.report = reinterpret_cast<SampleReport*>(scratch + head);
+    a.added = reinterpret_cast<int32_t*>(scratch + head + sizeof(SampleReport));
+    a.selection = static_cast<int32_t*>(t->buf[13].p);
+    a.n_selected = t->n_selected;
+    unsigned long long* const keys_a = reinterpret_cast<unsigned long long*>(scratch + head + tail);
+    PE_THIP(t, hipMemsetAsync(a.counters, 0, head, nullptr));
+    PE_THIP(t, launch_sample_choose(a, keys ? keys_a : nullptr, keys ? keys_a + keys : nullptr, nullptr));
+    std::vector<char> back(sizeof(SampleReport) + (size_t)max_new * sizeof(int32_t));       // one copy: the report and the ids
+    PE_THIP(t, hipMemcpy(back.data(), a.report, back.size(), hipMemcpyDeviceToHost));
+    memcpy(report, back.data(), sizeof(SampleReport));
+    if (added_out && report->n_added > 0) memcpy(added_out, back.data() + sizeof(SampleReport), (size_t)report->n_added * sizeof(int32_t));
+    t->n_selected = (int)report->n_selected;
+    if (probs_out) PE_THIP(t, hipMemcpy(probs_out, a.probs, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_trainer_sample_selected(pe_trainer* t, int32_t* out) {
+    if (!t) return PE_ERR_INVALID;
+    if (t->n_selected == 0) return PE_OK;
+    if (!out) return tfail(t, PE_ERR_INVALID, "pe_trainer_sample_selected: null pointer");
+    PE_THIP(t, hipSetDevice(t->device));
+    PE_THIP(t, hipMemcpy(out, t->buf[13].p, (size_t)t->n_selected * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PE_OK;
+}
+
+int pe_trainer_n_selected(const pe_trainer* t) { return t ? t->n_selected : -1; }
 
 }  // extern "C"
 

@@ -12,7 +12,8 @@ DESIGN.md 4.9); this module only shuffles indices and keeps the history.
     trainer.save('hey-computer.npz')            # then HipRunner('hey-computer.npz') / Listener serve it
 
 ``GeneratedTrainer`` is the ``fit_generator`` loop of ``precise-train-generated`` over a ``generated.Generator``; ``IncrementalTrainer``
-the policy of ``precise-train-incremental`` over a ``mining.Miner``.
+the policy of ``precise-train-incremental`` over a ``mining.Miner``; ``SampledTrainer`` the loop of ``precise-train-sampled``
+(the failing samples are chosen on the device) and the samples file of ``precise-train -sf [-is]``.
 
 ``TrainerGroup`` trains several candidate networks -- other widths, dropout rates, ``loss_bias`` values, seeds -- on the same
 data at once: one resident dataset, one launch per batch for all of them, and each candidate ends with exactly the bits that a
@@ -118,14 +119,17 @@ class Trainer:
         return self._fit(n, batch_size, epochs, shuffle, callback, lambda: self.evaluate(inputs, outputs),
                          None if validation_data is None else lambda: self.evaluate(*validation_data))
 
-    def _fit(self, n, batch_size, epochs, shuffle, callback, measure, measure_validation) -> dict:
-        """the epochs of ``fit`` over the resident training set of ``n`` samples; ``measure()`` -> (loss, acc) after an epoch"""
+    def _fit(self, n, batch_size, epochs, shuffle, callback, measure, measure_validation, rows=None) -> dict:
+        """the epochs of ``fit`` over the resident training set of ``n`` samples (``rows``: over these ``n`` rows of it);
+        ``measure()`` -> (loss, acc) after an epoch"""
         p = self.params
         history = {'loss': [], 'acc': []}
         if measure_validation is not None:
             history.update(val_loss=[], val_acc=[])
         for epoch in range(int(epochs)):
             order = self._rng.permutation(n) if shuffle else np.arange(n)
+            if rows is not None:
+                order = rows[order]
             losses = []
             for a in range(0, n, int(batch_size)):
                 losses.append(self._t.step(order[a:a + int(batch_size)], dropout_rate=p.dropout, seed=self.seed, step=self._step,
@@ -167,16 +171,29 @@ class Trainer:
         counts, summary, _ = self._t.stats_models(thresholds=thresholds, compare=compare, source='validation' if validation else 'data')
         return sweeps_of(np.array(thresholds, dtype=np.float64, ndmin=1), counts, summary, compare)[0]
 
-    def fit_resident(self, batch_size=5000, epochs=1, shuffle=True, callback=None) -> dict:
+    def fit_resident(self, batch_size=5000, epochs=1, shuffle=True, callback=None, subset=None) -> dict:
         """``fit`` on the resident training set, without an upload: the same steps -- the same weights, bit for bit, as ``fit``
         on the same samples from the same state -- with ``acc`` (and ``val_loss`` / ``val_acc`` when a validation set is
         resident) measured on the resident sets.  The optimizer state carries over from call to call, as it does when the
-        reference calls ``model.fit`` again on the model it keeps (train_incremental.py:106-109)."""
+        reference calls ``model.fit`` again on the model it keeps (train_incremental.py:106-109).
+
+        ``subset``: row indices of the resident set (repeats allowed, order kept): the epochs run over ``subset[perm]`` and
+        ``acc`` is measured over exactly those rows -- weights, accumulators and history of ``fit(inputs[subset],
+        outputs[subset], ...)`` from the same state, bit for bit."""
         n = self._t.n_samples()
         if n == 0 or int(batch_size) < 1:
             raise ValueError('fit_resident needs a resident training set (set_data / append) and batch_size >= 1')
-        return self._fit(n, batch_size, epochs, shuffle, callback, lambda: self._evaluate_resident('data'),
-                         (lambda: self._evaluate_resident('validation')) if self._t.n_samples(True) else None)
+        validation = (lambda: self._evaluate_resident('validation')) if self._t.n_samples(True) else None
+        if subset is None:
+            return self._fit(n, batch_size, epochs, shuffle, callback, lambda: self._evaluate_resident('data'), validation)
+        rows = np.array(subset, dtype=np.int64).reshape(-1)
+        if rows.size == 0 or rows.min() < 0 or rows.max() >= n:
+            raise ValueError('subset needs at least one row, each within the resident set of %d samples' % n)
+
+        def measure():
+            loss, acc, _ = self._t.evaluate_indices(rows, loss_bias=self.params.loss_bias, want_probs=False)
+            return float(loss[0]), float(acc[0])
+        return self._fit(rows.size, batch_size, epochs, shuffle, callback, measure, validation, rows=rows)
 
     def close(self):
         self._t.close()
@@ -537,3 +554,158 @@ class GeneratedTrainer:
             if callback is not None:
                 callback(epoch, logs)
         return history
+
+
+# ---- precise-train-sampled (scripts/train_sampled.py) and the samples file of precise-train -sf [-is] -----------------------
+def sample_hashes(inputs, outputs) -> list:
+    """``calc_sample_hash`` of every row, over the arrays as given (the reference hashes what ``TrainData.load`` returns)"""
+    from .util import calc_sample_hash
+    return [calc_sample_hash(inp, outp) for inp, outp in zip(inputs, outputs)]
+
+
+def eligible_mask(hashes) -> np.ndarray:
+    """bool [n]: the rows ``hash_to_ind`` points at -- of rows with the same hash the LAST (train.py:116-119)"""
+    mask = np.zeros(len(hashes), dtype=bool)
+    mask[list({h: i for i, h in enumerate(hashes)}.values())] = True
+    return mask
+
+
+def read_samples_file(path) -> list:
+    """The hashes of a samples file in file order, each once: a JSON array of strings or, failing that, one hash per line.
+    A missing or empty file is an empty selection."""
+    import json
+    import os
+    if not os.path.isfile(path):
+        return []
+    with open(path) as f:
+        text = f.read()
+    try:
+        found = json.loads(text) if text.strip() else []
+        if not isinstance(found, list):
+            raise ValueError('not an array')
+    except ValueError:
+        found = [line.strip() for line in text.splitlines() if line.strip()]
+    return list(dict.fromkeys(str(h) for h in found))
+
+
+def write_samples_file(path, hashes):
+    import json
+    with open(path, 'w') as f:
+        json.dump(list(hashes), f)
+
+
+def known_samples(found, hash_to_ind) -> list:
+    """``found`` without the hashes the data does not hold, each reported as the reference does (train.py:121-124)"""
+    kept = []
+    for h in found:
+        if h in hash_to_ind:
+            kept.append(h)
+        else:
+            print('Missing hash:', h)
+    return kept
+
+
+def metrics_line(n_selected: int, n: int, n_correct: int) -> str:
+    """a line of sampling-metrics.txt (train_sampled.py:55,59)"""
+    return '{}\t{}'.format(n_selected / n, float(n_correct / n))
+
+
+class SampledTrainer:
+    """The loop of ``precise-train-sampled`` (scripts/train_sampled.py:72-90) over a ``Trainer`` whose training set stays on
+    the device: per cycle ONE ``sample_choose`` -- predict all rows, count, pick at most ``num_sample_chunk`` rows the model
+    still gets wrong, all next to the predictions -- and one ``fit_resident(subset=selected)``.  A cycle uploads nothing.
+
+        st = SampledTrainer(trainer, inputs, outputs, num_sample_chunk=50, order='error', validation_data=(val_in, val_out))
+        st.load_samples('hey-computer.samples.json')        # continue an earlier run (a missing file: start empty)
+        st.run(cycles=200, epochs=1, samples_file='hey-computer.samples.json', metrics_file='sampling-metrics.txt')
+
+    ``order``: which failing rows come first.  The reference takes ``islice`` over a Python set, whose order changes from run
+    to run; ``'index'`` (lowest row first) and ``'error'`` (largest float32 ``|p - y|`` first, ties to the lower row) are each
+    one legal outcome of it.  Duplicated samples share a hash and the reference's ``hash_to_ind`` keeps the last row: only
+    that row is eligible here.  ``hashes`` / ``hash_to_ind``: as the script has them; ``selected``: the chosen rows in order;
+    ``samples``: the set of their hashes; ``metrics``: the lines of the metrics file.  ``hashes``: the rows' hashes when
+    the caller has them already (default: ``sample_hashes(inputs, outputs)``, once)."""
+
+    def __init__(self, trainer, inputs, outputs, num_sample_chunk: int = 50, order: str = 'index', validation_data=None, hashes=None):
+        from ._lib import SAMPLE_MAX_NEW, SAMPLE_ORDER
+        if order not in SAMPLE_ORDER:
+            raise ValueError("order must be 'index' or 'error', got %r" % (order,))
+        if not 0 <= int(num_sample_chunk) <= SAMPLE_MAX_NEW:
+            raise ValueError('num_sample_chunk = %d (0..%d rows are chosen per cycle)' % (num_sample_chunk, SAMPLE_MAX_NEW))
+        self.trainer, self.num_sample_chunk, self.order = trainer, int(num_sample_chunk), order
+        self.hashes = sample_hashes(inputs, outputs) if hashes is None else list(hashes)
+        if len(self.hashes) != len(inputs):
+            raise ValueError('%d hashes for %d rows' % (len(self.hashes), len(inputs)))
+        self.hash_to_ind = {h: i for i, h in enumerate(self.hashes)}
+        self.eligible = eligible_mask(self.hashes)
+        trainer.set_data(inputs, outputs)
+        if validation_data is not None:
+            trainer.set_data(*validation_data, validation=True)
+        self.n = trainer.n_samples()
+        self.metrics = []
+        self.samples_file = self.metrics_file = None
+        self._reset([])
+
+    def _reset(self, selected):
+        self.trainer._t.sample_reset(self.eligible, selected)
+        self.selected = [int(i) for i in selected]
+        self.samples = {self.hashes[i] for i in self.selected}
+
+    # -- the samples file ---------------------------------------------------------------------------------------------
+    def file_indices(self, path, invert=False) -> list:
+        """the rows a samples file stands for, in file order; ``invert``: every row of ``hash_to_ind`` NOT in it
+        (train.py:150-155), in ascending order"""
+        kept = known_samples(read_samples_file(path), self.hash_to_ind)
+        if invert:
+            return sorted(self.hash_to_ind[h] for h in set(self.hash_to_ind) - set(kept))
+        return [self.hash_to_ind[h] for h in kept]
+
+    def load_samples(self, path):
+        self._reset(self.file_indices(path))
+
+    def save_samples(self, path):
+        write_samples_file(path, [self.hashes[i] for i in self.selected])
+
+    def fit_samples(self, path, invert=False, batch_size=5000, epochs=10, shuffle=True, callback=None) -> dict:
+        """``precise-train -sf path [-is]``: fit on the rows of the samples file (``invert``: on all others); the selection
+        of this trainer is left alone"""
+        rows = self.file_indices(path, invert)
+        if not rows:
+            raise ValueError('%s selects no sample of this data' % path)
+        return self.trainer.fit_resident(batch_size, epochs, shuffle=shuffle, callback=callback, subset=rows)
+
+    # -- the loop -----------------------------------------------------------------------------------------------------
+    def cycle(self, epochs, batch_size=5000, shuffle=True) -> dict:
+        report, added, _ = self.trainer._t.sample_choose(self.num_sample_chunk, self.order)
+        self.selected += [int(i) for i in added]
+        self.samples.update(self.hashes[i] for i in added)
+        self.metrics.append(metrics_line(len(self.samples), report['n'], report['n_correct']))
+        if self.samples_file:
+            self.save_samples(self.samples_file)
+        if self.metrics_file:
+            with open(self.metrics_file, 'w') as f:
+                f.write('\n'.join(self.metrics))
+        history = None
+        if self.selected:
+            history = self.trainer.fit_resident(batch_size, epochs, shuffle=shuffle, subset=self.selected)
+        return {'remaining': report['n_remaining'], 'added': [int(i) for i in added], 'correct': float(report['n_correct'] / report['n']),
+                'ratio': len(self.samples) / report['n'], 'history': history}
+
+    def run(self, cycles, epochs, batch_size=5000, samples_file=None, metrics_file=None, callback=None) -> list:
+        """``cycles`` cycles; the samples file and the metrics file, when given, are rewritten after every choice, before
+        the fit, as the script does.  ``callback(cycle, result)`` runs after every cycle.  -> the cycles' results"""
+        self.samples_file, self.metrics_file = samples_file, metrics_file
+        results = []
+        try:
+            for c in range(int(cycles)):
+                results.append(self.cycle(epochs, batch_size))
+                if callback is not None:
+                    callback(c, results[-1])
+        finally:
+            self.samples_file = self.metrics_file = None
+        return results
+
+
+def fit_samples(trainer, inputs, outputs, path, invert=False, **fit_args) -> dict:
+    """``precise-train -sf path [-is]`` in one call: one upload, then ``fit_resident`` over the file's rows"""
+    return SampledTrainer(trainer, inputs, outputs).fit_samples(path, invert, **fit_args)

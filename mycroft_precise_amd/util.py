@@ -1,4 +1,6 @@
 """PCM helpers: drop-in for the hot-path part of ``precise.util`` (/root/reference/precise/util.py:25-42)."""
+import hashlib
+
 import numpy as np
 
 
@@ -20,6 +22,15 @@ def chunk_audio(audio: np.ndarray, chunk_size: int):
     """Whole chunks of ``chunk_size`` samples, all but the final one (util.py:30-32)."""
     for end in range(chunk_size, len(audio), chunk_size):
         yield audio[end - chunk_size:end]
+
+
+def calc_sample_hash(inp: np.ndarray, outp: np.ndarray) -> str:
+    """The identity of a training sample in a samples file: the md5 of the input's bytes followed by the target's
+    (util.py:113-118), over the arrays as they are -- ``TrainData.load`` hands out float64."""
+    md5 = hashlib.md5()
+    md5.update(np.asarray(inp).tobytes())
+    md5.update(np.asarray(outp).tobytes())
+    return md5.hexdigest()
 
 
 def pcm16_from(stream_input) -> np.ndarray:
