@@ -4,6 +4,17 @@ Bounds: gradients per tensor max|d| / max|reference tensor| <= 1
 torch float32 autograd against the same float64 reference: 0.4e-7 .. 5.4e-7), loss <= 1e-6, probabilities <= 1e-5.  All
 batches are built from kink-safe candidates only (train_reference.kink_safe): every hard-sigmoid pre-activation at least
 1e-3 from +-2.5 and |logit| <= 8 in the float64 reference, and every test asserts that at least half its candidates pass.
+
+The saturated-head tests drop the logit limit (the gate-kink rule stays) and hold the kernel to the float32 head contract
+(train_reference.head32, DESIGN.md 4.9 "The head is float32 by contract"): beyond logit 12 a float64 head is no reference for
+ds.  Their bounds follow the same 20x rule, the floors measured on the CPU by saturated_floors() below with torch float32 in
+the kernel's place, over the ten cases of test_gradients_saturated_head:
+  probabilities in neg and neg_sat, relative to float64: floor 1.78e-5 (2.41e-5 with masks), bound 20 x 2.41e-5 = 4.8e-4;
+    in mid PROB_TOL as everywhere; in pos and one |p - sigmoid64| <= 2^-23 (two float32 roundings at 2^-24 each), in one p == 1.0f;
+  gradients, the float64 Jacobian contracted with head32 of the kernel's own probabilities: floor 1.34e-6 (2.43e-6 with
+    masks), and 20x that is above GRAD_TOL = 1e-5, so the bounds are 20 x 1.34e-6 = 2.7e-5 and 20 x 2.43e-6 = 4.9e-5 with masks;
+  loss, relative to head32's loss: floor 9.81e-8, bound 20 x 9.81e-8 = 1.96e-6 (LOSS_TOL = 1e-6 absolute is less than the
+    float32 spacing of a loss near 5).
 """
 import functools
 
@@ -18,6 +29,7 @@ from mycroft_precise_amd.params import pr
 pytestmark = pytest.mark.gpu
 
 GRAD_TOL, LOSS_TOL, PROB_TOL = 1e-5, 1e-6, 1e-5
+SAT_PROB_REL_TOL, SAT_GRAD_TOL, SAT_GRAD_TOL_MASKS, SAT_LOSS_REL_TOL = 20 * 2.41e-5, 20 * 1.34e-6, 20 * 2.43e-6, 20 * 9.81e-8
 
 
 @functools.lru_cache(maxsize=None)
@@ -119,6 +131,270 @@ def test_gradients_constant_targets(stock_weights, target):
 def test_gradients_loss_bias(stock_weights, loss_bias):
     x, _ = safe_batch(stock_weights, 'mfcc', 33, 256, seed=5)
     check_against_reference(stock_weights, x, targets_for(33, 5), loss_bias=loss_bias)
+
+
+@pytest.mark.parametrize('F', [1, 13, 32])
+@pytest.mark.parametrize('H', [2, 3, 5, 7, 8, 12, 21, 31])
+def test_gradients_every_thread_layout(H, F):
+    """Widths whose blocks have idle lanes (16 H no multiple of 64), an odd 3 H, the most gradient elements per thread
+    (F = 32 at a small H) and one wave short of full (H = 31): one full tile and a tile of one sample."""
+    weights = synth.make_weights(F, (H,))
+    x, masks = safe_batch(weights, 'n01', 17, 256, T=3, F=F, rate=0.2, seed=H + F)
+    check_against_reference(weights, x, targets_for(17, H), masks, T=3)
+
+
+# ---- the saturated head (DESIGN.md 4.9, "The head is float32 by contract") -----------------------------------------------
+def scaled_head(weights, factor=8.0):
+    """the same GRU under a dense layer ``factor`` times as large (rounded to float32): logits out to +-50 and beyond"""
+    f = np.float32(factor)
+    return dict(weights, dense_kernel=(np.asarray(weights['dense_kernel'], dtype=np.float32) * f).astype(np.float32),
+                dense_bias=(np.asarray(weights['dense_bias'], dtype=np.float32) * f).astype(np.float32))
+
+
+SAT_N, SAT_CANDIDATES = 240, 480
+_saturated = {}
+
+
+def saturated_pool(stock_weights, rate=0.0):
+    """480 'n03' candidates (seed 0) through the scaled stock network in float64, computed once per mask rate and left alone:
+    dict(weights, x, masks, p, logit, bands, safe).  Kink-safe here keeps the gate-kink rule and drops the logit limit."""
+    if rate not in _saturated:
+        weights = scaled_head(stock_weights)
+        x = candidates('n03', SAT_CANDIDATES, seed=0)
+        masks = _lib.dropout_masks(0, 1, SAT_CANDIDATES, 13, rate) if rate > 0 else None
+        out = ref.forward_numpy(weights, x, masks)
+        safe = ref.kink_safe(out, max_logit=np.inf)
+        bands = ref.logit_bands(out['logit'])
+        print('rate %g: %d of %d candidates kink-safe, bands %s' %
+              (rate, safe.sum(), SAT_CANDIDATES, {b: int((bands == b).sum()) for b in ref.BANDS}))
+        _saturated[rate] = dict(weights=weights, x=x, masks=masks, p=out['p'], logit=out['logit'], bands=bands, safe=safe)
+    return _saturated[rate]
+
+
+def saturated_batch(stock_weights, n, bands, rate=0.0):
+    """-> dict(weights, x [n], masks or None, p, bands, rows): the first n kink-safe candidates whose float64 logit lies in
+    one of ``bands``; at least half the candidates are kink-safe and every band holds at least 16 of the n"""
+    pool = saturated_pool(stock_weights, rate)
+    assert pool['safe'].sum() >= SAT_CANDIDATES / 2
+    rows = np.flatnonzero(pool['safe'] & np.isin(pool['bands'], bands))[:n]
+    assert rows.size == n
+    counts = {b: int((pool['bands'][rows] == b).sum()) for b in bands}
+    print('%d kink-safe samples: %s' % (n, counts))
+    assert min(counts.values()) >= 16, counts
+    return dict(weights=pool['weights'], x=pool['x'][rows], masks=None if pool['masks'] is None else pool['masks'][:, rows],
+                p=pool['p'][rows], bands=pool['bands'][rows], rows=rows)
+
+
+ALL_BUT_EDGE = ('neg_sat', 'neg', 'mid', 'pos', 'one')
+
+
+def saturated_targets(kind, n):
+    return {'random': targets_for(n, 31), 'zeros': np.zeros(n, dtype=np.float32), 'ones': np.ones(n, dtype=np.float32)}[kind]
+
+
+def rel_err(got, want):
+    """|got - want| / |want|; a reference of exactly 0 asks for exactly 0"""
+    return abs(got - want) / abs(want) if want != 0 else (0.0 if got == 0 else float('inf'))
+
+
+def check_probabilities_in_bands(probs, want_p, bands):
+    d = np.abs(probs.astype(np.float64) - want_p)
+    mid, one = bands == 'mid', bands == 'one'
+    high, low = (bands == 'pos') | one, (bands == 'neg') | (bands == 'neg_sat')
+    assert not (bands == 'edge').any() and probs.dtype == np.float32
+    figures = (float(d[mid].max()), float(d[high].max()), float((d[low] / want_p[low]).max()))
+    print('probabilities: mid %.3g, pos and one %.3g (2^-23 = %.3g), neg and neg_sat relative %.3g' %
+          (figures[0], figures[1], 2.0 ** -23, figures[2]))
+    assert figures[0] <= PROB_TOL
+    assert figures[1] <= 2.0 ** -23
+    assert np.all(probs[one] == np.float32(1.0))
+    assert figures[2] <= SAT_PROB_REL_TOL
+
+
+def check_saturated(batch, y, loss_bias):
+    """one loss_grad call: the probabilities against float64 band by band, then gradients and loss against the float32 head
+    contract fed with the probabilities the kernel reported"""
+    weights, x, masks, n = batch['weights'], batch['x'], batch['masks'], len(batch['x'])
+    t = _lib.HipTrainer(weights, 29, 13)
+    try:
+        loss, grads, probs = t.loss_grad(x, y, masks=masks, loss_bias=loss_bias)
+    finally:
+        t.close()
+    check_probabilities_in_bands(probs, batch['p'], batch['bands'])
+    ds, _, _ = ref.head32(probs, y, loss_bias, n)
+    want = ref.grads_from_ds(weights, x, masks, ds)
+    worst = {}
+    for name, g in zip(ref.NAMES, np.split(grads.astype(np.float64), np.cumsum([13 * 60, 20 * 60, 60, 20]))):
+        w = want[name].reshape(-1)
+        scale = float(np.abs(w).max())
+        worst[name] = float(np.abs(g - w).max()) / scale if scale > 0 else (0.0 if not g.any() else float('inf'))
+    want_loss = ref.head32_loss(probs, y, loss_bias)
+    d_loss = rel_err(loss, want_loss)
+    tol = SAT_GRAD_TOL_MASKS if masks is not None else SAT_GRAD_TOL
+    print('bias %g, %d of %d targets 1: grads %s (bound %.3g) loss %.7g, relative %.3g' %
+          (loss_bias, int(y.sum()), n, ' '.join('%s %.3g' % kv for kv in worst.items()), tol, loss, d_loss))
+    assert np.all(np.isfinite(grads))
+    assert max(worst.values()) <= tol, worst
+    assert d_loss <= SAT_LOSS_REL_TOL
+    return loss, grads, probs
+
+
+SAT_CASES = [(targets, loss_bias, 0.0) for targets in ('random', 'zeros', 'ones') for loss_bias in (0.7, 0.0, 1.0)] + \
+    [('random', 0.7, 0.2)]                                                       # (the last one with supplied masks)
+
+
+@pytest.mark.parametrize('targets,loss_bias,rate', SAT_CASES)
+def test_gradients_saturated_head(stock_weights, targets, loss_bias, rate):
+    batch = saturated_batch(stock_weights, SAT_N, ALL_BUT_EDGE, rate)
+    check_saturated(batch, saturated_targets(targets, SAT_N), loss_bias)
+
+
+def test_head_is_the_float32_contract_bit_for_bit(stock_weights):
+    """A batch of ONE sample under a dense kernel of zeros: the logit is dense_bias, and the gradient of dense_bias is
+    0 + 1.0f ds (then fifteen times + 1.0f 0 for the empty places of the tile), which no rounding touches.  So it shows the
+    kernel's ds itself, and that is head32 of the reported probability to the bit.  The sweeps cross the logits where 1 - p
+    (11 .. 18, to p == 1.0f) or p (-17.5 .. -14.5) is within a few binades of eps: there a q or pe formed in another order
+    is off by whole ulps, and one formed in another precision rounds to the neighbouring float32 on about one point in ten."""
+    weights = dict(stock_weights, dense_kernel=np.zeros((20, 1), dtype=np.float32), dense_bias=np.zeros(1, dtype=np.float32))
+    x = candidates('n01', 1, seed=9)
+    t = _lib.HipTrainer(weights, 29, 13)
+    theta = t.get_weights()
+    seen = set()
+    try:
+        for lo, hi, n in ((-17.5, -14.5, 256), (11.0, 18.0, 128), (-8.0, 8.0, 16)):
+            for logit in np.linspace(lo, hi, n).astype(np.float32):
+                theta[-1] = logit
+                t.set_weights(theta)
+                for y in (0.0, 1.0):
+                    target = np.array([y], dtype=np.float32)
+                    _, grads, probs = t.loss_grad(x, target, loss_bias=0.7)
+                    ds = np.float32(ref.head32(probs, target, 0.7, 1)[0][0])              # (a float32 widened: exact)
+                    # (the logit is exact here; expf to a few ulps and two roundings: 2^-23 absolute or 1e-6 relative)
+                    assert abs(float(probs[0]) - 1.0 / (1.0 + np.exp(-float(logit)))) <= max(2.0 ** -23, 1e-6 * float(probs[0]))
+                    same = grads[-1] == 0 if ds == 0 else np.float32(grads[-1]).view(np.uint32) == ds.view(np.uint32)
+                    assert same, (float(logit), y, float(probs[0]), float(grads[-1]), float(ds))
+                    assert not grads[:-21].any()                 # delta_T = ds w_d = 0: nothing reaches the GRU
+                seen.add(float(probs[0]))
+    finally:
+        t.close()
+    assert 1.0 in seen and len(seen) >= 256                             # (p == 1.0f reached; the sweeps did not collapse)
+
+
+def test_certain_and_wrong_batch_has_zero_gradient(stock_weights):
+    """p == 1.0f: ds is exactly +-0 whatever the target (float32 Keras alike), so the batch teaches nothing -- by contract"""
+    n, beta, rho = 33, 0.7, 0.9
+    batch = saturated_batch(stock_weights, n, ('one',))
+    x, y = batch['x'], targets_for(n, 41)
+    assert 8 <= y.sum() <= n - 8
+    other = saturated_batch(stock_weights, n, ('mid',))
+    t = _lib.HipTrainer(batch['weights'], 29, 13)
+    try:
+        loss, grads, probs = t.loss_grad(x, y, loss_bias=beta)
+        assert np.all(probs == np.float32(1.0))
+        assert np.array_equal(grads, np.zeros_like(grads))                      # every entry +0.0 or -0.0, none NaN
+        eps32 = float(np.float32(ref.EPS))
+        _, _, pos_term = ref.head32(np.ones(n, dtype=np.float32), y, beta, n)
+        b = float(np.float32(beta))
+        want_loss = b * float(np.mean(1.0 - y)) * -np.log(eps32) + (1.0 - b) * float(np.mean(pos_term))
+        print('loss %.7g, expected %.7g: relative %.3g' % (loss, want_loss, rel_err(loss, want_loss)))
+        assert rel_err(loss, want_loss) <= SAT_LOSS_REL_TOL
+        # a step on that batch moves nothing
+        theta = t.get_weights()
+        t.set_data(np.concatenate([x, other['x']]), np.concatenate([y, targets_for(n, 42)]))
+        certain, ordinary = np.arange(n, dtype=np.int32), np.arange(n, 2 * n, dtype=np.int32)
+        step_loss = t.step(certain, 0.0, 0, 0, beta, 1e-3, rho, 1e-7, 0)
+        assert np.float32(step_loss) == np.float32(loss)
+        assert np.array_equal(t.get_weights().view(np.uint32), theta.view(np.uint32))
+        assert np.array_equal(t.get_accumulators(), np.zeros_like(theta))
+        # with accumulators loaded by an ordinary step (the weights put back): the weights stay, the accumulators decay by rho
+        t.step(ordinary, 0.0, 0, 1, beta, 1e-3, rho, 1e-7, 0)
+        loaded = t.get_accumulators()
+        assert np.count_nonzero(loaded) >= loaded.size / 2 and not np.array_equal(t.get_weights(), theta)
+        t.set_weights(theta)
+        t.step(certain, 0.0, 0, 2, beta, 1e-3, rho, 1e-7, 0)
+        assert np.array_equal(t.get_weights().view(np.uint32), theta.view(np.uint32))
+        decayed = (np.float64(np.float32(rho)) * loaded.astype(np.float64)).astype(np.float32)   # train_rmsprop with g = 0
+        assert np.array_equal(t.get_accumulators().view(np.uint32), decayed.view(np.uint32))
+    finally:
+        t.close()
+
+
+def test_forward_only_paths_agree_in_saturation(stock_weights):
+    batch = saturated_batch(stock_weights, SAT_N, ALL_BUT_EDGE)
+    weights, x, y = batch['weights'], batch['x'], saturated_targets('random', SAT_N)
+    single, group = _lib.HipTrainer(weights, 29, 13), _lib.HipTrainer([weights], 29, 13)
+    try:
+        loss, _, probs = single.loss_grad(x, y, loss_bias=0.7)
+        check_probabilities_in_bands(probs, batch['p'], batch['bands'])
+        group.set_data(x[::-1], y[::-1])
+        rows = np.arange(SAT_N - 1, -1, -1, dtype=np.int32)
+        results = {'evaluate': single.evaluate(x, y, loss_bias=0.7)}
+        for name, (l, a, p) in (('evaluate_models', group.evaluate_models(x, y, loss_bias=0.7)),
+                                ('evaluate_indices', group.evaluate_indices(rows, loss_bias=0.7))):
+            assert l.shape == a.shape == (1,) and p.shape == (1, SAT_N)
+            results[name] = (float(l[0]), float(a[0]), p[0])
+    finally:
+        single.close()
+        group.close()
+    want_acc = float(np.float32(np.mean(np.rint(probs) == y)))                   # (acc_out is a float32)
+    for name, (l, a, p) in results.items():
+        print('%s: loss %.7g against %.7g, accuracy %.6g' % (name, l, loss, a))
+        assert np.array_equal(p.view(np.uint32), probs.view(np.uint32)), name
+        assert rel_err(l, loss) <= SAT_LOSS_REL_TOL, name
+        assert a == want_acc, name
+
+
+def test_saturated_head_beside_other_networks(stock_weights):
+    """test_train_models.test_alone_equals_together on a batch whose tiles mix zero-gradient and ordinary samples"""
+    batch = saturated_batch(stock_weights, SAT_N, ALL_BUT_EDGE)
+    x, y = batch['x'], saturated_targets('random', SAT_N)
+    tiles = batch['bands'].reshape(-1, 16)
+    assert sum(('one' in tile) and ('mid' in tile) for tile in tiles) >= len(tiles) / 2
+    models = [synth.make_weights(13, (8,), seed=3), batch['weights']]
+    hp = dict(dropout_rate=(0.2, 0.0), seed=(7, 8), loss_bias=(0.3, 0.7), lr=(1e-3, 1e-3))
+    idx = np.arange(SAT_N, dtype=np.int32)
+    alone = []
+    for m, w in enumerate(models):
+        t = _lib.HipTrainer(w, 29, 13)
+        t.set_data(x, y)
+        loss = t.step(idx, hp['dropout_rate'][m], hp['seed'][m], 4, hp['loss_bias'][m], hp['lr'][m], 0.9, 1e-7, 0)
+        alone.append((np.float32(loss), t.get_weights(), t.get_accumulators()))
+        t.close()
+    g = _lib.HipTrainer(models, 29, 13)
+    g.set_data(x, y)
+    losses = g.step_models(idx, step=4, rho=0.9, eps=1e-7, **hp)
+    theta, accum = g.split(g.get_weights()), g.split(g.get_accumulators())
+    g.close()
+    for m, (loss, w, a) in enumerate(alone):
+        assert np.isfinite(loss) and np.all(np.isfinite(w)) and a.any()
+        assert np.float32(losses[m]).view(np.uint32) == loss.view(np.uint32), m
+        assert np.array_equal(theta[m].view(np.uint32), w.view(np.uint32)), m
+        assert np.array_equal(accum[m].view(np.uint32), a.view(np.uint32)), m
+
+
+def saturated_floors(stock_weights):
+    """CPU only: the float32 floors the SAT_* bounds are 20x of, over the cases of test_gradients_saturated_head, with
+    torch float32 in the kernel's place (its probabilities enter head32 as the kernel's do).  Not a test:
+    ``PYTHONPATH=. python tests/test_train.py`` prints them."""
+    import torch
+    floors = {}
+    for targets, loss_bias, rate in SAT_CASES:
+        batch = saturated_batch(stock_weights, SAT_N, ALL_BUT_EDGE, rate)
+        weights, x, masks, y = batch['weights'], batch['x'], batch['masks'], saturated_targets(targets, SAT_N)
+        p32 = ref.forward_numpy(weights, x, masks, dtype=torch.float32)['p'].astype(np.float32)
+        low = (batch['bands'] == 'neg') | (batch['bands'] == 'neg_sat')
+        prob = float((np.abs(p32.astype(np.float64) - batch['p']) / batch['p'])[low].max())
+        ds = ref.head32(p32, y, loss_bias, SAT_N)[0]
+        g64, g32 = ref.grads_from_ds(weights, x, masks, ds), ref.grads_from_ds(weights, x, masks, ds, dtype=torch.float32)
+        grad = max(float(np.abs(g32[k] - g64[k]).max() / np.abs(g64[k]).max()) for k in ref.NAMES if g64[k].any()) if ds.any() else 0.0
+        tp, ty, eps, b = torch.tensor(p32), torch.tensor(y), torch.tensor(np.float32(ref.EPS)), torch.tensor(np.float32(loss_bias))
+        loss32 = b * (-(1 - ty) * torch.log((1 - tp) + eps)).mean() + (1 - b) * (-ty * torch.log(tp + eps)).mean()
+        loss = rel_err(float(loss32), ref.head32_loss(p32, y, loss_bias))
+        print('%-6s bias %g rate %g: probabilities (neg, neg_sat) %.3g, gradients %.3g, loss %.3g' %
+              (targets, loss_bias, rate, prob, grad, loss))
+        key = 'masks' if rate > 0 else 'plain'
+        floors[key] = [max(u, v) for u, v in zip(floors.get(key, (0.0, 0.0, 0.0)), (prob, grad, loss))]
+    return floors
 
 
 def test_unsupported_shapes_are_refused_by_name():
@@ -327,3 +603,13 @@ def test_trained_model_round_trip(tmp_path, stock_weights):
     assert any(not np.array_equal(a, b) for a, b in zip(loaded['gru'][0], stock_weights['gru'][0]))
     got = HipRunner(path).predict(x)
     assert float(np.abs(got - want).max()) <= 1e-5
+
+
+if __name__ == '__main__':
+    from conftest import golden
+    stock = golden('weights_stock_seed42.npz')
+    for name, (prob, grad, loss) in saturated_floors({'gru': [(stock['kernel'], stock['recurrent_kernel'], stock['bias'])],
+                                                      'dense_kernel': stock['dense_kernel'],
+                                                      'dense_bias': stock['dense_bias']}).items():
+        print('%s: float32 floors: probabilities %.3g, gradients %.3g, loss %.3g; 20x: %.3g, %.3g, %.3g' %
+              (name, prob, grad, loss, 20 * prob, 20 * grad, 20 * loss))

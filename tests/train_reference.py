@@ -7,6 +7,10 @@ reference's ``weighted_log_loss`` (functions.py:47-50) and gradients by torch au
 may be lowered to float32 to measure the float32 floor).  It also returns every gate pre-activation and the logit, from which
 the tests pick kink-safe samples: the hard sigmoid has kinks at pre-activation +-2.5, and a float32 kernel may legitimately
 land on the other side of one.
+
+Beyond |logit| of about 8 the float64 head is no reference for the kernel any more: the head is float32 by contract (DESIGN.md
+4.9).  ``head32`` restates it in numpy float32, ``grads_from_ds`` is the float64 backward pass behind a given ds, and
+``logit_bands`` names the regions of the logit the tests pick their samples from.
 """
 import numpy as np
 import torch
@@ -88,12 +92,74 @@ def kink_safe(res, delta=1e-3, max_logit=8.0) -> np.ndarray:
     return far & (np.abs(res['logit']) <= max_logit)
 
 
-def pick_kink_safe(weights, x, masks=None, delta=1e-3):
-    """indices of the kink-safe candidates (the forward pass does not depend on the targets)"""
-    params = tensors(weights, requires_grad=False)
+def forward_numpy(weights, x, masks=None, dtype=torch.float64):
+    """``forward`` without a graph, as float64 numpy arrays (``dtype`` float32: the float32 floor of the forward pass)"""
+    params = tensors(weights, dtype, requires_grad=False)
     with torch.no_grad():
-        out = {k: v.numpy() for k, v in forward(params, x, masks).items()}
-    return np.flatnonzero(kink_safe(out, delta))
+        return {k: v.double().numpy() for k, v in forward(params, x, masks).items()}
+
+
+def pick_kink_safe(weights, x, masks=None, delta=1e-3, max_logit=8.0):
+    """indices of the kink-safe candidates (the forward pass does not depend on the targets)"""
+    return np.flatnonzero(kink_safe(forward_numpy(weights, x, masks), delta, max_logit))
+
+
+# ---- the float32 head (DESIGN.md 4.9, "The head is float32 by contract") -------------------------------------------------
+BANDS = ('neg_sat', 'neg', 'mid', 'pos', 'edge', 'one')
+
+
+def logit_bands(logit) -> np.ndarray:
+    """[N] of BANDS: neg_sat (-inf, -19], neg (-19, -8], mid (-8, 8), pos [8, 17), edge [17, 19), one [19, inf).
+    From 19 upward 1 - sigmoid <= 5.6e-9 < 2^-25, so the float32 sigmoid is 1.0f whatever the last bits of the logit;
+    in ``edge`` it may be 1.0f or one or two ulps below."""
+    logit = np.asarray(logit, dtype=np.float64)
+    out = np.full(logit.shape, 'mid', dtype='<U7')
+    out[logit <= -8.0] = 'neg'
+    out[logit <= -19.0] = 'neg_sat'
+    out[logit >= 8.0] = 'pos'
+    out[logit >= 17.0] = 'edge'
+    out[logit >= 19.0] = 'one'
+    return out
+
+
+def head32(p, y, loss_bias, n):
+    """The head in float32, every operation rounded where the training kernel rounds it: p, y float32 (scalars or [N]),
+    n the batch size the means divide by -> (ds, loss_neg, loss_pos) as float64.
+
+        q = fl(fl(1 - p) + eps)                 pe = fl(p + eps)                           eps = fl32(1e-7)
+        dp = fl(fl(fl(fl(b (1 - y)) / q) - fl(fl(fl(1 - b) y) / pe)) inv_n)              b = fl32(loss_bias), inv_n = fl(1 / n)
+        ds = fl(fl(dp p) (1 - p))
+
+    loss_neg = -(1 - y) log(q) and loss_pos = -y log(pe) per sample, the logarithms taken in float64 OF the float32 q and
+    pe; the loss is b mean(loss_neg) + (1 - b) mean(loss_pos).  At p == 1.0f q is eps, dp is finite and ds is exactly +-0."""
+    f = np.float32
+    p, y = np.asarray(p, dtype=f), np.asarray(y, dtype=f)
+    one, eps, beta = f(1.0), f(EPS), f(loss_bias)
+    inv_n = one / f(n)
+    q = (one - p) + eps
+    pe = p + eps
+    dp = ((beta * (one - y)) / q - ((one - beta) * y) / pe) * inv_n
+    ds = (dp * p) * (one - p)
+    assert all(v.dtype == f for v in (q, pe, dp, ds))
+    y64 = y.astype(np.float64)
+    return ds.astype(np.float64), -(1.0 - y64) * np.log(q.astype(np.float64)), -y64 * np.log(pe.astype(np.float64))
+
+
+def head32_loss(p, y, loss_bias) -> float:
+    """the loss of the batch from ``head32``'s per-sample terms, the means and the weighting in float64"""
+    _, neg, pos = head32(p, y, loss_bias, len(np.atleast_1d(p)))
+    beta = float(np.float32(loss_bias))
+    return beta * float(np.mean(neg)) + (1.0 - beta) * float(np.mean(pos))
+
+
+def grads_from_ds(weights, x, masks, ds, dtype=torch.float64):
+    """The Jacobian of the logits contracted with a GIVEN ds [N] (autograd over ``forward``): what the backward pass owes
+    once the head has spoken -> {name: array in the Keras shapes} as float64 numpy (``dtype`` float32: the float32 floor)"""
+    params = tensors(weights, dtype)
+    logit = forward(params, x, masks)['logit']
+    seed = torch.as_tensor(np.asarray(ds, dtype=np.float64).reshape(-1), dtype=dtype)
+    grads = torch.autograd.grad(logit, params, grad_outputs=seed)
+    return {name: g.double().numpy() for name, g in zip(NAMES, grads)}
 
 
 def rmsprop(theta, accum, g, lr=1e-3, rho=0.9, eps=1e-7):
