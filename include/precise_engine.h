@@ -514,8 +514,9 @@ int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms);
  * pe_trainer is independent of every pe_engine: it owns the parameters, the RMSprop accumulators and (pe_trainer_set_data) a
  * dataset on ONE device; it is not thread-safe; every entry point takes host pointers and synchronises.  The arithmetic
  * contract -- forward with Keras' per-gate input dropout, loss, backward, RMSprop -- is DESIGN.md 4.9; everything is float32.
- * Scope: ONE GRU layer of 1..32 units, feature_size 1..32, n_features 1..64; anything else is PE_ERR_UNSUPPORTED naming the
- * field, before any device work (stacked / wide networks and bf16 have no training kernel).
+ * Scope of pe_trainer_create[_models]: ONE GRU layer of 1..32 units, feature_size 1..32, n_features 1..64; anything else is
+ * PE_ERR_UNSUPPORTED naming the field, before any device work (stacked networks and bf16 have no training kernel).
+ * pe_trainer_create_wide has the same scope with units 1..256; see below.
  * Flat parameter order, used for weights, gradients and accumulators alike (Keras layout, gate order z|r|h):
  *   kernel[F][3H] | recurrent_kernel[H][3H] | bias[3H] | dense_kernel[H] | dense_bias      = pe_trainer_n_params floats.
  * PE_ERR_INVALID, before any device work and with the outputs untouched: null pointers, n <= 0, indices outside the dataset,
@@ -540,6 +541,16 @@ int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights
  * PE_ERR_UNSUPPORTED naming n_models; every refusal happens before any device work. */
 int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
                              pe_trainer** out);
+/* pe_trainer_create_models with units 1..256 per network, in any mix of widths; the refusals and their messages are the same
+ * with that range.  The handle is an ordinary pe_trainer: every pe_trainer_* entry point, pe_miner_append,
+ * pe_generator_append and pe_augmenter_append work on it unchanged.  A network of at most 32 units gets the bits it has in
+ * a pe_trainer_create_models trainer.  A network of 33..256 units trains on the f32 matrix cores (csrc/
+ * gru_train_wide_device.h) under the same arithmetic contract; its sums run in an order fixed by (n, n_features,
+ * feature_size, units) alone, so the same call gives the same bits every time, next to whatever other networks, and
+ * pe_trainer_step equals pe_trainer_loss_grad on the gathered rows followed by pe_trainer_apply.  A step keeps its tape on
+ * the device: about 20 (units rounded up to 16) + 12 feature_size bytes per sample and timestep. */
+int pe_trainer_create_wide(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
+                           pe_trainer** out);
 int pe_trainer_destroy(pe_trainer* t);
 const char* pe_trainer_last_error(const pe_trainer* t);
 int pe_trainer_n_models(const pe_trainer* t);          /* -1 for a null trainer */

@@ -144,6 +144,7 @@ EXPORTS = {
                                   C.c_float, C.c_float, C.c_int32, C.c_void_p]),
     'pe_trainer_evaluate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_trainer_create_models': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    'pe_trainer_create_wide': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     'pe_trainer_n_models': (C.c_int, [C.c_void_p]),
     'pe_trainer_n_params_model': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_trainer_step_models': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(PeTrainHparams), C.c_void_p]),
@@ -869,9 +870,12 @@ class HipTrainer:
     ``weights`` is one weights dict, or a list of them: then the trainer owns that many networks (their ``units`` may differ),
     trains them on the same batches in one launch (``step_models``) and evaluates them together (``evaluate_models``); the
     flat vector is the concatenation in model order, ``units`` and ``n_params`` are lists, ``n_params_total`` the length.
+
+    ``wide=False``: networks of 1..32 units (pe_trainer_create[_models]); ``wide=True``: 1..256 units in any mix
+    (pe_trainer_create_wide), the wider ones trained on the matrix cores.  Everything else is the same trainer.
     """
 
-    def __init__(self, weights, n_features, feature_size, device=0):
+    def __init__(self, weights, n_features, feature_size, device=0, wide=False):
         self._lib = load()
         self._h = C.c_void_p()
         many = isinstance(weights, (list, tuple))
@@ -881,7 +885,9 @@ class HipTrainer:
         for m, wm in enumerate(models):
             ws[m], held = _pe_weights(wm)
             keep.append(held)
-        if many:
+        if wide:
+            rc = self._lib.pe_trainer_create_wide(int(n_features), int(feature_size), ws, len(models), int(device), C.byref(self._h))
+        elif many:
             rc = self._lib.pe_trainer_create_models(int(n_features), int(feature_size), ws, len(models), int(device), C.byref(self._h))
         else:
             rc = self._lib.pe_trainer_create(int(n_features), int(feature_size), ws, int(device), C.byref(self._h))

@@ -7,6 +7,7 @@
 #include "gru_cw_pack.h"
 #include "mfcc_general_device.h"
 #include "gru_train_device.h"
+#include "gru_train_wide_device.h"
 #include "mine_device.h"
 #include "sample_device.h"
 #include "generate_device.h"
@@ -2645,6 +2646,7 @@ struct TrainSet {                           // a resident set: pe_trainer_set_da
 
 struct pe_trainer {
     int device = 0;
+    bool wide = false;              // pe_trainer_create_wide: networks of more than kTrainMaxUnits units take launch_train_wide
     int T = 0, F = 0, K = 0, n_params = 0;  // n_params: the total over the networks
     int H[kTrainMaxModels] = {}, ofs[kTrainMaxModels + 1] = {};        // units; offset of a network's flat vector
     std::string err;
@@ -2658,8 +2660,9 @@ struct pe_trainer {
     int sample_n = 0, n_selected = 0;
     // buffers that grow with the largest call: 0 feats, 1 targets, 2 masks, 3 indices, 4 tape, 5 partial, 6 probs,
     // 7 / 8 dataset, 9 / 10 validation set, 11 the scratch of pe_trainer_stats_models (StatsScratch),
-    // 12 selection state bytes, 13 selection list, 14 the scratch of pe_trainer_sample_choose
-    DeviceBuf buf[15];
+    // 12 selection state bytes, 13 selection list, 14 the scratch of pe_trainer_sample_choose,
+    // 15..19 the wide path's tape records, dL/dh_T, transposed recurrent kernel, per-tile partials, per-chunk gradient partials
+    DeviceBuf buf[20];
 };
 
 namespace {
@@ -2702,27 +2705,29 @@ int train_check_targets(pe_trainer* t, const float* y, int n) {
 // "model 2: " in front of a per-network complaint of a trainer of several
 std::string train_model_prefix(int n_models, int m) { return n_models > 1 ? "model " + std::to_string(m) + ": " : std::string(); }
 
-// Forward (+ backward) of every network over n samples, and the reduction.  The caller has filled a.n / feats / targets /
-// indices / masks / apply and, per network, mask_* / beta / lr / rho / eps / frozen_mask; the rest is set here.
-int train_run(pe_trainer* t, TrainArgs& a, bool backward) {
+// Forward (+ backward) of the networks [m0, m1) (each of at most kTrainMaxUnits units) over n samples in one launch, and the
+// reduction.  a0.model[m] holds what the caller set for network m of the trainer.
+int train_run_narrow(pe_trainer* t, const TrainArgs& a0, bool backward, int m0, int m1) {
+    TrainArgs a = a0;
     const int blocks = (a.n + kTrainTile - 1) / kTrainTile;
     int widest = 0;
-    for (int m = 0; m < t->K; ++m) widest = std::max(widest, t->H[m]);
-    a.T = t->T; a.F = t->F; a.n_models = t->K;
+    for (int m = m0; m < m1; ++m) widest = std::max(widest, t->H[m]);
+    a.T = t->T; a.F = t->F; a.n_models = m1 - m0;
     a.backward = backward ? 1 : 0;
     a.n_blocks = blocks;
     a.threads = train_threads(widest);
-    a.n_total = t->n_params;
+    a.n_total = t->ofs[m1] - t->ofs[m0];
     a.inv_n = 1.0f / (float)a.n;
-    a.theta = t->theta;
-    a.accum = t->accum;
-    a.grads = backward ? t->grads : nullptr;
-    a.loss = t->loss;
+    a.theta = t->theta + t->ofs[m0];
+    a.accum = t->accum + t->ofs[m0];
+    a.grads = backward ? t->grads + t->ofs[m0] : nullptr;
+    a.loss = t->loss + m0;
     size_t tape = 0, partial = 0;
-    for (int m = 0; m < t->K; ++m) {
-        TrainModel& r = a.model[m];
+    for (int m = m0; m < m1; ++m) {
+        TrainModel& r = a.model[m - m0];
+        r = a0.model[m];
         r.H = t->H[m];
-        r.ofs = t->ofs[m];
+        r.ofs = t->ofs[m] - t->ofs[m0];
         r.tape_ofs = tape;
         r.partial_ofs = partial;
         if (backward) tape += (size_t)blocks * t->T * 4 * a.threads;
@@ -2731,12 +2736,71 @@ int train_run(pe_trainer* t, TrainArgs& a, bool backward) {
     int rc = train_reserve(t, 5, partial * sizeof(float));
     if (rc) return rc;
     if (backward && (rc = train_reserve(t, 4, tape * sizeof(float)))) return rc;
-    if ((rc = train_reserve(t, 6, (size_t)t->K * a.n * sizeof(float)))) return rc;
     a.tape = static_cast<float*>(t->buf[4].p);
     a.partial = static_cast<float*>(t->buf[5].p);
-    a.probs = static_cast<float*>(t->buf[6].p);
+    a.probs = static_cast<float*>(t->buf[6].p) + (size_t)m0 * a.n;
     PE_THIP(t, launch_train(a, nullptr));
     PE_THIP(t, launch_train_reduce(a, nullptr));
+    return PE_OK;
+}
+
+// The same for ONE network of more than kTrainMaxUnits units (gru_train_wide_device.h)
+int train_run_wide(pe_trainer* t, const TrainArgs& a0, bool backward, int m) {
+    const TrainModel& r = a0.model[m];
+    TrainWideArgs w{};
+    w.n = a0.n; w.T = t->T; w.F = t->F; w.H = t->H[m]; w.Hp = tw_pad(w.H);
+    w.n_tiles = (a0.n + 15) / 16;
+    w.backward = backward ? 1 : 0;
+    w.apply = a0.apply;
+    w.frozen_mask = r.frozen_mask;
+    w.mask_mode = r.mask_mode;
+    w.rate = r.rate; w.keep_scale = r.keep_scale; w.beta = r.beta;
+    w.inv_n = 1.0f / (float)a0.n;
+    w.lr = r.lr; w.rho = r.rho; w.eps = r.eps;
+    w.mask_key = r.mask_key;
+    w.theta = t->theta + t->ofs[m];
+    w.accum = t->accum + t->ofs[m];
+    w.grads = t->grads + t->ofs[m];
+    w.loss = t->loss + m;
+    w.feats = a0.feats; w.targets = a0.targets; w.indices = a0.indices; w.masks = a0.masks;
+    int rc = train_reserve(t, 18, (size_t)w.n_tiles * (w.H + 3) * sizeof(float));
+    if (rc) return rc;
+    if (backward) {
+        const long long records = (long long)w.n_tiles * w.T;
+        if ((rc = train_reserve(t, 15, (size_t)records * tw_record(w.F, w.Hp) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 16, (size_t)w.n_tiles * w.Hp * 16 * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 17, (size_t)3 * w.Hp * w.Hp * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 19, (size_t)tw_chunks(records) * train_n_gru(w.F, w.H) * sizeof(float)))) return rc;
+    }
+    w.tape = static_cast<float*>(t->buf[15].p);
+    w.fin = static_cast<float*>(t->buf[16].p);
+    w.ut = static_cast<float*>(t->buf[17].p);
+    w.partial = static_cast<float*>(t->buf[18].p);
+    w.gpart = static_cast<float*>(t->buf[19].p);
+    w.probs = static_cast<float*>(t->buf[6].p) + (size_t)m * a0.n;
+    PE_THIP(t, launch_train_wide(w, nullptr));
+    return PE_OK;
+}
+
+// Forward (+ backward) of every network over n samples, and the reduction.  The caller has filled a.n / feats / targets /
+// indices / masks / apply and, per network, mask_* / beta / lr / rho / eps / frozen_mask; the rest is set here.  Runs of
+// neighbouring networks of at most kTrainMaxUnits units share a launch, as they do in a pe_trainer_create_models trainer (a
+// network's bits do not depend on its company); every wider network has its own launches.
+int train_run(pe_trainer* t, TrainArgs& a, bool backward) {
+    int rc = train_reserve(t, 6, (size_t)t->K * a.n * sizeof(float));
+    if (rc) return rc;
+    a.probs = static_cast<float*>(t->buf[6].p);
+    for (int m = 0; m < t->K;) {
+        if (t->H[m] > kTrainMaxUnits) {
+            if ((rc = train_run_wide(t, a, backward, m))) return rc;
+            ++m;
+            continue;
+        }
+        int m1 = m + 1;
+        while (m1 < t->K && t->H[m1] <= kTrainMaxUnits) ++m1;
+        if ((rc = train_run_narrow(t, a, backward, m, m1))) return rc;
+        m = m1;
+    }
     return PE_OK;
 }
 
@@ -2889,8 +2953,9 @@ int pe_trainer_destroy(pe_trainer* t) {
     return PE_OK;
 }
 
-int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
-                             pe_trainer** out) {
+namespace {
+int trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device, pe_trainer** out,
+                   const int max_units) {
     if (!init || !out) return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: null argument");
     *out = nullptr;
     if (n_models < 1) return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: n_models = %d", n_models);
@@ -2908,7 +2973,7 @@ int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_
         if (!w.layers || !w.layers[0].kernel || !w.layers[0].recurrent_kernel || !w.layers[0].bias || !w.dense_kernel)
             return tfail(nullptr, PE_ERR_INVALID, "%spe_trainer_create: null weight array", pre.c_str());
         const int H = w.layers[0].units;
-        if (H < 1 || H > kTrainMaxUnits) return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: units = %d (1..%d)", pre.c_str(), H, kTrainMaxUnits);
+        if (H < 1 || H > max_units) return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: units = %d (1..%d)", pre.c_str(), H, max_units);
         if (w.layers[0].n_in != feature_size)
             return tfail(nullptr, PE_ERR_INVALID, "%sthe GRU layer takes %d inputs, feature_size is %d", pre.c_str(), w.layers[0].n_in, feature_size);
     }
@@ -2916,6 +2981,7 @@ int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_
     if (herr != hipSuccess) return tfail(nullptr, PE_ERR_HIP, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(herr));
     pe_trainer* t = new pe_trainer;
     t->device = device;
+    t->wide = max_units > kTrainMaxUnits;
     t->T = n_features; t->F = feature_size; t->K = n_models;
     for (int m = 0; m < n_models; ++m) {
         t->H[m] = init[m].layers[0].units;
@@ -2952,6 +3018,17 @@ int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_
     }
     *out = t;
     return PE_OK;
+}
+}  // namespace
+
+int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
+                             pe_trainer** out) {
+    return trainer_create(n_features, feature_size, init, n_models, device, out, kTrainMaxUnits);
+}
+
+int pe_trainer_create_wide(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
+                           pe_trainer** out) {
+    return trainer_create(n_features, feature_size, init, n_models, device, out, kTwMaxUnits);
 }
 
 int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t device, pe_trainer** out) {

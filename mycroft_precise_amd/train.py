@@ -59,7 +59,9 @@ def unflatten_weights(flat, feature_size: int, units: int) -> dict:
 class Trainer:
     """``weights``: a weights dict to continue from; None = ``create_model``'s random network for the current ``pr`` and
     ``params.recurrent_units``.  ``params`` supplies ``dropout``, ``loss_bias`` (the reference passes ``1.0 - sensitivity``,
-    scripts/train.py:86) and ``freeze_till``.  ``seed`` drives the initial network, the shuffle and the dropout masks."""
+    scripts/train.py:86) and ``freeze_till``.  ``seed`` drives the initial network, the shuffle and the dropout masks.
+    ``recurrent_units`` 1..256: up to 32 units ``pe_trainer_create``, wider networks ``pe_trainer_create_wide``
+    (the matrix-core kernels of DESIGN.md 4.15); the trainer is the same object either way."""
 
     def __init__(self, weights=None, params: ModelParams = None, seed: int = 42, device: int = 0, n_features: int = None):
         self.params = params or ModelParams()
@@ -71,7 +73,7 @@ class Trainer:
         k, rk, _ = weights['gru'][0]
         self.feature_size, self.units = int(np.shape(k)[0]), int(np.shape(rk)[0])
         self.n_features = int(pr.n_features if n_features is None else n_features)
-        self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device)
+        self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, wide=self.units > 32)
         self._rng = np.random.default_rng(self.seed)
         self._step = 0                   # optimizer steps taken so far: the dropout masks' step counter
         self.frozen_mask = ((1 << max(0, int(self.params.freeze_till))) - 1) & 3      # model.py:84-85: layers[:freeze_till]
@@ -200,7 +202,9 @@ class Trainer:
 
 
 class TrainerGroup:
-    """K candidate networks trained together on ONE resident dataset (``pe_trainer_create_models``).
+    """K candidate networks trained together on ONE resident dataset (``pe_trainer_create_models``; with a
+    candidate of more than 32 units ``pe_trainer_create_wide``, DESIGN.md 4.15: widths 1..256 in any mix, the narrow ones with
+    the bits they have in a narrow group).
 
     ``candidates``: a list of ``ModelParams``; ``recurrent_units``, ``dropout``, ``loss_bias`` and ``freeze_till`` mean what
     they mean to ``Trainer``.  ``seeds[m]`` (default: ``seed`` for every candidate) drives candidate m's initial network and its
@@ -230,7 +234,7 @@ class TrainerGroup:
         self.feature_size = sizes.pop()
         self.units = [int(np.shape(w['gru'][0][1])[0]) for w in weights]
         self.n_features = int(pr.n_features if n_features is None else n_features)
-        self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device)
+        self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, wide=max(self.units) > 32)
         self._rng = np.random.default_rng(self.seed)
         self._step = 0
         self.frozen_masks = [((1 << max(0, int(p.freeze_till))) - 1) & 3 for p in self.candidates]
@@ -339,23 +343,40 @@ def trial_reports(group, runner, noise_audios, interaction_estimate=100, ambient
 
     The wake-word side is counted on the group's resident validation set (``TrainerGroup.stats``, two device calls for all
     candidates); the noise side on ``runner``, a K-model ``HipRunner`` that holds ``group.weights``, over ``noise_audios``
-    (``simulate.nww_buckets``, one call).  The reports are kept as ``group.reports`` for ``group.best('cost')``."""
+    (``simulate.nww_buckets``, one call).  A group of several widths takes a list of runners, one per width in the order the
+    widths first appear in ``group.units``, each a multi-model ``HipRunner`` over that width's weights in group order (a
+    multi-model engine holds networks of one width).  The reports are kept as ``group.reports`` for ``group.best('cost')``."""
     from . import annoyance, simulate
     K = len(group)
-    engine = runner.engine
-    if not getattr(engine, '_multi', False) or engine.n_models != K:
-        raise ValueError('trial_reports needs a multi-model HipRunner holding the %d networks of the group (HipRunner(weights=group.weights)), '
-                         'got one of %d model%s' % (K, engine.n_models, '' if getattr(engine, '_multi', False) else ' (single-model form)'))
-    if len(set(group.units)) != 1:
-        raise ValueError('trial_reports: a multi-model engine holds networks of one width, the group has units = %r' % (group.units,))
     thresholds = simulate.default_thresholds()
+    recordings = [np.asarray(a) for a in noise_audios]
+    if isinstance(runner, (list, tuple)):
+        widths = list(dict.fromkeys(group.units))
+        if len(runner) != len(widths):
+            raise ValueError('trial_reports: %d runners for the %d widths of the group, units = %r' % (len(runner), len(widths), group.units))
+        nww = np.zeros((K, len(thresholds)), dtype=np.float64)
+        for r, width in zip(runner, widths):
+            members = [m for m, u in enumerate(group.units) if u == width]
+            engine = r.engine
+            if not getattr(engine, '_multi', False) or engine.n_models != len(members) or engine.units != width:
+                raise ValueError('trial_reports: the runner of the %d candidate%s of %d units must be a multi-model HipRunner holding '
+                                 'their weights in group order' % (len(members), '' if len(members) == 1 else 's', width))
+            nww[members] = simulate.nww_buckets(r, recordings, thresholds, chunk_size).reshape(len(members), -1)
+    else:
+        engine = runner.engine
+        multi = getattr(engine, '_multi', False)
+        if multi and len(set(group.units)) != 1:
+            raise ValueError('trial_reports: a multi-model engine holds networks of one width, the group has units = %r; pass one '
+                             'runner per width' % (group.units,))
+        if not multi or engine.n_models != K:
+            raise ValueError('trial_reports needs a multi-model HipRunner holding the %d networks of the group (HipRunner(weights=group.weights)), '
+                             'got one of %d model%s' % (K, engine.n_models, '' if multi else ' (single-model form)'))
+        nww = simulate.nww_buckets(runner, recordings, thresholds, chunk_size).reshape(K, -1)
     at_half = group.stats((0.5,), validation=True, compare='f32')
     ww = group.stats(thresholds, validation=True, compare='f64')
-    recordings = [np.asarray(a) for a in noise_audios]
     seconds = 0.0
     for a in recordings:                          # (annoyance_estimator.py:67 adds file by file; an empty file adds 0)
         seconds += len(a) / pr.sample_rate
-    nww = simulate.nww_buckets(runner, recordings, thresholds, chunk_size).reshape(K, -1)
     reports = []
     for m in range(K):
         est = annoyance.estimate(ww[m].counts['pos_gt'], ww[m].n_pos, nww[m], seconds, interaction_estimate, ambient_annoyance, thresholds)
