@@ -66,7 +66,11 @@ typedef struct pe_params {
                                 network_runner.py:102,137);  1 = float32 front end        */
     int32_t gru_precision;   /* 0 = float32 matrix cores (reference precision, tol 1e-4);
                                 1 = bf16 operands / float32 accumulate (BASELINE configs[4],
-                                tol 1e-2)                                                    */
+                                tol 1e-2), any network the engine serves: <= 32 units, and wide /
+                                stacked networks of 33..256 units and 1-2 layers (DESIGN.md 4.4:
+                                weights, features, h and r*h of every layer and layer 2's input are
+                                rounded as operands; the carried state stays float32).  Wide
+                                networks take neither use_delta nor ring_precision = 1.      */
     int32_t vectorizer;      /* params.py:121-132: 2 = mfccs (sonopy, the default; also serves the
                                 offline mels entry), 3 = speechpy_mfccs (legacy .params files without
                                 a `vectorizer` key, params.py:147,155): one frame fewer per buffer
@@ -495,6 +499,8 @@ int pe_set_gru_waves(pe_engine* e, int32_t waves_per_tile);
  * across pe_update / pe_update_many / pe_predict): 1 (and -1, the default, where it fits: <= 20 units, <= 14 features) = five
  * gate values per lane (csrc/gru_b20_device.h: 9 MFMAs per timestep), 0 = eight values per lane (csrc/gru_bf16_device.h: 12
  * MFMAs, every width up to 32); 2 is refused.
+ * Wide / stacked bf16-operand networks (gru_precision = 1, 33..256 units or two layers; csrc/gru_wide_bf16_device.h) have ONE
+ * form: 0 is accepted, every other value is PE_ERR_UNSUPPORTED with a message that names the forms.
  * pe_get_gru_tiling: the form this engine's launches take now (0 / 1 / 2; -2 for a null engine). */
 int pe_set_gru_tiling(pe_engine* e, int32_t tiling);
 int pe_get_gru_tiling(const pe_engine* e);

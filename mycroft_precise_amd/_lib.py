@@ -810,13 +810,14 @@ class HipEngine:
     def set_gru_tiling(self, tiling: int):
         """-1 automatic, 0 classic four-tile layout, 1 re-tiled stock width (csrc/gru_cw_device.h), 2 float32 products on the
         bf16 matrix pipe (csrc/gru_x3_device.h; automatic above four stream tiles per compute unit).  bf16 networks: 1 / -1 = five
-        gate values per lane where the network fits (csrc/gru_b20_device.h), 0 = eight (csrc/gru_bf16_device.h)."""
+        gate values per lane where the network fits (csrc/gru_b20_device.h), 0 = eight (csrc/gru_bf16_device.h); wide / stacked
+        bf16 networks (csrc/gru_wide_bf16_device.h) have one form, 0: every other value raises NotImplementedError."""
         self._check(self._lib.pe_set_gru_tiling(self._h, int(tiling)))
 
     def gru_tiling(self) -> int:
         """The form this engine's network launches take now (pe_get_gru_tiling): float32 networks of <= 32 units 0 / 1 / 2 as
         above; wide / stacked networks 0 (f32-input MFMAs) or 2 (float32 products on the bf16 pipe); bf16-operand networks
-        1 (five gate values per lane) or 0 (eight)."""
+        1 (five gate values per lane) or 0 (eight; wide / stacked bf16 networks always)."""
         return int(self._lib.pe_get_gru_tiling(self._h))
 
     def set_timing(self, enabled: bool):

@@ -49,6 +49,8 @@ struct NetPack {
     float* wide_buf[2][6] = {{nullptr}}; float* wide_wd = nullptr;
     // the same network packed for gru_wide_x3_device.h (row i of tile tau = unit 16 tau + i; k-slot 8 gk + e = source unit 16 kappa + 4 gk + e)
     float* wide3_buf[2][6] = {{nullptr}}; float* wide3_wd = nullptr;
+    // ... and with bf16 operands (gru_wide_bf16_device.h; gru_precision = 1): per layer the weight stream of phase 1 and of phase 2 as eight bf16 per lane, b1, b2 as float32(hi + lo)
+    uint16_t* wideb_w[2][2] = {{nullptr}}; float* wideb_b[2][2] = {{nullptr}}; float* wideb_wd = nullptr;
     // bf16-operand network (pe_params.gru_precision = 1)
     uint16_t* wx_bf16 = nullptr; uint16_t* wr_bf16 = nullptr; float* wd_bf16 = nullptr;
     uint32_t* b20_blob = nullptr;     // the same network in the layout of gru_b20_device.h (<= 20 units, <= 14 features)
@@ -701,6 +703,60 @@ int pack_gru_weights_wide_x3(pe_engine* e, NetPack& n, const pe_weights* w) {
     return dev_upload(e, &n.wide3_wd, wd);
 }
 
+// The same network with bf16 operands (gru_wide_bf16_device.h; gru_precision = 1): every kernel entry rounded once (B1), the
+// bias as float32(hi + lo) for the accumulator (B2: the sum is exact).  Wave w owns output tiles tau = w TPW + t of every gate;
+// row i of a tile <-> unit 16 tau + i; k-group kappa, k-slot 8 gk + e <-> source unit 32 kappa + 16 (e >> 2) + 4 gk + (e & 3)
+// (layer 0 input: feature 8 gk + e, gk < 2).  Streams: [wave][kappa][tile][lane] x eight bf16.
+int pack_gru_weights_wide_bf16(pe_engine* e, NetPack& n, const pe_weights* w) {
+    const int H = w->layers[0].units, WV = 4, TPW = H / (16 * WV), KG = H / 32;
+    auto widen = [](uint16_t b) { const uint32_t u = (uint32_t)b << 16; float f; std::memcpy(&f, &u, 4); return f; };
+    for (int l = 0; l < w->n_layers; ++l) {
+        const pe_gru_layer& L = w->layers[l];
+        const int kin = l == 0 ? 1 : KG;
+        const int F = L.n_in;
+        for (int phase = 0; phase < 2; ++phase) {
+            const int NT = phase == 0 ? 2 * TPW : TPW;
+            const int NK = kin + KG;                    // one stream per phase: the input part's k-groups, then the recurrent part's
+            std::vector<uint16_t> ws((size_t)WV * NK * NT * 64 * 8, 0);
+            std::vector<float> bias((size_t)WV * NT * 4 * 64, 0.f);
+            for (int wv = 0; wv < WV; ++wv)
+                for (int tl = 0; tl < NT; ++tl) {
+                    const int gate = phase == 0 ? (tl < TPW ? 0 : 1) : 2;
+                    const int tau = wv * TPW + (tl % TPW);
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int i = lane & 15, gk = lane >> 4;
+                        const int col = gate * H + 16 * tau + i;
+                        for (int kap = 0; kap < kin; ++kap)
+                            for (int ek = 0; ek < 8; ++ek) {
+                                const int src = l == 0 ? (gk < 2 ? 8 * gk + ek : F) : 32 * kap + 16 * (ek >> 2) + 4 * gk + (ek & 3);
+                                if (src < F) ws[((((size_t)wv * NK + kap) * NT + tl) * 64 + lane) * 8 + ek] = to_bf16(L.kernel[(size_t)src * 3 * H + col]);
+                            }
+                        for (int kap = 0; kap < KG; ++kap)
+                            for (int ek = 0; ek < 8; ++ek) {
+                                const int src = 32 * kap + 16 * (ek >> 2) + 4 * gk + (ek & 3);
+                                ws[((((size_t)wv * NK + kin + kap) * NT + tl) * 64 + lane) * 8 + ek] = to_bf16(L.recurrent_kernel[(size_t)src * 3 * H + col]);
+                            }
+                        for (int q = 0; q < 4; ++q) {    // C operand: this lane's output rows 4 gk + q
+                            const float b = L.bias[gate * H + 16 * tau + 4 * gk + q];
+                            const float hi = widen(to_bf16(b));
+                            bias[(((size_t)wv * NT + tl) * 4 + q) * 64 + lane] = hi + widen(to_bf16(b - hi));
+                        }
+                    }
+                }
+            int rc;
+            if ((rc = dev_upload(e, &n.wideb_w[l][phase], ws))) return rc;
+            if ((rc = dev_upload(e, &n.wideb_b[l][phase], bias))) return rc;
+        }
+    }
+    std::vector<float> wd((size_t)WV * TPW * 4 * 64, 0.f);
+    for (int wv = 0; wv < WV; ++wv)
+        for (int tp = 0; tp < TPW; ++tp)
+            for (int q = 0; q < 4; ++q)
+                for (int lane = 0; lane < 64; ++lane)
+                    wd[(((size_t)wv * TPW + tp) * 4 + q) * 64 + lane] = w->dense_kernel[16 * (wv * TPW + tp) + 4 * (lane >> 4) + q];
+    return dev_upload(e, &n.wideb_wd, wd);
+}
+
 // Samples of the virtual stream that must have arrived, counted from a frame's first sample, before the
 // reference's Listener has that frame in its window: the whole analysis window (sonopy emits one frame per
 // full window), plus one hop for the legacy speechpy front end, whose stack_frames returns
@@ -894,6 +950,27 @@ int launch_networks(pe_engine* e, const GruArgs& g, int mode, hipStream_t s, lon
     }
     // two forms of the streamed-weight network (pe_set_gru_tiling): 0 = f32-input MFMAs (gru_wide_device.h), 2 = float32
     // products on the bf16 pipe with the float32 weights split in registers (gru_wide_x3_device.h)
+    // ... and, for gru_precision = 1, the bf16-operand network (gru_wide_bf16_device.h), the engine's only form
+    if (e->prm.gru_precision == 1) {
+        for (int m = 0; m < e->n_models; ++m) {
+            const NetPack& n = e->nets[m];
+            WideArgs wa{};
+            wa.base = with_model(e, g, m);
+            wa.base.out = g.out + (size_t)m * (size_t)out_stride;
+            wa.n_layers = e->n_layers;
+            wa.units = e->units;
+            wa.wd = n.wideb_wd;
+            for (int l = 0; l < e->n_layers; ++l) {
+                wa.layer[l].wx1 = reinterpret_cast<const float4*>(n.wideb_w[l][0]);      // (the whole stream of a phase: input part, then recurrent part)
+                wa.layer[l].wx2 = reinterpret_cast<const float4*>(n.wideb_w[l][1]);
+                wa.layer[l].b1 = n.wideb_b[l][0];
+                wa.layer[l].b2 = n.wideb_b[l][1];
+                wa.layer[l].kx4 = l == 0 ? 1 : e->units / 32;
+            }
+            PE_HIP(e, launch_gru_wide_bf16(wa, mode, s));
+        }
+        return PE_OK;
+    }
     const bool x3 = wide_uses_x3(e);
     for (int m = 0; m < e->n_models; ++m) {
         const NetPack& n = e->nets[m];
@@ -1130,9 +1207,10 @@ int pack_model(pe_engine* e, NetPack& n, const pe_weights* w, const bool wide, c
             e->units = Hp;
             if ((rc = pack_gru_weights_wide(e, n, &wp))) break;
             if ((rc = pack_gru_weights_wide_x3(e, n, &wp))) break;
+            if (e->prm.gru_precision == 1 && (rc = pack_gru_weights_wide_bf16(e, n, &wp))) break;
         }
         else if ((rc = pack_gru_weights(e, n, L, w->dense_kernel))) break;
-        if (e->prm.gru_precision == 1 && (rc = pack_gru_weights_bf16(e, n, L, w->dense_kernel))) break;
+        if (!wide && e->prm.gru_precision == 1 && (rc = pack_gru_weights_bf16(e, n, L, w->dense_kernel))) break;
         if (!wide && b20_eligible(e->prm, L) && (rc = pack_gru_weights_b20(e, n, L, w->dense_kernel))) break;
         if (!wide && x3_eligible(e->prm, L) && (rc = pack_gru_weights_x3(e, n, L, w->dense_kernel))) break;
     } while (false);
@@ -1178,7 +1256,8 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
             if (L2.units > hmax) hmax = L2.units;
         }
         if (hmax > 256) return fail(nullptr, PE_ERR_UNSUPPORTED, "the streamed-weight GRU kernel holds up to 256 units per layer (got %d)", hmax);
-        if (p->use_delta || p->gru_precision != 0) return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta / bf16 have no wide-GRU kernel");
+        if (p->use_delta) return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta has no wide-GRU kernel (networks of more than 32 units or two layers take plain feature rows)");
+        if (p->ring_precision == 1) return fail(nullptr, PE_ERR_UNSUPPORTED, "bf16 feature rows (ring_precision = 1) have no wide-GRU kernel: the bf16-operand wide network (gru_precision = 1) reads float32 rows");
         wide_units = (hmax + 63) / 64 * 64;
     }
     const int feature_size = p->use_delta ? 2 * p->n_mfcc : p->n_mfcc;          // params.py:99-109
@@ -2591,6 +2670,10 @@ int pe_set_gru_waves(pe_engine* e, int32_t waves) {
 int pe_set_gru_tiling(pe_engine* e, int32_t tiling) {
     if (!e) return PE_ERR_INVALID;
     if (tiling < -1 || tiling > 2) return fail(e, PE_ERR_INVALID, "gru tiling must be -1 (auto), 0 (classic), 1 (re-tiled) or 2 (XDL form)");
+    if (e->wide && e->prm.gru_precision == 1) {
+        if (tiling != 0) return fail(e, PE_ERR_UNSUPPORTED, "the bf16-operand wide network (gru_precision = 1) has one form, 0; forms 0 (f32-input MFMAs) and 2 (float32 products on the bf16 pipe) belong to the float32 wide network");
+        return PE_OK;
+    }
     if (e->wide) {
         if (tiling == 1) return fail(e, PE_ERR_UNSUPPORTED, "wide networks have two forms: 0 (f32-input MFMAs) and 2 (float32 products on the bf16 pipe)");
         PE_DRAIN(e);
@@ -2608,7 +2691,7 @@ int pe_set_gru_tiling(pe_engine* e, int32_t tiling) {
 
 int pe_get_gru_tiling(const pe_engine* e) {
     if (!e) return -2;               // (not PE_ERR_INVALID = 1, which is a valid answer)
-    if (e->wide) return wide_uses_x3(e) ? 2 : 0;
+    if (e->wide) return e->prm.gru_precision == 0 && wide_uses_x3(e) ? 2 : 0;
     if (e->prm.gru_precision != 0) return gru_args(e).b20 ? 1 : 0;
     const GruArgs a = gru_args(e);
     return a.x3 ? 2 : a.cw ? 1 : 0;

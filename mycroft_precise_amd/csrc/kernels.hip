@@ -15,6 +15,7 @@
 #include "gru_x3_device.h"
 #include "gru_wide_device.h"
 #include "gru_wide_x3_device.h"
+#include "gru_wide_bf16_device.h"
 #include "mfcc_general_device.h"
 #include "gru_train_device.h"
 
@@ -312,6 +313,29 @@ static hipError_t launch_wide_x3_t(const WideArgs& a, int mode, hipStream_t s) {
 hipError_t launch_gru_wide_x3(const WideArgs& a, int mode, hipStream_t s) {
     hipError_t err = hipErrorInvalidValue;
     with_const<1, 2, 3, 4>(a.units / 64, [&](auto T) { err = launch_wide_x3_t<PE_CONST(T)>(a, mode, s); });
+    return err;
+}
+
+// ---- the same network with bf16 operands (gru_precision = 1; gru_wide_bf16_device.h): four waves per 16-stream tile ----
+// (64 / 128 units: registers for four / two workgroups per compute unit -- wide_bf16_phase)
+template <int TPW, int MODE>
+__global__ __launch_bounds__(256, TPW == 1 ? 4 : TPW == 2 ? 2 : 1) void gru_wide_bf16_kernel(const WideArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kWideBf16LdsBytes];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    gru_wide_bf16_tile<TPW, MODE>(a, blockIdx.x, wave, threadIdx.x & 63, smem);
+}
+
+template <int TPW>
+static hipError_t launch_wide_bf16_t(const WideArgs& a, int mode, hipStream_t s) {
+    const int tiles = (a.base.n_streams + kTileStreams - 1) / kTileStreams;
+    if (tiles == 0) return hipSuccess;
+    if (!with_mode(mode, [&](auto M) { hipLaunchKernelGGL((gru_wide_bf16_kernel<TPW, PE_CONST(M)>), dim3(tiles), dim3(256), 0, s, a); })) return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_gru_wide_bf16(const WideArgs& a, int mode, hipStream_t s) {
+    hipError_t err = hipErrorInvalidValue;
+    with_const<1, 2, 3, 4>(a.units / 64, [&](auto T) { err = launch_wide_bf16_t<PE_CONST(T)>(a, mode, s); });
     return err;
 }
 

@@ -507,6 +507,7 @@ int gru_wide_waves(int units);                  // waves per workgroup of the wi
 int gru_small_tiles(int units);                 // NT = ceil(3R/4)
 hipError_t launch_gru_wide(const WideArgs& a, int input_mode, hipStream_t s);      // units 64..256, 1-2 layers
 hipError_t launch_gru_wide_x3(const WideArgs& a, int input_mode, hipStream_t s);   // the same, float32 products on the bf16 pipe (its own weight packing)
+hipError_t launch_gru_wide_bf16(const WideArgs& a, int input_mode, hipStream_t s); // the same with bf16 OPERANDS (gru_precision = 1): wx1 / wx2 hold a phase's whole stream in 16-byte groups of eight bf16, kx4 counts the input part's k-groups of 32
 hipError_t launch_gather(const GatherArgs& a, hipStream_t s);
 hipError_t launch_scatter(const GatherArgs& a, hipStream_t s);   // a.out is read
 // every record's wcall rewritten to 2 (current side) / 1 (other side): the host then continues counting calls from 3
