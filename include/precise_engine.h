@@ -505,6 +505,25 @@ int pe_set_gru_waves(pe_engine* e, int32_t waves_per_tile);
 int pe_set_gru_tiling(pe_engine* e, int32_t tiling);
 int pe_get_gru_tiling(const pe_engine* e);
 
+/* Carried window chains (csrc/gru_chain_device.h).  Consecutive windows of a stream share all but the rows an update makes
+ * visible, so an engine may keep, per stream, the GRU state of the chain of every live window start and advance each by those
+ * rows (at most two) instead of running all n_features timesteps again -- the same timestep arithmetic in the same order:
+ * bit-identical outputs.  mode: 0 = off; 1 (default) = automatic -- after 128 eligible update calls in a row the engine builds
+ * the chains from its feature ring (one extra launch) and the following eligible calls advance them; 2 = eager, the first
+ * eligible call already (tests).  Eligible: pe_update[_device|_device_keep], pe_update_subset[_device] and pe_update_async of
+ * an engine with ONE float32 network of 17..20 units in its re-tiled four-wave form (pe_get_gru_tiling == 1 by the automatic
+ * choice, <= 2 stream tiles per compute unit: 8192 streams on MI355X), n_features <= 29, no use_delta, no input-projection
+ * rows, a chunk the fused launch takes (<= window - frame length samples) of at most two hops, and none of
+ * pe_set_gru_tiling / pe_set_gru_waves / pe_set_fused(0) / pe_set_timing(1) / pe_reserve_updates in force.  Any other call
+ * that moves the streams' state or changes the network -- pe_clear (masked too), pe_set_weights, pe_set_vectors,
+ * pe_update_many, pe_update_vectors, an update of an ineligible chunk, the knobs above -- simply runs as it always did and
+ * leaves the chains invalid; they are built again after the next 128 eligible calls (what the rebuild costs, in updates saved).  The chain state (2560 bytes per stream)
+ * is allocated at the first entry: pe_get_info().device_bytes of an engine that never enters does not change.
+ * pe_get_chain_carry: *mode = the setting, *active = 1 while the chains are valid (the next eligible call advances them);
+ * either pointer may be null. */
+int pe_set_chain_carry(pe_engine* e, int32_t mode);
+int pe_get_chain_carry(const pe_engine* e, int32_t* mode, int32_t* active);
+
 /* HIP-event timing of the kernels launched by the last *_device/host update on this engine
  * (milliseconds; measured on the stream the kernels ran on).  Enabled with pe_set_timing(e,1).
  * With a fused launch mfcc_ms is the whole update and gru_ms is 0.

@@ -126,6 +126,8 @@ EXPORTS = {
     'pe_get_gru_tiling': (C.c_int, [C.c_void_p]),
     'pe_set_input_projection': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_set_timing': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pe_set_chain_carry': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pe_get_chain_carry': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'pe_get_last_timing': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     # training (pe_trainer)
     'pe_trainer_create': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.POINTER(C.c_void_p)]),
@@ -819,6 +821,17 @@ class HipEngine:
         above; wide / stacked networks 0 (f32-input MFMAs) or 2 (float32 products on the bf16 pipe); bf16-operand networks
         1 (five gate values per lane) or 0 (eight; wide / stacked bf16 networks always)."""
         return int(self._lib.pe_get_gru_tiling(self._h))
+
+    def set_chain_carry(self, mode: int):
+        """Carried window chains (pe_set_chain_carry): 0 off, 1 automatic (the default: after 128 eligible updates in a row),
+        2 eager.  Outputs are bit-identical in every mode."""
+        self._check(self._lib.pe_set_chain_carry(self._h, int(mode)))
+
+    def chain_carry(self):
+        """(mode, active) of pe_get_chain_carry: the setting, and whether the next eligible update advances carried chains."""
+        m, a = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.pe_get_chain_carry(self._h, C.byref(m), C.byref(a)))
+        return m.value, bool(a.value)
 
     def set_timing(self, enabled: bool):
         self._check(self._lib.pe_set_timing(self._h, int(bool(enabled))))

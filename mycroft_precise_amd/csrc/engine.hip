@@ -89,6 +89,15 @@ struct pe_engine {
     uint32_t call_no = 1;                    // number of the last call that wrote records (readers of later launches pass call_no + 1)
     uint32_t renumber_at = 0x7fff0000u;      // call number at which every record is renumbered and the count restarts (pe_set_renumber_at: tests)
     bool fused = true;      // MFCC || GRU in one launch when the chunk size allows it
+    // carried window chains (gru_chain_device.h; pe_set_chain_carry).  The state is valid while chains_built_epoch ==
+    // chain_epoch: every call that moves the streams' state or changes what a chain is made of bumps chain_epoch
+    // (begin_state_call and the setters), and only a chain launch -- which moves the chains WITH the streams -- catches up.
+    int chain_mode = 1;                      // 0 off, 1 automatic (after kChainEnterAfter eligible calls in a row), 2 eager
+    float* chains = nullptr;                 // [n_tiles][kCwSlots][5][64], allocated at the first entry into chain mode
+    uint32_t* chain_ke = nullptr;            // [n_padded]
+    uint64_t chain_epoch = 1, chains_built_epoch = 0;
+    int chain_streak = 0;                    // eligible update calls in a row so far, nothing else bumping the epoch in between
+    uint64_t chain_seen_epoch = 0;           // the epoch as the last update call left it
     int gru_waves = 0;      // 0 = auto (4 waves per tile while tiles <= CUs, else 1), or forced 1 / 4
     // general front end (mfcc_general_device.h): any n_fft / n_filt / n_mfcc the stock-shape wave kernel has no tables for
     bool general = false;
@@ -814,6 +823,7 @@ int begin_state_call(pe_engine* e, hipStream_t s, uint32_t* call) {
         e->call_no = 2u;
     }
     *call = ++e->call_no;
+    ++e->chain_epoch;       // the streams move: carried chains fall behind (a chain launch moves them along and catches up, do_update)
     return PE_OK;
 }
 
@@ -1110,6 +1120,26 @@ bool can_fuse(const pe_engine* e, int chunk) {
     return true;
 }
 
+// Updates in a row that must be eligible before an engine in automatic mode builds its chains (pe_set_chain_carry): hysteresis
+// against callers that alternate between eligible and other calls.  Every entry costs one rebuild launch
+// (gru_chains_rebuild_kernel: the 435 chain steps of every stream), measured at 4096 streams: 102 us, against 0.99 us that a
+// chain launch saves per update (15.13 -> 14.14 us) -- 103 updates to earn it back, rounded up to a power of two.
+constexpr int kChainEnterAfter = 128;
+
+// May this update advance carried chains instead of running every window again?  Exactly the headline rows of DESIGN 0:
+// the stock float32 network re-tiled on four waves per tile over the 32-slot float32 ring (<= 8192 streams), one model, no
+// delta inputs, no projection rows, a chunk the fused launch takes and that makes at most two rows visible, and no explicit
+// launch-shape knob.  Full and subset calls, carry and keep styles alike.
+bool chain_eligible(const pe_engine* e, int chunk) {
+    if (e->chain_mode == 0 || e->n_models != 1 || e->prm.use_delta || e->prm.ring_precision != 0 || e->timing) return false;
+    if (e->gru_tiling >= 0 || e->gru_waves != 0 || !e->fused || e->max_updates > 1) return false;
+    if (e->ring_slots != kCwSlots || e->prm.n_features > kCwSlots - 3) return false;
+    if ((chunk + e->prm.hop_samples - 1) / e->prm.hop_samples > 2) return false;
+    if (!can_fuse(e, chunk)) return false;
+    const GruArgs g = gru_args(e);
+    return g.cw && g.waves_per_tile == 4 && !g.proj_ring && !g.bf16 && !g.x3;
+}
+
 // ids / n_active: the streams that take part (pe_update_subset; device pointer, PCM rows and outputs in that order), or
 // null / 0 = every stream
 // keep: the caller promises that pcm_dev stays alive and unchanged until the NEXT state-moving call's work has completed
@@ -1135,10 +1165,36 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
     // (whatever happens below, the launches of later calls must not inherit this call's style)
     struct Reset { pe_engine* e; ~Reset() { e->call_head = nullptr; e->call_head_chunk = 0; e->call_keep = false; } } reset{e};
     e->kept = keep_call ? pcm_dev : nullptr; e->kept_chunk = keep_call ? chunk : 0;
+    // carried chains: valid only if nothing but chain launches moved the streams since they were built (decided BEFORE this
+    // call's own bump of the epoch)
+    const bool chain_call = raw_out_dev && !feats_out_dev && chain_eligible(e, chunk);
+    const bool chains_current = chain_call && e->chains && e->chains_built_epoch == e->chain_epoch;
+    // (the streak is of eligible calls with nothing else in between: any other bump of the epoch starts it again)
+    if (!chain_call || e->chain_epoch != e->chain_seen_epoch) e->chain_streak = 0;
+    if (chain_call) ++e->chain_streak;
+    const bool chains_enter = chain_call && !chains_current && (e->chain_mode == 2 || e->chain_streak > kChainEnterAfter);
     uint32_t call = 0;
     if ((rc = begin_state_call(e, s, &call))) return rc;
+    e->chain_seen_epoch = e->chain_epoch;
     if (t) { PE_HIP(e, hipEventRecord(e->ev[0], s)); }
-    if (raw_out_dev && can_fuse(e, chunk)) {
+    if (chains_current || chains_enter) {
+        if (!e->chains) {
+            if ((rc = dev_alloc(e, &e->chain_ke, (size_t)e->n_padded))) return rc;
+            if ((rc = dev_alloc(e, &e->chains, (size_t)e->n_tiles * kCwSlots * 5 * 64))) return rc;
+        }
+        const ChainArgs ch{e->chains, e->chain_ke};
+        GruArgs g = gru_args(e);
+        g.call = call;
+        // entering: every live chain from the ring and the records as they stand before this update, in front of the launch
+        if (chains_enter) PE_HIP(e, launch_chains_rebuild(g, ch, e->n_padded, s));
+        g.predict_ke = 1;
+        g.chunk = chunk;
+        g.out = raw_out_dev;
+        if (ids) { g.ids = ids; g.n_streams = n_active; }
+        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_chains(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, ch, e->n_cus, s));
+        else PE_HIP(e, launch_fused_chains(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, ch, e->n_cus, s));
+        e->chains_built_epoch = e->chain_epoch;          // (only now: a launch that failed leaves the chains behind the streams)
+    } else if (raw_out_dev && can_fuse(e, chunk)) {
         GruArgs g = gru_args(e);             // the records as they stand BEFORE the update; the waves predict ke
         g.call = call;                       // (records this launch writes are not read by it)
         g.predict_ke = 1;
@@ -1396,6 +1452,7 @@ int pe_set_weights(pe_engine* e, const pe_weights* w, int32_t model) {
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
     PE_HIP(e, hipDeviceSynchronize());                    // no launch may still read the buffers that are rewritten
+    ++e->chain_epoch;                                     // carried chains were made with the old weights
     int rc = pack_model(e, e->nets[(size_t)model], w, e->wide, e->wide_units);
     if (rc) return rc;
     if (e->proj_ok && model == 0 && !e->general) {
@@ -2498,6 +2555,7 @@ int pe_reserve_updates(pe_engine* e, int32_t max_updates, int32_t max_chunk_samp
         if (rc) return rc;
     }
     e->max_updates = max_updates;
+    ++e->chain_epoch;
     return pe_clear(e, nullptr);          // the ring was re-laid out: streams restart
 }
 
@@ -2638,6 +2696,7 @@ int pe_set_renumber_at(pe_engine* e, uint32_t call_number) {
 int pe_set_fused(pe_engine* e, int32_t enabled) {
     if (!e) return PE_ERR_INVALID;
     PE_DRAIN(e);
+    ++e->chain_epoch;
     e->fused = enabled != 0;
     return PE_OK;
 }
@@ -2652,6 +2711,7 @@ int pe_set_input_projection(pe_engine* e, int32_t enabled) {
     PE_DRAIN(e);
     PE_HIP(e, hipDeviceSynchronize());
     e->proj_on = enabled != 0;
+    ++e->chain_epoch;
     if (e->proj_on && !e->proj_ring) {
         int rc = dev_alloc(e, &e->proj_ring, (size_t)e->n_tiles * e->ring_slots * kTileStreams * kProjRow);
         if (rc) { e->proj_on = false; return rc; }
@@ -2663,6 +2723,7 @@ int pe_set_gru_waves(pe_engine* e, int32_t waves) {
     if (!e) return PE_ERR_INVALID;
     if (waves != 0 && waves != 1 && waves != 4) return fail(e, PE_ERR_INVALID, "gru kernel shape must be 0 (auto), 1 or 4 (waves per tile)");
     PE_DRAIN(e);
+    ++e->chain_epoch;
     e->gru_waves = waves;
     return PE_OK;
 }
@@ -2685,6 +2746,7 @@ int pe_set_gru_tiling(pe_engine* e, int32_t tiling) {
     if (tiling == 1 && e->prm.gru_precision == 1 && !e->nets[0].b20_blob)
         return fail(e, PE_ERR_UNSUPPORTED, "the five-values layout of the bf16 network (tiling 1) takes <= 20 units and <= 14 features");
     PE_DRAIN(e);
+    ++e->chain_epoch;
     e->gru_tiling = tiling;
     return PE_OK;
 }
@@ -2701,6 +2763,24 @@ int pe_set_timing(pe_engine* e, int32_t enabled) {
     if (!e) return PE_ERR_INVALID;
     e->timing = enabled != 0;
     e->ev_valid = false;
+    ++e->chain_epoch;
+    return PE_OK;
+}
+
+int pe_set_chain_carry(pe_engine* e, int32_t mode) {
+    if (!e) return PE_ERR_INVALID;
+    if (mode < 0 || mode > 2) return fail(e, PE_ERR_INVALID, "chain carry must be 0 (off), 1 (automatic) or 2 (eager)");
+    PE_DRAIN(e);
+    ++e->chain_epoch;
+    e->chain_streak = 0;
+    e->chain_mode = mode;
+    return PE_OK;
+}
+
+int pe_get_chain_carry(const pe_engine* e, int32_t* mode, int32_t* active) {
+    if (!e) return PE_ERR_INVALID;
+    if (mode) *mode = e->chain_mode;
+    if (active) *active = (e->chain_mode != 0 && e->chains && e->chains_built_epoch == e->chain_epoch) ? 1 : 0;
     return PE_OK;
 }
 

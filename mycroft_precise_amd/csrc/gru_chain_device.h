@@ -1,0 +1,201 @@
+// Stock-width float32 GRU (gru_cw_device.h), form 1 CARRIED: the chain of every live window start stays on the device
+// between updates, and an update advances each of them by the rows it makes visible instead of running 29 timesteps again.
+//
+// Consecutive windows of a stream share all but the k rows an update makes visible (k <= 2 for the chunks this form is
+// launched for: engine.hip chain_eligible).  The window that ends at emitted row ke - 1 is the chain that started at row
+// ke - T; the window of the NEXT update started k rows later.  So a stream keeps the state h of the chain of every start
+// s in (ke - T - 1, ke - 1]: T of them, the chain of age a = ke - s having consumed the rows s .. ke - 1.  An update then
+//   * computes the input projections of its k new rows ONCE (they were 16 of the 41 MFMAs of every timestep of every window),
+//   * advances each of the T chains by min(a, k) steps of CwStep<false>::step -- the function gru_tile_v runs, bit-identical
+//     to gru_tile_cw -- (a chain of age a <= k is born in this update: it starts from h = 0),
+//   * and the chain that reaches age T is the window: Dense + sigmoid of its state is the output.
+// T independent chains of <= 2 steps instead of one chain of 29: a throughput job for the SIMDs of the machine, with no LDS
+// and no barrier.
+//
+// State.  chains: float32 [stream tile][kCwSlots][5 rho][64 lanes]; slot = start row & (kCwSlots - 1), the indexing of the
+// feature ring; lane (g, j) holds unit 4 rho + g of stream 16 tile + j (CwStep's h[rho]).  A slot is reused by the chain
+// that starts kCwSlots rows later, when its old chain (age > T) is dead.  chain_ke[stream]: the emitted count the stream's
+// chains are current to -- a cross-check only (the host decides validity, engine.hip: chain_epoch): a stream whose stamp is
+// not the count its record holds gets a quiet NaN for an output, which no caller and no test can miss.
+#pragma once
+#include "gru_cw_device.h"
+
+namespace pe {
+
+// (ChainArgs: pe_common.h)
+constexpr int kChainMaxRows = 2;        // rows one chain launch may make visible per stream
+
+// first float of the chain that started at a row of slot `slot`, for the lane of lane group g that serves stream sid
+__device__ __forceinline__ size_t chain_cell(const long long sid, const uint32_t slot, const int g) {
+    return (((size_t)(sid >> 4) * kCwSlots + slot) * 5) * 64 + (size_t)(g * 16) + (size_t)(sid & 15);
+}
+__device__ __forceinline__ void chain_load(const float* chains, const size_t cell, float (&h)[5]) {
+#pragma unroll
+    for (int rho = 0; rho < 5; ++rho) h[rho] = chains[cell + (size_t)rho * 64];
+}
+__device__ __forceinline__ void chain_store(float* chains, const size_t cell, const float (&h)[5], const bool on) {
+    if (!on) return;
+#pragma unroll
+    for (int rho = 0; rho < 5; ++rho) chains[cell + (size_t)rho * 64] = h[rho];
+}
+
+// the weights every wave of this form keeps: the timestep's, the input kernel and the biases
+struct ChainNet {
+    CwStep<false> S;
+    float wx[4][4];
+    f32x4 bias[4];
+    __device__ __forceinline__ void load(const float* cw, const int lane) {
+        S.load(cw, lane);
+#pragma unroll
+        for (int tl = 0; tl < 4; ++tl)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                wx[tl][kk] = cw[CwPack::WX + (tl * 4 + kk) * 64 + lane];
+                bias[tl][kk] = cw[CwPack::BIAS + (tl * 4 + kk) * 64 + lane];
+            }
+    }
+    // x.W + b of the four tiles, as gru_tile_v forms them
+    __device__ __forceinline__ void project(const f32x4& x, f32x4 (&p)[4]) const {
+        p[kTZ] = cw_xproj(wx[kTZ], bias[kTZ], x); p[kTX] = cw_xproj(wx[kTX], bias[kTX], x);
+        p[kTC] = cw_xproj(wx[kTC], bias[kTC], x); p[kTV] = cw_xproj(wx[kTV], bias[kTV], x);
+    }
+    // one timestep for the lanes with `on`; the others keep their state (an MFMA column depends on its own B column only, so
+    // what the other lanes computed is dropped without a trace in these)
+    __device__ __forceinline__ void step_if(float (&h)[5], const f32x4 (&p)[4], const bool on) const {
+        float hn[5];
+#pragma unroll
+        for (int rho = 0; rho < 5; ++rho) hn[rho] = h[rho];
+        S.step(hn, p[kTZ], p[kTX], p[kTC], p[kTV]);
+#pragma unroll
+        for (int rho = 0; rho < 5; ++rho) h[rho] = on ? hn[rho] : h[rho];
+    }
+};
+
+// ---- the network role of a chain launch: NW waves per tile, wave w takes the chains of age a = w (mod NW) ----------------
+// NW = 4 (one workgroup per tile) when the call names most of the engine's streams: the frame role is then the long pole of
+// the launch and every chain wave's MFMAs take issue cycles from it.  NW = 8 (two workgroups per tile) for sparse subset
+// calls, where this role is the long pole: a chain of memory round trips and of a wave's chains two at a time, which more
+// waves shorten (and there the next two chains' state is requested ahead).  Measured: profiles/chain_carry/README.md.
+template <int NW>
+// The records hold the state BEFORE the update (predict_ke, as for every network role of a fused launch).  Lanes of one
+// tile may make different numbers of rows visible (subset calls, streams out of phase): the wave runs the largest trip
+// count and every lane keeps what is its own.
+__device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane) {
+    const int g = lane >> 4, j = lane & 15;
+    const long long stream = (long long)tile * kTileStreams + j;
+    const bool valid = stream < a.n_streams;
+    const int T = a.n_features;
+    // ---- one round trip: the record, the stamp, the weights -----------------------------------------------------
+    const long long sid = gru_stream_of(a, stream, valid);
+    const KeRequest ke_req = gru_ke_request(a, sid);
+    const uint32_t stamp = ch.chain_ke[sid];
+    ChainNet N;
+    N.load(a.cw, lane);
+    float wd[5];
+#pragma unroll
+    for (int rho = 0; rho < 5; ++rho) wd[rho] = a.wd[rho * 64 + lane];
+    const uint32_t ke_pre = rec_pick(ke_req.p, rec_side(ke_req.p, a.call)).ke;
+    const uint32_t ke_post = gru_ke_resolve(a, ke_req);
+    const uint32_t k = ke_post - ke_pre;
+    const int kmax = __any(k >= 2u) ? 2 : __any(k >= 1u) ? 1 : 0;       // (k > kChainMaxRows: refused below, never run)
+    const int head_wave = T % NW;
+    constexpr bool kAhead = NW > 4;
+    const uint32_t smask = (uint32_t)(kCwSlots - 1);
+    // ---- second round trip: the new rows (projected once, here) and the first chains ----------------------------
+    const float* xbase = a.ring + gru_ring_cell(a, sid) * kRowFloats + 4 * g;
+    f32x4 p0[4], p1[4];
+    if (kmax >= 1) N.project(*reinterpret_cast<const f32x4*>(xbase + (size_t)(ke_pre & smask) * kTileStreams * kRowFloats), p0);
+    if (kmax >= 2) N.project(*reinterpret_cast<const f32x4*>(xbase + (size_t)((ke_pre + 1u) & smask) * kTileStreams * kRowFloats), p1);
+    // row ke_pre + i is consumed by the chain of (post-update) age A iff it exists then: i < k and i >= k - A
+    auto advance = [&](float (&h)[5], const uint32_t A) {
+        if (kmax >= 1) N.step_if(h, p0, 0u < k && k <= A);
+        if (kmax >= 2) N.step_if(h, p1, 1u < k && k <= A + 1u);
+    };
+    const bool moved = valid && k > 0u;
+    float hw[5];                            // the window's state, on the wave that holds the chain of age T
+#pragma unroll
+    for (int rho = 0; rho < 5; ++rho) hw[rho] = 0.f;
+    if (kmax == 0) {
+        // nothing became visible anywhere in the tile: the window is the stored chain of age T
+        if (wave == head_wave) chain_load(ch.chains, chain_cell(sid, (ke_post - (uint32_t)T) & smask, g), hw);
+    } else {
+        // two chains at a time: their timesteps are independent, so one's MFMAs fill the other's waits.  kAhead: the state of the
+        // NEXT two is requested before the steps of these (the stores below go to other cells of the same array, which the
+        // compiler cannot know: left to it, every pair waits a whole memory round trip for its loads)
+        auto cell_of = [&](const int age) -> size_t { return chain_cell(sid, (ke_post - (uint32_t)(age <= T ? age : T)) & smask, g); };
+        const int first = wave ? wave : NW;
+        float n0[5], n1[5];
+        if (kAhead) {
+            chain_load(ch.chains, cell_of(first), n0);
+            chain_load(ch.chains, cell_of(first + NW), n1);
+        }
+        for (int a0 = first; a0 <= T; a0 += 2 * NW) {
+            const uint32_t A0 = (uint32_t)a0, A1 = A0 + (uint32_t)NW;
+            const bool two = a0 + NW <= T;
+            const size_t c0 = cell_of(a0), c1 = cell_of(a0 + NW);
+            float h0[5], h1[5];
+            if (!kAhead) {
+                chain_load(ch.chains, c0, n0);
+                chain_load(ch.chains, c1, n1);
+            }
+#pragma unroll
+            for (int rho = 0; rho < 5; ++rho) {             // born in this update: from h = 0
+                h0[rho] = A0 <= k ? 0.f : n0[rho];
+                h1[rho] = A1 <= k ? 0.f : n1[rho];
+            }
+            if (kAhead && a0 + 2 * NW <= T) {
+                chain_load(ch.chains, cell_of(a0 + 2 * NW), n0);
+                chain_load(ch.chains, cell_of(a0 + 3 * NW), n1);
+            }
+            advance(h0, A0);
+            if (two) advance(h1, A1);
+            chain_store(ch.chains, c0, h0, moved);
+            if (two) chain_store(ch.chains, c1, h1, moved);
+            if (a0 == T) {
+#pragma unroll
+                for (int rho = 0; rho < 5; ++rho) hw[rho] = h0[rho];
+            }
+            if (two && a0 + NW == T) {
+#pragma unroll
+                for (int rho = 0; rho < 5; ++rho) hw[rho] = h1[rho];
+            }
+        }
+    }
+    if (wave == head_wave) {
+        // a stream whose chains are not current to its record (or that makes more rows visible than this form carries) must
+        // not pass for a result
+        if (stamp != ke_pre || k > (uint32_t)kChainMaxRows) hw[0] = __builtin_nanf("");
+        cw_head(a, hw, wd, stream, valid, g);
+        if (valid && g == 0) ch.chain_ke[sid] = ke_post;
+    }
+}
+
+// ---- entering chain mode: all T live chains of every stream from the ring and the records as they stand ------------------
+// Chain of age a = a steps from h = 0 over rows ke - a .. ke - 1 (T (T + 1) / 2 steps per stream; once per entry).  Four
+// waves per tile, wave w the ages a = w (mod 4), the same step function.
+__device__ __forceinline__ void gru_tile_chains_rebuild(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane) {
+    const int g = lane >> 4, j = lane & 15;
+    const long long sid = (long long)tile * kTileStreams + j;       // every stream of the engine, padded ones too (records exist)
+    const int T = a.n_features;
+    const KeRequest ke_req = gru_ke_request(a, sid);
+    ChainNet N;
+    N.load(a.cw, lane);
+    const uint32_t ke = gru_ke_resolve(a, ke_req);
+    const uint32_t smask = (uint32_t)(kCwSlots - 1);
+    const float* xbase = a.ring + gru_ring_cell(a, sid) * kRowFloats + 4 * g;
+    for (int a0 = wave ? wave : 4; a0 <= T; a0 += 4) {
+        float h[5];
+#pragma unroll
+        for (int rho = 0; rho < 5; ++rho) h[rho] = 0.f;
+        const uint32_t start = ke - (uint32_t)a0;
+        for (int i = 0; i < a0; ++i) {
+            f32x4 p[4];
+            N.project(*reinterpret_cast<const f32x4*>(xbase + (size_t)((start + (uint32_t)i) & smask) * kTileStreams * kRowFloats), p);
+            N.S.step(h, p[kTZ], p[kTX], p[kTC], p[kTV]);
+        }
+        chain_store(ch.chains, chain_cell(sid, start & smask, g), h, true);
+    }
+    if (wave == 0 && g == 0) ch.chain_ke[sid] = ke;
+}
+
+}  // namespace pe

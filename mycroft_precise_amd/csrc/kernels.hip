@@ -10,6 +10,7 @@
 #include "mfcc_wave_device.h"
 #include "gru_device.h"
 #include "gru_cw_device.h"
+#include "gru_chain_device.h"
 #include "gru_bf16_device.h"
 #include "gru_b20_device.h"
 #include "gru_x3_device.h"
@@ -484,6 +485,42 @@ PE_KERNEL_PAIR((template <class R, class SH, int RG, bool MW, bool PROJ, bool CW
 PE_KERNEL_PAIR((template <class R, class SH, int RG, bool MW, bool CW>), PE_FRAME_KERNEL(256, PE_FRAME_WPE), fused_update_models_kernel, PE_FUSED_MODELS_PARAMS,
                { fused_update_body<R, SH, RG, MW, false, CW, true>(m, t, g, &ms, n_gru_blocks, n_models, n_frame_blocks, n_tiles, frames_first); })
 
+// ---- chain launch (gru_chain_device.h): the fused update of form 1 with the window chains CARRIED between updates -----
+// The same three roles in the same order; the network role advances the tile's resident chains by the rows this update makes
+// visible (four waves, no LDS of its own, no barrier) instead of running every window again from h = 0.
+template <class R, class SH, int NW>
+__device__ __forceinline__ void fused_update_chains_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ChainArgs& ch,
+                                                         const int n_gru_blocks, const int n_frame_blocks, const int frames_first) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    touch_kernel_arguments<kFusedArgBytes<R, false> + (int)sizeof(ChainArgs)>();
+    const int b = role_block(blockIdx.x, n_gru_blocks, n_frame_blocks, frames_first & kFramesFirst);
+    if (b < n_gru_blocks) {
+        // (no s_setprio here: this role is the SHORT one -- see the frame role below)
+        constexpr int per_tile = NW / 4;                // network workgroups per tile
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) + 4 * (b % per_tile);
+        gru_tile_chains<NW>(g, ch, b / per_tile, wave, threadIdx.x & 63);
+    } else if (b < n_gru_blocks + n_frame_blocks) {
+        // The frame role is the long pole of this launch, and an f32-input MFMA keeps its SIMD from issuing while it runs
+        // (DESIGN 4.6): the chain waves' matrix time ADDS to the frame waves' on every SIMD.  With the frame waves winning every
+        // issue arbitration the chain waves' MFMAs go into the cycles in which no frame wave has an instruction ready.  The
+        // chains load all four SIMDs alike, so the frame waves split their slots evenly (no by-SIMD split).  Measured at 4096
+        // streams (profiles/chain_carry/README.md): 14.14 us per update against 15.02 with the plain launch's shape.
+        __builtin_amdgcn_s_setprio(3);
+        mfcc_frame_tasks<R, SH, true, true>(m, t, smem, (b - n_gru_blocks) * kFrameWaves, n_frame_blocks * kFrameWaves, false);
+    } else {
+        mfcc_book_tile<R>(m, b - n_gru_blocks - n_frame_blocks);
+    }
+}
+PE_KERNEL_PAIR((template <class R, class SH, int NW>), PE_FRAME_KERNEL(256, PE_FRAME_WPE), fused_update_chains_kernel,
+               (const MfccStreamArgs<R> m, const WaveTables<R> t, const GruArgs g, const int n_gru_blocks, const int n_frame_blocks, const int n_tiles,
+                const int frames_first, const ChainArgs ch),
+               { (void)n_tiles; fused_update_chains_body<R, SH, NW>(m, t, g, ch, n_gru_blocks, n_frame_blocks, frames_first); })
+// entering chain mode: every live chain of every stream from the ring as it stands (once per entry: a throughput kernel)
+__global__ __launch_bounds__(256) void gru_chains_rebuild_kernel(const GruArgs a, const ChainArgs ch) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    gru_tile_chains_rebuild(a, ch, blockIdx.x, wave, threadIdx.x & 63);
+}
+
 
 // Workgroups of the frame role: one wave per task while that fits the machine (4 workgroups of 4 waves per compute
 // unit are resident: LDS and a 128-register budget), more tasks per wave beyond.
@@ -755,6 +792,36 @@ hipError_t launch_fused(const MfccStreamArgs<double>& m, const WaveTables<double
 }
 hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms, int n_models) {
     return launch_fused_t<float>(m, t, g, n_cus, s, ms, n_models);
+}
+
+// The chain launch of engine.hip do_update (chain_eligible: stock float32 network re-tiled, four waves per tile, one model): one
+// network workgroup per tile, two for sparse subset calls (gru_tile_chains<NW>), no LDS of their own; two resident frame
+// workgroups per compute unit at one tile per compute unit, four above, as in launch_fused_rg's four-wave branch.
+template <class R>
+static hipError_t launch_fused_chains_t(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s) {
+    if (t.L.mel_pad != ShapeStock::MEL || !blob_matches_shape(t)) return hipErrorInvalidValue;
+    if (!g.cw || g.waves_per_tile != 4 || !cw_four_waves_ok(g) || !g.predict_ke || !ch.chains || !ch.chain_ke) return hipErrorInvalidValue;
+    const int tiles = (m.geo.n_streams + kTileStreams - 1) / kTileStreams;
+    if (tiles == 0) return hipSuccess;
+    const int fb = stream_frame_blocks(m.geo.n_streams, n_cus, tiles <= n_cus ? 2 : 4);
+    // a subset call of at most half of the engine's streams: the network role is the long pole, eight waves share a tile's chains
+    const bool sparse = g.ids && 2u * (uint32_t)tiles * kTileStreams <= g.n_padded;
+    if (sparse) PE_LAUNCH_R(R, fused_update_chains_kernel, (ShapeStock, 8), dim3(2 * tiles + fb + tiles), dim3(256), frame_lds(t), s, m, t, g, 2 * tiles, fb, tiles, 0, ch);
+    else PE_LAUNCH_R(R, fused_update_chains_kernel, (ShapeStock, 4), dim3(tiles + fb + tiles), dim3(256), frame_lds(t), s, m, t, g, tiles, fb, tiles, 0, ch);
+    return hipGetLastError();
+}
+hipError_t launch_fused_chains(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s) {
+    return launch_fused_chains_t<double>(m, t, g, ch, n_cus, s);
+}
+hipError_t launch_fused_chains(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s) {
+    return launch_fused_chains_t<float>(m, t, g, ch, n_cus, s);
+}
+// a: the engine's network arguments over ALL its streams (no ids, predict_ke = 0: the records as they stand)
+hipError_t launch_chains_rebuild(const GruArgs& a, const ChainArgs& ch, int n_padded, hipStream_t s) {
+    if (!a.cw || !cw_four_waves_ok(a) || a.ids || a.predict_ke || !ch.chains || !ch.chain_ke) return hipErrorInvalidValue;
+    if (n_padded == 0) return hipSuccess;
+    hipLaunchKernelGGL(gru_chains_rebuild_kernel, dim3(n_padded / kTileStreams), dim3(256), 0, s, a, ch);
+    return hipGetLastError();
 }
 
 // ---- general front end (mfcc_general_device.h): one wave per stream / per frame -------------------------------------

@@ -489,6 +489,16 @@ hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStr
 // (ms != null: a K-model engine -- K network roles, outputs [K][windows])
 hipError_t launch_fused(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1);
 hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, int n_cus, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1);
+// the chain launch (gru_chain_device.h): the same three roles, the network role advancing the CARRIED chains of every live
+// window start by the rows this update makes visible
+struct ChainArgs {
+    float* chains;          // [n_padded / 16][kCwSlots][5 rho][64 lanes] state of the chain that started at a row of that slot
+    uint32_t* chain_ke;     // [n_padded] emitted count each stream's chains are current to (a cross-check: engine.hip chain_epoch)
+};
+hipError_t launch_fused_chains(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s);
+hipError_t launch_fused_chains(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s);
+// all live chains of every stream from the ring and the records as they stand (entering chain mode)
+hipError_t launch_chains_rebuild(const GruArgs& a, const ChainArgs& ch, int n_padded, hipStream_t s);
 hipError_t launch_mfcc_offline_f64(const MfccOfflineArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s);
 hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s);
 // the same frames for many clips at once, every clip's window padded in place (ClipTable)
