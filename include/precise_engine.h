@@ -541,7 +541,8 @@ int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms);
  * contract -- forward with Keras' per-gate input dropout, loss, backward, RMSprop -- is DESIGN.md 4.9; everything is float32.
  * Scope of pe_trainer_create[_models]: ONE GRU layer of 1..32 units, feature_size 1..32, n_features 1..64; anything else is
  * PE_ERR_UNSUPPORTED naming the field, before any device work (stacked networks and bf16 have no training kernel).
- * pe_trainer_create_wide has the same scope with units 1..256; see below.
+ * pe_trainer_create_wide has the same scope with units 1..256, pe_trainer_create_stacked also takes networks of
+ * two GRU layers; see below.
  * Flat parameter order, used for weights, gradients and accumulators alike (Keras layout, gate order z|r|h):
  *   kernel[F][3H] | recurrent_kernel[H][3H] | bias[3H] | dense_kernel[H] | dense_bias      = pe_trainer_n_params floats.
  * PE_ERR_INVALID, before any device work and with the outputs untouched: null pointers, n <= 0, indices outside the dataset,
@@ -576,6 +577,28 @@ int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_
  * the device: about 20 (units rounded up to 16) + 12 feature_size bytes per sample and timestep. */
 int pe_trainer_create_wide(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
                            pe_trainer** out);
+/* Stacked networks: every one of the n_models networks has ONE or TWO GRU layers, units 1..256 per layer in
+ * any mix.  pe_trainer_create, _models and _wide keep refusing n_layers = 2 by name; this constructor is the only way in.
+ * A two-layer network is Sequential[GRU(H1, linear, dropout, return_sequences), GRU(H2, linear, dropout), Dense(1, sigmoid)],
+ * both layers under the contract of DESIGN.md 4.9, layer 1 reading h1_t under its own per-gate masks [3][n][H1] (the same
+ * for every timestep) and handing dx_t back to layer 0's chain.  It always trains on the f32 matrix cores (csrc/
+ * gru_train_stacked_device.h), whatever its widths.  A one-layer network gets the bits it has in a pe_trainer_create_wide
+ * trainer.  Refusals, before any device work and with the "model <index>: " prefix in a trainer of several: n_layers
+ * outside 1..2 and a layer's units outside 1..256 (PE_ERR_UNSUPPORTED naming the field); layers[1].n_in != layers[0].units,
+ * layers[0].n_in != feature_size and null arrays (PE_ERR_INVALID).
+ * Flat parameter order of a two-layer network, for weights, gradients and accumulators:
+ *   kernel_0[F][3H1] | recurrent_kernel_0[H1][3H1] | bias_0[3H1] | kernel_1[H1][3H2] | recurrent_kernel_1[H2][3H2] |
+ *   bias_1[3H2] | dense_kernel[H2] | dense_bias.
+ * frozen_mask of a two-layer network has three bits, one per layer of the Sequential: bit 0 = GRU 0, bit 1 = GRU 1, bit 2 =
+ * Dense; a one-layer network keeps its two.  pe_trainer_loss_grad reads masks_host as [3][n][feature_size] followed by
+ * [3][n][H1].  The handle is an ordinary pe_trainer: every pe_trainer_* entry point, pe_miner_append, pe_generator_append
+ * and pe_augmenter_append work on it.  Every sum's order is a function of (n, n_features, feature_size, H1, H2) and the
+ * element alone and there is no floating-point atomic: the same call gives the same bits every time, next to whatever other
+ * networks, and pe_trainer_step equals pe_trainer_loss_grad on the gathered rows with the generated masks followed by
+ * pe_trainer_apply.  A step keeps its tape on the device: with H1p, H2p the widths rounded up to 16, 20 H1p + 12 feature_size
+ * (layer 0's records) + 20 H2p (layer 1's) + 4 H1p (dx) bytes per sample and timestep. */
+int pe_trainer_create_stacked(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
+                              pe_trainer** out);
 int pe_trainer_destroy(pe_trainer* t);
 const char* pe_trainer_last_error(const pe_trainer* t);
 int pe_trainer_n_models(const pe_trainer* t);          /* -1 for a null trainer */
@@ -591,7 +614,8 @@ int pe_trainer_reset_optimizer(pe_trainer* t);
 
 /* Loss and its gradient for one batch, no state changed: feats[n][n_features][feature_size], targets[n] in [0, 1],
  * masks[3][n][feature_size] the per-gate (z, r, h) input dropout masks of the batch -- each multiplies x_t before that gate's
- * input product, the same for every timestep -- or NULL for no dropout.  loss_out[1] = weighted_log_loss with
+ * input product, the same for every timestep -- or NULL for no dropout (a two-layer network of pe_trainer_create_stacked:
+ * masks[3][n][feature_size] followed by layer 1's masks[3][n][H1]).  loss_out[1] = weighted_log_loss with
  * loss_bias (functions.py:47-50, both means over the n samples of the call), grads_out in the flat order, probs_out[n]
  * (may be NULL) the network outputs under those masks.  The same inputs give the same bits in every call: partial sums are
  * added in a fixed order, no floating-point atomics. */
@@ -600,7 +624,8 @@ int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* ta
 
 /* One RMSprop update from given gradients (keras.optimizers.RMSprop: a = rho a + (1 - rho) g^2, theta -= lr g / (sqrt(a) + eps);
  * Keras 2.2.4 defaults lr 1e-3, rho 0.9, eps 1e-7).  frozen_mask: bit 0 = the GRU layer, bit 1 = the Dense layer keep their
- * parameters AND accumulators (model.py:84-85 freeze_till: layers[:freeze_till] -> mask (1 << freeze_till) - 1). */
+ * parameters AND accumulators (model.py:84-85 freeze_till: layers[:freeze_till] -> mask (1 << freeze_till) - 1).  A two-layer
+ * network has three bits: GRU 0, GRU 1, Dense. */
 int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho, float eps, int32_t frozen_mask);
 
 /* model.fit's inner step without leaving the device: pe_trainer_set_data uploads the dataset once
@@ -661,6 +686,13 @@ int pe_trainer_stats_models(pe_trainer* t, int32_t source, const float* feats_ho
  * and element (gate, i, f) is kept iff (float)(bits >> 40) / 2^24 >= rate (both float32; the quotient is exact).  A kept
  * element is 1 / (1 - rate) evaluated in float32, a dropped one 0. */
 int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feature_size, float rate, float* out);
+/* The masks of one layer of a stacked network, out[3][n][width].  layer 0 (width 1..32) is pe_train_dropout_masks, byte for
+ * byte.  layer 1 (width = H1, 1..256) uses the same mix, G and keep rule with
+ *   key_1 = mix(key ^ G)
+ *   ctr   = (i << 10) | (gate << 8) | f               f < 256
+ *   bits  = mix(key_1 + G (ctr + 1)).
+ * Any other layer is PE_ERR_INVALID. */
+int pe_train_dropout_masks_layer(uint64_t seed, uint64_t step, int32_t layer, int32_t n, int32_t width, float rate, float* out);
 
 /* A resident set that grows (TrainData.merge of scripts/train_incremental.py:101-102 without a new upload of what is already
  * there).  source = PE_TRAIN_SOURCE_DATA or PE_TRAIN_SOURCE_VALIDATION.

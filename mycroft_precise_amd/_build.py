@@ -16,7 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ_DIR = os.path.join(CSRC, 'build')
 LIB_PATH = os.path.join(HERE, 'libprecise_engine.so')
-SOURCES = ['engine.hip', 'kernels.hip', 'mine.hip', 'generate.hip', 'augment.hip', 'stats.hip', 'sample.hip', 'train_wide.hip']
+SOURCES = ['engine.hip', 'kernels.hip', 'mine.hip', 'generate.hip', 'augment.hip', 'stats.hip', 'sample.hip', 'train_wide.hip',
+           'train_stacked.hip']
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + \
     [os.path.join(os.path.dirname(HERE), 'include', 'precise_engine.h')]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs (gfx950's register file is unified): the gate arithmetic

@@ -147,6 +147,7 @@ EXPORTS = {
     'pe_trainer_evaluate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_trainer_create_models': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     'pe_trainer_create_wide': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    'pe_trainer_create_stacked': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     'pe_trainer_n_models': (C.c_int, [C.c_void_p]),
     'pe_trainer_n_params_model': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_trainer_step_models': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(PeTrainHparams), C.c_void_p]),
@@ -157,6 +158,7 @@ EXPORTS = {
     'pe_trainer_stats_models': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_train_dropout_masks': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    'pe_train_dropout_masks_layer': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     'pe_trainer_append': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     'pe_trainer_get_data': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     # sampled training (pe_trainer_sample_*)
@@ -864,12 +866,17 @@ class HipEngine:
             pass
 
 
-def dropout_masks(seed: int, step: int, n: int, feature_size: int, rate: float) -> np.ndarray:
+def dropout_masks(seed: int, step: int, n: int, feature_size: int, rate: float, layer: int = 0) -> np.ndarray:
     """The per-gate input dropout masks of one training step, float32 [3, n, feature_size] (pe_train_dropout_masks: host
-    arithmetic, no GPU): what ``HipTrainer.step`` generates inside its kernel for the same (seed, step)."""
+    arithmetic, no GPU): what ``HipTrainer.step`` generates inside its kernel for the same (seed, step).  ``layer=1``: the masks
+    of a stacked network's second GRU layer, ``feature_size`` then being the first layer's units
+    (pe_train_dropout_masks_layer)."""
     lib = load()
     out = np.empty((3, int(n), int(feature_size)), dtype=np.float32)
-    rc = lib.pe_train_dropout_masks(int(seed), int(step), int(n), int(feature_size), float(rate), out.ctypes.data)
+    if int(layer) != 0:
+        rc = lib.pe_train_dropout_masks_layer(int(seed), int(step), int(layer), int(n), int(feature_size), float(rate), out.ctypes.data)
+    else:
+        rc = lib.pe_train_dropout_masks(int(seed), int(step), int(n), int(feature_size), float(rate), out.ctypes.data)
     if rc != PE_OK:
         HipEngine._raise(rc, lib.pe_trainer_last_error(None).decode())
     return out
@@ -887,9 +894,14 @@ class HipTrainer:
 
     ``wide=False``: networks of 1..32 units (pe_trainer_create[_models]); ``wide=True``: 1..256 units in any mix
     (pe_trainer_create_wide), the wider ones trained on the matrix cores.  Everything else is the same trainer.
+
+    ``stacked=True`` (pe_trainer_create_stacked): each network has one or two GRU layers of 1..256 units.  A two-layer network's
+    flat vector is kernel_0 | recurrent_kernel_0 | bias_0 | kernel_1 | recurrent_kernel_1 | bias_1 | dense_kernel | dense_bias,
+    its ``units`` entry the tuple (H1, H2), its ``frozen_mask`` three bits (GRU 0, GRU 1, Dense) and ``loss_grad`` takes
+    ``masks=(m0 [3, n, feature_size], m1 [3, n, H1])``.
     """
 
-    def __init__(self, weights, n_features, feature_size, device=0, wide=False):
+    def __init__(self, weights, n_features, feature_size, device=0, wide=False, stacked=False):
         self._lib = load()
         self._h = C.c_void_p()
         many = isinstance(weights, (list, tuple))
@@ -899,7 +911,9 @@ class HipTrainer:
         for m, wm in enumerate(models):
             ws[m], held = _pe_weights(wm)
             keep.append(held)
-        if wide:
+        if stacked:
+            rc = self._lib.pe_trainer_create_stacked(int(n_features), int(feature_size), ws, len(models), int(device), C.byref(self._h))
+        elif wide:
             rc = self._lib.pe_trainer_create_wide(int(n_features), int(feature_size), ws, len(models), int(device), C.byref(self._h))
         elif many:
             rc = self._lib.pe_trainer_create_models(int(n_features), int(feature_size), ws, len(models), int(device), C.byref(self._h))
@@ -912,7 +926,7 @@ class HipTrainer:
         self.n_features, self.feature_size = int(n_features), int(feature_size)
         self.n_models = int(self._lib.pe_trainer_n_models(self._h))
         self.n_params_total = int(self._lib.pe_trainer_n_params(self._h))
-        units = [wm['gru'][0][1].shape[0] for wm in models]
+        units = [wm['gru'][0][1].shape[0] if len(wm['gru']) == 1 else tuple(layer[1].shape[0] for layer in wm['gru']) for wm in models]
         per_model = [int(self._lib.pe_trainer_n_params_model(self._h, m)) for m in range(self.n_models)]
         self.units = units if many else units[0]
         self.n_params = per_model if many else per_model[0]
@@ -962,7 +976,15 @@ class HipTrainer:
         feats = self._feats(feats)
         n = feats.shape[0]
         targets = self._targets(targets, n)
-        if masks is not None:
+        if masks is not None and isinstance(self.units, tuple):
+            if not isinstance(masks, (tuple, list)) or len(masks) != 2:
+                raise ValueError('a stacked network takes masks=(layer 0 [3, n, feature_size], layer 1 [3, n, H1])')
+            parts = [np.ascontiguousarray(m, dtype=np.float32) for m in masks]
+            for part, width in zip(parts, (self.feature_size, self.units[0])):
+                if part.shape != (3, n, width):
+                    raise ValueError('masks must be [3, %d, %d], got %r' % (n, width, part.shape))
+            masks = np.concatenate([part.reshape(-1) for part in parts])
+        elif masks is not None:
             masks = np.ascontiguousarray(masks, dtype=np.float32)
             if masks.shape != (3, n, self.feature_size):
                 raise ValueError('masks must be [3, %d, %d], got %r' % (n, self.feature_size, masks.shape))

@@ -8,6 +8,7 @@
 #include "mfcc_general_device.h"
 #include "gru_train_device.h"
 #include "gru_train_wide_device.h"
+#include "gru_train_stacked_device.h"
 #include "mine_device.h"
 #include "sample_device.h"
 #include "generate_device.h"
@@ -2812,6 +2813,7 @@ struct pe_trainer {
     bool wide = false;              // pe_trainer_create_wide: networks of more than kTrainMaxUnits units take launch_train_wide
     int T = 0, F = 0, K = 0, n_params = 0;  // n_params: the total over the networks
     int H[kTrainMaxModels] = {}, ofs[kTrainMaxModels + 1] = {};        // units; offset of a network's flat vector
+    int H2[kTrainMaxModels] = {};   // pe_trainer_create_stacked: units of the second GRU layer, 0 for a one-layer network
     std::string err;
     float* theta = nullptr;         // concatenated flat parameters
     float* accum = nullptr;         // RMSprop accumulators
@@ -2825,7 +2827,10 @@ struct pe_trainer {
     // 7 / 8 dataset, 9 / 10 validation set, 11 the scratch of pe_trainer_stats_models (StatsScratch),
     // 12 selection state bytes, 13 selection list, 14 the scratch of pe_trainer_sample_choose,
     // 15..19 the wide path's tape records, dL/dh_T, transposed recurrent kernel, per-tile partials, per-chunk gradient partials
-    DeviceBuf buf[20];
+    // (a stacked network: layer 0's records, layer 1's dL/dh_T, U0^T, partials, layer 0's chunk partials),
+    // 20..25 the stacked path's: layer 1's records, dx, layer 0's final state / sequence, U1^T | W1^T, layer 1's masks per
+    // tile, layer 1's chunk partials
+    DeviceBuf buf[26];
 };
 
 namespace {
@@ -2945,6 +2950,63 @@ int train_run_wide(pe_trainer* t, const TrainArgs& a0, bool backward, int m) {
     return PE_OK;
 }
 
+// The same for ONE network of two GRU layers (gru_train_stacked_device.h)
+int train_run_stacked(pe_trainer* t, const TrainArgs& a0, bool backward, int m) {
+    const TrainModel& r = a0.model[m];
+    TrainStackedArgs w{};
+    w.n = a0.n; w.T = t->T; w.F = t->F;
+    w.H1 = t->H[m]; w.H1p = tw_pad(w.H1);
+    w.H2 = t->H2[m]; w.H2p = tw_pad(w.H2);
+    w.n_tiles = (a0.n + 15) / 16;
+    w.backward = backward ? 1 : 0;
+    w.apply = a0.apply;
+    w.frozen_mask = r.frozen_mask;
+    w.mask_mode = r.mask_mode;
+    w.rate = r.rate; w.keep_scale = r.keep_scale; w.beta = r.beta;
+    w.inv_n = 1.0f / (float)a0.n;
+    w.lr = r.lr; w.rho = r.rho; w.eps = r.eps;
+    w.mask_key = r.mask_key;
+    w.mask_key1 = train_mask_key_layer1(r.mask_key);
+    w.theta = t->theta + t->ofs[m];
+    w.accum = t->accum + t->ofs[m];
+    w.grads = t->grads + t->ofs[m];
+    w.loss = t->loss + m;
+    w.feats = a0.feats; w.targets = a0.targets; w.indices = a0.indices;
+    w.masks0 = a0.masks;
+    w.masks1 = a0.masks ? a0.masks + (size_t)3 * a0.n * t->F : nullptr;
+    const size_t records = (size_t)w.n_tiles * w.T, row1 = (size_t)w.H1p * 16 * sizeof(float);
+    int rc = train_reserve(t, 18, (size_t)w.n_tiles * (w.H2 + 3) * sizeof(float));
+    if (rc) return rc;
+    if ((rc = train_reserve(t, 22, (backward ? (size_t)w.n_tiles : records) * row1))) return rc;
+    if (backward) {
+        const size_t chunks = (size_t)tw_chunks((long long)records);
+        if ((rc = train_reserve(t, 15, records * tw_record(w.F, w.H1p) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 16, (size_t)w.n_tiles * w.H2p * 16 * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 17, (size_t)3 * w.H1p * w.H1p * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 19, chunks * train_n_gru(w.F, w.H1) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 20, records * tw_record(0, w.H2p) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 21, records * row1))) return rc;
+        if ((rc = train_reserve(t, 23, (size_t)3 * w.H2p * (w.H2p + w.H1p) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, 24, (size_t)w.n_tiles * 3 * row1))) return rc;
+        if ((rc = train_reserve(t, 25, chunks * train_n_gru(w.H1, w.H2) * sizeof(float)))) return rc;
+    }
+    w.tape0 = static_cast<float*>(t->buf[15].p);
+    w.fin = static_cast<float*>(t->buf[16].p);
+    w.ut0 = static_cast<float*>(t->buf[17].p);
+    w.partial = static_cast<float*>(t->buf[18].p);
+    w.gpart0 = static_cast<float*>(t->buf[19].p);
+    w.tape1 = static_cast<float*>(t->buf[20].p);
+    w.dx = static_cast<float*>(t->buf[21].p);
+    w.hfin0 = static_cast<float*>(t->buf[22].p);
+    w.ut1 = static_cast<float*>(t->buf[23].p);
+    w.w1t = w.ut1 ? w.ut1 + (size_t)3 * w.H2p * w.H2p : nullptr;
+    w.mtape = static_cast<float*>(t->buf[24].p);
+    w.gpart1 = static_cast<float*>(t->buf[25].p);
+    w.probs = static_cast<float*>(t->buf[6].p) + (size_t)m * a0.n;
+    PE_THIP(t, launch_train_stacked(w, nullptr));
+    return PE_OK;
+}
+
 // Forward (+ backward) of every network over n samples, and the reduction.  The caller has filled a.n / feats / targets /
 // indices / masks / apply and, per network, mask_* / beta / lr / rho / eps / frozen_mask; the rest is set here.  Runs of
 // neighbouring networks of at most kTrainMaxUnits units share a launch, as they do in a pe_trainer_create_models trainer (a
@@ -2954,13 +3016,18 @@ int train_run(pe_trainer* t, TrainArgs& a, bool backward) {
     if (rc) return rc;
     a.probs = static_cast<float*>(t->buf[6].p);
     for (int m = 0; m < t->K;) {
+        if (t->H2[m] > 0) {
+            if ((rc = train_run_stacked(t, a, backward, m))) return rc;
+            ++m;
+            continue;
+        }
         if (t->H[m] > kTrainMaxUnits) {
             if ((rc = train_run_wide(t, a, backward, m))) return rc;
             ++m;
             continue;
         }
         int m1 = m + 1;
-        while (m1 < t->K && t->H[m1] <= kTrainMaxUnits) ++m1;
+        while (m1 < t->K && t->H[m1] <= kTrainMaxUnits && t->H2[m1] == 0) ++m1;
         if ((rc = train_run_narrow(t, a, backward, m, m1))) return rc;
         m = m1;
     }
@@ -3118,7 +3185,7 @@ int pe_trainer_destroy(pe_trainer* t) {
 
 namespace {
 int trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device, pe_trainer** out,
-                   const int max_units) {
+                   const int max_units, const bool stacked = false) {
     if (!init || !out) return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: null argument");
     *out = nullptr;
     if (n_models < 1) return tfail(nullptr, PE_ERR_INVALID, "pe_trainer_create: n_models = %d", n_models);
@@ -3131,14 +3198,23 @@ int trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* i
     for (int m = 0; m < n_models; ++m) {
         const pe_weights& w = init[m];
         const std::string pre = train_model_prefix(n_models, m);
-        if (w.n_layers != 1)
+        if (stacked && (w.n_layers < 1 || w.n_layers > 2))
+            return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: n_layers = %d (1..2)", pre.c_str(), w.n_layers);
+        if (!stacked && w.n_layers != 1)
             return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: n_layers = %d (one GRU layer has a training kernel)", pre.c_str(), w.n_layers);
-        if (!w.layers || !w.layers[0].kernel || !w.layers[0].recurrent_kernel || !w.layers[0].bias || !w.dense_kernel)
-            return tfail(nullptr, PE_ERR_INVALID, "%spe_trainer_create: null weight array", pre.c_str());
-        const int H = w.layers[0].units;
-        if (H < 1 || H > max_units) return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: units = %d (1..%d)", pre.c_str(), H, max_units);
+        if (!w.layers || !w.dense_kernel) return tfail(nullptr, PE_ERR_INVALID, "%spe_trainer_create: null weight array", pre.c_str());
+        for (int l = 0; l < w.n_layers; ++l)
+            if (!w.layers[l].kernel || !w.layers[l].recurrent_kernel || !w.layers[l].bias)
+                return tfail(nullptr, PE_ERR_INVALID, "%spe_trainer_create: null weight array", pre.c_str());
+        for (int l = 0; l < w.n_layers; ++l) {
+            const int H = w.layers[l].units;
+            if (H < 1 || H > max_units) return tfail(nullptr, PE_ERR_UNSUPPORTED, "%straining: units = %d (1..%d)", pre.c_str(), H, max_units);
+        }
         if (w.layers[0].n_in != feature_size)
             return tfail(nullptr, PE_ERR_INVALID, "%sthe GRU layer takes %d inputs, feature_size is %d", pre.c_str(), w.layers[0].n_in, feature_size);
+        if (w.n_layers == 2 && w.layers[1].n_in != w.layers[0].units)
+            return tfail(nullptr, PE_ERR_INVALID, "%sGRU layer 1 takes %d inputs, layer 0 has %d units", pre.c_str(), w.layers[1].n_in,
+                         w.layers[0].units);
     }
     hipError_t herr = hipSetDevice(device);
     if (herr != hipSuccess) return tfail(nullptr, PE_ERR_HIP, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(herr));
@@ -3148,7 +3224,8 @@ int trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* i
     t->T = n_features; t->F = feature_size; t->K = n_models;
     for (int m = 0; m < n_models; ++m) {
         t->H[m] = init[m].layers[0].units;
-        t->ofs[m + 1] = t->ofs[m] + train_n_params(feature_size, t->H[m]);
+        t->H2[m] = init[m].n_layers == 2 ? init[m].layers[1].units : 0;
+        t->ofs[m + 1] = t->ofs[m] + (t->H2[m] ? ts_n_params(feature_size, t->H[m], t->H2[m]) : train_n_params(feature_size, t->H[m]));
     }
     t->n_params = t->ofs[n_models];
     const size_t pb = (size_t)t->n_params * sizeof(float);
@@ -3169,8 +3246,18 @@ int trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* i
         memcpy(f, init[m].layers[0].kernel, (size_t)F * H3 * sizeof(float));
         memcpy(f + F * H3, init[m].layers[0].recurrent_kernel, (size_t)H * H3 * sizeof(float));
         memcpy(f + (F + H) * H3, init[m].layers[0].bias, (size_t)H3 * sizeof(float));
-        memcpy(f + (F + H + 1) * H3, init[m].dense_kernel, (size_t)H * sizeof(float));
-        f[(F + H + 1) * H3 + H] = init[m].dense_bias;
+        f += (F + H + 1) * H3;
+        int last = H;
+        if (t->H2[m]) {
+            const int G = t->H2[m], G3 = 3 * G;
+            memcpy(f, init[m].layers[1].kernel, (size_t)H * G3 * sizeof(float));
+            memcpy(f + H * G3, init[m].layers[1].recurrent_kernel, (size_t)G * G3 * sizeof(float));
+            memcpy(f + (H + G) * G3, init[m].layers[1].bias, (size_t)G3 * sizeof(float));
+            f += (H + G + 1) * G3;
+            last = G;
+        }
+        memcpy(f, init[m].dense_kernel, (size_t)last * sizeof(float));
+        f[last] = init[m].dense_bias;
     }
     int rc = pe_trainer_set_weights(t, flat.data());
     if (!rc) rc = pe_trainer_reset_optimizer(t);
@@ -3192,6 +3279,11 @@ int pe_trainer_create_models(int32_t n_features, int32_t feature_size, const pe_
 int pe_trainer_create_wide(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
                            pe_trainer** out) {
     return trainer_create(n_features, feature_size, init, n_models, device, out, kTwMaxUnits);
+}
+
+int pe_trainer_create_stacked(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t n_models, int32_t device,
+                              pe_trainer** out) {
+    return trainer_create(n_features, feature_size, init, n_models, device, out, kTwMaxUnits, true);
 }
 
 int pe_trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* init, int32_t device, pe_trainer** out) {
@@ -3249,7 +3341,7 @@ int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* ta
     TrainArgs a{};
     if ((rc = train_upload_batch(t, feats_host, targets_host, n, &a))) return rc;
     if (masks_host) {
-        const size_t mb = (size_t)3 * n * t->F * sizeof(float);
+        const size_t mb = (size_t)3 * n * (t->F + (t->H2[0] ? t->H[0] : 0)) * sizeof(float);      // stacked: then [3][n][H1]
         if ((rc = train_reserve(t, 2, mb))) return rc;
         PE_THIP(t, hipMemcpy(t->buf[2].p, masks_host, mb, hipMemcpyHostToDevice));
         a.model[0].mask_mode = 1;
@@ -3270,6 +3362,18 @@ int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho
     if (!grads_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_apply: null pointer");
     PE_THIP(t, hipSetDevice(t->device));
     PE_THIP(t, hipMemcpy(t->grads, grads_host, (size_t)t->n_params * sizeof(float), hipMemcpyHostToDevice));
+    if (t->H2[0]) {
+        TrainStackedArgs w{};
+        w.F = t->F; w.T = t->T;
+        w.H1 = t->H[0]; w.H1p = tw_pad(w.H1);
+        w.H2 = t->H2[0]; w.H2p = tw_pad(w.H2);
+        w.theta = t->theta; w.accum = t->accum; w.grads = t->grads;
+        w.lr = lr; w.rho = rho; w.eps = eps;
+        w.frozen_mask = frozen_mask;
+        PE_THIP(t, launch_train_stacked_apply(w, nullptr));
+        PE_THIP(t, hipDeviceSynchronize());
+        return PE_OK;
+    }
     TrainArgs a{};
     a.F = t->F; a.n_models = 1;
     a.n_total = t->n_params;
@@ -3368,6 +3472,23 @@ int pe_train_dropout_masks(uint64_t seed, uint64_t step, int32_t n, int32_t feat
         for (int64_t i = 0; i < n; ++i)
             for (int f = 0; f < feature_size; ++f)
                 out[((size_t)g * n + i) * feature_size + f] = train_mask_keep(key, g, i, f, rate) ? scale : 0.0f;
+    return PE_OK;
+}
+
+int pe_train_dropout_masks_layer(uint64_t seed, uint64_t step, int32_t layer, int32_t n, int32_t width, float rate, float* out) {
+    if (layer == 0) return pe_train_dropout_masks(seed, step, n, width, rate, out);
+    if (layer != 1) return tfail(nullptr, PE_ERR_INVALID, "pe_train_dropout_masks_layer: layer = %d (0..1)", layer);
+    if (!out) return tfail(nullptr, PE_ERR_INVALID, "pe_train_dropout_masks_layer: null pointer");
+    if (n <= 0) return tfail(nullptr, PE_ERR_INVALID, "pe_train_dropout_masks_layer: n = %d", n);
+    if (width < 1 || width > kTwMaxUnits)
+        return tfail(nullptr, PE_ERR_INVALID, "pe_train_dropout_masks_layer: width = %d (1..%d)", width, kTwMaxUnits);
+    if (!(rate >= 0.0f && rate < 1.0f)) return tfail(nullptr, PE_ERR_INVALID, "dropout rate %g is outside [0, 1)", (double)rate);
+    const uint64_t key = train_mask_key_layer1(train_mask_key(seed, step));
+    const float scale = train_keep_scale(rate);
+    for (int g = 0; g < 3; ++g)
+        for (int64_t i = 0; i < n; ++i)
+            for (int f = 0; f < width; ++f)
+                out[((size_t)g * n + i) * width + f] = train_mask_keep_layer1(key, g, i, f, rate) ? scale : 0.0f;
     return PE_OK;
 }
 

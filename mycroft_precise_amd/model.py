@@ -25,7 +25,8 @@ class ModelParams:
     ``recurrent_units``; training (``train.Trainer``) also reads ``dropout`` (the GRU's input dropout rate), ``loss_bias``
     (weighted_log_loss: near 1 punishes false activations, near 0 missed ones; the reference passes ``1.0 - sensitivity``) and
     ``freeze_till`` (the first ``freeze_till`` layers -- GRU, then Dense -- keep their weights).  ``extra_metrics`` and
-    ``skip_acc`` only select what Keras prints and are not used."""
+    ``skip_acc`` only select what Keras prints and are not used.  ``recurrent_units`` may be a tuple ``(H1, H2)``: two stacked GRU
+    layers (not something the reference's ``create_model`` builds), which ``create_model`` and ``train.Trainer`` take."""
 
     def __init__(self, recurrent_units=20, dropout=0.2, extra_metrics=False, skip_acc=False,
                  loss_bias=0.7, freeze_till=0):
@@ -131,4 +132,5 @@ def create_model(model_name, params: ModelParams = None, seed: int = 42) -> dict
     if model_name and isfile(model_name):
         return load_precise_model(model_name)
     params = params or ModelParams()
-    return make_weights(n_in=pr.feature_size, units=(params.recurrent_units,), seed=seed)
+    units = params.recurrent_units          # an int: the reference's one GRU; a tuple: stacked GRUs
+    return make_weights(n_in=pr.feature_size, units=tuple(units) if isinstance(units, (tuple, list)) else (units,), seed=seed)

@@ -38,22 +38,51 @@ RMSPROP_LR, RMSPROP_RHO, RMSPROP_EPS = 1e-3, 0.9, 1e-7
 
 
 def flatten_weights(weights: dict) -> np.ndarray:
-    """weights dict (one GRU layer) -> the trainer's flat float32 vector: kernel | recurrent_kernel | bias | dense_kernel |
-    dense_bias."""
-    (k, rk, b), = weights['gru']
-    parts = [k, rk, b, weights['dense_kernel'], weights['dense_bias']]
+    """weights dict (one or two GRU layers) -> the trainer's flat float32 vector: per layer kernel | recurrent_kernel | bias,
+    then dense_kernel | dense_bias."""
+    if len(weights['gru']) not in (1, 2):
+        raise ValueError('flatten_weights: %d GRU layers (1..2)' % len(weights['gru']))
+    parts = [a for layer in weights['gru'] for a in layer] + [weights['dense_kernel'], weights['dense_bias']]
     return np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in parts])
 
 
-def unflatten_weights(flat, feature_size: int, units: int) -> dict:
+def _layer_units(units) -> tuple:
+    """``recurrent_units`` as a tuple of one or two widths"""
+    widths = tuple(int(u) for u in units) if isinstance(units, (tuple, list)) else (int(units),)
+    if len(widths) not in (1, 2):
+        raise ValueError('units must name one or two GRU layers, got %r' % (units,))
+    return widths
+
+
+def unflatten_weights(flat, feature_size: int, units) -> dict:
+    """``units``: an int (one GRU layer) or a tuple of one or two widths"""
     flat = np.asarray(flat, dtype=np.float32).reshape(-1)
-    F, H = int(feature_size), int(units)
-    sizes = [F * 3 * H, H * 3 * H, 3 * H, H, 1]
+    widths = _layer_units(units)
+    shapes, n_in = [], int(feature_size)
+    for H in widths:
+        shapes += [(n_in, 3 * H), (H, 3 * H), (3 * H,)]
+        n_in = H
+    shapes += [(n_in, 1), (1,)]
+    sizes = [int(np.prod(shape)) for shape in shapes]
     if flat.size != sum(sizes):
-        raise ValueError('expected %d values for F = %d, H = %d, got %d' % (sum(sizes), F, H, flat.size))
-    k, rk, b, dk, db = np.split(flat, np.cumsum(sizes)[:-1])
-    return {'gru': [(k.reshape(F, 3 * H).copy(), rk.reshape(H, 3 * H).copy(), b.copy())],
-            'dense_kernel': dk.reshape(H, 1).copy(), 'dense_bias': db.copy()}
+        raise ValueError('expected %d values for F = %d, H = %s, got %d' %
+                         (sum(sizes), int(feature_size), widths[0] if len(widths) == 1 else widths, flat.size))
+    arrays = [a.reshape(shape).copy() for a, shape in zip(np.split(flat, np.cumsum(sizes)[:-1]), shapes)]
+    return {'gru': [tuple(arrays[3 * i:3 * i + 3]) for i in range(len(widths))], 'dense_kernel': arrays[-2], 'dense_bias': arrays[-1]}
+
+
+def _units_of(weights: dict):
+    """int for a one-layer network, (H1, H2) for a stacked one; anything else has no training kernel"""
+    if len(weights['gru']) not in (1, 2):
+        raise NotImplementedError('training: n_layers = %d (1..2)' % len(weights['gru']))
+    widths = tuple(int(np.shape(rk)[0]) for _, rk, _ in weights['gru'])
+    return widths[0] if len(widths) == 1 else widths
+
+
+def _frozen_mask(freeze_till, units) -> int:
+    """model.py:84-85, layers[:freeze_till]: one bit per layer of the Sequential, two for a one-layer network, three for a
+    stacked one"""
+    return ((1 << max(0, int(freeze_till))) - 1) & (7 if isinstance(units, tuple) else 3)
 
 
 class Trainer:
@@ -61,22 +90,25 @@ class Trainer:
     ``params.recurrent_units``.  ``params`` supplies ``dropout``, ``loss_bias`` (the reference passes ``1.0 - sensitivity``,
     scripts/train.py:86) and ``freeze_till``.  ``seed`` drives the initial network, the shuffle and the dropout masks.
     ``recurrent_units`` 1..256: up to 32 units ``pe_trainer_create``, wider networks ``pe_trainer_create_wide``
-    (the matrix-core kernels of DESIGN.md 4.15); the trainer is the same object either way."""
+    (the matrix-core kernels of DESIGN.md 4.15); the trainer is the same object either way.  Two-layer ``weights``, or
+    ``recurrent_units=(H1, H2)``, train the stacked network GRU(H1, return_sequences) -> GRU(H2) -> Dense
+    (``pe_trainer_create_stacked``): ``units`` is then the tuple and ``frozen_mask`` has three bits."""
 
     def __init__(self, weights=None, params: ModelParams = None, seed: int = 42, device: int = 0, n_features: int = None):
         self.params = params or ModelParams()
         self.seed = int(seed)
         if weights is None:
             weights = create_model(None, self.params, seed=self.seed)
-        if len(weights['gru']) != 1:
-            raise NotImplementedError('training: n_layers = %d (one GRU layer has a training kernel)' % len(weights['gru']))
-        k, rk, _ = weights['gru'][0]
-        self.feature_size, self.units = int(np.shape(k)[0]), int(np.shape(rk)[0])
+        self.units = _units_of(weights)
+        self.feature_size = int(np.shape(weights['gru'][0][0])[0])
         self.n_features = int(pr.n_features if n_features is None else n_features)
-        self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, wide=self.units > 32)
+        if isinstance(self.units, tuple):
+            self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, stacked=True)
+        else:
+            self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, wide=self.units > 32)
         self._rng = np.random.default_rng(self.seed)
         self._step = 0                   # optimizer steps taken so far: the dropout masks' step counter
-        self.frozen_mask = ((1 << max(0, int(self.params.freeze_till))) - 1) & 3      # model.py:84-85: layers[:freeze_till]
+        self.frozen_mask = _frozen_mask(self.params.freeze_till, self.units)
 
     # -- the network --------------------------------------------------------------------------------------------------
     @property
@@ -104,7 +136,8 @@ class Trainer:
 
     def loss_and_grads(self, inputs, outputs, masks=None):
         """-> (loss, gradients as a weights dict, probabilities [N, 1]) of one batch; ``masks`` float32
-        [3, N, feature_size] per-gate input dropout masks or None.  Changes no state."""
+        [3, N, feature_size] per-gate input dropout masks or None (a stacked network: the pair of layer 0's and layer 1's
+        [3, N, H1]).  Changes no state."""
         loss, grads, probs = self._t.loss_grad(inputs, outputs, masks=masks, loss_bias=self.params.loss_bias)
         return loss, unflatten_weights(grads, self.feature_size, self.units), probs.reshape(-1, 1)
 
@@ -207,7 +240,8 @@ class TrainerGroup:
     the bits they have in a narrow group).
 
     ``candidates``: a list of ``ModelParams``; ``recurrent_units``, ``dropout``, ``loss_bias`` and ``freeze_till`` mean what
-    they mean to ``Trainer``.  ``seeds[m]`` (default: ``seed`` for every candidate) drives candidate m's initial network and its
+    they mean to ``Trainer``.  One- and two-layer candidates mix (``pe_trainer_create_stacked``): a stacked
+    candidate's ``units`` entry is the tuple (H1, H2) and its frozen mask has three bits.  ``seeds[m]`` (default: ``seed`` for every candidate) drives candidate m's initial network and its
     dropout masks; ``weights[m]`` (a weights dict or None) continues candidate m from a given network.  The group shuffles
     ONCE per epoch for all candidates, with the generator ``Trainer(seed=seed)`` uses.  Candidate m gets, bit for bit, what
     ``Trainer(weights[m], candidates[m], seed=seeds[m])`` gets from the same batches."""
@@ -225,19 +259,19 @@ class TrainerGroup:
         if len(weights) != K:
             raise ValueError('%d weights for %d candidates' % (len(weights), K))
         weights = [create_model(None, p, seed=s) if w is None else w for w, p, s in zip(weights, self.candidates, self.seeds)]
-        for w in weights:
-            if len(w['gru']) != 1:
-                raise NotImplementedError('training: n_layers = %d (one GRU layer has a training kernel)' % len(w['gru']))
+        self.units = [_units_of(w) for w in weights]
         sizes = {int(np.shape(w['gru'][0][0])[0]) for w in weights}
         if len(sizes) != 1:
             raise ValueError('the candidates of a group share feature_size, got %s' % sorted(sizes))
         self.feature_size = sizes.pop()
-        self.units = [int(np.shape(w['gru'][0][1])[0]) for w in weights]
         self.n_features = int(pr.n_features if n_features is None else n_features)
-        self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, wide=max(self.units) > 32)
+        if any(isinstance(u, tuple) for u in self.units):
+            self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, stacked=True)
+        else:
+            self._t = HipTrainer(weights, self.n_features, self.feature_size, device=device, wide=max(self.units) > 32)
         self._rng = np.random.default_rng(self.seed)
         self._step = 0
-        self.frozen_masks = [((1 << max(0, int(p.freeze_till))) - 1) & 3 for p in self.candidates]
+        self.frozen_masks = [_frozen_mask(p.freeze_till, u) for p, u in zip(self.candidates, self.units)]
 
     def __len__(self):
         return len(self.candidates)
@@ -358,7 +392,8 @@ def trial_reports(group, runner, noise_audios, interaction_estimate=100, ambient
         for r, width in zip(runner, widths):
             members = [m for m, u in enumerate(group.units) if u == width]
             engine = r.engine
-            if not getattr(engine, '_multi', False) or engine.n_models != len(members) or engine.units != width:
+            last = width[-1] if isinstance(width, tuple) else width          # (an engine's ``units`` is its last GRU layer's)
+            if not getattr(engine, '_multi', False) or engine.n_models != len(members) or engine.units != last:
                 raise ValueError('trial_reports: the runner of the %d candidate%s of %d units must be a multi-model HipRunner holding '
                                  'their weights in group order' % (len(members), '' if len(members) == 1 else 's', width))
             nww[members] = simulate.nww_buckets(r, recordings, thresholds, chunk_size).reshape(len(members), -1)
