@@ -2808,9 +2808,22 @@ struct TrainSet {                           // a resident set: pe_trainer_set_da
     int n = 0;
 };
 
+enum TrainBuf {                             // the slots of pe_trainer::buf
+    kBufFeats, kBufTargets, kBufMasks, kBufIndices,     // what one call uploads
+    kBufTape, kBufPartial,                              // the narrow path's tape and per-block partials
+    kBufProbs,                                          // [K][n], every path
+    kBufDataFeats, kBufDataTargets,                     // the resident dataset: the targets of a set follow its features
+    kBufValFeats, kBufValTargets,                       // the resident validation set
+    kBufStats,                                          // the scratch of pe_trainer_stats_models (StatsScratch)
+    kBufSampleState, kBufSampleList, kBufSampleScratch, // selection state bytes, selection list, the scratch of pe_trainer_sample_choose
+    kBufLayerTape, kBufFin, kBufLayerUt, kBufLayerPartial, kBufLayerGpart,  // wide: records, dL/dh_T, U^T, per-tile and per-chunk partials
+    kBufTape1, kBufDx, kBufHfin0, kBufUt1W1t, kBufMtape, kBufGpart1,        // stacked: layer 1's records, dx, layer 0's final state /
+    kBufCount                                                               // sequence, U1^T | W1^T, layer 1's masks per tile, its chunk partials
+};
+constexpr TrainBuf train_targets_of(TrainBuf feats) { return static_cast<TrainBuf>(feats + 1); }
+
 struct pe_trainer {
     int device = 0;
-    bool wide = false;              // pe_trainer_create_wide: networks of more than kTrainMaxUnits units take launch_train_wide
     int T = 0, F = 0, K = 0, n_params = 0;  // n_params: the total over the networks
     int H[kTrainMaxModels] = {}, ofs[kTrainMaxModels + 1] = {};        // units; offset of a network's flat vector
     int H2[kTrainMaxModels] = {};   // pe_trainer_create_stacked: units of the second GRU layer, 0 for a one-layer network
@@ -2823,14 +2836,10 @@ struct pe_trainer {
     // the selection state of the training set (pe_trainer_sample_*): rows [0, sample_n) have their state byte; rows behind
     // them (a fresh or grown set) are eligible and unselected, and get theirs when a sample call next needs it
     int sample_n = 0, n_selected = 0;
-    // buffers that grow with the largest call: 0 feats, 1 targets, 2 masks, 3 indices, 4 tape, 5 partial, 6 probs,
-    // 7 / 8 dataset, 9 / 10 validation set, 11 the scratch of pe_trainer_stats_models (StatsScratch),
-    // 12 selection state bytes, 13 selection list, 14 the scratch of pe_trainer_sample_choose,
-    // 15..19 the wide path's tape records, dL/dh_T, transposed recurrent kernel, per-tile partials, per-chunk gradient partials
-    // (a stacked network: layer 0's records, layer 1's dL/dh_T, U0^T, partials, layer 0's chunk partials),
-    // 20..25 the stacked path's: layer 1's records, dx, layer 0's final state / sequence, U1^T | W1^T, layer 1's masks per
-    // tile, layer 1's chunk partials
-    DeviceBuf buf[26];
+    // buffers that grow with the largest call (TrainBuf).  The wide and the stacked path share kBufLayer*: there a stacked
+    // network keeps layer 0's records, U0^T and chunk partials, kBufFin is the dL/dh_T of its layer 1, and kBufLayerPartial
+    // the per-tile partials of its head.
+    DeviceBuf buf[kBufCount];
 };
 
 namespace {
@@ -2852,7 +2861,7 @@ int tfail(pe_trainer* t, int code, const char* fmt, ...) {
             return tfail((t), PE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
     } while (0)
 
-int train_reserve(pe_trainer* t, int which, size_t bytes) {
+int train_reserve(pe_trainer* t, TrainBuf which, size_t bytes) {
     DeviceBuf& b = t->buf[which];
     if (b.bytes >= bytes && b.p) return PE_OK;
     if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
@@ -2901,108 +2910,105 @@ int train_run_narrow(pe_trainer* t, const TrainArgs& a0, bool backward, int m0, 
         if (backward) tape += (size_t)blocks * t->T * 4 * a.threads;
         partial += (size_t)blocks * ((backward ? t->ofs[m + 1] - t->ofs[m] : 0) + 2);
     }
-    int rc = train_reserve(t, 5, partial * sizeof(float));
+    int rc = train_reserve(t, kBufPartial, partial * sizeof(float));
     if (rc) return rc;
-    if (backward && (rc = train_reserve(t, 4, tape * sizeof(float)))) return rc;
-    a.tape = static_cast<float*>(t->buf[4].p);
-    a.partial = static_cast<float*>(t->buf[5].p);
-    a.probs = static_cast<float*>(t->buf[6].p) + (size_t)m0 * a.n;
+    if (backward && (rc = train_reserve(t, kBufTape, tape * sizeof(float)))) return rc;
+    a.tape = static_cast<float*>(t->buf[kBufTape].p);
+    a.partial = static_cast<float*>(t->buf[kBufPartial].p);
+    a.probs = static_cast<float*>(t->buf[kBufProbs].p) + (size_t)m0 * a.n;
     PE_THIP(t, launch_train(a, nullptr));
     PE_THIP(t, launch_train_reduce(a, nullptr));
     return PE_OK;
 }
 
+// What TrainWideArgs and TrainStackedArgs have in common, for network m of the trainer: the caller's per-call and per-network
+// settings (train_run), and where the network's parameters live.  `a0.n` is 0 where nothing runs over samples (pe_trainer_apply).
+template <class Args>
+void train_fill_common(const pe_trainer* t, const TrainArgs& a0, bool backward, int m, Args* w) {
+    const TrainModel& r = a0.model[m];
+    w->n = a0.n; w->T = t->T; w->F = t->F;
+    w->n_tiles = (a0.n + 15) / 16;
+    w->backward = backward ? 1 : 0;
+    w->apply = a0.apply;
+    w->frozen_mask = r.frozen_mask;
+    w->mask_mode = r.mask_mode;
+    w->rate = r.rate; w->keep_scale = r.keep_scale; w->beta = r.beta;
+    w->inv_n = a0.n > 0 ? 1.0f / (float)a0.n : 0.0f;
+    w->lr = r.lr; w->rho = r.rho; w->eps = r.eps;
+    w->mask_key = r.mask_key;
+    w->theta = t->theta + t->ofs[m];
+    w->accum = t->accum + t->ofs[m];
+    w->grads = t->grads + t->ofs[m];
+    w->loss = t->loss + m;
+    w->feats = a0.feats; w->targets = a0.targets; w->indices = a0.indices;
+    w->probs = static_cast<float*>(t->buf[kBufProbs].p) + (size_t)m * a0.n;
+}
+
+void train_stacked_units(const pe_trainer* t, int m, TrainStackedArgs* w) {
+    w->H1 = t->H[m]; w->H1p = tw_pad(w->H1);
+    w->H2 = t->H2[m]; w->H2p = tw_pad(w->H2);
+}
+
 // The same for ONE network of more than kTrainMaxUnits units (gru_train_wide_device.h)
 int train_run_wide(pe_trainer* t, const TrainArgs& a0, bool backward, int m) {
-    const TrainModel& r = a0.model[m];
     TrainWideArgs w{};
-    w.n = a0.n; w.T = t->T; w.F = t->F; w.H = t->H[m]; w.Hp = tw_pad(w.H);
-    w.n_tiles = (a0.n + 15) / 16;
-    w.backward = backward ? 1 : 0;
-    w.apply = a0.apply;
-    w.frozen_mask = r.frozen_mask;
-    w.mask_mode = r.mask_mode;
-    w.rate = r.rate; w.keep_scale = r.keep_scale; w.beta = r.beta;
-    w.inv_n = 1.0f / (float)a0.n;
-    w.lr = r.lr; w.rho = r.rho; w.eps = r.eps;
-    w.mask_key = r.mask_key;
-    w.theta = t->theta + t->ofs[m];
-    w.accum = t->accum + t->ofs[m];
-    w.grads = t->grads + t->ofs[m];
-    w.loss = t->loss + m;
-    w.feats = a0.feats; w.targets = a0.targets; w.indices = a0.indices; w.masks = a0.masks;
-    int rc = train_reserve(t, 18, (size_t)w.n_tiles * (w.H + 3) * sizeof(float));
+    train_fill_common(t, a0, backward, m, &w);
+    w.H = t->H[m]; w.Hp = tw_pad(w.H);
+    w.masks = a0.masks;
+    int rc = train_reserve(t, kBufLayerPartial, (size_t)w.n_tiles * (w.H + 3) * sizeof(float));
     if (rc) return rc;
     if (backward) {
         const long long records = (long long)w.n_tiles * w.T;
-        if ((rc = train_reserve(t, 15, (size_t)records * tw_record(w.F, w.Hp) * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 16, (size_t)w.n_tiles * w.Hp * 16 * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 17, (size_t)3 * w.Hp * w.Hp * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 19, (size_t)tw_chunks(records) * train_n_gru(w.F, w.H) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufLayerTape, (size_t)records * tw_record(w.F, w.Hp) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufFin, (size_t)w.n_tiles * w.Hp * 16 * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufLayerUt, (size_t)3 * w.Hp * w.Hp * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufLayerGpart, (size_t)tw_chunks(records) * train_n_gru(w.F, w.H) * sizeof(float)))) return rc;
     }
-    w.tape = static_cast<float*>(t->buf[15].p);
-    w.fin = static_cast<float*>(t->buf[16].p);
-    w.ut = static_cast<float*>(t->buf[17].p);
-    w.partial = static_cast<float*>(t->buf[18].p);
-    w.gpart = static_cast<float*>(t->buf[19].p);
-    w.probs = static_cast<float*>(t->buf[6].p) + (size_t)m * a0.n;
+    w.tape = static_cast<float*>(t->buf[kBufLayerTape].p);
+    w.fin = static_cast<float*>(t->buf[kBufFin].p);
+    w.ut = static_cast<float*>(t->buf[kBufLayerUt].p);
+    w.partial = static_cast<float*>(t->buf[kBufLayerPartial].p);
+    w.gpart = static_cast<float*>(t->buf[kBufLayerGpart].p);
     PE_THIP(t, launch_train_wide(w, nullptr));
     return PE_OK;
 }
 
 // The same for ONE network of two GRU layers (gru_train_stacked_device.h)
 int train_run_stacked(pe_trainer* t, const TrainArgs& a0, bool backward, int m) {
-    const TrainModel& r = a0.model[m];
     TrainStackedArgs w{};
-    w.n = a0.n; w.T = t->T; w.F = t->F;
-    w.H1 = t->H[m]; w.H1p = tw_pad(w.H1);
-    w.H2 = t->H2[m]; w.H2p = tw_pad(w.H2);
-    w.n_tiles = (a0.n + 15) / 16;
-    w.backward = backward ? 1 : 0;
-    w.apply = a0.apply;
-    w.frozen_mask = r.frozen_mask;
-    w.mask_mode = r.mask_mode;
-    w.rate = r.rate; w.keep_scale = r.keep_scale; w.beta = r.beta;
-    w.inv_n = 1.0f / (float)a0.n;
-    w.lr = r.lr; w.rho = r.rho; w.eps = r.eps;
-    w.mask_key = r.mask_key;
-    w.mask_key1 = train_mask_key_layer1(r.mask_key);
-    w.theta = t->theta + t->ofs[m];
-    w.accum = t->accum + t->ofs[m];
-    w.grads = t->grads + t->ofs[m];
-    w.loss = t->loss + m;
-    w.feats = a0.feats; w.targets = a0.targets; w.indices = a0.indices;
+    train_fill_common(t, a0, backward, m, &w);
+    train_stacked_units(t, m, &w);
+    w.mask_key1 = train_mask_key_layer1(w.mask_key);
     w.masks0 = a0.masks;
     w.masks1 = a0.masks ? a0.masks + (size_t)3 * a0.n * t->F : nullptr;
     const size_t records = (size_t)w.n_tiles * w.T, row1 = (size_t)w.H1p * 16 * sizeof(float);
-    int rc = train_reserve(t, 18, (size_t)w.n_tiles * (w.H2 + 3) * sizeof(float));
+    int rc = train_reserve(t, kBufLayerPartial, (size_t)w.n_tiles * (w.H2 + 3) * sizeof(float));
     if (rc) return rc;
-    if ((rc = train_reserve(t, 22, (backward ? (size_t)w.n_tiles : records) * row1))) return rc;
+    if ((rc = train_reserve(t, kBufHfin0, (backward ? (size_t)w.n_tiles : records) * row1))) return rc;
     if (backward) {
         const size_t chunks = (size_t)tw_chunks((long long)records);
-        if ((rc = train_reserve(t, 15, records * tw_record(w.F, w.H1p) * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 16, (size_t)w.n_tiles * w.H2p * 16 * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 17, (size_t)3 * w.H1p * w.H1p * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 19, chunks * train_n_gru(w.F, w.H1) * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 20, records * tw_record(0, w.H2p) * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 21, records * row1))) return rc;
-        if ((rc = train_reserve(t, 23, (size_t)3 * w.H2p * (w.H2p + w.H1p) * sizeof(float)))) return rc;
-        if ((rc = train_reserve(t, 24, (size_t)w.n_tiles * 3 * row1))) return rc;
-        if ((rc = train_reserve(t, 25, chunks * train_n_gru(w.H1, w.H2) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufLayerTape, records * tw_record(w.F, w.H1p) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufFin, (size_t)w.n_tiles * w.H2p * 16 * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufLayerUt, (size_t)3 * w.H1p * w.H1p * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufLayerGpart, chunks * train_n_gru(w.F, w.H1) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufTape1, records * tw_record(0, w.H2p) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufDx, records * row1))) return rc;
+        if ((rc = train_reserve(t, kBufUt1W1t, (size_t)3 * w.H2p * (w.H2p + w.H1p) * sizeof(float)))) return rc;
+        if ((rc = train_reserve(t, kBufMtape, (size_t)w.n_tiles * 3 * row1))) return rc;
+        if ((rc = train_reserve(t, kBufGpart1, chunks * train_n_gru(w.H1, w.H2) * sizeof(float)))) return rc;
     }
-    w.tape0 = static_cast<float*>(t->buf[15].p);
-    w.fin = static_cast<float*>(t->buf[16].p);
-    w.ut0 = static_cast<float*>(t->buf[17].p);
-    w.partial = static_cast<float*>(t->buf[18].p);
-    w.gpart0 = static_cast<float*>(t->buf[19].p);
-    w.tape1 = static_cast<float*>(t->buf[20].p);
-    w.dx = static_cast<float*>(t->buf[21].p);
-    w.hfin0 = static_cast<float*>(t->buf[22].p);
-    w.ut1 = static_cast<float*>(t->buf[23].p);
+    w.tape0 = static_cast<float*>(t->buf[kBufLayerTape].p);
+    w.fin = static_cast<float*>(t->buf[kBufFin].p);
+    w.ut0 = static_cast<float*>(t->buf[kBufLayerUt].p);
+    w.partial = static_cast<float*>(t->buf[kBufLayerPartial].p);
+    w.gpart0 = static_cast<float*>(t->buf[kBufLayerGpart].p);
+    w.tape1 = static_cast<float*>(t->buf[kBufTape1].p);
+    w.dx = static_cast<float*>(t->buf[kBufDx].p);
+    w.hfin0 = static_cast<float*>(t->buf[kBufHfin0].p);
+    w.ut1 = static_cast<float*>(t->buf[kBufUt1W1t].p);
     w.w1t = w.ut1 ? w.ut1 + (size_t)3 * w.H2p * w.H2p : nullptr;
-    w.mtape = static_cast<float*>(t->buf[24].p);
-    w.gpart1 = static_cast<float*>(t->buf[25].p);
-    w.probs = static_cast<float*>(t->buf[6].p) + (size_t)m * a0.n;
+    w.mtape = static_cast<float*>(t->buf[kBufMtape].p);
+    w.gpart1 = static_cast<float*>(t->buf[kBufGpart1].p);
     PE_THIP(t, launch_train_stacked(w, nullptr));
     return PE_OK;
 }
@@ -3012,9 +3018,9 @@ int train_run_stacked(pe_trainer* t, const TrainArgs& a0, bool backward, int m) 
 // neighbouring networks of at most kTrainMaxUnits units share a launch, as they do in a pe_trainer_create_models trainer (a
 // network's bits do not depend on its company); every wider network has its own launches.
 int train_run(pe_trainer* t, TrainArgs& a, bool backward) {
-    int rc = train_reserve(t, 6, (size_t)t->K * a.n * sizeof(float));
+    int rc = train_reserve(t, kBufProbs, (size_t)t->K * a.n * sizeof(float));
     if (rc) return rc;
-    a.probs = static_cast<float*>(t->buf[6].p);
+    a.probs = static_cast<float*>(t->buf[kBufProbs].p);
     for (int m = 0; m < t->K;) {
         if (t->H2[m] > 0) {
             if ((rc = train_run_stacked(t, a, backward, m))) return rc;
@@ -3036,21 +3042,21 @@ int train_run(pe_trainer* t, TrainArgs& a, bool backward) {
 
 int train_upload_batch(pe_trainer* t, const float* feats_host, const float* targets_host, int n, TrainArgs* a) {
     const size_t fb = (size_t)n * t->T * t->F * sizeof(float);
-    int rc = train_reserve(t, 0, fb);
+    int rc = train_reserve(t, kBufFeats, fb);
     if (rc) return rc;
-    PE_THIP(t, hipMemcpy(t->buf[0].p, feats_host, fb, hipMemcpyHostToDevice));
-    a->feats = static_cast<const float*>(t->buf[0].p);
+    PE_THIP(t, hipMemcpy(t->buf[kBufFeats].p, feats_host, fb, hipMemcpyHostToDevice));
+    a->feats = static_cast<const float*>(t->buf[kBufFeats].p);
     a->targets = nullptr;
     if (targets_host) {
-        if ((rc = train_reserve(t, 1, (size_t)n * sizeof(float)))) return rc;
-        PE_THIP(t, hipMemcpy(t->buf[1].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        a->targets = static_cast<const float*>(t->buf[1].p);
+        if ((rc = train_reserve(t, kBufTargets, (size_t)n * sizeof(float)))) return rc;
+        PE_THIP(t, hipMemcpy(t->buf[kBufTargets].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        a->targets = static_cast<const float*>(t->buf[kBufTargets].p);
     }
     a->n = n;
     return PE_OK;
 }
 
-int train_upload_set(pe_trainer* t, const char* who, TrainSet* set, int slot, const float* feats_host, const float* targets_host, int n) {
+int train_upload_set(pe_trainer* t, const char* who, TrainSet* set, TrainBuf slot, const float* feats_host, const float* targets_host, int n) {
     if (!feats_host || !targets_host) return tfail(t, PE_ERR_INVALID, "%s: null pointer", who);
     if (n <= 0) return tfail(t, PE_ERR_INVALID, "%s: n = %d", who, n);
     int rc = train_check_targets(t, targets_host, n);
@@ -3058,11 +3064,11 @@ int train_upload_set(pe_trainer* t, const char* who, TrainSet* set, int slot, co
     PE_THIP(t, hipSetDevice(t->device));
     set->n = 0;
     const size_t fb = (size_t)n * t->T * t->F * sizeof(float);
-    if ((rc = train_reserve(t, slot, fb)) || (rc = train_reserve(t, slot + 1, (size_t)n * sizeof(float)))) return rc;
+    if ((rc = train_reserve(t, slot, fb)) || (rc = train_reserve(t, train_targets_of(slot), (size_t)n * sizeof(float)))) return rc;
     PE_THIP(t, hipMemcpy(t->buf[slot].p, feats_host, fb, hipMemcpyHostToDevice));
-    PE_THIP(t, hipMemcpy(t->buf[slot + 1].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(t->buf[train_targets_of(slot)].p, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     set->feats = static_cast<const float*>(t->buf[slot].p);
-    set->targets = static_cast<const float*>(t->buf[slot + 1].p);
+    set->targets = static_cast<const float*>(t->buf[train_targets_of(slot)].p);
     set->n = n;
     return PE_OK;
 }
@@ -3079,14 +3085,14 @@ int train_step(pe_trainer* t, const char* who, const int32_t* indices_host, int 
         if (indices_host[i] < 0 || indices_host[i] >= t->data.n)
             return tfail(t, PE_ERR_INVALID, "indices[%d] = %d is outside the dataset of %d samples", i, indices_host[i], t->data.n);
     PE_THIP(t, hipSetDevice(t->device));
-    int rc = train_reserve(t, 3, (size_t)n * sizeof(int32_t));
+    int rc = train_reserve(t, kBufIndices, (size_t)n * sizeof(int32_t));
     if (rc) return rc;
-    PE_THIP(t, hipMemcpy(t->buf[3].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(t->buf[kBufIndices].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     TrainArgs a{};
     a.n = n;
     a.feats = t->data.feats;
     a.targets = t->data.targets;
-    a.indices = static_cast<const int32_t*>(t->buf[3].p);
+    a.indices = static_cast<const int32_t*>(t->buf[kBufIndices].p);
     a.apply = 1;
     for (int m = 0; m < t->K; ++m) {
         TrainModel& r = a.model[m];
@@ -3220,7 +3226,6 @@ int trainer_create(int32_t n_features, int32_t feature_size, const pe_weights* i
     if (herr != hipSuccess) return tfail(nullptr, PE_ERR_HIP, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(herr));
     pe_trainer* t = new pe_trainer;
     t->device = device;
-    t->wide = max_units > kTrainMaxUnits;
     t->T = n_features; t->F = feature_size; t->K = n_models;
     for (int m = 0; m < n_models; ++m) {
         t->H[m] = init[m].layers[0].units;
@@ -3342,16 +3347,16 @@ int pe_trainer_loss_grad(pe_trainer* t, const float* feats_host, const float* ta
     if ((rc = train_upload_batch(t, feats_host, targets_host, n, &a))) return rc;
     if (masks_host) {
         const size_t mb = (size_t)3 * n * (t->F + (t->H2[0] ? t->H[0] : 0)) * sizeof(float);      // stacked: then [3][n][H1]
-        if ((rc = train_reserve(t, 2, mb))) return rc;
-        PE_THIP(t, hipMemcpy(t->buf[2].p, masks_host, mb, hipMemcpyHostToDevice));
+        if ((rc = train_reserve(t, kBufMasks, mb))) return rc;
+        PE_THIP(t, hipMemcpy(t->buf[kBufMasks].p, masks_host, mb, hipMemcpyHostToDevice));
         a.model[0].mask_mode = 1;
-        a.masks = static_cast<const float*>(t->buf[2].p);
+        a.masks = static_cast<const float*>(t->buf[kBufMasks].p);
     }
     a.model[0].beta = loss_bias;
     if ((rc = train_run(t, a, true))) return rc;
     PE_THIP(t, hipMemcpy(loss_out, t->loss, sizeof(float), hipMemcpyDeviceToHost));
     PE_THIP(t, hipMemcpy(grads_out, t->grads, (size_t)t->n_params * sizeof(float), hipMemcpyDeviceToHost));
-    if (probs_out) PE_THIP(t, hipMemcpy(probs_out, t->buf[6].p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (probs_out) PE_THIP(t, hipMemcpy(probs_out, t->buf[kBufProbs].p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return PE_OK;
 }
 
@@ -3362,28 +3367,24 @@ int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho
     if (!grads_host) return tfail(t, PE_ERR_INVALID, "pe_trainer_apply: null pointer");
     PE_THIP(t, hipSetDevice(t->device));
     PE_THIP(t, hipMemcpy(t->grads, grads_host, (size_t)t->n_params * sizeof(float), hipMemcpyHostToDevice));
+    TrainArgs a{};
+    TrainModel& r = a.model[0];
+    r.lr = lr; r.rho = rho; r.eps = eps;
+    r.frozen_mask = frozen_mask;
     if (t->H2[0]) {
         TrainStackedArgs w{};
-        w.F = t->F; w.T = t->T;
-        w.H1 = t->H[0]; w.H1p = tw_pad(w.H1);
-        w.H2 = t->H2[0]; w.H2p = tw_pad(w.H2);
-        w.theta = t->theta; w.accum = t->accum; w.grads = t->grads;
-        w.lr = lr; w.rho = rho; w.eps = eps;
-        w.frozen_mask = frozen_mask;
+        train_fill_common(t, a, false, 0, &w);
+        train_stacked_units(t, 0, &w);
         PE_THIP(t, launch_train_stacked_apply(w, nullptr));
         PE_THIP(t, hipDeviceSynchronize());
         return PE_OK;
     }
-    TrainArgs a{};
     a.F = t->F; a.n_models = 1;
     a.n_total = t->n_params;
     a.grads = t->grads;
     a.theta = t->theta;
     a.accum = t->accum;
-    TrainModel& r = a.model[0];
     r.H = t->H[0];
-    r.lr = lr; r.rho = rho; r.eps = eps;
-    r.frozen_mask = frozen_mask;
     PE_THIP(t, launch_train_apply(a, nullptr));
     PE_THIP(t, hipDeviceSynchronize());
     return PE_OK;
@@ -3391,14 +3392,14 @@ int pe_trainer_apply(pe_trainer* t, const float* grads_host, float lr, float rho
 
 int pe_trainer_set_data(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n) {
     if (!t) return PE_ERR_INVALID;
-    const int rc = train_upload_set(t, "pe_trainer_set_data", &t->data, 7, feats_host, targets_host, n);
+    const int rc = train_upload_set(t, "pe_trainer_set_data", &t->data, kBufDataFeats, feats_host, targets_host, n);
     if (rc == PE_OK || t->data.n == 0) t->sample_n = t->n_selected = 0;      // a new set: nothing selected, every row eligible
     return rc;
 }
 
 int pe_trainer_set_validation(pe_trainer* t, const float* feats_host, const float* targets_host, int32_t n) {
     if (!t) return PE_ERR_INVALID;
-    return train_upload_set(t, "pe_trainer_set_validation", &t->validation, 9, feats_host, targets_host, n);
+    return train_upload_set(t, "pe_trainer_set_validation", &t->validation, kBufValFeats, feats_host, targets_host, n);
 }
 
 int pe_trainer_step_models(pe_trainer* t, const int32_t* indices_host, int32_t n, uint64_t step, const pe_train_hparams* hp,
@@ -3446,9 +3447,9 @@ int pe_trainer_stats_models(pe_trainer* t, int32_t source, const float* feats_ho
     int rc = train_evaluate(t, who, source, feats_host, targets_host, n, nullptr, nullptr, nullptr, probs_out);
     if (rc) return rc;
     const StatsScratch s = stats_scratch(t->K, n, n_thresholds, false, false);
-    if ((rc = train_reserve(t, 11, s.total))) return rc;
-    PE_THIP(t, stats_run(static_cast<char*>(t->buf[11].p), s, static_cast<const float*>(t->buf[6].p), n,
-                         set ? set->targets : static_cast<const float*>(t->buf[1].p), n, t->K, q));
+    if ((rc = train_reserve(t, kBufStats, s.total))) return rc;
+    PE_THIP(t, stats_run(static_cast<char*>(t->buf[kBufStats].p), s, static_cast<const float*>(t->buf[kBufProbs].p), n,
+                         set ? set->targets : static_cast<const float*>(t->buf[kBufTargets].p), n, t->K, q));
     return PE_OK;
 }
 
@@ -3498,7 +3499,7 @@ int pe_train_dropout_masks_layer(uint64_t seed, uint64_t step, int32_t layer, in
 namespace {
 
 // buf[slot] holds at least `bytes`, its first `keep` bytes kept (device to device) when it has to move; grows by doubling
-int train_grow(pe_trainer* t, int slot, size_t keep, size_t bytes) {
+int train_grow(pe_trainer* t, TrainBuf slot, size_t keep, size_t bytes) {
     DeviceBuf& b = t->buf[slot];
     if (b.p && b.bytes >= bytes) return PE_OK;
     const size_t want = std::max(bytes, 2 * b.bytes);
@@ -3515,10 +3516,10 @@ int train_grow(pe_trainer* t, int slot, size_t keep, size_t bytes) {
 }
 
 // room for n more samples behind the resident set `source`: *set / *slot name it, its pointers follow the buffers
-int train_set_room(pe_trainer* t, const char* who, int source, int n, TrainSet** set, int* slot) {
+int train_set_room(pe_trainer* t, const char* who, int source, int n, TrainSet** set, TrainBuf* slot) {
     if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return tfail(t, PE_ERR_INVALID, "%s: source = %d", who, source);
     *set = source == PE_TRAIN_SOURCE_DATA ? &t->data : &t->validation;
-    *slot = source == PE_TRAIN_SOURCE_DATA ? 7 : 9;
+    *slot = source == PE_TRAIN_SOURCE_DATA ? kBufDataFeats : kBufValFeats;
     const int have = (*set)->n;
     if (n > 0x7fffffff - have) return tfail(t, PE_ERR_INVALID, "%s: %d + %d samples are more than a set holds", who, have, n);
     const size_t row = (size_t)t->T * t->F * sizeof(float);
@@ -3526,35 +3527,35 @@ int train_set_room(pe_trainer* t, const char* who, int source, int n, TrainSet**
     // (the set follows each buffer as soon as it has moved: a failure of the second leaves a valid set of `have` samples)
     if ((rc = train_grow(t, *slot, (size_t)have * row, (size_t)(have + n) * row))) return rc;
     (*set)->feats = static_cast<const float*>(t->buf[*slot].p);
-    if ((rc = train_grow(t, *slot + 1, (size_t)have * sizeof(float), (size_t)(have + n) * sizeof(float)))) return rc;
-    (*set)->targets = static_cast<const float*>(t->buf[*slot + 1].p);
+    if ((rc = train_grow(t, train_targets_of(*slot), (size_t)have * sizeof(float), (size_t)(have + n) * sizeof(float)))) return rc;
+    (*set)->targets = static_cast<const float*>(t->buf[train_targets_of(*slot)].p);
     return PE_OK;
 }
 
 // n samples whose rows are on the trainer's device already, every target = `target`
 int train_append_device(pe_trainer* t, const char* who, int source, const float* feats_dev, int n, float target) {
     if (!(target >= 0.0f && target <= 1.0f)) return tfail(t, PE_ERR_INVALID, "%s: target %g is outside [0, 1]", who, (double)target);
-    TrainSet* set; int slot;
+    TrainSet* set; TrainBuf slot;
     PE_THIP(t, hipSetDevice(t->device));
     int rc = train_set_room(t, who, source, n, &set, &slot);
     if (rc) return rc;
     const size_t row = (size_t)t->T * t->F;
     const std::vector<float> y((size_t)n, target);
     PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot].p) + (size_t)set->n * row, feats_dev, (size_t)n * row * sizeof(float), hipMemcpyDeviceToDevice));
-    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot + 1].p) + set->n, y.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[train_targets_of(slot)].p) + set->n, y.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     set->n += n;
     return PE_OK;
 }
 
 // ... one target per sample, on the device as well (the caller has checked that each lies in [0, 1])
 int train_append_device_targets(pe_trainer* t, const char* who, int source, const float* feats_dev, const float* targets_dev, int n) {
-    TrainSet* set; int slot;
+    TrainSet* set; TrainBuf slot;
     PE_THIP(t, hipSetDevice(t->device));
     int rc = train_set_room(t, who, source, n, &set, &slot);
     if (rc) return rc;
     const size_t row = (size_t)t->T * t->F;
     PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot].p) + (size_t)set->n * row, feats_dev, (size_t)n * row * sizeof(float), hipMemcpyDeviceToDevice));
-    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot + 1].p) + set->n, targets_dev, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice));
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[train_targets_of(slot)].p) + set->n, targets_dev, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice));
     set->n += n;
     return PE_OK;
 }
@@ -3572,11 +3573,11 @@ int pe_trainer_append(pe_trainer* t, int32_t source, const float* feats_host, co
     int rc = train_check_targets(t, targets_host, n);
     if (rc) return rc;
     PE_THIP(t, hipSetDevice(t->device));
-    TrainSet* set; int slot;
+    TrainSet* set; TrainBuf slot;
     if ((rc = train_set_room(t, who, source, n, &set, &slot))) return rc;
     const size_t row = (size_t)t->T * t->F;
     PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot].p) + (size_t)set->n * row, feats_host, (size_t)n * row * sizeof(float), hipMemcpyHostToDevice));
-    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[slot + 1].p) + set->n, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(static_cast<float*>(t->buf[train_targets_of(slot)].p) + set->n, targets_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     set->n += n;
     return PE_OK;
 }
@@ -3608,10 +3609,10 @@ namespace {
 int sample_state_room(pe_trainer* t) {
     const int n = t->data.n;
     int rc;
-    if ((rc = train_grow(t, 12, (size_t)t->sample_n, (size_t)n))) return rc;
-    if ((rc = train_grow(t, 13, (size_t)t->n_selected * sizeof(int32_t), (size_t)n * sizeof(int32_t)))) return rc;
+    if ((rc = train_grow(t, kBufSampleState, (size_t)t->sample_n, (size_t)n))) return rc;
+    if ((rc = train_grow(t, kBufSampleList, (size_t)t->n_selected * sizeof(int32_t), (size_t)n * sizeof(int32_t)))) return rc;
     if (t->sample_n < n) {
-        PE_THIP(t, hipMemset(static_cast<uint8_t*>(t->buf[12].p) + t->sample_n, kSampleEligible, (size_t)(n - t->sample_n)));
+        PE_THIP(t, hipMemset(static_cast<uint8_t*>(t->buf[kBufSampleState].p) + t->sample_n, kSampleEligible, (size_t)(n - t->sample_n)));
         t->sample_n = n;
     }
     return PE_OK;
@@ -3637,20 +3638,20 @@ int pe_trainer_evaluate_indices(pe_trainer* t, int32_t source, const int32_t* in
         if (indices_host[i] < 0 || indices_host[i] >= set.n)
             return tfail(t, PE_ERR_INVALID, "%s: indices[%d] = %d is outside the set of %d samples", who, i, indices_host[i], set.n);
     PE_THIP(t, hipSetDevice(t->device));
-    int rc = train_reserve(t, 3, (size_t)n * sizeof(int32_t));
+    int rc = train_reserve(t, kBufIndices, (size_t)n * sizeof(int32_t));
     if (rc) return rc;
-    PE_THIP(t, hipMemcpy(t->buf[3].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    PE_THIP(t, hipMemcpy(t->buf[kBufIndices].p, indices_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     TrainArgs a{};
     a.n = n;
     a.feats = set.feats;
     a.targets = set.targets;
-    a.indices = static_cast<const int32_t*>(t->buf[3].p);
+    a.indices = static_cast<const int32_t*>(t->buf[kBufIndices].p);
     for (int m = 0; m < t->K; ++m) a.model[m].beta = loss_bias ? loss_bias[m] : 0.0f;
     if ((rc = train_run(t, a, false))) return rc;
     const float* targets = nullptr;
     if (acc_out) {                                      // the accuracy count reads targets in launch order
-        if ((rc = train_reserve(t, 1, (size_t)n * sizeof(float)))) return rc;
-        SampleGatherArgs g{set.targets, a.indices, n, static_cast<float*>(t->buf[1].p)};
+        if ((rc = train_reserve(t, kBufTargets, (size_t)n * sizeof(float)))) return rc;
+        SampleGatherArgs g{set.targets, a.indices, n, static_cast<float*>(t->buf[kBufTargets].p)};
         PE_THIP(t, launch_sample_gather_targets(g, nullptr));
         targets = g.out;
     }
@@ -3675,9 +3676,9 @@ int pe_trainer_sample_reset(pe_trainer* t, const uint8_t* eligible_host, const i
     }
     PE_THIP(t, hipSetDevice(t->device));
     int rc;
-    if ((rc = train_grow(t, 12, 0, (size_t)n)) || (rc = train_grow(t, 13, 0, (size_t)n * sizeof(int32_t)))) return rc;
-    PE_THIP(t, hipMemcpy(t->buf[12].p, state.data(), (size_t)n, hipMemcpyHostToDevice));
-    if (n_selected) PE_THIP(t, hipMemcpy(t->buf[13].p, selected_host, (size_t)n_selected * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = train_grow(t, kBufSampleState, 0, (size_t)n)) || (rc = train_grow(t, kBufSampleList, 0, (size_t)n * sizeof(int32_t)))) return rc;
+    PE_THIP(t, hipMemcpy(t->buf[kBufSampleState].p, state.data(), (size_t)n, hipMemcpyHostToDevice));
+    if (n_selected) PE_THIP(t, hipMemcpy(t->buf[kBufSampleList].p, selected_host, (size_t)n_selected * sizeof(int32_t), hipMemcpyHostToDevice));
     t->sample_n = n;
     t->n_selected = n_selected;
     return PE_OK;
@@ -3700,8 +3701,8 @@ int pe_trainer_sample_choose(pe_trainer* t, int32_t model, int32_t max_new, int3
     // scratch: counters[4] | report | added[PE_SAMPLE_MAX_NEW] | keys_a | keys_b
     const size_t head = 4 * sizeof(unsigned long long), tail = sizeof(SampleReport) + (size_t)PE_SAMPLE_MAX_NEW * sizeof(int32_t);
     const size_t keys = (size_t)sample_blocks(n) * max_new;
-    if ((rc = train_reserve(t, 14, head + tail + 2 * keys * sizeof(unsigned long long)))) return rc;
-    char* const scratch = static_cast<char*>(t->buf[14].p);
+    if ((rc = train_reserve(t, kBufSampleScratch, head + tail + 2 * keys * sizeof(unsigned long long)))) return rc;
+    char* const scratch = static_cast<char*>(t->buf[kBufSampleScratch].p);
     TrainArgs f{};
     f.n = n;
     f.feats = t->data.feats;
@@ -3710,14 +3711,14 @@ int pe_trainer_sample_choose(pe_trainer* t, int32_t model, int32_t max_new, int3
     SampleArgs a{};
     a.probs = f.probs + (size_t)model * n;
     a.targets = t->data.targets;
-    a.state = static_cast<uint8_t*>(t->buf[12].p);
+    a.state = static_cast<uint8_t*>(t->buf[kBufSampleState].p);
     a.n = n;
     a.k = max_new;
     a.order = order;
     a.counters = reinterpret_cast<unsigned long long*>(scratch);
     a.report = reinterpret_cast<SampleReport*>(scratch + head);
     a.added = reinterpret_cast<int32_t*>(scratch + head + sizeof(SampleReport));
-    a.selection = static_cast<int32_t*>(t->buf[13].p);
+    a.selection = static_cast<int32_t*>(t->buf[kBufSampleList].p);
     a.n_selected = t->n_selected;
     unsigned long long* const keys_a = reinterpret_cast<unsigned long long*>(scratch + head + tail);
     PE_THIP(t, hipMemsetAsync(a.counters, 0, head, nullptr));
@@ -3736,7 +3737,7 @@ int pe_trainer_sample_selected(pe_trainer* t, int32_t* out) {
     if (t->n_selected == 0) return PE_OK;
     if (!out) return tfail(t, PE_ERR_INVALID, "pe_trainer_sample_selected: null pointer");
     PE_THIP(t, hipSetDevice(t->device));
-    PE_THIP(t, hipMemcpy(out, t->buf[13].p, (size_t)t->n_selected * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PE_THIP(t, hipMemcpy(out, t->buf[kBufSampleList].p, (size_t)t->n_selected * sizeof(int32_t), hipMemcpyDeviceToHost));
     return PE_OK;
 }
 

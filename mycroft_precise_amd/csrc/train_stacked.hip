@@ -23,17 +23,25 @@ __global__ __launch_bounds__(64 * kTwMaxWaves) void ts_backward1_kernel(const Tr
     float* const DZ = ts_lds;
     float* const DR = DZ + a.H2p * 16;
     float* const DH = DR + a.H2p * 16;
-    ts_backward<1>(a, DZ, DR, DH, DH + a.H2p * 16);
+    tw_backward<TwDx::kWrite>(a.T, ts_layer1(a), a.fin, TwDxArgs{a.dx, a.H1p, a.w1t, a.mtape, DH + a.H2p * 16}, DZ, DR, DH);
 }
 __global__ __launch_bounds__(64 * kTwMaxWaves) void ts_backward0_kernel(const TrainStackedArgs a) {
     __shared__ __attribute__((aligned(16))) float DZ[kTwLdsState];
     __shared__ __attribute__((aligned(16))) float DR[kTwLdsState];
     __shared__ __attribute__((aligned(16))) float DH[kTwLdsState];
-    ts_backward<0>(a, DZ, DR, DH, nullptr);
+    tw_backward<TwDx::kRead>(a.T, ts_layer0(a), nullptr, TwDxArgs{a.dx, a.H1p, nullptr, nullptr, nullptr}, DZ, DR, DH);
 }
-__global__ __launch_bounds__(256) void ts_gemm0_kernel(const TrainWideArgs a) { tw_gemm(a); }
-__global__ __launch_bounds__(256) void ts_gemm1_kernel(const TrainStackedArgs a) { ts_gemm1(a); }
-__global__ __launch_bounds__(256) void ts_reduce_kernel(const TrainStackedArgs a) { ts_reduce(a); }
+__global__ __launch_bounds__(256) void ts_gemm0_kernel(const TrainStackedArgs a) {
+    tw_gemm<false>(a.T, a.n_tiles, ts_layer0(a), TwGemmBelow{});
+}
+__global__ __launch_bounds__(256) void ts_gemm1_kernel(const TrainStackedArgs a) {
+    tw_gemm<true>(a.T, a.n_tiles, ts_layer1(a), TwGemmBelow{a.tape0, tw_record(a.F, a.H1p), a.hfin0, a.mtape, a.H1p});
+}
+__global__ __launch_bounds__(256) void ts_reduce_kernel(const TrainStackedArgs a) {
+    const TwLayer l0 = ts_layer0(a), l1 = ts_layer1(a);
+    const TwLayer* const l[2] = {&l0, &l1};
+    tw_reduce(a, l, a.partial);
+}
 __global__ __launch_bounds__(256) void ts_apply_kernel(const TrainStackedArgs a) { ts_apply(a); }
 
 namespace pe {
@@ -80,19 +88,8 @@ hipError_t launch_train_stacked(const TrainStackedArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(ts_pack_kernel, dim3((unsigned)(packed + 255) / 256), dim3(256), 0, s, a);
         hipLaunchKernelGGL(ts_backward1_kernel, tiles, dim3(th1), lb, s, a);
         hipLaunchKernelGGL(ts_backward0_kernel, tiles, dim3(th0), 0, s, a);
-        const unsigned S = (unsigned)tw_chunks((long long)a.n_tiles * a.T);
-        {
-            TrainWideArgs w{};                      // what tw_gemm reads
-            w.n = a.n; w.T = a.T; w.F = a.F; w.H = a.H1; w.Hp = a.H1p; w.n_tiles = a.n_tiles;
-            w.tape = a.tape0;
-            w.gpart = a.gpart0;
-            const int R = a.F + a.H1 + 1, RB = ((R + 15) / 16 + 1) / 2, CB = (a.H1p / 16 + 3) / 4;
-            hipLaunchKernelGGL(ts_gemm0_kernel, dim3((unsigned)(3 * RB * CB + 3) / 4, S), dim3(256), 0, s, w);
-        }
-        {
-            const int R = a.H1 + a.H2 + 1, RB = ((R + 15) / 16 + 1) / 2, CB = (a.H2p / 16 + 3) / 4;
-            hipLaunchKernelGGL(ts_gemm1_kernel, dim3((unsigned)(3 * RB * CB + 3) / 4, S), dim3(256), 0, s, a);
-        }
+        hipLaunchKernelGGL(ts_gemm0_kernel, tw_gemm_grid(a.T, a.n_tiles, a.F, a.H1), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(ts_gemm1_kernel, tw_gemm_grid(a.T, a.n_tiles, a.H1, a.H2), dim3(256), 0, s, a);
         n_par = ts_n_params(a.F, a.H1, a.H2);
     }
     hipLaunchKernelGGL(ts_reduce_kernel, dim3((unsigned)(n_par + 1 + 255) / 256), dim3(256), 0, s, a);

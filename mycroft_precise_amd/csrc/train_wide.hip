@@ -13,15 +13,22 @@ __global__ __launch_bounds__(64 * kTwMaxWaves) void tw_forward_kernel(const Trai
     __shared__ float SC[kTwMaxWaves * 16 + 48];
     tw_forward<BACKWARD>(a, HT, RHT, XM, MS, SC);
 }
-__global__ __launch_bounds__(256) void tw_pack_kernel(const TrainWideArgs a) { tw_pack(a); }
+__global__ __launch_bounds__(256) void tw_pack_kernel(const TrainWideArgs a) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < 3 * a.Hp * a.Hp) tw_pack(a.ut, a.theta + a.F * 3 * a.H, e, a.H, a.Hp, a.H, a.Hp);
+}
 __global__ __launch_bounds__(64 * kTwMaxWaves) void tw_backward_kernel(const TrainWideArgs a) {
     __shared__ __attribute__((aligned(16))) float DZ[kTwLdsState];
     __shared__ __attribute__((aligned(16))) float DR[kTwLdsState];
     __shared__ __attribute__((aligned(16))) float DH[kTwLdsState];
-    tw_backward(a, DZ, DR, DH);
+    tw_backward<TwDx::kNone>(a.T, tw_layer(a), a.fin, TwDxArgs{}, DZ, DR, DH);
 }
-__global__ __launch_bounds__(256) void tw_gemm_kernel(const TrainWideArgs a) { tw_gemm(a); }
-__global__ __launch_bounds__(256) void tw_reduce_kernel(const TrainWideArgs a) { tw_reduce(a); }
+__global__ __launch_bounds__(256) void tw_gemm_kernel(const TrainWideArgs a) { tw_gemm<false>(a.T, a.n_tiles, tw_layer(a), TwGemmBelow{}); }
+__global__ __launch_bounds__(256) void tw_reduce_kernel(const TrainWideArgs a) {
+    const TwLayer l0 = tw_layer(a);
+    const TwLayer* const l[1] = {&l0};
+    tw_reduce(a, l, a.partial);
+}
 
 namespace pe {
 
@@ -37,9 +44,7 @@ hipError_t launch_train_wide(const TrainWideArgs& a, hipStream_t s) {
     if (a.backward) {
         hipLaunchKernelGGL(tw_pack_kernel, dim3((unsigned)(3 * a.Hp * a.Hp + 255) / 256), dim3(256), 0, s, a);
         hipLaunchKernelGGL(tw_backward_kernel, dim3((unsigned)a.n_tiles), dim3(threads), 0, s, a);
-        const int R = a.F + a.H + 1, RB = ((R + 15) / 16 + 1) / 2, CB = (a.Hp / 16 + 3) / 4;
-        const int S = tw_chunks((long long)a.n_tiles * a.T);
-        hipLaunchKernelGGL(tw_gemm_kernel, dim3((unsigned)(3 * RB * CB + 3) / 4, (unsigned)S), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(tw_gemm_kernel, tw_gemm_grid(a.T, a.n_tiles, a.F, a.H), dim3(256), 0, s, a);
         n_par = train_n_params(a.F, a.H);
     }
     hipLaunchKernelGGL(tw_reduce_kernel, dim3((unsigned)(n_par + 1 + 255) / 256), dim3(256), 0, s, a);

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Kernel-by-kernel comparison of two builds of kernels.hip (gfx950 ISA as the compiler emits it), no GPU needed: the proof
-that a refactor left the generated code alone.
+"""Kernel-by-kernel comparison of two builds of one source of csrc/ (kernels.hip unless --source names another; gfx950 ISA as
+the compiler emits it), no GPU needed: the proof that a refactor left the generated code alone.
 
-    python tools/isa_compare.py OLD NEW --work DIR [--out TABLE.txt]
+    python tools/isa_compare.py OLD NEW --work DIR [--source NAME.hip] [--out TABLE.txt]
 
-OLD / NEW: a `.s` file (hipcc -S --cuda-device-only), or a source tree, whose kernels.hip is compiled into DIR with the flags
+OLD / NEW: a `.s` file (hipcc -S --cuda-device-only), or a source tree, whose csrc/NAME.hip is compiled into DIR with the flags
 of mycroft_precise_amd/_build.py.  For every kernel, keyed by mangled name: `identical` when the instruction streams agree
 after label normalisation; otherwise the instruction counts, next_free_vgpr / next_free_sgpr / group_segment_fixed_size /
 private_segment_fixed_size of both sides and the opcodes whose counts differ -- `same-shape` when all of those agree (only
@@ -21,11 +21,11 @@ def build_flags(tree):
     return [f for f in flags if f not in ('-fPIC', '-Wall', '-Wno-unused-function')]
 
 
-def assembly(path, work, tag):
+def assembly(path, work, tag, source):
     if os.path.isfile(path):
         return open(path).read()
-    out = os.path.join(work, tag + '_kernels.s')
-    src = os.path.join(path, 'mycroft_precise_amd', 'csrc', 'kernels.hip')
+    out = os.path.join(work, tag + '_' + os.path.splitext(source)[0] + '.s')
+    src = os.path.join(path, 'mycroft_precise_amd', 'csrc', source)
     hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'          # (as _build.py finds it)
     subprocess.run([hipcc] + build_flags(path) + ['--cuda-device-only', '-S', src, '-o', out], check=True)
     return open(out).read()
@@ -60,10 +60,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('old'), ap.add_argument('new')
     ap.add_argument('--work', required=True, help='directory for the compiled .s files')
+    ap.add_argument('--source', default='kernels.hip', help='the file of mycroft_precise_amd/csrc to compile (default kernels.hip)')
     ap.add_argument('--out', help='also write the table here')
     args = ap.parse_args()
     os.makedirs(args.work, exist_ok=True)
-    old, new = kernels(assembly(args.old, args.work, 'old')), kernels(assembly(args.new, args.work, 'new'))
+    old, new = (kernels(assembly(p, args.work, tag, args.source)) for p, tag in ((args.old, 'old'), (args.new, 'new')))
     rows, tally, bad = [], collections.Counter(), 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
