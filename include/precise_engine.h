@@ -127,7 +127,8 @@ const char* pe_last_error(const pe_engine* e);
  *   - Outputs: every entry point that writes network outputs writes n_models blocks, model first; block m is
  *     bit for bit what a one-model engine with model m, the same params, n_streams and form
  *     (pe_get_gru_tiling) writes: pe_update[_device|_device_keep], pe_run_device, pe_update_async (its pinned
- *     landing zones are sized for it) [K][n_streams]; pe_update_subset[_device] [K][n_active];
+ *     landing zones are sized for it) [K][n_streams]; pe_update_subset[_device|_async] [K][n_active]
+ *     (pe_decode_subset[_device] and the conf / fired of pe_update_subset_async likewise);
  *     pe_update_many[_device] [K][n_updates][n_streams]; pe_predict[_device] [K][n];
  *     pe_evaluate [K][max_windows] (n_windows_out is the same for every model); pe_decode[_device] reads
  *     raw[K][n_streams] and writes conf / fired [K][n_streams].  Entry points without a network (vectors,
@@ -220,6 +221,23 @@ int pe_host_alloc(pe_engine* e, size_t bytes, void** out);
 int pe_host_free(pe_engine* e, void* p);
 int pe_update_async(pe_engine* e, const int16_t* pcm_host, int32_t chunk_samples, float* raw_out_host);
 int pe_wait(pe_engine* e);
+
+/* The pipeline for streams that advance independently -- what a server that multiplexes many clients on one engine calls
+ * per tick: host PCM for SOME streams in, raw output, decoded confidence and activation per active stream out.  The update
+ * is pe_update_subset's (same launch choice, same bits), enqueued on pe_update_async's ring of 3 (the chunks cross PCIe on the
+ * copy stream, the ids in front of the update on the compute stream); when conf_out_host or fired_out_host is given, ONE pe_decode_subset launch over the update's raw
+ * outputs follows it on the compute stream, then the copies back.  All three outputs are [n_models][n_active] in the order
+ * of the ids and valid after pe_wait (or once 3 more updates have been enqueued); each of them is, independently, pageable
+ * (filled at delivery) or pe_host_alloc'ed (written by the DMA).  The ids are read at the call.
+ *   - stream_ids_host == NULL: every stream in order; n_active must be n_streams.  That is pe_update_async's update plus
+ *     the decode -- a pipelined update + pe_decode for lock-step callers;
+ *   - refused before anything is enqueued (PE_ERR_INVALID): n_active outside 0..n_streams, ids out of range or named twice,
+ *     raw_out_host NULL, conf / fired asked for without pe_set_decoder.  chunk_samples == 0 with n_active > 0 -> PE_ERR_EOF;
+ *     n_active == 0 is a no-op (PE_OK) that leaves the outputs untouched;
+ *   - a stream named in two updates in flight is served in the order of the calls (one compute stream).
+ * pe_update_async and this call may be mixed freely. */
+int pe_update_subset_async(pe_engine* e, const int32_t* stream_ids_host, int32_t n_active, const int16_t* pcm_host,
+                           int32_t chunk_samples, float* raw_out_host, double* conf_out_host, unsigned char* fired_out_host);
 
 /* n_updates consecutive pe_update calls in two launches (results bit-identical): chunk u of stream s at
  * pcm[(u * n_streams + s) * chunk_samples], raw_out[u * n_streams + s].  First one launch computes every
@@ -438,6 +456,16 @@ int pe_set_decoder_model(pe_engine* e, int32_t model, const double* cd, int32_t 
 int pe_set_trigger_model(pe_engine* e, int32_t model, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level);
 int pe_decode_device(pe_engine* e, const float* raw_dev, double* conf_out_dev, unsigned char* fired_out_dev, void* hip_stream);
 int pe_decode(pe_engine* e, const float* raw_host, double* conf_out_host, unsigned char* fired_out_host);
+/* The same after pe_update_subset: row i of raw / conf / fired ([n_models][n_active], in the order of the ids) belongs to
+ * stream stream_ids[i], and only the named streams' TriggerDetectors move -- a stream that received no audio neither decays
+ * nor fires (pe_decode would step every stream's).  One launch for all models.  The host entry point validates the ids as
+ * pe_update_subset does (PE_ERR_INVALID: out of range / named twice), the device one cannot.  n_active == 0 is a no-op
+ * (PE_OK); without pe_set_decoder the error is pe_decode's; without a trigger fired is zeros.
+ * All four decode calls, like the setters above, first wait for updates in flight (pe_update_subset_async moves triggers). */
+int pe_decode_subset_device(pe_engine* e, const int32_t* stream_ids_dev, int32_t n_active, const float* raw_dev,
+                            double* conf_out_dev, unsigned char* fired_out_dev, void* hip_stream);
+int pe_decode_subset(pe_engine* e, const int32_t* stream_ids_host, int32_t n_active, const float* raw_host,
+                     double* conf_out_host, unsigned char* fired_out_host);
 
 /* Introspection used by tests and the bench. */
 typedef struct pe_info {

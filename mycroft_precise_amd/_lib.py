@@ -83,6 +83,7 @@ EXPORTS = {
     'pe_host_free': (C.c_int, [C.c_void_p, C.c_void_p]),
     'pe_update_async': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'pe_wait': (C.c_int, [C.c_void_p]),
+    'pe_update_subset_async': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_reserve_updates': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     'pe_update_many': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'pe_update_many_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -118,6 +119,8 @@ EXPORTS = {
     'pe_set_trigger_model': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
     'pe_decode_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pe_decode_subset_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pe_decode_subset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_get_info': (C.c_int, [C.c_void_p, C.POINTER(PeInfo)]),
     'pe_get_stream_state': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pe_set_fused': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -492,6 +495,47 @@ class HipEngine:
         self._async_keep = (self._async_keep + [(pcm, out)])[-4:]          # the buffers of the updates in flight stay alive
         return out
 
+    def _ids(self, stream_ids) -> np.ndarray:
+        """stream ids as int32 [n_active], each in range and named once (checked here: no native call sees a bad list)"""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.n_streams):
+            raise ValueError('stream ids must lie in 0..%d' % (self.n_streams - 1))
+        if np.unique(ids).size != ids.size:
+            raise ValueError('a stream is named twice')
+        return ids
+
+    def _out(self, a, dtype, n_rows, what):
+        """an output array of a subset call: float32 / float64 / uint8 [n_rows] ([K, n_rows] on a K-model engine), C order"""
+        if a is None:
+            return np.zeros(self._lead(n_rows), dtype=dtype)
+        if not isinstance(a, np.ndarray) or a.dtype != dtype or a.size != self.n_models * n_rows or not a.flags.c_contiguous:
+            raise ValueError('%s must be a contiguous %s array of %d elements' % (what, np.dtype(dtype).name, self.n_models * n_rows))
+        return a
+
+    def update_subset_async(self, stream_ids, pcm, out=None, conf=None, fired=None):
+        """``update_subset`` through the pipeline of ``update_async`` (pe_update_subset_async): the streams named in
+        ``stream_ids`` (unique, in range; None = every stream in order) take one chunk each -- pcm int16 [n_active, chunk].
+        -> the float32 [n_active] array (``out`` or a new one) the raw outputs are in after ``wait()`` or once 3 more updates
+        have been enqueued.  ``conf`` (float64 [n_active]) and ``fired`` (uint8 [n_active]), when given, receive the decoded
+        confidences and the activations of this update at the same moment: one subset decode on the device behind the
+        update, which moves the named streams' triggers only.  [K, n_active] each on a K-model engine.  Every array may be
+        pageable or from ``host_array``; the rules of ``update_async`` apply to each."""
+        ids = None if stream_ids is None else self._ids(stream_ids)
+        n = self.n_streams if ids is None else ids.size
+        pcm = np.ascontiguousarray(pcm, dtype='<i2')
+        if pcm.ndim == 1:
+            pcm = pcm.reshape(1, -1)
+        if pcm.ndim != 2 or pcm.shape[0] != n:
+            raise ValueError('pcm must be int16 [%d active streams, chunk_samples], got %r' % (n, pcm.shape))
+        out = self._out(out, np.float32, n, 'out')
+        conf = None if conf is None else self._out(conf, np.float64, n, 'conf')
+        fired = None if fired is None else self._out(fired, np.uint8, n, 'fired')
+        self._check(self._lib.pe_update_subset_async(
+            self._h, None if ids is None else ids.ctypes.data, n, pcm.ctypes.data, pcm.shape[1], out.ctypes.data,
+            None if conf is None else conf.ctypes.data, None if fired is None else fired.ctypes.data))
+        self._async_keep = (self._async_keep + [(ids, pcm, out, conf, fired)])[-4:]
+        return out
+
     def wait(self):
         self._check(self._lib.pe_wait(self._h))
         self._async_keep = []
@@ -761,6 +805,18 @@ class HipEngine:
         conf = np.empty(self._lead(self.n_streams), dtype=np.float64)
         fired = np.zeros(self._lead(self.n_streams), dtype=np.uint8)
         self._check(self._lib.pe_decode(self._h, raw.ctypes.data, conf.ctypes.data, fired.ctypes.data))
+        return (conf, fired.astype(bool)) if want_fired else conf
+
+    def decode_subset(self, stream_ids, raw, want_fired=False):
+        """``decode`` after ``update_subset``: raw float32 [n_active] in the order of ``stream_ids`` -> confidences float64
+        [n_active] (, fired bool [n_active]); [K, n_active] each on a K-model engine.  Only the named streams' triggers move."""
+        ids = self._ids(stream_ids)
+        raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(-1)
+        if raw.size != self.n_models * ids.size:
+            raise ValueError('expected %d raw outputs for %d streams' % (self.n_models * ids.size, ids.size))
+        conf = np.empty(self._lead(ids.size), dtype=np.float64)
+        fired = np.zeros(self._lead(ids.size), dtype=np.uint8)
+        self._check(self._lib.pe_decode_subset(self._h, ids.ctypes.data, ids.size, raw.ctypes.data, conf.ctypes.data, fired.ctypes.data))
         return (conf, fired.astype(bool)) if want_fired else conf
 
     def clear(self, mask=None):

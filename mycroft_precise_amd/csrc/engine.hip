@@ -144,15 +144,21 @@ struct pe_engine {
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     bool ev_valid = false, ev_has_gru = false;
-    // host-fed pipeline (pe_update_async / pe_wait): a ring of kAsyncDepth updates in flight, each with its own device
+    // host-fed pipeline (pe_update_async / pe_update_subset_async / pe_wait): a ring of kAsyncDepth updates in flight, each with its own device
     // buffers and pinned staging; the chunk of update u + 1 crosses PCIe (copy stream) while update u runs (compute stream)
     static constexpr int kAsyncDepth = 3;
     struct AsyncSlot {
-        float* pin_out = nullptr; size_t pin_out_bytes = 0;     // pinned landing zone for callers whose output array is pageable
-        DeviceBuf dev_in, dev_out;
+        // what an update hands back: raw outputs, and from pe_update_subset_async decoded confidence and activations
+        struct Out {
+            DeviceBuf dev;
+            void* pin = nullptr; size_t pin_bytes = 0;          // pinned landing zone for callers whose array is pageable
+            void* user = nullptr; size_t bytes = 0;             // this update: where it goes (null: not asked for)
+            bool direct = false;                                // ... and whether the DMA writes there itself
+        } out[3];                                               // raw, conf, fired
+        DeviceBuf dev_in, dev_ids;                              // the chunks and (subset updates) the stream ids of this update
+        void* pin_ids = nullptr; size_t pin_ids_bytes = 0;      // the ids as the call found them: the DMA reads them from here
         hipEvent_t copied = nullptr, done = nullptr;
-        float* user_out = nullptr; size_t out_bytes = 0;
-        bool direct_out = false, busy = false;
+        bool busy = false;
     } aslot[kAsyncDepth];
     hipStream_t s_copy = nullptr, s_compute = nullptr;
     // the stream of the last *_device call that moved the streams' state: pe_update_async runs on the engine's own
@@ -1056,7 +1062,8 @@ int finish_slot(pe_engine* e, pe_engine::AsyncSlot& sl) {
     sl.busy = false;                                  // (also when the wait failed: a slot that stays busy would fail every later drain)
     --e->async_inflight;
     if (err != hipSuccess) return fail(e, PE_ERR_HIP, "hipEventSynchronize(update in flight) failed: %s", hipGetErrorString(err));
-    if (!sl.direct_out) std::memcpy(sl.user_out, sl.pin_out, sl.out_bytes);
+    for (auto& o : sl.out)
+        if (o.user && !o.direct) std::memcpy(o.user, o.pin, o.bytes);
     return PE_OK;
 }
 
@@ -1080,6 +1087,50 @@ int check_chunk(pe_engine* e, const void* pcm, int chunk) {
     if (!e) return PE_ERR_INVALID;
     if (chunk == 0) return fail(e, PE_ERR_EOF, "empty chunk");
     if (chunk < 0 || !pcm) return fail(e, PE_ERR_INVALID, "bad pcm buffer / chunk_samples=%d", chunk);
+    return PE_OK;
+}
+
+int check_decoder(pe_engine* e) {
+    for (int m = 0; m < e->n_models; ++m) {
+        const DecState& d = e->dec[m];
+        if (!d.cd && d.out_range != 0) return fail(e, PE_ERR_INVALID, "pe_set_decoder has not been called");
+        if (!d.cd_len && !d.cd) return fail(e, PE_ERR_INVALID, m ? "pe_set_decoder has not been called for model %d" : "pe_set_decoder has not been called", m);
+    }
+    return PE_OK;
+}
+
+// every id in range, none twice (two rows for one stream in one launch would race on its record / its trigger state)
+int check_ids(pe_engine* e, const int32_t* ids, int n_active) {
+    e->seen_ids.assign((size_t)e->n_streams, 0);
+    for (int i = 0; i < n_active; ++i) {
+        const int32_t id = ids[i];
+        if (id < 0 || id >= e->n_streams) return fail(e, PE_ERR_INVALID, "stream_ids[%d]=%d outside 0..%d", i, id, e->n_streams - 1);
+        if (e->seen_ids[(size_t)id]) return fail(e, PE_ERR_INVALID, "stream %d is named twice (stream_ids[%d])", id, i);
+        e->seen_ids[(size_t)id] = 1;
+    }
+    return PE_OK;
+}
+
+// ONE decode launch (a K-model engine: per-model tables) over n_rows rows per model: every stream in order (ids null,
+// n_rows = n_streams), or the streams ids[0 .. n_rows) (device pointer).  raw / conf_out / fired_out: [n_models][n_rows].
+int launch_decode_rows(pe_engine* e, const int32_t* ids_dev, int n_rows, const float* raw_dev, double* conf_out_dev,
+                       unsigned char* fired_out_dev, hipStream_t s) {
+    const size_t n = (size_t)n_rows;
+    DecodeSet set{};
+    for (int m = 0; m < e->n_models; ++m) {
+        DecodeArgs& a = set.m[m];
+        a.n_streams = n_rows; a.raw = raw_dev + m * n;
+        a.conf_out = conf_out_dev ? conf_out_dev + m * n : nullptr;
+        a.fired_out = fired_out_dev ? fired_out_dev + m * n : nullptr;
+        const DecState& d = e->dec[m];
+        a.cd = d.cd; a.cd_len = d.cd_len;
+        a.min_out = d.min_out; a.out_range = d.out_range; a.center = d.center;
+        a.activation = d.on ? e->activation + (size_t)m * e->n_padded : nullptr;
+        a.threshold = d.threshold; a.trigger_level = d.level; a.rearm = d.rearm;
+        a.ids = ids_dev;
+    }
+    if (e->n_models == 1) PE_HIP(e, launch_decode(set.m[0], s));
+    else PE_HIP(e, launch_decode_models(set, e->n_models, n_rows, s));
     return PE_OK;
 }
 
@@ -1482,9 +1533,13 @@ int pe_destroy(pe_engine* e) {
     if (e->s_compute) (void)hipStreamSynchronize(e->s_compute);
     if (e->s_copy) (void)hipStreamSynchronize(e->s_copy);
     for (auto& sl : e->aslot) {
-        if (sl.pin_out) (void)hipHostFree(sl.pin_out);
+        for (auto& o : sl.out) {
+            if (o.pin) (void)hipHostFree(o.pin);
+            if (o.dev.p) (void)hipFree(o.dev.p);
+        }
         if (sl.dev_in.p) (void)hipFree(sl.dev_in.p);
-        if (sl.dev_out.p) (void)hipFree(sl.dev_out.p);
+        if (sl.dev_ids.p) (void)hipFree(sl.dev_ids.p);
+        if (sl.pin_ids) (void)hipHostFree(sl.pin_ids);
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -1604,15 +1659,8 @@ int pe_update_subset(pe_engine* e, const int32_t* stream_ids_host, int32_t n_act
     int rc = check_chunk(e, pcm_host, chunk);
     if (rc) return rc;
     if (!stream_ids_host || !raw_out_host) return fail(e, PE_ERR_INVALID, "null argument to pe_update_subset");
-    // the host entry point checks what the device one cannot: every id in range, none twice (two rows for one stream in one
-    // launch would race on its record)
-    e->seen_ids.assign((size_t)e->n_streams, 0);
-    for (int i = 0; i < n_active; ++i) {
-        const int32_t id = stream_ids_host[i];
-        if (id < 0 || id >= e->n_streams) return fail(e, PE_ERR_INVALID, "stream_ids[%d]=%d outside 0..%d", i, id, e->n_streams - 1);
-        if (e->seen_ids[(size_t)id]) return fail(e, PE_ERR_INVALID, "stream %d is named twice (stream_ids[%d])", id, i);
-        e->seen_ids[(size_t)id] = 1;
-    }
+    // the host entry point checks what the device one cannot
+    if ((rc = check_ids(e, stream_ids_host, n_active))) return rc;
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
     const size_t pcm_bytes = (size_t)n_active * chunk * sizeof(int16_t), out_bytes = (size_t)e->n_models * n_active * sizeof(float), id_bytes = (size_t)n_active * sizeof(int32_t);
@@ -1651,28 +1699,43 @@ int pe_host_free(pe_engine* e, void* p) {
     return fail(e, PE_ERR_INVALID, "pe_host_free: not a pe_host_alloc'ed pointer of this engine");
 }
 
-int pe_update_async(pe_engine* e, const int16_t* pcm_host, int32_t chunk, float* raw_out_host) {
-    int rc = check_chunk(e, pcm_host, chunk);
-    if (rc) return rc;
-    if (!raw_out_host) return fail(e, PE_ERR_INVALID, "raw_out_host is null");
-    PE_HIP(e, hipSetDevice(e->device));
+namespace {
+// One update through the host-fed pipeline (pe_update_async: every stream, raw outputs; pe_update_subset_async: the streams
+// ids_host[0 .. n_active) or, ids_host null, every stream; decoded confidence and activations on request).  The caller has
+// checked every argument: from here on only the runtime can fail.
+int update_async(pe_engine* e, const char* who, const int32_t* ids_host, int n_active, const int16_t* pcm_host, int chunk,
+                 float* raw_out_host, double* conf_out_host, unsigned char* fired_out_host) {
+    int rc;
     if ((rc = async_init(e))) return rc;
     pe_engine::AsyncSlot& sl = e->aslot[e->async_next % pe_engine::kAsyncDepth];
     if ((rc = finish_slot(e, sl))) return rc;          // the ring is full: the oldest update is delivered first
-    const size_t pcm_bytes = (size_t)e->n_streams * chunk * sizeof(int16_t), out_bytes = (size_t)e->n_models * e->n_streams * sizeof(float);
+    const size_t rows = (size_t)e->n_models * n_active;
+    const size_t pcm_bytes = (size_t)n_active * chunk * sizeof(int16_t), id_bytes = (size_t)n_active * sizeof(int32_t);
     if ((rc = ensure(e, sl.dev_in, pcm_bytes))) return rc;
-    if ((rc = ensure(e, sl.dev_out, out_bytes))) return rc;
+    if (ids_host) {
+        // (a copy of the ids in pinned memory of the slot: the caller's list is free again at once)
+        if ((rc = ensure(e, sl.dev_ids, id_bytes))) return rc;
+        if ((rc = ensure_pinned(e, &sl.pin_ids, &sl.pin_ids_bytes, id_bytes))) return rc;
+        std::memcpy(sl.pin_ids, ids_host, id_bytes);
+    }
     // (pageable memory: hipMemcpyAsync stages it through the runtime's own pinned buffers and returns once the last piece is
     //  staged -- the caller gets its buffer back at the return of this call; measured: 207 us per 8.4 MB update that
     //  way against 295 us with a memcpy into a pinned ring of the engine's own, 165 us zero-copy from pe_host_alloc'ed memory.
     //  Memory the runtime knows as pinned -- pe_host_alloc, but also hipHostRegister / torch pin_memory -- is read by the DMA
     //  AFTER this call returns: such a buffer must stay untouched until the update is delivered)
-    sl.direct_out = is_pinned(e, raw_out_host, out_bytes);
-    if (!sl.direct_out) {
-        void* po = sl.pin_out;
-        if ((rc = ensure_pinned(e, &po, &sl.pin_out_bytes, out_bytes))) return rc;
-        sl.pin_out = static_cast<float*>(po);
+    void* const user[3] = {raw_out_host, conf_out_host, fired_out_host};
+    const size_t bytes[3] = {rows * sizeof(float), rows * sizeof(double), rows};
+    for (int i = 0; i < 3; ++i) {
+        pe_engine::AsyncSlot::Out& o = sl.out[i];
+        o.user = nullptr;                              // (set when the update is in flight)
+        if (!user[i]) continue;
+        if ((rc = ensure(e, o.dev, bytes[i]))) return rc;
+        o.direct = is_pinned(e, user[i], bytes[i]);
+        if (!o.direct && (rc = ensure_pinned(e, &o.pin, &o.pin_bytes, bytes[i]))) return rc;
     }
+    const bool decode = conf_out_host || fired_out_host;
+    bool every_trigger = true;                          // a model without a trigger leaves its rows of `fired` alone: zeros
+    for (const DecState& d : e->dec) every_trigger = every_trigger && d.on;
     // state-moving work the caller queued through a *_device entry point (on the NULL stream or its own) comes first
     if (e->user_dirty) {
         PE_HIP(e, hipEventRecord(e->ev_user, e->last_user_stream));
@@ -1683,16 +1746,33 @@ int pe_update_async(pe_engine* e, const int16_t* pcm_host, int32_t chunk, float*
     // free, and the error goes to the caller (the streams' state may then be one update ahead of what was delivered --
     // the message says so; pe_clear restarts the streams).
     auto enqueue = [&]() -> int {
-        // this slot's device chunk was the `head` of the update AFTER the one the slot last carried (the leftovers stay in the
-        // chunks: do_update(..., keep)): that update must be through before the copy overwrites it
+        // This slot's device chunk may still be read by the update AFTER the one the slot last carried.  Only a full update
+        // leaves its leftovers in its chunk (do_update(..., keep); a subset update writes the carry), and only the very next
+        // update reads them there: a full one as the `head` of its first frames, a subset one through flush_kept, which it
+        // runs on the compute stream in front of its own launches.  Either way that reader is the update in the next slot of
+        // the ring, and its `done` event lies behind everything it launched -- so, for any mix of full and subset updates,
+        // that update must be through before the copy overwrites the chunk (a slot that is not busy was delivered: through)
         pe_engine::AsyncSlot& reader = e->aslot[(e->async_next + 1) % pe_engine::kAsyncDepth];
         if (reader.busy) PE_HIP(e, hipStreamWaitEvent(e->s_copy, reader.done, 0));
         PE_HIP(e, hipMemcpyAsync(sl.dev_in.p, pcm_host, pcm_bytes, hipMemcpyHostToDevice, e->s_copy));
         PE_HIP(e, hipEventRecord(sl.copied, e->s_copy));
         PE_HIP(e, hipStreamWaitEvent(e->s_compute, sl.copied, 0));
-        int urc = do_update(e, static_cast<const int16_t*>(sl.dev_in.p), chunk, static_cast<float*>(sl.dev_out.p), nullptr, e->s_compute, nullptr, 0, true);
+        // the ids cross PCIe on the COMPUTE stream, in front of the update that reads them: the copy stream is what bounds the
+        // pipeline, and a second transfer there costs its fixed latency on every update (measured at 4096 ids beside 8 MB of
+        // audio: 183.2 us per update against 170.7 us for pe_update_async; here: 169.1 against 168.2, profiles/subset_async)
+        if (ids_host) PE_HIP(e, hipMemcpyAsync(sl.dev_ids.p, sl.pin_ids, id_bytes, hipMemcpyHostToDevice, e->s_compute));
+        const int32_t* const ids_dev = ids_host ? static_cast<const int32_t*>(sl.dev_ids.p) : nullptr;
+        float* const raw_dev = static_cast<float*>(sl.out[0].dev.p);
+        int urc = do_update(e, static_cast<const int16_t*>(sl.dev_in.p), chunk, raw_dev, nullptr, e->s_compute, ids_dev, ids_dev ? n_active : 0, true);
         if (urc) return urc;
-        PE_HIP(e, hipMemcpyAsync(sl.direct_out ? raw_out_host : sl.pin_out, sl.dev_out.p, out_bytes, hipMemcpyDeviceToHost, e->s_compute));
+        if (decode) {
+            double* const conf_dev = conf_out_host ? static_cast<double*>(sl.out[1].dev.p) : nullptr;
+            unsigned char* const fired_dev = fired_out_host ? static_cast<unsigned char*>(sl.out[2].dev.p) : nullptr;
+            if (fired_dev && !every_trigger) PE_HIP(e, hipMemsetAsync(fired_dev, 0, rows, e->s_compute));
+            if ((urc = launch_decode_rows(e, ids_dev, n_active, raw_dev, conf_dev, fired_dev, e->s_compute))) return urc;
+        }
+        for (int i = 0; i < 3; ++i)
+            if (user[i]) PE_HIP(e, hipMemcpyAsync(sl.out[i].direct ? user[i] : sl.out[i].pin, sl.out[i].dev.p, bytes[i], hipMemcpyDeviceToHost, e->s_compute));
         PE_HIP(e, hipEventRecord(sl.done, e->s_compute));
         return PE_OK;
     };
@@ -1700,12 +1780,41 @@ int pe_update_async(pe_engine* e, const int16_t* pcm_host, int32_t chunk, float*
         const std::string why = e->err;
         (void)hipStreamSynchronize(e->s_copy);
         (void)hipStreamSynchronize(e->s_compute);
-        return fail(e, rc, "pe_update_async: %s (this update was not delivered; the engine's streams were drained)", why.c_str());
+        return fail(e, rc, "%s: %s (this update was not delivered; the engine's streams were drained)", who, why.c_str());
     }
-    sl.user_out = raw_out_host; sl.out_bytes = out_bytes; sl.busy = true;
+    for (int i = 0; i < 3; ++i) { sl.out[i].user = user[i]; sl.out[i].bytes = bytes[i]; }
+    sl.busy = true;
     ++e->async_inflight;
     ++e->async_next;
     return PE_OK;
+}
+}  // namespace
+
+int pe_update_async(pe_engine* e, const int16_t* pcm_host, int32_t chunk, float* raw_out_host) {
+    int rc = check_chunk(e, pcm_host, chunk);
+    if (rc) return rc;
+    if (!raw_out_host) return fail(e, PE_ERR_INVALID, "raw_out_host is null");
+    PE_HIP(e, hipSetDevice(e->device));
+    return update_async(e, "pe_update_async", nullptr, e->n_streams, pcm_host, chunk, raw_out_host, nullptr, nullptr);
+}
+
+// The pipeline for streams that advance on their own (pe_update_subset's update, then ONE decode launch over the slot's
+// raw outputs when conf or fired is asked for -- it moves the named streams' triggers only -- then the copies back).
+// stream_ids_host null: every stream (n_active = n_streams), which is pe_update_async's update plus the decode.
+int pe_update_subset_async(pe_engine* e, const int32_t* stream_ids_host, int32_t n_active, const int16_t* pcm_host, int32_t chunk,
+                           float* raw_out_host, double* conf_out_host, unsigned char* fired_out_host) {
+    if (!e) return fail(e, PE_ERR_INVALID, "null argument to pe_update_subset_async");
+    if (n_active < 0 || n_active > e->n_streams) return fail(e, PE_ERR_INVALID, "n_active=%d outside 0..%d", n_active, e->n_streams);
+    if (!stream_ids_host && n_active != e->n_streams)
+        return fail(e, PE_ERR_INVALID, "stream_ids is null (every stream) but n_active=%d is not n_streams=%d", n_active, e->n_streams);
+    if (n_active == 0) return PE_OK;                 // nobody has audio: nothing moves, nothing is enqueued
+    int rc = check_chunk(e, pcm_host, chunk);
+    if (rc) return rc;
+    if (!raw_out_host) return fail(e, PE_ERR_INVALID, "raw_out_host is null");
+    if ((conf_out_host || fired_out_host) && (rc = check_decoder(e))) return rc;
+    if (stream_ids_host && (rc = check_ids(e, stream_ids_host, n_active))) return rc;
+    PE_HIP(e, hipSetDevice(e->device));
+    return update_async(e, "pe_update_subset_async", stream_ids_host, n_active, pcm_host, chunk, raw_out_host, conf_out_host, fired_out_host);
 }
 
 int pe_wait(pe_engine* e) {
@@ -2450,6 +2559,7 @@ int pe_set_decoder(pe_engine* e, const double* cd, int32_t cd_len, int32_t min_o
     if (!e || cd_len < 0 || (cd_len > 0 && !cd)) return fail(e, PE_ERR_INVALID, "bad decoder table");
     if (out_range != 0 && cd_len < 1) return fail(e, PE_ERR_INVALID, "decoder needs a non-empty table when out_range != 0");
     PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
     PE_HIP(e, hipDeviceSynchronize());                    // no decode launch may still read the old table
     for (int m = 0; m < e->n_models; ++m) {               // (every model of the engine)
         const int rc = set_decoder(e, m, cd, cd_len, min_out, out_range, center);
@@ -2463,6 +2573,7 @@ int pe_set_decoder_model(pe_engine* e, int32_t model, const double* cd, int32_t 
     if (model < 0 || model >= e->n_models) return fail(e, PE_ERR_INVALID, "model %d outside 0..%d", model, e->n_models - 1);
     if (out_range != 0 && cd_len < 1) return fail(e, PE_ERR_INVALID, "decoder needs a non-empty table when out_range != 0");
     PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
     PE_HIP(e, hipDeviceSynchronize());
     return set_decoder(e, model, cd, cd_len, min_out, out_range, center);
 }
@@ -2470,6 +2581,7 @@ int pe_set_decoder_model(pe_engine* e, int32_t model, const double* cd, int32_t 
 int pe_set_trigger(pe_engine* e, int32_t chunk_size_bytes, double sensitivity, int32_t trigger_level) {
     if (!e || chunk_size_bytes <= 0) return fail(e, PE_ERR_INVALID, "bad trigger parameters");
     PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
     for (int m = 0; m < e->n_models; ++m) {               // (every model of the engine)
         const int rc = set_trigger(e, m, chunk_size_bytes, sensitivity, trigger_level);
         if (rc) return rc;
@@ -2481,34 +2593,19 @@ int pe_set_trigger_model(pe_engine* e, int32_t model, int32_t chunk_size_bytes, 
     if (!e || chunk_size_bytes <= 0) return fail(e, PE_ERR_INVALID, "bad trigger parameters");
     if (model < 0 || model >= e->n_models) return fail(e, PE_ERR_INVALID, "model %d outside 0..%d", model, e->n_models - 1);
     PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
     return set_trigger(e, model, chunk_size_bytes, sensitivity, trigger_level);
 }
 
 // raw_dev / conf_out_dev / fired_out_dev: [n_models][n_streams]; ONE decode launch (a K-model engine: per-model tables)
 int pe_decode_device(pe_engine* e, const float* raw_dev, double* conf_out_dev, unsigned char* fired_out_dev, void* stream) {
     if (!e || !raw_dev) return fail(e, PE_ERR_INVALID, "null argument to pe_decode_device");
-    for (int m = 0; m < e->n_models; ++m) {
-        const DecState& d = e->dec[m];
-        if (!d.cd && d.out_range != 0) return fail(e, PE_ERR_INVALID, "pe_set_decoder has not been called");
-        if (!d.cd_len && !d.cd) return fail(e, PE_ERR_INVALID, m ? "pe_set_decoder has not been called for model %d" : "pe_set_decoder has not been called", m);
-    }
+    int rc = check_decoder(e);
+    if (rc) return rc;
     PE_HIP(e, hipSetDevice(e->device));
-    const size_t n = (size_t)e->n_streams;
-    DecodeSet set{};
-    for (int m = 0; m < e->n_models; ++m) {
-        DecodeArgs& a = set.m[m];
-        a.n_streams = e->n_streams; a.raw = raw_dev + m * n;
-        a.conf_out = conf_out_dev ? conf_out_dev + m * n : nullptr;
-        a.fired_out = fired_out_dev ? fired_out_dev + m * n : nullptr;
-        const DecState& d = e->dec[m];
-        a.cd = d.cd; a.cd_len = d.cd_len;
-        a.min_out = d.min_out; a.out_range = d.out_range; a.center = d.center;
-        a.activation = d.on ? e->activation + (size_t)m * e->n_padded : nullptr;
-        a.threshold = d.threshold; a.trigger_level = d.level; a.rearm = d.rearm;
-    }
-    if (e->n_models == 1) PE_HIP(e, launch_decode(set.m[0], static_cast<hipStream_t>(stream)));
-    else PE_HIP(e, launch_decode_models(set, e->n_models, e->n_streams, static_cast<hipStream_t>(stream)));
-    return PE_OK;
+    PE_DRAIN(e);                                          // (updates in flight may carry decodes: they move the trigger state)
+    note_user_stream(e, stream);
+    return launch_decode_rows(e, nullptr, e->n_streams, raw_dev, conf_out_dev, fired_out_dev, static_cast<hipStream_t>(stream));
 }
 
 int pe_decode(pe_engine* e, const float* raw_host, double* conf_out_host, unsigned char* fired_out_host) {
@@ -2523,6 +2620,48 @@ int pe_decode(pe_engine* e, const float* raw_host, double* conf_out_host, unsign
     PE_HIP(e, hipMemset(e->st_fired.p, 0, n));
     if ((rc = pe_decode_device(e, static_cast<const float*>(e->st_out.p), static_cast<double*>(e->st_conf.p),
                                static_cast<unsigned char*>(e->st_fired.p), nullptr))) return rc;
+    if (conf_out_host) PE_HIP(e, hipMemcpy(conf_out_host, e->st_conf.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (fired_out_host) PE_HIP(e, hipMemcpy(fired_out_host, e->st_fired.p, n, hipMemcpyDeviceToHost));
+    if (!conf_out_host && !fired_out_host) PE_HIP(e, hipStreamSynchronize(nullptr));
+    return PE_OK;
+}
+
+// The same for streams that advance on their own: rows [n_models][n_active] in the order of the ids; only the named streams'
+// trigger state moves (a stream that got no audio neither decays nor fires).  The ids must be distinct and in range (the
+// host entry point checks, the device one cannot).
+int pe_decode_subset_device(pe_engine* e, const int32_t* stream_ids_dev, int32_t n_active, const float* raw_dev,
+                            double* conf_out_dev, unsigned char* fired_out_dev, void* stream) {
+    if (!e) return fail(e, PE_ERR_INVALID, "null argument to pe_decode_subset_device");
+    if (n_active < 0 || n_active > e->n_streams) return fail(e, PE_ERR_INVALID, "n_active=%d outside 0..%d", n_active, e->n_streams);
+    if (n_active == 0) return PE_OK;
+    if (!stream_ids_dev || !raw_dev) return fail(e, PE_ERR_INVALID, "null argument to pe_decode_subset_device");
+    int rc = check_decoder(e);
+    if (rc) return rc;
+    PE_HIP(e, hipSetDevice(e->device));
+    PE_DRAIN(e);
+    note_user_stream(e, stream);
+    return launch_decode_rows(e, stream_ids_dev, n_active, raw_dev, conf_out_dev, fired_out_dev, static_cast<hipStream_t>(stream));
+}
+
+int pe_decode_subset(pe_engine* e, const int32_t* stream_ids_host, int32_t n_active, const float* raw_host,
+                     double* conf_out_host, unsigned char* fired_out_host) {
+    if (!e) return fail(e, PE_ERR_INVALID, "null argument to pe_decode_subset");
+    if (n_active < 0 || n_active > e->n_streams) return fail(e, PE_ERR_INVALID, "n_active=%d outside 0..%d", n_active, e->n_streams);
+    if (n_active == 0) return PE_OK;
+    if (!stream_ids_host || !raw_host) return fail(e, PE_ERR_INVALID, "null argument to pe_decode_subset");
+    int rc;
+    if ((rc = check_ids(e, stream_ids_host, n_active))) return rc;
+    PE_HIP(e, hipSetDevice(e->device));
+    const size_t n = (size_t)e->n_models * n_active, id_bytes = (size_t)n_active * sizeof(int32_t);
+    if ((rc = ensure(e, e->st_out, n * sizeof(float)))) return rc;
+    if ((rc = ensure(e, e->st_conf, n * sizeof(double)))) return rc;
+    if ((rc = ensure(e, e->st_fired, n))) return rc;
+    if ((rc = ensure(e, e->st_ids, id_bytes))) return rc;
+    PE_HIP(e, hipMemcpy(e->st_ids.p, stream_ids_host, id_bytes, hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(e->st_out.p, raw_host, n * sizeof(float), hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemset(e->st_fired.p, 0, n));
+    if ((rc = pe_decode_subset_device(e, static_cast<const int32_t*>(e->st_ids.p), n_active, static_cast<const float*>(e->st_out.p),
+                                      static_cast<double*>(e->st_conf.p), static_cast<unsigned char*>(e->st_fired.p), nullptr))) return rc;
     if (conf_out_host) PE_HIP(e, hipMemcpy(conf_out_host, e->st_conf.p, n * sizeof(double), hipMemcpyDeviceToHost));
     if (fired_out_host) PE_HIP(e, hipMemcpy(fired_out_host, e->st_fired.p, n, hipMemcpyDeviceToHost));
     if (!conf_out_host && !fired_out_host) PE_HIP(e, hipStreamSynchronize(nullptr));

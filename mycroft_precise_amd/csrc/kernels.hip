@@ -1039,7 +1039,8 @@ hipError_t launch_project_rows(const float* ring, float* proj, const float* w, c
     return hipGetLastError();
 }
 
-// ThresholdDecoder.decode + TriggerDetector.update of stream s (decode_kernel, decode_models_kernel)
+// ThresholdDecoder.decode + TriggerDetector.update of row s (decode_kernel, decode_models_kernel): stream s, or with a.ids
+// stream a.ids[s] -- the row's input and outputs stay at s, only the trigger state is the named stream's
 __device__ __forceinline__ void decode_stream(const DecodeArgs& a, const int s) {
     const float rawf = a.raw[s];
     const double raw = (double)rawf;
@@ -1060,7 +1061,8 @@ __device__ __forceinline__ void decode_stream(const DecodeArgs& a, const int s) 
     }
     if (a.conf_out) a.conf_out[s] = conf;
     if (a.activation) {
-        int act = a.activation[s];
+        const int t = a.ids ? a.ids[s] : s;
+        int act = a.activation[t];
         const bool hot = conf > a.threshold;
         bool fired = false;
         if (!hot && act >= 0) {
@@ -1070,7 +1072,7 @@ __device__ __forceinline__ void decode_stream(const DecodeArgs& a, const int s) 
             fired = act > a.trigger_level;
             if (fired || (hot && act < 0)) act = a.rearm;
         }
-        a.activation[s] = act;
+        a.activation[t] = act;
         if (a.fired_out) a.fired_out[s] = fired ? 1 : 0;
     }
 }

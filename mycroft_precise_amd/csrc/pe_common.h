@@ -468,6 +468,9 @@ struct DecodeArgs {
     unsigned char* fired_out;   // [n] 1 where this update caused an activation, may be null
     double threshold;           // 1 - sensitivity
     int trigger_level, rearm;   // rearm = -(8 * 2048) // chunk_size
+    // streams that advance on their own (pe_decode_subset): row i of raw / conf_out / fired_out belongs to stream ids[i], whose
+    // trigger state activation[ids[i]] it moves (n_streams = rows); null = row i is stream i
+    const int32_t* ids = nullptr;
 };
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
 struct DecodeSet { DecodeArgs m[kMaxModels]; };     // a K-model engine: model m's table, thresholds and trigger row

@@ -385,25 +385,47 @@ class BatchedListener:
         return np.array([self.threshold_decoder.decode(r) for r in raw], dtype=np.float64)
 
     # -- host-fed pipeline: what a server that receives audio over the network does (scripts/engine.py:60-63 per stream) --
-    def chunk_buffer(self, chunk_samples: int = 1024) -> np.ndarray:
-        """A pinned [n_streams, chunk_samples] int16 array to receive audio into: ``update_raw_async`` reads it in place
-        (no staging copy), which is what reaches PCIe line rate.  Keep a few and rotate: a buffer is read until ``wait()``
-        or until three more updates have been enqueued."""
-        return self.engine.host_array((self.n_streams, int(chunk_samples)), '<i2')
+    def chunk_buffer(self, chunk_samples: int = 1024, n_rows: int = None) -> np.ndarray:
+        """A pinned [n_streams, chunk_samples] int16 array ([n_rows, chunk_samples] for subset updates) to receive audio into:
+        ``update_raw_async`` / ``update_detect_async`` read it in place (no staging copy), which is what reaches PCIe line
+        rate.  Keep a few and rotate: a buffer is read until ``wait()`` or until three more updates have been enqueued."""
+        return self.engine.host_array((self.n_streams if n_rows is None else int(n_rows), int(chunk_samples)), '<i2')
 
-    def update_raw_async(self, chunks, out: np.ndarray = None) -> np.ndarray:
+    def update_raw_async(self, chunks, out: np.ndarray = None, streams=None) -> np.ndarray:
         """Enqueue one update; returns the float32 [n_streams] array its raw outputs land in after ``wait()``.  Up to three
-        updates are in flight: chunk u + 1 crosses PCIe while update u runs.  Same bits as ``update_raw``."""
-        return self.engine.update_async(self._pcm(chunks), out)
+        updates are in flight: chunk u + 1 crosses PCIe while update u runs.  Same bits as ``update_raw``.  With
+        ``streams=ids`` only those streams take a chunk ([len(ids), chunk_samples]) and the array is [len(ids)]; a stream
+        named in several updates in flight takes its chunks in the order of the calls.  ([K, ...] on a K-model listener.)"""
+        if streams is None:
+            return self.engine.update_async(self._pcm(chunks), out)
+        ids = self._ids(streams)
+        return self.engine.update_subset_async(ids, self._pcm(chunks, ids.size), out)
 
     def wait(self):
         self.engine.wait()
 
-    def update_detect(self, chunks):
-        """-> (confidences float64 [n_streams], activations bool [n_streams]); needs set_trigger()."""
+    def update_detect(self, chunks, streams=None):
+        """-> (confidences float64 [n_streams], activations bool [n_streams]); needs set_trigger().  With ``streams=ids``:
+        [len(ids)] each, decoded on the device, and only those streams' TriggerDetectors move -- a stream without audio
+        neither decays nor fires, as with one reference runner per client.  ([K, ...] on a K-model listener.)"""
         if not self._trigger:
             raise RuntimeError('call set_trigger() first')
-        return self.engine.decode(self.update_raw(chunks), want_fired=True)
+        if streams is None:
+            return self.engine.decode(self.update_raw(chunks), want_fired=True)
+        ids = self._ids(streams)
+        return self.engine.decode_subset(ids, self.update_raw(chunks, ids), want_fired=True)
+
+    def update_detect_async(self, chunks, streams=None):
+        """``update_detect`` through the pipeline: enqueue one update (every stream, or ``streams=ids``) with its decode and
+        trigger step behind it on the device; -> (raw float32, confidences float64, activations bool), valid after ``wait()``
+        or once three more updates have been enqueued.  Same bits as ``update_detect``."""
+        if not self._trigger:
+            raise RuntimeError('call set_trigger() first')
+        ids = None if streams is None else self._ids(streams)
+        shape = self.engine._lead(self.n_streams if ids is None else ids.size)
+        conf, fired = np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.uint8)
+        raw = self.engine.update_subset_async(ids, self._pcm(chunks, None if ids is None else ids.size), None, conf, fired)
+        return raw, conf, fired.view(bool)
 
 
 class MultiModelListener(BatchedListener):
@@ -472,13 +494,3 @@ class MultiModelListener(BatchedListener):
             return self.engine.decode(self.update_raw(chunks))
         raw = self.update_raw(chunks, streams)
         return np.array([[d.decode(r) for r in row] for d, row in zip(self.threshold_decoders, raw)], dtype=np.float64).reshape(raw.shape)
-
-    def update_raw_async(self, chunks, out: np.ndarray = None) -> np.ndarray:
-        """Enqueue one update; returns the float32 [K, n_streams] array its raw outputs land in after ``wait()``."""
-        return self.engine.update_async(self._pcm(chunks), out)
-
-    def update_detect(self, chunks):
-        """-> (confidences float64 [K, n_streams], activations bool [K, n_streams]); needs set_trigger()."""
-        if not self._trigger:
-            raise RuntimeError('call set_trigger() first')
-        return self.engine.decode(self.update_raw(chunks), want_fired=True)

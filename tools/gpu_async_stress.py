@@ -1,4 +1,6 @@
-"""(round 5; round 6: the pipeline keeps its leftovers in its own device chunks -- masked clears and subset updates added) randomized interleaving of the host-fed pipeline (pe_update_async / pe_wait, pinned and pageable buffers) with every
+"""(round 5; round 6: the pipeline keeps its leftovers in its own device chunks -- masked clears and subset updates added; then
+pe_update_subset_async: random subsets through the pipeline, between full updates that keep their leftovers in the slots)
+randomized interleaving of the host-fed pipeline (pe_update_async / pe_update_subset_async / pe_wait, pinned and pageable buffers) with every
 other entry point that has to drain it (pe_update, pe_update_many, pe_get_vectors, pe_predict, pe_clear), against an engine that only
 ever takes synchronous updates: every probability and every feature window bit for bit.
     python tools/gpu_async_stress.py [seconds] [seed]"""
@@ -46,7 +48,7 @@ while time.time() - t0 < budget:
         return np.ascontiguousarray(np.concatenate([x, base[(u + 1) % 8][np.arange(n) % base.shape[1]]], axis=1)[:, :chunk])
     slot = 0
     for step in range(int(rng.integers(20, 60))):
-        op = int(rng.integers(0, 10))
+        op = int(rng.integers(0, 13))
         ops += 1
         if op <= 4:                                       # asynchronous update, pinned or pageable
             x = next_pcm()
@@ -59,6 +61,19 @@ while time.time() - t0 < budget:
                 slot = (slot + 1) % 4
             else:
                 out = b.update_async(x)
+            pending.append((out, want))
+        elif op >= 10:                                    # a random subset through the pipeline, pinned or pageable
+            ids = rng.permutation(n)[:int(rng.integers(1, n + 1))].astype(np.int32)
+            x = next_pcm()[ids]
+            want = a.update_subset(ids, x)
+            if len(pending) >= 3:
+                b.wait(); settle()
+            if rng.integers(0, 2):
+                pins[slot][:ids.size] = x
+                out = b.update_subset_async(ids, pins[slot][:ids.size], pouts[slot][:ids.size])
+                slot = (slot + 1) % 4
+            else:
+                out = b.update_subset_async(ids, x)
             pending.append((out, want))
         elif op == 5:
             b.wait(); settle()
