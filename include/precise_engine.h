@@ -53,8 +53,10 @@ typedef struct pe_params {
                                 lanes of a wave, <= 16 coefficients) runs on the one-frame-per-wave kernel and the fused
                                 launch; EVERY OTHER shape in the ranges above runs on the general front end (same
                                 results contract, two launches per update and per pe_update_many call -- one network
-                                launch per update of the call for rows of 17..32 coefficients).  17..32 coefficients feed the float32 network of <= 32 units without
-                                use_delta only; bf16 operands / rows take <= 16 coefficients on either front end.  An n_fft that is
+                                launch per update of the call for rows of 17..32 coefficients).  17..32 coefficients feed the float32 network
+                                (gru_precision = 0) of any width it serves -- <= 32 units, and wide / stacked networks of
+                                33..256 units -- without use_delta only: a network's first layer takes up to 32 inputs.  bf16
+                                operands / rows take <= 16 coefficients on either front end.  An n_fft that is
                                 not a power of two >= 64 (16 and 32 included) runs as Bluestein's chirp-z transform over
                                 the next power of two >= max(128, 2 n_fft - 1) (one wave's LDS holds it up to n_fft =
                                 1024).  Outside the ranges (n_fft > 2048, not a power of two and > 1024, < 16, ...):
@@ -64,13 +66,17 @@ typedef struct pe_params {
                                        (vectorization.py:53-59), layer n_in = 2 n_mfcc   params.py:143 */
     int32_t mfcc_precision;  /* 0 = float64 front end (what the reference computes in,
                                 network_runner.py:102,137);  1 = float32 front end        */
-    int32_t gru_precision;   /* 0 = float32 matrix cores (reference precision, tol 1e-4);
+    int32_t gru_precision;   /* 0 = float32 matrix cores (reference precision, tol 1e-4): every network
+                                the trainers save -- 1..256 units, 1-2 layers, up to 32 inputs per frame
+                                (use_delta over <= 16 coefficients, or 17..32 coefficients; wide / stacked
+                                networks read them as two k-groups of 16);
                                 1 = bf16 operands / float32 accumulate (BASELINE configs[4],
                                 tol 1e-2), any network the engine serves: <= 32 units, and wide /
                                 stacked networks of 33..256 units and 1-2 layers (DESIGN.md 4.4:
                                 weights, features, h and r*h of every layer and layer 2's input are
-                                rounded as operands; the carried state stays float32).  Wide
-                                networks take neither use_delta nor ring_precision = 1.      */
+                                rounded as operands; the carried state stays float32).  bf16-operand
+                                wide networks take plain rows of <= 16 coefficients: no use_delta; and
+                                no wide network takes ring_precision = 1.                    */
     int32_t vectorizer;      /* params.py:121-132: 2 = mfccs (sonopy, the default; also serves the
                                 offline mels entry), 3 = speechpy_mfccs (legacy .params files without
                                 a `vectorizer` key, params.py:147,155): one frame fewer per buffer

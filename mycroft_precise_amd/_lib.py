@@ -336,6 +336,10 @@ class HipEngine:
     MI355X.  Thin, allocation-free wrapper; the reference-shaped classes live in
     ``network_runner.py``.
 
+    ``gru_precision='f32'`` serves every network the trainers save: 1..256 units, one or two GRU layers, up to 32 inputs per
+    frame (``use_delta`` over <= 16 coefficients, or 17..32 coefficients).  ``'bf16'`` serves the same widths on plain rows of
+    <= 16 coefficients (<= 32 units: ``use_delta`` over <= 14).  Anything else raises NotImplementedError naming the limit.
+
     ``weights`` a LIST of weight dicts (same architecture) builds a K-model engine (pe_create_models): one
     front end for all models, and every network output gains a leading model axis ``[K, ...]`` -- even for K = 1.
     """

@@ -617,18 +617,28 @@ int pack_gru_weights_b20(pe_engine* e, NetPack& n, const pe_gru_layer& L, const 
     return dev_upload(e, &n.b20_blob, blob);
 }
 
+// The layer-0 input of the float32 wide networks (gru_wide_device.h WideInput): one k-group of 16 inputs, or two -- with
+// use_delta (inputs [x, x_t - x_(t-1)], 2 n_mfcc <= 32 kernel rows) and with 17..32 coefficients per frame (32-float rows).
+int wide_input_groups(const pe_engine* e) { return (e->prm.use_delta || e->prm.n_mfcc > kRowFloats) ? 2 : 1; }
+// kernel row of input phi (0..15) of k-group `group`; a row >= the layer's n_in has no weight (zero in the stream)
+int wide_input_row(const pe_engine* e, int group, int phi) {
+    if (group == 0) return e->prm.use_delta && phi >= e->prm.n_mfcc ? 1 << 30 : phi;      // (delta: rows F .. belong to group 2)
+    if (e->prm.use_delta) return phi < e->prm.n_mfcc ? e->prm.n_mfcc + phi : 1 << 30;      // the first difference of feature phi
+    return kRowFloats + phi;                                                               // feature 16 + phi of a 32-float row
+}
+
 // Wide / stacked network (gru_wide_device.h): wave w owns output tiles tau = w TPW + t of every gate;
 // row i of a tile <-> unit 16 tau + 4 (i & 3) + (i >> 2); k-step rho, k-slot gk <-> source unit 4 rho + gk
-// (layer 0 input: k-step kk <-> feature 4 gk + kk).  Streams: [wave][k-group][tile][lane] float4.
+// (layer 0 input: k-step 4 group + kk <-> input 4 gk + kk of the k-group, wide_input_row).  Streams: [wave][k-group][tile][lane] float4.
 int pack_gru_weights_wide(pe_engine* e, NetPack& n, const pe_weights* w) {
     const int H = w->layers[0].units, WV = gru_wide_waves(H), TPW = H / (16 * WV), H16 = H / 16;
     for (int l = 0; l < w->n_layers; ++l) {
         const pe_gru_layer& L = w->layers[l];
-        const int kx4 = l == 0 ? 1 : H16;
+        const int kx4 = l == 0 ? wide_input_groups(e) : H16;
         const int F = L.n_in;
         e->wide_kx4[l] = kx4;
         auto in_weight = [&](int rho, int gk, int col) -> float {      // input part, k-step rho, k-slot gk
-            if (l == 0) { const int phi = 4 * gk + rho; return phi < F ? L.kernel[(size_t)phi * 3 * H + col] : 0.f; }
+            if (l == 0) { const int row = wide_input_row(e, rho >> 2, 4 * gk + (rho & 3)); return row < F ? L.kernel[(size_t)row * 3 * H + col] : 0.f; }
             return L.kernel[(size_t)(4 * rho + gk) * 3 * H + col];
         };
         for (int phase = 0; phase < 2; ++phase) {
@@ -670,12 +680,12 @@ int pack_gru_weights_wide(pe_engine* e, NetPack& n, const pe_weights* w) {
 
 // The same network for gru_wide_x3_device.h: float32 weights (split into bf16 pieces in registers, every timestep), wave w
 // owns output tiles tau = w TPW + t of every gate; row i of a tile <-> unit 16 tau + i; k-group kappa, lane (row i, k-group
-// slot gk) <-> source units 16 kappa + 4 gk + e, e = 0..3 (layer 0 input: feature 4 gk + e).  Streams: [wave][kappa][tile][lane] float4.
+// slot gk) <-> source units 16 kappa + 4 gk + e, e = 0..3 (layer 0: input 4 gk + e of k-group kappa, wide_input_row).  Streams: [wave][kappa][tile][lane] float4.
 int pack_gru_weights_wide_x3(pe_engine* e, NetPack& n, const pe_weights* w) {
     const int H = w->layers[0].units, WV = 4, TPW = H / (16 * WV), H16 = H / 16;
     for (int l = 0; l < w->n_layers; ++l) {
         const pe_gru_layer& L = w->layers[l];
-        const int kin = l == 0 ? 1 : H16;
+        const int kin = l == 0 ? wide_input_groups(e) : H16;
         const int F = L.n_in;
         for (int phase = 0; phase < 2; ++phase) {
             const int NT = phase == 0 ? 2 * TPW : TPW;
@@ -693,7 +703,7 @@ int pack_gru_weights_wide_x3(pe_engine* e, NetPack& n, const pe_weights* w) {
                         const int gsel = phase == 0 ? tl / TPW : 0, tp = tl % TPW;
                         for (int kap = 0; kap < kin; ++kap)
                             for (int q = 0; q < 4; ++q) {
-                                const int src = 16 * kap + 4 * gk + q;
+                                const int src = l == 0 ? wide_input_row(e, kap, 4 * gk + q) : 16 * kap + 4 * gk + q;
                                 wx[(((((size_t)gsel * WV + wv) * kin + kap) * TPW + tp) * 64 + lane) * 4 + q] = src < F ? L.kernel[(size_t)src * 3 * H + col] : 0.f;
                             }
                         for (int kap = 0; kap < H16; ++kap)
@@ -1364,7 +1374,14 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
             if (L2.units > hmax) hmax = L2.units;
         }
         if (hmax > 256) return fail(nullptr, PE_ERR_UNSUPPORTED, "the streamed-weight GRU kernel holds up to 256 units per layer (got %d)", hmax);
-        if (p->use_delta) return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta has no wide-GRU kernel (networks of more than 32 units or two layers take plain feature rows)");
+        // the float32 forms take up to 32 inputs per frame as two k-groups of 16 (gru_wide_device.h WideInput): use_delta over
+        // <= 16 coefficients, or 17..32 coefficients; the bf16-operand form reads plain rows of <= 16 coefficients
+        if (p->use_delta && p->gru_precision == 1)
+            return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta has no bf16-operand wide-GRU kernel (gru_precision = 1 networks of more than 32 units or two layers take plain feature rows)");
+        if (p->use_delta && p->n_mfcc > kRowFloats)
+            return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta over more than 16 coefficients (n_mfcc = %d: %d inputs per frame) has no wide-GRU kernel: the first layer takes up to 32 inputs", p->n_mfcc, 2 * p->n_mfcc);
+        if (p->n_mfcc > kRowFloats && p->gru_precision == 1)
+            return fail(nullptr, PE_ERR_UNSUPPORTED, "more than 16 coefficients per frame (n_mfcc = %d) have no bf16-operand wide-GRU kernel: gru_precision = 1 networks of more than 32 units or two layers take rows of <= 16 coefficients", p->n_mfcc);
         if (p->ring_precision == 1) return fail(nullptr, PE_ERR_UNSUPPORTED, "bf16 feature rows (ring_precision = 1) have no wide-GRU kernel: the bf16-operand wide network (gru_precision = 1) reads float32 rows");
         wide_units = (hmax + 63) / 64 * 64;
     }
@@ -1397,8 +1414,8 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return fail(nullptr, PE_ERR_UNSUPPORTED, "device %d is %s: libprecise_engine.so is built for gfx950 (MI355X) only", device, prop.gcnArchName);
     }
-    if (p->n_mfcc > kRowFloats && (wide || p->use_delta || p->gru_precision != 0))
-        return fail(nullptr, PE_ERR_UNSUPPORTED, "more than 16 coefficients per frame feed the float32 network of <= 32 units without delta features only");
+    if (p->n_mfcc > kRowFloats && !wide && (p->use_delta || p->gru_precision != 0))
+        return fail(nullptr, PE_ERR_UNSUPPORTED, "more than 16 coefficients per frame feed a float32 network without delta features only");
     // (bf16 operands / bf16 rows behind the general front end: the same network kernels, fed from rows of <= 16 coefficients --
     //  more than 16 were refused above)
 

@@ -70,9 +70,11 @@ __device__ __forceinline__ void wide_accumulate(f32x4 (&acc)[NT], const float4* 
     }
 }
 
-// same with the B operands in registers (layer 0: the 16-float feature row, one k-group)
-template <int NT>
-__device__ __forceinline__ void wide_accumulate_x(f32x4 (&acc)[NT], const float4* __restrict__ w, const f32x4& x) {
+// same with the B operands in registers (layer 0: the feature row).  KX k-groups of 16 inputs: x, and for KX = 2 x2 (the
+// first differences of x under use_delta, or features 16..31 of a 32-float row) against the second k-group of the stream,
+// NT float4 further.  Per accumulator: first group, then second group.
+template <int NT, int KX = 1>
+__device__ __forceinline__ void wide_accumulate_x(f32x4 (&acc)[NT], const float4* __restrict__ w, const f32x4& x, const f32x4& x2) {
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl) {
         const float4 a = w[tl * 64];
@@ -81,10 +83,89 @@ __device__ __forceinline__ void wide_accumulate_x(f32x4 (&acc)[NT], const float4
         acc[tl] = mfma(a.z, x[2], acc[tl]);
         acc[tl] = mfma(a.w, x[3], acc[tl]);
     }
+    if (KX == 2) {
+#pragma unroll
+        for (int tl = 0; tl < NT; ++tl) {
+            const float4 a = w[(NT + tl) * 64];
+            acc[tl] = mfma(a.x, x2[0], acc[tl]);
+            acc[tl] = mfma(a.y, x2[1], acc[tl]);
+            acc[tl] = mfma(a.z, x2[2], acc[tl]);
+            acc[tl] = mfma(a.w, x2[3], acc[tl]);
+        }
+    }
 }
 
+// The layer-0 input of the streamed-weight kernels (this file and gru_wide_x3_device.h): lane (g, j) supplies inputs
+// 4 g .. 4 g + 3 of stream j to every k-group.  KX = 1: one k-group, the 16-float feature row (n_in <= 16).  KX = 2: a second
+// k-group beside it, chosen per launch (wave-uniform):
+//   * use_delta (n_in <= 16 coefficients, 16-float rows): d_t = x_t - x_(t-1) in float32, formed here from the rows as they
+//     are loaded, ZERO at timestep 0 of every window (add_deltas works on the window's own rows, vectorization.py:53-59:
+//     never the ring row before the window); an explicit batch carries its delta columns, [n][T][2 n_in];
+//   * 17..32 coefficients (32-float rows, a.row_floats): features 16..31 of the row; an explicit batch is [n][T][n_in].
+// Every accumulator sums bias, first group, second group, recurrent part in every input mode, so the modes agree bit for bit.
+template <int MODE, int KX>
+struct WideInput {
+    const float* xbase = nullptr;
+    uint32_t first = 0, mask = 0;
+    int T = 0, n_in = 0, g = 0;
+    int rf = kRowFloats;         // floats per feature row (KX = 2: a.row_floats)
+    int frow = 0;                // floats per timestep of an explicit batch
+    bool valid = false, delta = false;
+
+    __device__ __forceinline__ WideInput(const GruArgs& a, const long long stream, const bool valid_, const int g_) {
+        valid = valid_; g = g_; T = a.n_features; n_in = a.n_in;
+        mask = (uint32_t)(a.ring_slots - 1);
+        if (KX == 2) { delta = a.use_delta != 0; rf = a.row_floats; }
+        frow = delta ? 2 * a.n_in : a.n_in;
+        if (MODE == kRing) {
+            const long long sid = gru_stream_of(a, stream, valid);      // the stream whose record and ring rows this lane reads
+            const uint32_t ke = gru_window_end(a, sid);
+            first = ke - (uint32_t)T;
+            xbase = a.ring + gru_ring_cell(a, sid) * rf + 4 * g;
+        } else if (MODE == kRows) {
+            xbase = a.feats + ((size_t)(valid ? stream : 0) * a.row_stride) * rf + 4 * g;
+        } else {
+            xbase = a.feats + (size_t)(valid ? stream : 0) * T * frow;
+        }
+    }
+    // floats [col0 + 4 g, + 4) of timestep t of an explicit batch, zero from column `end` on
+    __device__ __forceinline__ f32x4 load_cols(const int tc, const int col0, const int end) const {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        const float* p = xbase + (size_t)tc * frow + col0 + 4 * g;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) if (valid && col0 + 4 * g + kk < end) v[kk] = p[kk];
+        return v;
+    }
+    // first group of timestep t (clamped to the last row: the prefetch of the last timestep reads an existing row)
+    __device__ __forceinline__ f32x4 load_x(const int t) const {
+        const int tc = t < T ? t : T - 1;
+        if (MODE == kRing)
+            return *reinterpret_cast<const f32x4*>(xbase + (size_t)((first + (uint32_t)tc) & mask) * kTileStreams * rf);
+        if (MODE == kRows) return *reinterpret_cast<const f32x4*>(xbase + (size_t)tc * rf);
+        return load_cols(tc, 0, n_in);
+    }
+    // second group of timestep t as far as it is LOADED: features 16..31 of a 32-float row, the delta columns of an explicit
+    // batch; zero where the deltas are formed from the rows (next_x2)
+    __device__ __forceinline__ f32x4 load_x2(const int t) const {
+        const int tc = t < T ? t : T - 1;
+        if (delta) {
+            if (MODE == kFeats) return load_cols(tc, n_in, 2 * n_in);
+            return f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if (MODE == kRing)
+            return *reinterpret_cast<const f32x4*>(xbase + (size_t)((first + (uint32_t)tc) & mask) * kTileStreams * rf + 16);
+        if (MODE == kRows) return *reinterpret_cast<const f32x4*>(xbase + (size_t)tc * rf + 16);
+        return load_cols(tc, 16, n_in);
+    }
+    // the second group of the NEXT timestep, at the end of a timestep: the loaded one, or x_(t+1) - x_t
+    __device__ __forceinline__ f32x4 next_x2(const f32x4& x, const f32x4& xn, const f32x4& x2n) const {
+        if (KX == 2 && MODE != kFeats && delta) return xn - x;
+        return x2n;
+    }
+};
+
 // MODE as in gru_device.h (kFeats / kRing / kRows).  LDS: [layer][HB | RH][H/16][64 lanes][4] floats.
-template <int TPW, int MODE, int WAVES>
+template <int TPW, int MODE, int WAVES, int KX = 1>
 __device__ __forceinline__ void gru_wide_tile(const WideArgs& wa, const int tile, const int wave, const int lane, float* lds) {
 #pragma clang fp contract(off)      // every fusion in the gate arithmetic is spelled out: all kernel shapes round alike
     const GruArgs& a = wa.base;
@@ -96,30 +177,7 @@ __device__ __forceinline__ void gru_wide_tile(const WideArgs& wa, const int tile
     const int L = wa.n_layers;
 
     // ---- input addressing (k-step kk of the layer-0 input projection <-> feature 4 g + kk) ------------
-    const float* xbase = nullptr;
-    uint32_t first = 0;
-    const uint32_t mask = (uint32_t)(a.ring_slots - 1);
-    if (MODE == kRing) {
-        const long long sid = gru_stream_of(a, stream, valid);      // the stream whose record and ring rows this lane reads
-        const uint32_t ke = gru_window_end(a, sid);
-        first = ke - (uint32_t)T;
-        xbase = a.ring + gru_ring_cell(a, sid) * kRowFloats + 4 * g;
-    } else if (MODE == kRows) {
-        xbase = a.feats + ((size_t)(valid ? stream : 0) * a.row_stride) * kRowFloats + 4 * g;
-    } else {
-        xbase = a.feats + (size_t)(valid ? stream : 0) * T * a.n_in;
-    }
-    auto load_x = [&](int t) -> f32x4 {
-        const int tc = t < T ? t : T - 1;
-        if (MODE == kRing)
-            return *reinterpret_cast<const f32x4*>(xbase + (size_t)((first + (uint32_t)tc) & mask) * kTileStreams * kRowFloats);
-        if (MODE == kRows) return *reinterpret_cast<const f32x4*>(xbase + (size_t)tc * kRowFloats);
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        const float* p = xbase + (size_t)tc * a.n_in + 4 * g;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) if (valid && 4 * g + kk < a.n_in) v[kk] = p[kk];
-        return v;
-    };
+    const WideInput<MODE, KX> in(a, stream, valid, g);
 
     // ---- LDS state: h0 = 0 ------------------------------------------------------------------------------
     float* HB[2] = {lds, lds + 2 * H16 * 256};
@@ -134,9 +192,12 @@ __device__ __forceinline__ void gru_wide_tile(const WideArgs& wa, const int tile
             for (int q = 0; q < 4; ++q) hown[l][tp][q] = 0.f;
     __syncthreads();
 
-    f32x4 x = load_x(0);
+    f32x4 x = in.load_x(0), x2 = {0.f, 0.f, 0.f, 0.f};
+    if (KX == 2) x2 = in.load_x2(0);
     for (int t = 0; t < T; ++t) {
-        const f32x4 xn = load_x(t + 1);
+        const f32x4 xn = in.load_x(t + 1);
+        f32x4 x2n = {0.f, 0.f, 0.f, 0.f};
+        if (KX == 2) x2n = in.load_x2(t + 1);
 #pragma unroll
         for (int l = 0; l < 2; ++l) {
             if (l >= L) break;
@@ -149,7 +210,7 @@ __device__ __forceinline__ void gru_wide_tile(const WideArgs& wa, const int tile
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc[tl][q] = W.b1[((wave * 2 * TPW + tl) * 4 + q) * 64 + lane];
             const float4* wx1 = W.wx1 + (size_t)wave * W.kx4 * 2 * TPW * 64 + lane;
-            if (l == 0) wide_accumulate_x<2 * TPW>(acc, wx1, x);
+            if (l == 0) wide_accumulate_x<2 * TPW, KX>(acc, wx1, x, x2);
             else wide_accumulate<2 * TPW>(acc, wx1, Xin, W.kx4);
             wide_accumulate<2 * TPW>(acc, W.wr1 + (size_t)wave * H16 * 2 * TPW * 64 + lane, HB[l] + lane * 4, H16);
             float z[TPW][4];
@@ -172,7 +233,7 @@ __device__ __forceinline__ void gru_wide_tile(const WideArgs& wa, const int tile
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc2[tl][q] = W.b2[((wave * TPW + tl) * 4 + q) * 64 + lane];
             const float4* wx2 = W.wx2 + (size_t)wave * W.kx4 * TPW * 64 + lane;
-            if (l == 0) wide_accumulate_x<TPW>(acc2, wx2, x);
+            if (l == 0) wide_accumulate_x<TPW, KX>(acc2, wx2, x, x2);
             else wide_accumulate<TPW>(acc2, wx2, Xin, W.kx4);
             wide_accumulate<TPW>(acc2, W.wr2 + (size_t)wave * H16 * TPW * 64 + lane, RH[l] + lane * 4, H16);
 #pragma unroll
@@ -185,6 +246,7 @@ __device__ __forceinline__ void gru_wide_tile(const WideArgs& wa, const int tile
             }
             __syncthreads();
         }
+        if (KX == 2) x2 = in.next_x2(x, xn, x2n);
         x = xn;
     }
 

@@ -169,7 +169,7 @@ __device__ __forceinline__ void wide_x3_publish(const f32x4& v, uint4* HL, uint2
 // partial sum, then z itself until the blend), HO (the lead wave's float32 state of both layers).
 template <int TPW> constexpr size_t wide_x3_lds_bytes() { return (size_t)3 * (4 * TPW) * 64 * 24 + (size_t)4 * (2 * TPW + TPW + 2 * TPW) * 64 * 16; }
 
-template <int TPW, int MODE, int KS>
+template <int TPW, int MODE, int KS, int KX = 1>
 __device__ __forceinline__ void gru_wide_x3_tile(const WideArgs& wa, const int tile, const int wave_in_wg, const int lane, unsigned char* lds) {
 #pragma clang fp contract(off)      // every fusion in the gate arithmetic is spelled out: all kernel shapes round alike
     const GruArgs& a = wa.base;
@@ -185,31 +185,8 @@ __device__ __forceinline__ void gru_wide_x3_tile(const WideArgs& wa, const int t
     const int L = wa.n_layers;
     const X3Ident ident = x3_identity(lane);
 
-    // ---- input addressing (lane group g supplies features 4 g .. 4 g + 3 of the layer-0 input) -----------------------
-    const float* xbase = nullptr;
-    uint32_t first = 0;
-    const uint32_t mask = (uint32_t)(a.ring_slots - 1);
-    if (MODE == kRing) {
-        const long long sid = gru_stream_of(a, stream, valid);      // the stream whose record and ring rows this lane reads
-        const uint32_t ke = gru_window_end(a, sid);
-        first = ke - (uint32_t)T;
-        xbase = a.ring + gru_ring_cell(a, sid) * kRowFloats + 4 * g;
-    } else if (MODE == kRows) {
-        xbase = a.feats + ((size_t)(valid ? stream : 0) * a.row_stride) * kRowFloats + 4 * g;
-    } else {
-        xbase = a.feats + (size_t)(valid ? stream : 0) * T * a.n_in;
-    }
-    auto load_x = [&](int t) -> f32x4 {
-        const int tc = t < T ? t : T - 1;
-        if (MODE == kRing)
-            return *reinterpret_cast<const f32x4*>(xbase + (size_t)((first + (uint32_t)tc) & mask) * kTileStreams * kRowFloats);
-        if (MODE == kRows) return *reinterpret_cast<const f32x4*>(xbase + (size_t)tc * kRowFloats);
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        const float* p = xbase + (size_t)tc * a.n_in + 4 * g;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) if (valid && 4 * g + kk < a.n_in) v[kk] = p[kk];
-        return v;
-    };
+    // ---- input addressing (lane group g supplies inputs 4 g .. 4 g + 3 of every layer-0 k-group: WideInput) -----------
+    const WideInput<MODE, KX> in(a, stream, valid, g);
 
     // ---- LDS ---------------------------------------------------------------------------------------------------------------
     uint4* const HL0 = reinterpret_cast<uint4*>(lds) + lane;                           // state vector v: HL0 + v * (kVecBytes / 16)
@@ -233,26 +210,41 @@ __device__ __forceinline__ void gru_wide_x3_tile(const WideArgs& wa, const int t
     auto contract = [&](f32x4 (&acc)[TPW], const float4* wA, const int nA, const int svA, const float4* wB, const int nB, const int svB, const int kB) {
         wide_x3_accumulate<TPW>(acc, wA, nA, HLv(svA), MDv(svA), wB + (size_t)kB * TPW * 64, nB, HLv(svB) + kB * 64, MDv(svB) + kB * 64, ident, lane);
     };
-    auto contract_x = [&](f32x4 (&acc)[TPW], const float4* wx, const WideX3B& xb) {          // the layer-0 input: one k-group, B operands in registers
+    // the layer-0 input: KX k-groups (the second one TPW float4 further in the stream), B operands in registers; the second
+    // group's weights are fetched once the first group's products are issued, into the same registers
+    auto contract_x = [&](f32x4 (&acc)[TPW], const float4* wx, const WideX3B& xb, const WideX3B& xb2) {
         float4 w0[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) w0[tl] = wx[tl * 64 + lane];
         wide_x3_kgroup<TPW>(acc, w0, xb, ident);
+        if (KX == 2) {
+#pragma unroll
+            for (int tl = 0; tl < TPW; ++tl) w0[tl] = wx[(TPW + tl) * 64 + lane];
+            wide_x3_kgroup<TPW>(acc, w0, xb2, ident);
+        }
     };
-    f32x4 x = load_x(0);
+    f32x4 x = in.load_x(0), x2 = {0.f, 0.f, 0.f, 0.f};
+    if (KX == 2) x2 = in.load_x2(0);
     for (int t = 0; t < T; ++t) {
-        const f32x4 xn = load_x(t + 1);
-        // the layer-0 input as B operands (the lead waves split the same four features of their lanes: 2 MFMAs)
-        WideX3B xb;
+        const f32x4 xn = in.load_x(t + 1);
+        f32x4 x2n = {0.f, 0.f, 0.f, 0.f};
+        if (KX == 2) x2n = in.load_x2(t + 1);
+        // the layer-0 input as B operands (the lead waves split the same four features of their lanes: 2 MFMAs per k-group)
+        WideX3B xb, xb2 = {};
         {
             const X3Ops o = x3_split_tile(x, keep_x, ident);
             xb.hl = uint4{o.b0.x, o.b0.y, o.b2.x, o.b2.y};
             xb.md = uint2{o.b0.z, o.b0.w};
         }
+        if (KX == 2) {              // (keep_x: scratch of the split -- its stale half meets zeros of -I)
+            const X3Ops o = x3_split_tile(x2, keep_x, ident);
+            xb2.hl = uint4{o.b0.x, o.b0.y, o.b2.x, o.b2.y};
+            xb2.md = uint2{o.b0.z, o.b0.w};
+        }
 #pragma unroll 1
         for (int l = 0; l < L; ++l) {
             const WideLayerArgs& W = wa.layer[l];
-            const int kin = W.kx4;                               // k-groups of the input contraction: 1 (layer 0: the feature row) or H16
+            const int kin = W.kx4;                               // k-groups of the input contraction: KX (layer 0: the feature row) or H16
             // weight streams, gate-major: [gate][wave][k-group][tile][lane] float4
             const size_t gx = (size_t)WAVES * kin * TPW * 64, gr = (size_t)WAVES * H16 * TPW * 64;
             f32x4 acc[TPW];
@@ -267,7 +259,7 @@ __device__ __forceinline__ void gru_wide_x3_tile(const WideArgs& wa, const int t
                 const float4* const wx = W.wx1 + ox;
                 const float4* const wr = W.wr1 + orr;
                 if (l == 0) {
-                    if (lead) contract_x(acc, wx, xb);
+                    if (lead) contract_x(acc, wx, xb, xb2);
                     contract(acc, wr, 0, 0, wr, HK, 0, ko);
                 } else if (KS == 1) {
                     contract(acc, wx, kin, 0, wr, H16, 1, 0);
@@ -311,7 +303,7 @@ __device__ __forceinline__ void gru_wide_x3_tile(const WideArgs& wa, const int t
                 const float4* const wx = W.wx2 + ox;
                 const float4* const wr = W.wr2 + orr;
                 if (l == 0) {
-                    if (lead) contract_x(acc, wx, xb);
+                    if (lead) contract_x(acc, wx, xb, xb2);
                     contract(acc, wr, 0, 2, wr, HK, 2, ko);
                 } else if (KS == 1) {
                     contract(acc, wx, kin, 0, wr, H16, 2, 0);
@@ -342,6 +334,7 @@ __device__ __forceinline__ void gru_wide_x3_tile(const WideArgs& wa, const int t
             }
             __syncthreads();
         }
+        if (KX == 2) x2 = in.next_x2(x, xn, x2n);
         x = xn;
     }
 

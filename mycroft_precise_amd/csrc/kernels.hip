@@ -271,14 +271,22 @@ struct NetModels { const ModelSet* ms; int n; long long out_stride; };
     } while (0)
 
 // ---- wide / stacked GRU: one workgroup per 16-stream tile, weights streamed from L2 -------------------
-template <int TPW, int MODE, int WAVES>
+// k-groups of the layer-0 input of a float32 wide launch: 2 with use_delta or 32-float rows, else 1; 0 where the packed
+// weight stream (layer[0].kx4) says otherwise
+static int wide_input_groups(const WideArgs& a) {
+    const int kx = (a.base.use_delta || a.base.row_floats != kRowFloats) ? 2 : 1;
+    if (a.base.use_delta && a.base.row_floats != kRowFloats) return 0;
+    return a.layer[0].kx4 == kx ? kx : 0;
+}
+// KX: 16-input k-groups of layer 0 (2: use_delta or 32-float rows, gru_wide_device.h WideInput)
+template <int TPW, int MODE, int WAVES, int KX>
 __global__ __launch_bounds__(64 * WAVES) void gru_wide_kernel(const WideArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef PE_WIDE_STAGGER
     for (int i = (blockIdx.x >> 3) & 31; i > 0; --i) __builtin_amdgcn_s_sleep(PE_WIDE_STAGGER);
 #endif
-    gru_wide_tile<TPW, MODE, WAVES>(a, blockIdx.x, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
+    gru_wide_tile<TPW, MODE, WAVES, KX>(a, blockIdx.x, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
 }
 
 template <int TPW, int WAVES>
@@ -286,7 +294,10 @@ static hipError_t launch_wide_t(const WideArgs& a, int mode, hipStream_t s) {
     const int tiles = (a.base.n_streams + kTileStreams - 1) / kTileStreams;
     if (tiles == 0) return hipSuccess;
     const size_t lds = (size_t)4 * (TPW * WAVES) * 256 * sizeof(float);      // 2 layers x {h, r*h}
-    if (!with_mode(mode, [&](auto M) { hipLaunchKernelGGL((gru_wide_kernel<TPW, PE_CONST(M), WAVES>), dim3(tiles), dim3(64 * WAVES), lds, s, a); })) return hipErrorInvalidValue;
+    const int kx = wide_input_groups(a);
+    if (!kx) return hipErrorInvalidValue;
+    if (!with_mode(mode, [&](auto M) { with_const<1, 2>(kx, [&](auto K) {
+            hipLaunchKernelGGL((gru_wide_kernel<TPW, PE_CONST(M), WAVES, PE_CONST(K)>), dim3(tiles), dim3(64 * WAVES), lds, s, a); }); })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -294,11 +305,11 @@ static hipError_t launch_wide_t(const WideArgs& a, int mode, hipStream_t s) {
 #ifndef PE_WIDE_X3_KS
 #define PE_WIDE_X3_KS 2         // 2: eight waves per workgroup, the k-groups of every contraction cut in two (widths that are multiples of 128)
 #endif
-template <int TPW, int MODE, int KS>
+template <int TPW, int MODE, int KS, int KX>
 __global__ __launch_bounds__(256 * KS) void gru_wide_x3_kernel(const WideArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    gru_wide_x3_tile<TPW, MODE, KS>(a, blockIdx.x, wave, threadIdx.x & 63, smem);
+    gru_wide_x3_tile<TPW, MODE, KS, KX>(a, blockIdx.x, wave, threadIdx.x & 63, smem);
 }
 
 template <int TPW>
@@ -307,7 +318,10 @@ static hipError_t launch_wide_x3_t(const WideArgs& a, int mode, hipStream_t s) {
     if (tiles == 0) return hipSuccess;
     constexpr int KS = (PE_WIDE_X3_KS == 2 && TPW % 2 == 0) ? 2 : 1;
     const size_t lds = wide_x3_lds_bytes<TPW>();          // three state vectors + partial sums / z / float32 state of the lead waves
-    if (!with_mode(mode, [&](auto M) { hipLaunchKernelGGL((gru_wide_x3_kernel<TPW, PE_CONST(M), KS>), dim3(tiles), dim3(256 * KS), lds, s, a); })) return hipErrorInvalidValue;
+    const int kx = wide_input_groups(a);
+    if (!kx) return hipErrorInvalidValue;
+    if (!with_mode(mode, [&](auto M) { with_const<1, 2>(kx, [&](auto K) {
+            hipLaunchKernelGGL((gru_wide_x3_kernel<TPW, PE_CONST(M), KS, PE_CONST(K)>), dim3(tiles), dim3(256 * KS), lds, s, a); }); })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -423,7 +423,8 @@ struct WideLayerArgs {
     const float4* wr2;      // phase 2, recurrent part [wave][H/16][TPW][64] float4
     const float* b1;        // [wave][2 TPW][4][64]
     const float* b2;        // [wave][TPW][4][64]
-    int kx4;                // k-groups of the input part: 1 for layer 0 (<= 16 features), H/16 above
+    int kx4;                // k-groups of the input part: H/16 for layer 1; for layer 0 one (<= 16 inputs) or, float32 forms only,
+                            // two (use_delta: [x, x_t - x_(t-1)] over <= 16 coefficients; or 17..32 coefficients per frame)
 };
 
 struct WideArgs {

@@ -40,7 +40,7 @@ class Runner(metaclass=ABCMeta):
 
 
 def _require_streamable(params):
-    """The streaming kernels carry MFCC rows (<= 16 coefficients per frame) of the sonopy (``mfccs``) or the
+    """The streaming kernels carry MFCC rows (<= 32 coefficients per frame) of the sonopy (``mfccs``) or the
     legacy speechpy (``speechpy_mfccs``) front end; mel rows (n_filt = 20 wide, Vectorizer.mels) exist in the
     offline form only -- the reference's own Listener cannot stream them either (network_runner.py:104,144)."""
     if params.vectorizer not in (Vectorizer.mfccs, Vectorizer.speechpy_mfccs):
