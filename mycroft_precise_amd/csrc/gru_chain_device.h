@@ -5,12 +5,13 @@
 // launched for: engine.hip chain_eligible).  The window that ends at emitted row ke - 1 is the chain that started at row
 // ke - T; the window of the NEXT update started k rows later.  So a stream keeps the state h of the chain of every start
 // s in (ke - T - 1, ke - 1]: T of them, the chain of age a = ke - s having consumed the rows s .. ke - 1.  An update then
-//   * computes the input projections of its k new rows ONCE (they were 16 of the 41 MFMAs of every timestep of every window),
+//   * computes the input projections of its k new rows ONCE per workgroup, a tile of them per wave, handed round through an LDS
+//     mailbox behind one barrier (they were 16 of the 41 MFMAs of every timestep of every window),
 //   * advances each of the T chains by min(a, k) steps of CwStep<false>::step -- the function gru_tile_v runs, bit-identical
 //     to gru_tile_cw -- (a chain of age a <= k is born in this update: it starts from h = 0),
 //   * and the chain that reaches age T is the window: Dense + sigmoid of its state is the output.
-// T independent chains of <= 2 steps instead of one chain of 29: a throughput job for the SIMDs of the machine, with no LDS
-// and no barrier.
+// T independent chains of <= 2 steps instead of one chain of 29: a throughput job for the SIMDs of the machine; its only LDS
+// is the projections' mailbox and its only barrier the one behind it (gru_tile_chains, "The prologue").
 //
 // State.  chains: float32 [stream tile][kCwSlots][5 rho][64 lanes]; slot = start row & (kCwSlots - 1), the indexing of the
 // feature ring; lane (g, j) holds unit 4 rho + g of stream 16 tile + j (CwStep's h[rho]).  A slot is reused by the chain
@@ -39,9 +40,22 @@ __device__ __forceinline__ void chain_store(float* chains, const size_t cell, co
     for (int rho = 0; rho < 5; ++rho) chains[cell + (size_t)rho * 64] = h[rho];
 }
 
-// the weights every wave of this form keeps: the timestep's, the input kernel and the biases
-struct ChainNet {
+// the timestep's weights, which every wave of this form keeps
+struct ChainStep {
     CwStep<false> S;
+    // one timestep for the lanes with `on`; the others keep their state (an MFMA column depends on its own B column only, so
+    // what the other lanes computed is dropped without a trace in these)
+    __device__ __forceinline__ void step_if(float (&h)[5], const f32x4 (&p)[4], const bool on) const {
+        float hn[5];
+#pragma unroll
+        for (int rho = 0; rho < 5; ++rho) hn[rho] = h[rho];
+        S.step(hn, p[kTZ], p[kTX], p[kTC], p[kTV]);
+#pragma unroll
+        for (int rho = 0; rho < 5; ++rho) h[rho] = on ? hn[rho] : h[rho];
+    }
+};
+// ... with the whole input kernel and the biases (the rebuild: every wave projects the rows of its own chains)
+struct ChainNet : ChainStep {
     float wx[4][4];
     f32x4 bias[4];
     __device__ __forceinline__ void load(const float* cw, const int lane) {
@@ -59,53 +73,66 @@ struct ChainNet {
         p[kTZ] = cw_xproj(wx[kTZ], bias[kTZ], x); p[kTX] = cw_xproj(wx[kTX], bias[kTX], x);
         p[kTC] = cw_xproj(wx[kTC], bias[kTC], x); p[kTV] = cw_xproj(wx[kTV], bias[kTV], x);
     }
-    // one timestep for the lanes with `on`; the others keep their state (an MFMA column depends on its own B column only, so
-    // what the other lanes computed is dropped without a trace in these)
-    __device__ __forceinline__ void step_if(float (&h)[5], const f32x4 (&p)[4], const bool on) const {
-        float hn[5];
-#pragma unroll
-        for (int rho = 0; rho < 5; ++rho) hn[rho] = h[rho];
-        S.step(hn, p[kTZ], p[kTX], p[kTC], p[kTV]);
-#pragma unroll
-        for (int rho = 0; rho < 5; ++rho) h[rho] = on ? hn[rho] : h[rho];
-    }
 };
+
+// LDS of a chain workgroup (floats): the mailbox of the new rows' projections, at the start of the launch's dynamic LDS
+struct ChainLds {
+    static constexpr int BOX = 0;                               // [kChainMaxRows][4 tiles][64 lanes][4]
+    static constexpr int FLOATS = kChainMaxRows * 4 * 256;
+};
+constexpr size_t kChainLdsBytes = (size_t)ChainLds::FLOATS * sizeof(float);
 
 // ---- the network role of a chain launch: NW waves per tile, wave w takes the chains of age a = w (mod NW) ----------------
 // NW = 4 (one workgroup per tile) when the call names most of the engine's streams: the frame role is then the long pole of
 // the launch and every chain wave's MFMAs take issue cycles from it.  NW = 8 (two workgroups per tile) for sparse subset
 // calls, where this role is the long pole: a chain of memory round trips and of a wave's chains two at a time, which more
-// waves shorten (and there the next two chains' state is requested ahead).  Measured: profiles/chain_carry/README.md.
-template <int NW>
+// waves shorten (and there the next two chains' state is requested ahead).
+// Measured: profiles/chain_carry/README.md, profiles/chain_launch/README.md.
+//
+// The prologue.  One round trip for the record, the stamp and the weights; a second for the new rows and the first two
+// chains.  The new rows are projected once per WORKGROUP, not once per wave: wave w computes tile w of {TZ, TX, TC, TV} --
+// it holds that tile's input kernel and bias only (8 registers, where the whole kernel took 32) --, leaves its f32x4 per row
+// in the LDS mailbox, and after one workgroup barrier every wave reads all four.  cw_xproj is a function of (tile, row)
+// alone, so the bits are those of a wave that projects for itself; what goes is three quarters of the projections' matrix
+// cycles, which an f32-input MFMA takes from every wave of its SIMD, the frame role's included.
+// S: the workgroup's dynamic LDS, kChainLdsBytes of it (kernels.hip: launch_fused_chains_t asserts the budget).
+//
 // The records hold the state BEFORE the update (predict_ke, as for every network role of a fused launch).  Lanes of one
 // tile may make different numbers of rows visible (subset calls, streams out of phase): the wave runs the largest trip
 // count and every lane keeps what is its own.
-__device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane) {
+template <int NW>
+__device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane, float* const S) {
     const int g = lane >> 4, j = lane & 15;
     const long long stream = (long long)tile * kTileStreams + j;
     const bool valid = stream < a.n_streams;
     const int T = a.n_features;
+    const int wl = wave & 3;                // the wave within its workgroup: the tile it projects
     // ---- one round trip: the record, the stamp, the weights -----------------------------------------------------
     const long long sid = gru_stream_of(a, stream, valid);
     const KeRequest ke_req = gru_ke_request(a, sid);
     const uint32_t stamp = ch.chain_ke[sid];
-    ChainNet N;
-    N.load(a.cw, lane);
+    ChainStep N;
+    N.S.load(a.cw, lane);
+    float wx[4];
+    f32x4 bias;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        wx[kk] = a.cw[CwPack::WX + (wl * 4 + kk) * 64 + lane];
+        bias[kk] = a.cw[CwPack::BIAS + (wl * 4 + kk) * 64 + lane];
+    }
     float wd[5];
 #pragma unroll
     for (int rho = 0; rho < 5; ++rho) wd[rho] = a.wd[rho * 64 + lane];
     const uint32_t ke_pre = rec_pick(ke_req.p, rec_side(ke_req.p, a.call)).ke;
     const uint32_t ke_post = gru_ke_resolve(a, ke_req);
     const uint32_t k = ke_post - ke_pre;
+    // (the waves of a workgroup serve the same 16 streams, so kmax is uniform across the WORKGROUP, not only across the wave)
     const int kmax = __any(k >= 2u) ? 2 : __any(k >= 1u) ? 1 : 0;       // (k > kChainMaxRows: refused below, never run)
     const int head_wave = T % NW;
     constexpr bool kAhead = NW > 4;
     const uint32_t smask = (uint32_t)(kCwSlots - 1);
-    // ---- second round trip: the new rows (projected once, here) and the first chains ----------------------------
     const float* xbase = a.ring + gru_ring_cell(a, sid) * kRowFloats + 4 * g;
     f32x4 p0[4], p1[4];
-    if (kmax >= 1) N.project(*reinterpret_cast<const f32x4*>(xbase + (size_t)(ke_pre & smask) * kTileStreams * kRowFloats), p0);
-    if (kmax >= 2) N.project(*reinterpret_cast<const f32x4*>(xbase + (size_t)((ke_pre + 1u) & smask) * kTileStreams * kRowFloats), p1);
     // row ke_pre + i is consumed by the chain of (post-update) age A iff it exists then: i < k and i >= k - A
     auto advance = [&](float (&h)[5], const uint32_t A) {
         if (kmax >= 1) N.step_if(h, p0, 0u < k && k <= A);
@@ -119,22 +146,39 @@ __device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArg
         // nothing became visible anywhere in the tile: the window is the stored chain of age T
         if (wave == head_wave) chain_load(ch.chains, chain_cell(sid, (ke_post - (uint32_t)T) & smask, g), hw);
     } else {
-        // two chains at a time: their timesteps are independent, so one's MFMAs fill the other's waits.  kAhead: the state of the
-        // NEXT two is requested before the steps of these (the stores below go to other cells of the same array, which the
-        // compiler cannot know: left to it, every pair waits a whole memory round trip for its loads)
+        // ---- second round trip: the new rows and the first chains -----------------------------------------------
+        // (the second row is requested whether or not it is new -- its slot exists: a load under a branch is waited for at the
+        //  join, in front of the chains' requests)
+        const f32x4 x0 = *reinterpret_cast<const f32x4*>(xbase + (size_t)(ke_pre & smask) * kTileStreams * kRowFloats);
+        const f32x4 x1 = *reinterpret_cast<const f32x4*>(xbase + (size_t)((ke_pre + 1u) & smask) * kTileStreams * kRowFloats);
         auto cell_of = [&](const int age) -> size_t { return chain_cell(sid, (ke_post - (uint32_t)(age <= T ? age : T)) & smask, g); };
         const int first = wave ? wave : NW;
         float n0[5], n1[5];
-        if (kAhead) {
-            chain_load(ch.chains, cell_of(first), n0);
-            chain_load(ch.chains, cell_of(first + NW), n1);
+        chain_load(ch.chains, cell_of(first), n0);
+        chain_load(ch.chains, cell_of(first + NW), n1);
+        // ---- one projection per workgroup.  This branch is uniform across the workgroup (kmax, above) and no lane-divergent
+        // code encloses it, so every wave of the workgroup reaches the barrier.  Only what THIS launch wrote is read back: row
+        // 0 is written by all four waves whenever the branch is taken, row 1 is written and read under the same kmax >= 2
+        // (what an earlier workgroup left in the LDS is never looked at)
+        float* const box = S + ChainLds::BOX + lane * 4;
+        *reinterpret_cast<f32x4*>(box + (0 * 4 + wl) * 256) = cw_xproj(wx, bias, x0);
+        if (kmax >= 2) *reinterpret_cast<f32x4*>(box + (1 * 4 + wl) * 256) = cw_xproj(wx, bias, x1);
+        cw_barrier();
+#pragma unroll
+        for (int tl = 0; tl < 4; ++tl) {
+            p0[tl] = *reinterpret_cast<const f32x4*>(box + (0 * 4 + tl) * 256);
+            if (kmax >= 2) p1[tl] = *reinterpret_cast<const f32x4*>(box + (1 * 4 + tl) * 256);
         }
+        // two chains at a time: their timesteps are independent, so one's MFMAs fill the other's waits.  The first two came with
+        // the rows.  kAhead: the state of the NEXT two is requested before the steps of these (the stores below go to other
+        // cells of the same array, which the compiler cannot know: left to it, every pair waits a whole memory round trip for
+        // its loads)
         for (int a0 = first; a0 <= T; a0 += 2 * NW) {
             const uint32_t A0 = (uint32_t)a0, A1 = A0 + (uint32_t)NW;
             const bool two = a0 + NW <= T;
             const size_t c0 = cell_of(a0), c1 = cell_of(a0 + NW);
             float h0[5], h1[5];
-            if (!kAhead) {
+            if (!kAhead && a0 != first) {
                 chain_load(ch.chains, c0, n0);
                 chain_load(ch.chains, c1, n1);
             }

@@ -501,7 +501,8 @@ PE_KERNEL_PAIR((template <class R, class SH, int RG, bool MW, bool CW>), PE_FRAM
 
 // ---- chain launch (gru_chain_device.h): the fused update of form 1 with the window chains CARRIED between updates -----
 // The same three roles in the same order; the network role advances the tile's resident chains by the rows this update makes
-// visible (four waves, no LDS of its own, no barrier) instead of running every window again from h = 0.
+// visible (four waves; the new rows' projections pass through the workgroup's LDS, one barrier: ChainLds) instead of running
+// every window again from h = 0.
 template <class R, class SH, int NW>
 __device__ __forceinline__ void fused_update_chains_body(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ChainArgs& ch,
                                                          const int n_gru_blocks, const int n_frame_blocks, const int frames_first) {
@@ -512,7 +513,7 @@ __device__ __forceinline__ void fused_update_chains_body(const MfccStreamArgs<R>
         // (no s_setprio here: this role is the SHORT one -- see the frame role below)
         constexpr int per_tile = NW / 4;                // network workgroups per tile
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) + 4 * (b % per_tile);
-        gru_tile_chains<NW>(g, ch, b / per_tile, wave, threadIdx.x & 63);
+        gru_tile_chains<NW>(g, ch, b / per_tile, wave, threadIdx.x & 63, reinterpret_cast<float*>(smem));
     } else if (b < n_gru_blocks + n_frame_blocks) {
         // The frame role is the long pole of this launch, and an f32-input MFMA keeps its SIMD from issuing while it runs
         // (DESIGN 4.6): the chain waves' matrix time ADDS to the frame waves' on every SIMD.  With the frame waves winning every
@@ -809,8 +810,9 @@ hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>&
 }
 
 // The chain launch of engine.hip do_update (chain_eligible: stock float32 network re-tiled, four waves per tile, one model): one
-// network workgroup per tile, two for sparse subset calls (gru_tile_chains<NW>), no LDS of their own; two resident frame
-// workgroups per compute unit at one tile per compute unit, four above, as in launch_fused_rg's four-wave branch.
+// network workgroup per tile, two for sparse subset calls (gru_tile_chains<NW>); their mailbox (ChainLds, 8 KB) is the start of
+// the dynamic LDS the launch asks for on the frame role's behalf; two resident frame workgroups per compute unit at one tile
+// per compute unit, four above, as in launch_fused_rg's four-wave branch.
 template <class R>
 static hipError_t launch_fused_chains_t(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s) {
     if (t.L.mel_pad != ShapeStock::MEL || !blob_matches_shape(t)) return hipErrorInvalidValue;
@@ -820,8 +822,11 @@ static hipError_t launch_fused_chains_t(const MfccStreamArgs<R>& m, const WaveTa
     const int fb = stream_frame_blocks(m.geo.n_streams, n_cus, tiles <= n_cus ? 2 : 4);
     // a subset call of at most half of the engine's streams: the network role is the long pole, eight waves share a tile's chains
     const bool sparse = g.ids && 2u * (uint32_t)tiles * kTileStreams <= g.n_padded;
-    if (sparse) PE_LAUNCH_R(R, fused_update_chains_kernel, (ShapeStock, 8), dim3(2 * tiles + fb + tiles), dim3(256), frame_lds(t), s, m, t, g, 2 * tiles, fb, tiles, 0, ch);
-    else PE_LAUNCH_R(R, fused_update_chains_kernel, (ShapeStock, 4), dim3(tiles + fb + tiles), dim3(256), frame_lds(t), s, m, t, g, tiles, fb, tiles, 0, ch);
+    // the chain workgroups' mailbox (ChainLds) sits at the start of the dynamic LDS every workgroup of the launch is given
+    const size_t lds = frame_lds(t);
+    if (lds < kChainLdsBytes) return hipErrorInvalidValue;
+    if (sparse) PE_LAUNCH_R(R, fused_update_chains_kernel, (ShapeStock, 8), dim3(2 * tiles + fb + tiles), dim3(256), lds, s, m, t, g, 2 * tiles, fb, tiles, 0, ch);
+    else PE_LAUNCH_R(R, fused_update_chains_kernel, (ShapeStock, 4), dim3(tiles + fb + tiles), dim3(256), lds, s, m, t, g, tiles, fb, tiles, 0, ch);
     return hipGetLastError();
 }
 hipError_t launch_fused_chains(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s) {
