@@ -338,11 +338,15 @@ __device__ __forceinline__ void general_frame_blue(const GeneralTables& t, R* S,
 #pragma unroll 1
         for (int s = BITS - 1; s >= 0; --s) stage(s, true);
         for (int p0 = 0; p0 < L; p0 += 256) {
-            cplx<R> bh[4];
+            // (PW points per lane and round: L = 128 is half a round of 256 -- bhat and Z end at L.  A constant, not a test of
+            //  p < L per point: the compiler knows no bound of `lane`, and such a test became a branch per point at every length)
+            constexpr int PW = L < 256 ? L / 64 : 4;
+            static_assert(PW >= 1 && (L < 256 ? 64 * PW == L : L % 256 == 0), "whole rounds: no point at or beyond L");
+            cplx<R> bh[PW];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) bh[i] = bhat[p0 + 64 * i + lane];
+            for (int i = 0; i < PW; ++i) bh[i] = bhat[p0 + 64 * i + lane];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < PW; ++i) {
                 const int p = p0 + 64 * i + lane;
                 const cplx<R> av = Z[p];
                 Z[p] = cplx<R>{av.x * bh[i].x - av.y * bh[i].y, av.x * bh[i].y + av.y * bh[i].x};
