@@ -557,6 +557,21 @@ int pe_get_gru_tiling(const pe_engine* e);
  * either pointer may be null. */
 int pe_set_chain_carry(pe_engine* e, int32_t mode);
 int pe_get_chain_carry(const pe_engine* e, int32_t* mode, int32_t* active);
+/* Chains that are never handed out.  An update returns ONE window per stream, so with chunks longer than a hop the window
+ * start that an update emitting two rows steps over is never read: 1 - hop / chunk of all starts under a constant chunk (21.9 %
+ * at 1024 samples).  After 128 eligible calls in a row with the same chunk > hop the chain launches stop loading, stepping and
+ * storing those chains (bit-identical outputs: the chains that are handed out are advanced as before).  The first eligible call
+ * with ANOTHER chunk first builds every live chain again from the feature ring (one extra launch, as at entry), the engine
+ * stays active throughout, and skipping resumes after the next 128 calls with one chunk.  Subset calls count like full ones:
+ * the run and the chunk belong to the engine, a stream that sits out keeps its phase.
+ * pe_get_chain_skip: *chunk = the chunk size chains are currently being skipped for, 0 = none (or chains not valid).
+ * pe_chain_alive_mask: the predicate itself, pure arithmetic (no engine, no device): for a stream whose record BEFORE an update
+ * of `chunk` samples holds q leftover samples, kc computed frames and ke emitted rows, bit A (1 <= A <= T <= 31) of the result
+ * says that the chain of age A after that update -- the one started at row ke_after - A -- will be handed out if the chunk
+ * holds; bit T is this update's own window.  q is the record's signed leftover, q >= frame_len - hop (negative where a frame is
+ * shorter than a hop: the next frame starts beyond the last sample held).  0 for arguments out of range. */
+int pe_get_chain_skip(const pe_engine* e, int32_t* chunk);
+uint32_t pe_chain_alive_mask(int32_t q, uint32_t kc, uint32_t ke, int32_t chunk, int32_t hop, int32_t frame_len, int32_t window, int32_t T);
 
 /* HIP-event timing of the kernels launched by the last *_device/host update on this engine
  * (milliseconds; measured on the stream the kernels ran on).  Enabled with pe_set_timing(e,1).

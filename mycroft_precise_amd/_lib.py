@@ -131,6 +131,8 @@ EXPORTS = {
     'pe_set_timing': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_set_chain_carry': (C.c_int, [C.c_void_p, C.c_int32]),
     'pe_get_chain_carry': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'pe_get_chain_skip': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    'pe_chain_alive_mask': (C.c_uint32, [C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'pe_get_last_timing': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     # training (pe_trainer)
     'pe_trainer_create': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(PeWeights), C.c_int32, C.POINTER(C.c_void_p)]),
@@ -894,6 +896,12 @@ class HipEngine:
         m, a = C.c_int32(0), C.c_int32(0)
         self._check(self._lib.pe_get_chain_carry(self._h, C.byref(m), C.byref(a)))
         return m.value, bool(a.value)
+
+    def chain_skip(self) -> int:
+        """The chunk size for which chain launches currently leave out the chains no update hands out (pe_get_chain_skip), or 0."""
+        c = C.c_int32(0)
+        self._check(self._lib.pe_get_chain_skip(self._h, C.byref(c)))
+        return c.value
 
     def set_timing(self, enabled: bool):
         self._check(self._lib.pe_set_timing(self._h, int(bool(enabled))))

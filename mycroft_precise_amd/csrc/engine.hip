@@ -99,6 +99,9 @@ struct pe_engine {
     uint64_t chain_epoch = 1, chains_built_epoch = 0;
     int chain_streak = 0;                    // eligible update calls in a row so far, nothing else bumping the epoch in between
     uint64_t chain_seen_epoch = 0;           // the epoch as the last update call left it
+    // chains no update will hand out are not advanced once a caller's chunk holds (do_update, kChainSkipAfter)
+    int chain_run = 0, chain_run_chunk = 0;  // eligible update calls in a row with the same chunk, and that chunk
+    int chain_skip_chunk = 0;                // the chunk the valid chains were last advanced for with skipping on; 0 = every live chain is current
     int gru_waves = 0;      // 0 = auto (4 waves per tile while tiles <= CUs, else 1), or forced 1 / 4
     // general front end (mfcc_general_device.h): any n_fft / n_filt / n_mfcc the stock-shape wave kernel has no tables for
     bool general = false;
@@ -1188,6 +1191,13 @@ bool can_fuse(const pe_engine* e, int chunk) {
 // chain launch saves per update (15.13 -> 14.14 us) -- 103 updates to earn it back, rounded up to a power of two.
 constexpr int kChainEnterAfter = 128;
 
+// Eligible updates in a row with ONE chunk longer than a hop before a chain launch stops advancing the chains that no update of
+// that cadence hands out (gru_chain_device.h, ChainArgs::skip; 1 - hop / chunk of them).  Nothing is rebuilt when skipping
+// starts; leaving the cadence costs one rebuild launch in front of the first call with another chunk.  Derived as
+// kChainEnterAfter was: that launch, 103.4 us at 4096 streams, against 0.85 us saved per update of 1024 samples (13.67 -> 12.82 us
+// by HIP events, profiles/chain_skip/README.md) -- 122 updates to earn it back, rounded up to a power of two.
+constexpr int kChainSkipAfter = 128;
+
 // May this update advance carried chains instead of running every window again?  Exactly the headline rows of DESIGN 0:
 // the stock float32 network re-tiled on four waves per tile over the 32-slot float32 ring (<= 8192 streams), one model, no
 // delta inputs, no projection rows, a chunk the fused launch takes and that makes at most two rows visible, and no explicit
@@ -1235,6 +1245,12 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
     if (!chain_call || e->chain_epoch != e->chain_seen_epoch) e->chain_streak = 0;
     if (chain_call) ++e->chain_streak;
     const bool chains_enter = chain_call && !chains_current && (e->chain_mode == 2 || e->chain_streak > kChainEnterAfter);
+    // (the run is of eligible calls with one chunk; chains left out for another chunk -- or left behind by anything else -- are
+    //  made whole again before they are advanced)
+    if (!chain_call || e->chain_epoch != e->chain_seen_epoch || chunk != e->chain_run_chunk) e->chain_run = 0;
+    if (chain_call) { ++e->chain_run; e->chain_run_chunk = chunk; }
+    if (!chains_current) e->chain_skip_chunk = 0;
+    const bool chains_leave = e->chain_skip_chunk != 0 && chunk != e->chain_skip_chunk;
     uint32_t call = 0;
     if ((rc = begin_state_call(e, s, &call))) return rc;
     e->chain_seen_epoch = e->chain_epoch;
@@ -1244,11 +1260,16 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
             if ((rc = dev_alloc(e, &e->chain_ke, (size_t)e->n_padded))) return rc;
             if ((rc = dev_alloc(e, &e->chains, (size_t)e->n_tiles * kCwSlots * 5 * 64))) return rc;
         }
-        const ChainArgs ch{e->chains, e->chain_ke};
+        const bool skip = chunk > e->prm.hop_samples && e->chain_run >= kChainSkipAfter;
+        const ChainArgs ch{e->chains, e->chain_ke, skip ? 1 : 0};
         GruArgs g = gru_args(e);
         g.call = call;
-        // entering: every live chain from the ring and the records as they stand before this update, in front of the launch
-        if (chains_enter) PE_HIP(e, launch_chains_rebuild(g, ch, e->n_padded, s));
+        // entering, or leaving a cadence that left chains out: every live chain from the ring and the records as they stand
+        // before this update, in front of the launch
+        if (chains_enter || chains_leave) {
+            PE_HIP(e, launch_chains_rebuild(g, ch, e->n_padded, s));
+            e->chain_skip_chunk = 0;
+        }
         g.predict_ke = 1;
         g.chunk = chunk;
         g.out = raw_out_dev;
@@ -1256,6 +1277,7 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
         if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_chains(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, ch, e->n_cus, s));
         else PE_HIP(e, launch_fused_chains(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, ch, e->n_cus, s));
         e->chains_built_epoch = e->chain_epoch;          // (only now: a launch that failed leaves the chains behind the streams)
+        if (skip) e->chain_skip_chunk = chunk;
     } else if (raw_out_dev && can_fuse(e, chunk)) {
         GruArgs g = gru_args(e);             // the records as they stand BEFORE the update; the waves predict ke
         g.call = call;                       // (records this launch writes are not read by it)
@@ -2939,6 +2961,20 @@ int pe_get_chain_carry(const pe_engine* e, int32_t* mode, int32_t* active) {
     if (mode) *mode = e->chain_mode;
     if (active) *active = (e->chain_mode != 0 && e->chains && e->chains_built_epoch == e->chain_epoch) ? 1 : 0;
     return PE_OK;
+}
+
+int pe_get_chain_skip(const pe_engine* e, int32_t* chunk) {
+    if (!e) return PE_ERR_INVALID;
+    if (chunk) *chunk = (e->chain_mode != 0 && e->chains && e->chains_built_epoch == e->chain_epoch) ? e->chain_skip_chunk : 0;
+    return PE_OK;
+}
+
+uint32_t pe_chain_alive_mask(int32_t q, uint32_t kc, uint32_t ke, int32_t chunk, int32_t hop, int32_t frame_len, int32_t window, int32_t T) {
+    // (a record's q is what mfcc_book_tile leaves: avail - nnew * hop, in [frame_len - hop, frame_len) -- negative where a frame is
+    //  shorter than a hop and the next one starts beyond the last sample held; anything below that is no record)
+    if ((q < 0 && q < frame_len - hop) || chunk < 1 || hop < 1 || frame_len < 1 || window < 1 || T < 1 || T > 31) return 0u;
+    const KeStep st = ke_step(q, kc, ke, chunk, hop, frame_len, window);
+    return chain_alive_bits(st.rem, chunk, hop, window, T, 0, T - 1) | (1u << T);
 }
 
 int pe_get_last_timing(pe_engine* e, float* mfcc_ms, float* gru_ms) {

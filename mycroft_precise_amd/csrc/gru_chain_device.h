@@ -25,6 +25,12 @@ namespace pe {
 
 // (ChainArgs: pe_common.h)
 constexpr int kChainMaxRows = 2;        // rows one chain launch may make visible per stream
+constexpr int kChainSkipAges = 7;       // ages of a stream whose alive bits one of its four lane groups forms (ChainArgs::skip)
+static_assert(4 * kChainSkipAges >= kCwSlots - 3 - 1, "the four lane groups cover the ages 1 .. T - 1 of the longest window (chain_eligible)");
+// OR over the wave's active lanes: the DPP reduction of the ROCm device library (ockl), the one hip/amd_detail/amd_warp_sync_functions.h
+// builds __reduce_or_sync on.  It is no documented interface: checked against ROCm 7.2.0; should a release drop it the link
+// fails (nothing falls back quietly), and six __shfl_xor steps in its place give the same value.
+extern "C" __device__ uint32_t __ockl_wfred_or_u32(uint32_t);
 
 // first float of the chain that started at a row of slot `slot`, for the lane of lane group g that serves stream sid
 __device__ __forceinline__ size_t chain_cell(const long long sid, const uint32_t slot, const int g) {
@@ -100,8 +106,11 @@ constexpr size_t kChainLdsBytes = (size_t)ChainLds::FLOATS * sizeof(float);
 // The records hold the state BEFORE the update (predict_ke, as for every network role of a fused launch).  Lanes of one
 // tile may make different numbers of rows visible (subset calls, streams out of phase): the wave runs the largest trip
 // count and every lane keeps what is its own.
-template <int NW>
-__device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane, float* const S) {
+// SKIP: ChainArgs::skip, as a template argument.  The two settings are two instantiations behind ONE branch that is uniform across
+// the launch (gru_tile_chains, below), not one body with tests inside: with both loops in one body the register allocator spilled
+// 48 bytes per lane, and callers whose chunks are at most a hop, or change, keep the stride loop this form always had.
+template <int NW, bool SKIP>
+__device__ __forceinline__ void gru_tile_chains_t(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane, float* const S) {
     const int g = lane >> 4, j = lane & 15;
     const long long stream = (long long)tile * kTileStreams + j;
     const bool valid = stream < a.n_streams;
@@ -123,12 +132,32 @@ __device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArg
     float wd[5];
 #pragma unroll
     for (int rho = 0; rho < 5; ++rho) wd[rho] = a.wd[rho * 64 + lane];
-    const uint32_t ke_pre = rec_pick(ke_req.p, rec_side(ke_req.p, a.call)).ke;
-    const uint32_t ke_post = gru_ke_resolve(a, ke_req);
+    // (gru_ke_resolve's arithmetic with its remainder: the launcher refuses a launch without predict_ke or with ke_plain)
+    const StreamRec rec = rec_pick(ke_req.p, rec_side(ke_req.p, a.call));
+    const KeStep st = ke_step(rec.q, rec.kc, rec.ke, a.chunk, a.hop, a.frame_len, a.window);
+    const uint32_t ke_pre = rec.ke, ke_post = st.ke;
     const uint32_t k = ke_post - ke_pre;
+    // (decided here, as a lane mask in scalar registers: left to the compiler the stamp stays in a register through the loop)
+    const unsigned long long stale = __ballot(stamp != ke_pre || k > (uint32_t)kChainMaxRows);
     // (the waves of a workgroup serve the same 16 streams, so kmax is uniform across the WORKGROUP, not only across the wave)
     const int kmax = __any(k >= 2u) ? 2 : __any(k >= 1u) ? 1 : 0;       // (k > kChainMaxRows: refused below, never run)
+    // ---- the chains this wave advances: bit A of `mine` = the chain of (post-update) age A ---------------------------
+    // ch.skip: a chain that no update of a caller who keeps this chunk will hand out (chain_alive_bits, pe_common.h) is neither
+    // loaded, stepped nor stored.  A lane group g forms the bits of seven of its stream's ages; the OR over the valid lanes is
+    // what the tile acts on (streams of a subset call are out of phase: a chain is skipped only if it is dead for all sixteen;
+    // one that rides along for a neighbour computes on stale state in its own MFMA column, and nobody reads it).  Every wave
+    // of the tile finds the same mask: they serve the same sixteen streams.  Age T is the window of this update.
+    uint32_t alive = (2u << T) - 2u;
+    if constexpr (SKIP) {
+        const uint32_t own = valid ? chain_alive_bits(st.rem, a.chunk, a.hop, a.window, T, g * kChainSkipAges, kChainSkipAges) : 0u;
+        alive = (uint32_t)__builtin_amdgcn_readfirstlane((int)__ockl_wfred_or_u32(own)) | (1u << T);
+    }
+    // Wave w takes the alive ages = w (mod NW), the head the wave of age T, with or without skipping.  Handing the alive ages
+    // round by RANK instead (dead ages lie four or five apart and pile onto one wave) was built and measured too: slower on every
+    // path (12.93 against 12.82 us per full update, 10.79 against 10.33 for a quarter subset, profiles/chain_skip/README.md).
+    uint32_t mine = alive & ((NW == 4 ? 0x11111111u : 0x01010101u) << wave);
     const int head_wave = T % NW;
+    auto pop = [](uint32_t& m) -> int { const int age = m ? __builtin_ctz(m) : 0; m &= m - 1u; return age; };   // lowest age, 0 = none left
     constexpr bool kAhead = NW > 4;
     const uint32_t smask = (uint32_t)(kCwSlots - 1);
     const float* xbase = a.ring + gru_ring_cell(a, sid) * kRowFloats + 4 * g;
@@ -139,23 +168,27 @@ __device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArg
         if (kmax >= 2) N.step_if(h, p1, 1u < k && k <= A + 1u);
     };
     const bool moved = valid && k > 0u;
-    float hw[5];                            // the window's state, on the wave that holds the chain of age T
+    // the pair of chains in flight.  A wave takes its ages in rising order, so on the wave that owns age T the window's state is
+    // what its last pair leaves: h1 if that was a pair (last_two), else h0
+    float h0[5], h1[5];
+    bool last_two = false;
 #pragma unroll
-    for (int rho = 0; rho < 5; ++rho) hw[rho] = 0.f;
+    for (int rho = 0; rho < 5; ++rho) h0[rho] = h1[rho] = 0.f;
     if (kmax == 0) {
         // nothing became visible anywhere in the tile: the window is the stored chain of age T
-        if (wave == head_wave) chain_load(ch.chains, chain_cell(sid, (ke_post - (uint32_t)T) & smask, g), hw);
+        if (wave == head_wave) chain_load(ch.chains, chain_cell(sid, (ke_post - (uint32_t)T) & smask, g), h0);
     } else {
         // ---- second round trip: the new rows and the first chains -----------------------------------------------
         // (the second row is requested whether or not it is new -- its slot exists: a load under a branch is waited for at the
         //  join, in front of the chains' requests)
         const f32x4 x0 = *reinterpret_cast<const f32x4*>(xbase + (size_t)(ke_pre & smask) * kTileStreams * kRowFloats);
         const f32x4 x1 = *reinterpret_cast<const f32x4*>(xbase + (size_t)((ke_pre + 1u) & smask) * kTileStreams * kRowFloats);
-        auto cell_of = [&](const int age) -> size_t { return chain_cell(sid, (ke_post - (uint32_t)(age <= T ? age : T)) & smask, g); };
-        const int first = wave ? wave : NW;
+        // (age 0 = no chain: the cell of age T is requested in its place and the state dropped)
+        auto cell_of = [&](const int age) -> size_t { return chain_cell(sid, (ke_post - (uint32_t)(age ? age : T)) & smask, g); };
+        int a0 = pop(mine), a1 = pop(mine);
         float n0[5], n1[5];
-        chain_load(ch.chains, cell_of(first), n0);
-        chain_load(ch.chains, cell_of(first + NW), n1);
+        chain_load(ch.chains, cell_of(a0), n0);
+        chain_load(ch.chains, cell_of(a1), n1);
         // ---- one projection per workgroup.  This branch is uniform across the workgroup (kmax, above) and no lane-divergent
         // code encloses it, so every wave of the workgroup reaches the barrier.  Only what THIS launch wrote is read back: row
         // 0 is written by all four waves whenever the branch is taken, row 1 is written and read under the same kmax >= 2
@@ -173,12 +206,12 @@ __device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArg
         // the rows.  kAhead: the state of the NEXT two is requested before the steps of these (the stores below go to other
         // cells of the same array, which the compiler cannot know: left to it, every pair waits a whole memory round trip for
         // its loads)
-        for (int a0 = first; a0 <= T; a0 += 2 * NW) {
-            const uint32_t A0 = (uint32_t)a0, A1 = A0 + (uint32_t)NW;
-            const bool two = a0 + NW <= T;
-            const size_t c0 = cell_of(a0), c1 = cell_of(a0 + NW);
-            float h0[5], h1[5];
-            if (!kAhead && a0 != first) {
+        // (fresh: the pair's state is still to be requested; b0, b1: the ages of the wave's next pair, 0 = none)
+        auto pair = [&](const int a0, const int a1, const bool fresh, const int b0, const int b1) {
+            const uint32_t A0 = (uint32_t)a0, A1 = (uint32_t)a1;
+            const bool two = a1 != 0;
+            const size_t c0 = cell_of(a0), c1 = cell_of(a1);
+            if (!kAhead && fresh) {
                 chain_load(ch.chains, c0, n0);
                 chain_load(ch.chains, c1, n1);
             }
@@ -187,31 +220,45 @@ __device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArg
                 h0[rho] = A0 <= k ? 0.f : n0[rho];
                 h1[rho] = A1 <= k ? 0.f : n1[rho];
             }
-            if (kAhead && a0 + 2 * NW <= T) {
-                chain_load(ch.chains, cell_of(a0 + 2 * NW), n0);
-                chain_load(ch.chains, cell_of(a0 + 3 * NW), n1);
+            if (kAhead && b0) {
+                chain_load(ch.chains, cell_of(b0), n0);
+                chain_load(ch.chains, cell_of(b1), n1);
             }
             advance(h0, A0);
             if (two) advance(h1, A1);
             chain_store(ch.chains, c0, h0, moved);
             if (two) chain_store(ch.chains, c1, h1, moved);
-            if (a0 == T) {
-#pragma unroll
-                for (int rho = 0; rho < 5; ++rho) hw[rho] = h0[rho];
-            }
-            if (two && a0 + NW == T) {
-#pragma unroll
-                for (int rho = 0; rho < 5; ++rho) hw[rho] = h1[rho];
+            last_two = two;
+        };
+        // Flag clear: the stride of the ages is known.  Flag set: the wave walks the set bits of its part of the mask.
+        if constexpr (!SKIP) {
+            auto upto = [&](const int age) -> int { return age <= T ? age : 0; };
+            for (int s0 = a0; s0; s0 = upto(s0 + 2 * NW))
+                pair(s0, upto(s0 + NW), s0 != a0, upto(s0 + 2 * NW), upto(s0 + 3 * NW));
+        } else {
+            for (bool first = true; a0; first = false) {
+                const int b0 = pop(mine), b1 = pop(mine);
+                pair(a0, a1, !first, b0, b1);
+                a0 = b0; a1 = b1;
             }
         }
     }
     if (wave == head_wave) {
+        float hw[5];
+#pragma unroll
+        for (int rho = 0; rho < 5; ++rho) hw[rho] = last_two ? h1[rho] : h0[rho];
         // a stream whose chains are not current to its record (or that makes more rows visible than this form carries) must
         // not pass for a result
-        if (stamp != ke_pre || k > (uint32_t)kChainMaxRows) hw[0] = __builtin_nanf("");
+        if ((stale >> lane) & 1ull) hw[0] = __builtin_nanf("");
         cw_head(a, hw, wd, stream, valid, g);
         if (valid && g == 0) ch.chain_ke[sid] = ke_post;
     }
+}
+
+template <int NW>
+__device__ __forceinline__ void gru_tile_chains(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane, float* const S) {
+    if (ch.skip) gru_tile_chains_t<NW, true>(a, ch, tile, wave, lane, S);
+    else gru_tile_chains_t<NW, false>(a, ch, tile, wave, lane, S);
 }
 
 // ---- entering chain mode: all T live chains of every stream from the ring and the records as they stand ------------------

@@ -816,7 +816,7 @@ hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>&
 template <class R>
 static hipError_t launch_fused_chains_t(const MfccStreamArgs<R>& m, const WaveTables<R>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s) {
     if (t.L.mel_pad != ShapeStock::MEL || !blob_matches_shape(t)) return hipErrorInvalidValue;
-    if (!g.cw || g.waves_per_tile != 4 || !cw_four_waves_ok(g) || !g.predict_ke || !ch.chains || !ch.chain_ke) return hipErrorInvalidValue;
+    if (!g.cw || g.waves_per_tile != 4 || !cw_four_waves_ok(g) || !g.predict_ke || g.ke_plain || !ch.chains || !ch.chain_ke) return hipErrorInvalidValue;
     const int tiles = (m.geo.n_streams + kTileStreams - 1) / kTileStreams;
     if (tiles == 0) return hipSuccess;
     const int fb = stream_frame_blocks(m.geo.n_streams, n_cus, tiles <= n_cus ? 2 : 4);

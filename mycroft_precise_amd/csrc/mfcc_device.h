@@ -82,6 +82,8 @@ __device__ __forceinline__ void mfcc_book_tile(const MfccStreamArgs<R>& a, const
     //  instructions, and this role had six of them per stream)
     auto by_hop = [&](int x) -> int { return (int)a.div_hop.div((uint32_t)x); };
     auto by_chunk = [&](int x) -> int { return (int)a.div_chunk.div((uint32_t)x); };
+    // (the records' arithmetic is stated twice more for the network roles that predict it: pe_common.h gru_ke_resolve and ke_step
+    //  -- change all three together)
     const int nnew = avail >= flen ? 1 + by_hop(avail - flen) : 0;
     const size_t carry_side = (size_t)a.st.n_padded * kCarryCap;
     const int16_t* car = a.st.carry + (size_t)side * carry_side + (size_t)sid * kCarryCap;

@@ -401,6 +401,10 @@ __device__ __forceinline__ KeRequest gru_ke_request(const GruArgs& a, const long
 }
 // emitted-frame count the window of this launch ends at: the record's own, or -- predict_ke, the network role of a fused
 // launch -- what this update will make of it (same arithmetic as mfcc_book_tile)
+// (a THIRD statement of that arithmetic is ke_step below, which also returns the remainder and is what the chain launch and
+//  pe_chain_alive_mask use; this one is kept as it is so that the code of every kernel that calls it stays what was measured.
+//  tests/test_chain_skip_host.py replays the arithmetic against ke_step, the chain tests compare the kernels bit for bit: change
+//  all three together)
 __device__ __forceinline__ uint32_t gru_ke_resolve(const GruArgs& a, const KeRequest& r) {
     if (a.ke_plain) return r.plain;
     const StreamRec c = rec_pick(r.p, rec_side(r.p, a.call));
@@ -415,6 +419,42 @@ __device__ __forceinline__ uint32_t gru_ke_resolve(const GruArgs& a, const KeReq
     return ke;
 }
 __device__ __forceinline__ uint32_t gru_window_end(const GruArgs& a, const long long sid) { return gru_ke_resolve(a, gru_ke_request(a, sid)); }
+
+// ---- which carried chains (gru_chain_device.h) a caller with a constant chunk will ever be handed --------------------------
+// One update of `chunk` samples on a stream's record (q leftover samples, kc frames computed, ke rows emitted): the emitted
+// count afterwards -- gru_ke_resolve's arithmetic -- and rem = the samples held toward the next emission (rem < window).
+struct KeStep { uint32_t ke; int rem; };
+__host__ __device__ __forceinline__ KeStep ke_step(const int q, const uint32_t kc, const uint32_t ke, const int chunk, const int hop, const int frame_len, const int window) {
+    const int avail = q + chunk;
+    const int nnew = avail >= frame_len ? 1 + (avail - frame_len) / hop : 0;
+    const int qn = avail - nnew * hop;
+    int m = qn + hop * (int)(kc + (uint32_t)nnew - ke);
+    KeStep r{ke, m};
+    if (m >= window) {
+        const uint32_t rows = 1u + (uint32_t)((m - window) / hop);
+        r.ke = ke + rows;
+        r.rem = m - hop * (int)rows;
+    }
+    return r;
+}
+// Under a constant chunk c row ke_post + d is emitted j(d) = ceil((window + d hop - rem) / c) updates from now, and an update
+// hands out ONE window: the chain that started T rows before its last row.  The chain of (post-update) age A < T ends with
+// row d = T - 1 - A and is dead -- stepped over, never read -- iff row d + 1 comes out in the same update: j(d) == j(d + 1),
+// which with u(d) = window + d hop - rem - 1 and hop < c is u(d) mod c + hop < c.
+// Bits A = T - 1 - d of the rows d_lo <= d < d_lo + d_n (d <= T - 2): ONE division, then a running remainder.  c <= hop: an
+// update emits at most one row and every chain is alive.
+__host__ __device__ __forceinline__ uint32_t chain_alive_bits(const int rem, const int c, const int hop, const int window, const int T, const int d_lo, const int d_n) {
+    uint32_t bits = 0u;
+    const bool all = c <= hop;
+    uint32_t r = all ? 0u : (uint32_t)(window - rem - 1 + d_lo * hop) % (uint32_t)c;
+    for (int i = 0; i < d_n; ++i) {
+        const int d = d_lo + i;
+        if (d <= T - 2 && (all || r + (uint32_t)hop >= (uint32_t)c)) bits |= 1u << (T - 1 - d);
+        r += (uint32_t)hop;
+        r = r >= (uint32_t)c ? r - (uint32_t)c : r;
+    }
+    return bits;
+}
 
 struct WideLayerArgs {
     const float4* wx1;      // phase 1, input part     [wave][kx4][2 TPW][64] float4
@@ -498,6 +538,7 @@ hipError_t launch_fused(const MfccStreamArgs<float>& m, const WaveTables<float>&
 struct ChainArgs {
     float* chains;          // [n_padded / 16][kCwSlots][5 rho][64 lanes] state of the chain that started at a row of that slot
     uint32_t* chain_ke;     // [n_padded] emitted count each stream's chains are current to (a cross-check: engine.hip chain_epoch)
+    int skip;               // != 0: the caller's chunk holds (engine.hip kChainSkipAfter): chains no update will hand out are not advanced
 };
 hipError_t launch_fused_chains(const MfccStreamArgs<double>& m, const WaveTables<double>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s);
 hipError_t launch_fused_chains(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s);
