@@ -77,12 +77,27 @@ typedef struct pe_params {
                                 rounded as operands; the carried state stays float32).  bf16-operand
                                 wide networks take plain rows of <= 16 coefficients: no use_delta; and
                                 no wide network takes ring_precision = 1.                    */
-    int32_t vectorizer;      /* params.py:121-132: 2 = mfccs (sonopy, the default; also serves the
-                                offline mels entry), 3 = speechpy_mfccs (legacy .params files without
+    int32_t vectorizer;      /* params.py:121-132: 2 = mfccs (sonopy, the default; pe_vectorize_mels and
+                                pe_vectorize_clips(mels = 1) also give its log-mel rows),
+                                3 = speechpy_mfccs (legacy .params files without
                                 a `vectorizer` key, params.py:147,155): one frame fewer per buffer
                                 (a frame is emitted one hop later), exact zeros -- not small values --
                                 replaced by eps before the log; the caller supplies that library's
-                                filterbank as mel_filters.  0 is read as 2.                     */
+                                filterbank as mel_filters.  0 is read as 2.
+                                1 = mels (vectorization.py:32-35 -> sonopy.mel_spec): a row is the n_filt
+                                log-mel energies safe_log(power . filters^T) -- no DCT, value 0 NOT replaced
+                                by the log power -- over sonopy's filterbank.  The row width W = n_filt stands
+                                wherever an mfccs engine has n_mfcc: the window is [n_features][W], the
+                                first layer takes W inputs (2 W with use_delta), pe_get_vectors /
+                                pe_set_vectors / pe_update_vectors / pe_vectorize_raw / pe_vectorize_clips
+                                (whatever its mels flag) are W wide, pe_get_info reports n_mfcc = W; the
+                                given n_mfcc keeps its range check and is otherwise ignored.  Limits, each
+                                PE_ERR_UNSUPPORTED before any device work: n_filt <= 32; more than 16 values
+                                per row feed a float32 network without use_delta and without bf16 rows; a
+                                first layer of another width ("Vectorizer.mels feeds 20 inputs per frame,
+                                this network takes 13"); pe_miner_create, pe_generator_create and
+                                pe_augmenter_create refuse such an engine.  (The filterbank is the
+                                caller's table: the Python layer refuses the speechpy one.)  DESIGN 4.17 */
     int32_t ring_precision;  /* 0 = float32 feature rows (64 B per frame and stream);
                                 1 = bf16 feature rows (32 B), rounded to nearest even where the row is
                                 stored -- needs gru_precision = 1 (BASELINE configs[4])         */
@@ -295,14 +310,15 @@ int pe_predict_device(pe_engine* e, const float* feats_dev, int32_t n, float* ou
 
 /* vectorize_raw (vectorization.py:46-50) for the Vectorizer.mfccs entry (:36-39): stateless
  * MFCC of one whole buffer.  audio: float64 samples in [-1,1) (what the reference's vectorizer
- * receives).  feats_out[max_frames][n_mfcc] float64; *n_frames_out = 1+(n-window)//hop or 0. */
+ * receives).  feats_out[max_frames][n_mfcc] float64; *n_frames_out = 1+(n-window)//hop or 0.
+ * An engine created with vectorizer = 1 dispatches as vectorize_raw does: the mel rows, [max_frames][n_filt]. */
 int pe_vectorize_raw(pe_engine* e, const double* audio_host, int64_t n_samples,
                      double* feats_out_host, int64_t max_frames, int64_t* n_frames_out);
 
 /* The same buffer through the Vectorizer.mels entry (vectorization.py:32-35 -> sonopy.mel_spec): log of the
- * mel filterbank energies, no DCT.  mels_out[max_frames][n_filt] float64.  Offline form only, as in the reference:
- * its Listener allocates the feature window n_mfcc wide (network_runner.py:104,123), so mel rows of n_filt columns
- * cannot stream through it either; pe_create refuses vectorizer = 1. */
+ * mel filterbank energies, no DCT.  mels_out[max_frames][n_filt] float64.  Any engine has this entry: an mfccs engine
+ * gives the log-mel rows beside its MFCC rows (the reference's offline tools under pr.vectorizer = mels), an engine created
+ * with vectorizer = 1 gives the rows it streams -- the bits pe_vectorize_raw returns there. */
 int pe_vectorize_mels(pe_engine* e, const double* audio_host, int64_t n_samples,
                       double* mels_out_host, int64_t max_frames, int64_t* n_frames_out);
 
@@ -325,7 +341,7 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
  * (anchored at its start; one fewer with vectorizer = 3), the last n_features of them, all-zero rows in front up to
  * n_features; a clip shorter than one window gives an all-zero window.
  * pe_vectorize_clips: feats_out[n_clips][n_features][n_mfcc] float64, or -- mels = 1, the Vectorizer.mels entry --
- * [n_clips][n_features][n_filt] log-mel rows.
+ * [n_clips][n_features][n_filt] log-mel rows (an engine created with vectorizer = 1: those rows whatever the flag).
  * pe_score_clips: the network over every clip's window, out[n_models][n_clips] raw outputs (use_delta models: the deltas
  * of the padded window, zero in its first row, as vectorize_delta forms them, vectorization.py:87-89).
  * One front-end launch and (scores) one network launch per pass; the clips are staged in passes of 256 MiB of audio (a pass

@@ -342,6 +342,10 @@ class HipEngine:
     frame (``use_delta`` over <= 16 coefficients, or 17..32 coefficients).  ``'bf16'`` serves the same widths on plain rows of
     <= 16 coefficients (<= 32 units: ``use_delta`` over <= 14).  Anything else raises NotImplementedError naming the limit.
 
+    ``params.vectorizer = Vectorizer.mels``: the rows are the ``n_filt`` log-mel energies (no DCT; ``n_mfcc`` is ignored), so
+    ``row_width`` -- the width of a window row, of ``get_vectors`` / ``set_vectors`` / ``vectorize_raw`` / ``vectorize_clips`` --
+    is ``n_filt``, and the same limits hold for it: up to 32 values, more than 16 for float32 networks without ``use_delta``.
+
     ``weights`` a LIST of weight dicts (same architecture) builds a K-model engine (pe_create_models): one
     front end for all models, and every network output gains a leading model axis ``[K, ...]`` -- even for K = 1.
     """
@@ -350,7 +354,6 @@ class HipEngine:
                  gru_precision='f32', ring_precision='f32'):
         from .vectorization import mel_filterbank, speechpy_filterbank
         from .params import Vectorizer
-        self._lib = load()
         self._h = C.c_void_p()
         self._async_keep = []
         self._miners = weakref.WeakSet()   # HipMiner / HipGenerator / HipAugmenter sessions over this engine: closed before the engine is destroyed
@@ -360,11 +363,15 @@ class HipEngine:
         self.n_features = int(params.n_features)
         self.n_mfcc = int(params.n_mfcc)
         self.n_filt = int(params.n_filt)
-        self.feature_size = int(params.n_mfcc) * (2 if params.use_delta else 1)
         prec = {'f64': 0, 'f32': 1}[mfcc_precision]
         vec = int(getattr(params, 'vectorizer', Vectorizer.mfccs))
-        if vec == Vectorizer.mels:          # the mels entry is the mfccs pipeline without its DCT (offline form)
-            vec = Vectorizer.mfccs
+        self.mels = vec == Vectorizer.mels
+        self.row_width = self.n_filt if self.mels else self.n_mfcc          # values per frame (params.py:99-109 without the deltas)
+        self.feature_size = self.row_width * (2 if params.use_delta else 1)
+        self._multi = isinstance(weights, (list, tuple))
+        if self.mels:                       # refused by name before the library is touched
+            self._check_mels(params, list(weights) if self._multi else [weights], mel_filters, gru_precision, ring_precision)
+        self._lib = load()
         p = PeParams(params.sample_rate, params.window_samples, params.hop_samples, params.n_fft,
                      params.n_filt, params.n_mfcc, params.n_features, int(bool(params.use_delta)), prec,
                      {'f32': 0, 'bf16': 1}[gru_precision], vec, {'f32': 0, 'bf16': 1}[ring_precision])
@@ -374,7 +381,6 @@ class HipEngine:
         mel = np.ascontiguousarray(mel_filters, dtype=np.float64)
         if mel.shape != (params.n_filt, params.n_fft // 2 + 1):
             raise ValueError('mel filterbank has shape %r' % (mel.shape,))
-        self._multi = isinstance(weights, (list, tuple))
         models = list(weights) if self._multi else [weights]
         if not models:
             raise ValueError('no models')
@@ -396,6 +402,27 @@ class HipEngine:
         self.units = models[0]['gru'][-1][1].shape[0]
         self.n_models = len(models)
         self._win_hop = (int(params.window_samples), int(params.hop_samples))
+
+    def _check_mels(self, params, models, mel_filters, gru_precision, ring_precision):
+        """The limits of a Vectorizer.mels engine (pe_create names the same ones): NotImplementedError for each."""
+        from .vectorization import speechpy_filterbank
+        w = self.row_width
+        if w > 32:
+            raise NotImplementedError('Vectorizer.mels feeds n_filt = %d values per frame: the networks take up to 32 inputs per frame' % w)
+        if w > 16 and (params.use_delta or gru_precision != 'f32' or ring_precision != 'f32'):
+            raise NotImplementedError('Vectorizer.mels with n_filt = %d: rows of more than 16 values feed a float32 network without '
+                                      'use_delta, bf16 operands or bf16 rows (got use_delta=%r, gru_precision=%r, ring_precision=%r)'
+                                      % (w, bool(params.use_delta), gru_precision, ring_precision))
+        if mel_filters is not None:
+            given = np.asarray(mel_filters, dtype=np.float64)
+            theirs = speechpy_filterbank(params.sample_rate, params.n_filt, params.n_fft // 2 + 1)
+            if given.shape == theirs.shape and np.array_equal(given, theirs):
+                raise NotImplementedError('Vectorizer.mels is sonopy\'s mel_spec over sonopy\'s filterbank (mel_filterbank): the speechpy '
+                                          'filterbank belongs to Vectorizer.speechpy_mfccs')
+        for wm in models:
+            n_in = int(np.shape(wm['gru'][0][0])[0])
+            if n_in != self.feature_size:
+                raise NotImplementedError('Vectorizer.mels feeds %d inputs per frame, this network takes %d' % (self.feature_size, n_in))
 
     def _lead(self, *shape):
         """shape of a network output: a leading model axis on a K-model engine"""
@@ -565,22 +592,22 @@ class HipEngine:
 
     def update_vectors(self, pcm, want_features=True):
         pcm = self._pcm(pcm)
-        feats = np.empty((self.n_streams, self.n_features, self.n_mfcc), dtype=np.float32) if want_features else None
+        feats = np.empty((self.n_streams, self.n_features, self.row_width), dtype=np.float32) if want_features else None
         self._check(self._lib.pe_update_vectors(self._h, pcm.ctypes.data, pcm.shape[1],
                                                 feats.ctypes.data if want_features else None))
         return feats
 
     def get_vectors(self) -> np.ndarray:
         """Current feature windows float32 [n_streams, T, F], oldest row first."""
-        feats = np.empty((self.n_streams, self.n_features, self.n_mfcc), dtype=np.float32)
+        feats = np.empty((self.n_streams, self.n_features, self.row_width), dtype=np.float32)
         self._check(self._lib.pe_get_vectors(self._h, feats.ctypes.data))
         return feats
 
     def set_vectors(self, feats):
         """Restart every stream with the given feature windows [n_streams, T, F] already emitted."""
         feats = np.ascontiguousarray(feats, dtype=np.float32)
-        if feats.shape != (self.n_streams, self.n_features, self.n_mfcc):
-            raise ValueError('expected [%d, %d, %d] features, got %r' % (self.n_streams, self.n_features, self.n_mfcc, feats.shape))
+        if feats.shape != (self.n_streams, self.n_features, self.row_width):
+            raise ValueError('expected [%d, %d, %d] features, got %r' % (self.n_streams, self.n_features, self.row_width, feats.shape))
         self._check(self._lib.pe_set_vectors(self._h, feats.ctypes.data))
 
     def predict(self, feats) -> np.ndarray:
@@ -592,11 +619,12 @@ class HipEngine:
         return out
 
     def vectorize_raw(self, audio) -> np.ndarray:
-        """float64 audio [n] -> MFCC frames float64 [1 + (n - window)//hop, n_mfcc] (stateless)."""
+        """float64 audio [n] -> MFCC frames float64 [1 + (n - window)//hop, n_mfcc] (stateless); on a Vectorizer.mels engine
+        the log-mel frames [.., n_filt]."""
         audio = np.ascontiguousarray(audio, dtype=np.float64).reshape(-1)
         win, hop = self._win_hop
         max_frames = 1 + (audio.size - win) // hop if audio.size >= win else 0
-        out = np.empty((max_frames, self.n_mfcc), dtype=np.float64)
+        out = np.empty((max_frames, self.row_width), dtype=np.float64)
         n = C.c_int64(0)
         self._check(self._lib.pe_vectorize_raw(self._h, audio.ctypes.data if audio.size else None, audio.size,
                                                out.ctypes.data if max_frames else None, max_frames, C.byref(n)))
@@ -645,10 +673,11 @@ class HipEngine:
 
     def vectorize_clips(self, clips, max_samples, mels=False, out=None) -> np.ndarray:
         """vectorize (vectorization.py:62-84) of every clip in one call: a sequence of 1-D sample arrays of any lengths ->
-        float64 [n, n_features, n_mfcc] (mels: [n, n_features, n_filt] log-mel rows); max_samples <= 0 = no crop."""
+        float64 [n, n_features, n_mfcc] (mels, or a Vectorizer.mels engine: [n, n_features, n_filt] log-mel rows);
+        max_samples <= 0 = no crop."""
         audio, offsets, fmt = self._clips(clips)
         n = offsets.size - 1
-        shape = (n, self.n_features, self.n_filt if mels else self.n_mfcc)
+        shape = (n, self.n_features, self.n_filt if mels else self.row_width)
         if out is None:
             out = np.empty(shape, dtype=np.float64)
         if out.dtype != np.float64 or out.shape != shape or not out.flags.c_contiguous:

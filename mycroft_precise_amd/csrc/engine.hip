@@ -800,6 +800,9 @@ int64_t frames_of_buffer(const pe_params& p, int64_t n) {
     return n >= ew ? 1 + (n - ew) / p.hop_samples : 0;
 }
 
+// Vectorizer.mels: the front-end launchers run their MELS instantiation (rows = log-mel energies; prm.n_mfcc == prm.n_filt)
+bool mel_rows(const pe_engine* e) { return e->prm.vectorizer == 1; }
+
 StreamGeom geom(const pe_engine* e) {
     StreamGeom g;
     g.n_streams = e->n_streams;
@@ -890,10 +893,10 @@ int launch_mfcc(pe_engine* e, const int16_t* pcm_dev, int chunk, hipStream_t s, 
     //  network_runner.py:125-146; the frame tasks skip every row that the ring would overwrite again -- v_first in
     //  mfcc_frame_tasks -- so a long chunk costs its last ring_slots frames plus a scalar walk over the row indices)
     if (e->general) {
-        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_general_stream_f64(general_args<double>(e, pcm_dev, chunk, call, ids, n_active), s));
-        else PE_HIP(e, launch_general_stream_f32(general_args<float>(e, pcm_dev, chunk, call, ids, n_active), s));
-    } else if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_mfcc_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), e->n_cus, s));
-    else PE_HIP(e, launch_mfcc_f32(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), e->n_cus, s));
+        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_general_stream_f64(general_args<double>(e, pcm_dev, chunk, call, ids, n_active), s, mel_rows(e)));
+        else PE_HIP(e, launch_general_stream_f32(general_args<float>(e, pcm_dev, chunk, call, ids, n_active), s, mel_rows(e)));
+    } else if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_mfcc_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), e->n_cus, s, mel_rows(e)));
+    else PE_HIP(e, launch_mfcc_f32(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), e->n_cus, s, mel_rows(e)));
     return PE_OK;
 }
 
@@ -1169,6 +1172,7 @@ bool can_fuse(const pe_engine* e, int chunk) {
     // (the fused kernels exist for the stock table shape: filterbanks whose runs need the wide loop bounds take two launches;
     //  so do networks of 21..32 units on the one-wave kernel: their register-resident weights do not fit beside the
     //  frame role's 128-register budget -- fused, that shape spilled 96-240 bytes per lane into the time loop)
+    if (mel_rows(e)) return false;      // (mel rows on the stock wave kernel, n_filt <= 16: the frame role of the fused kernels has no MELS instantiation)
     if (!(e->fused && !e->general && !e->wide && e->table_layout.mel_pad == 10 && chunk <= emit_window(e->prm) - frame_len_of(e->prm))) return false;
     // (gru_x3_device.h: ~220 registers per lane against the frame role's ~100, and one kernel has one budget.  The same
     //  concurrency as TWO kernels -- the network on a side stream between two events -- was built and measured: 142 vs
@@ -1358,10 +1362,23 @@ int pack_model(pe_engine* e, NetPack& n, const pe_weights* w, const bool wide, c
 }
 
 // pe_create / pe_create_models: w[0 .. n_models) (checked against w[0] by pe_create_models before it comes here)
-int create_engine(const pe_params* p, const double* mel_filters, const pe_weights* w, int32_t n_models, int32_t n_streams,
+int create_engine(const pe_params* p_given, const double* mel_filters, const pe_weights* w, int32_t n_models, int32_t n_streams,
                   int32_t device, pe_engine** out) {
-    if (!p || !mel_filters || !w || !out) return fail(nullptr, PE_ERR_INVALID, "null argument to pe_create");
+    if (!p_given || !mel_filters || !w || !out) return fail(nullptr, PE_ERR_INVALID, "null argument to pe_create");
     *out = nullptr;
+    // Vectorizer.mels (vectorizer = 1, vectorization.py:32-35): a row is the n_filt log-mel energies, no DCT.  Behind the
+    // checks of n_mfcc itself the engine's n_mfcc IS that row width W = n_filt (params.py:99-109: feature_size), so ring rows,
+    // window, network inputs and every eligibility rule below are keyed on W; the front-end kernels run their MELS
+    // instantiation (mel_rows).  The given n_mfcc is range-checked and otherwise ignored.
+    pe_params p_rows = *p_given;
+    const pe_params* const p = &p_rows;
+    const bool mels = p_given->vectorizer == 1;
+    if (p->n_mfcc < 1 || p->n_mfcc > kGeneralMaxMfcc) return fail(nullptr, PE_ERR_UNSUPPORTED, "n_mfcc must be in 1..%d (got %d)", kGeneralMaxMfcc, p->n_mfcc);
+    if (mels) {
+        if (p->n_filt < 1 || p->n_filt > kGeneralMaxMfcc)
+            return fail(nullptr, PE_ERR_UNSUPPORTED, "Vectorizer.mels feeds n_filt values per frame and the networks take up to %d inputs per frame (got n_filt=%d)", kGeneralMaxMfcc, p->n_filt);
+        p_rows.n_mfcc = p->n_filt;
+    }
     if (n_streams <= 0) return fail(nullptr, PE_ERR_INVALID, "n_streams must be positive, got %d", n_streams);
     // ListenerParams (params.py:28-118): the stock shape (n_fft = 512, <= 64 filters, <= 16 coefficients) runs on the
     // one-frame-per-wave kernel, every other shape on the general front end (mfcc_general_device.h)
@@ -1370,7 +1387,6 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
     // (general_is_pow2: powers of two from 64 on; 16 and 32 run as Bluestein transforms over 128 points like every other short length)
     if (p->n_fft < 16 || p->n_fft > kGeneralMaxFft || (!general_is_pow2(p->n_fft) && p->n_fft > kGeneralMaxBlueFft))
         return fail(nullptr, PE_ERR_UNSUPPORTED, "n_fft must be any length in 16..%d or a power of two up to %d (got %d)", kGeneralMaxBlueFft, kGeneralMaxFft, p->n_fft);
-    if (p->n_mfcc < 1 || p->n_mfcc > kGeneralMaxMfcc) return fail(nullptr, PE_ERR_UNSUPPORTED, "n_mfcc must be in 1..%d (got %d)", kGeneralMaxMfcc, p->n_mfcc);
     if (p->n_filt < 1 || p->n_filt > kGeneralMaxFilt || p->n_mfcc > p->n_filt)
         return fail(nullptr, PE_ERR_UNSUPPORTED, "need 1 <= n_mfcc <= n_filt <= %d (got n_filt=%d n_mfcc=%d)", kGeneralMaxFilt, p->n_filt, p->n_mfcc);
     bool general = p->n_fft != kNfft || p->n_filt > kMaxFilt || p->n_mfcc > kRowFloats;
@@ -1378,8 +1394,8 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
         return fail(nullptr, PE_ERR_INVALID, "window/hop/n_features must be positive");
     if (p->mfcc_precision != 0 && p->mfcc_precision != 1) return fail(nullptr, PE_ERR_INVALID, "mfcc_precision must be 0 (f64) or 1 (f32)");
     if (p->gru_precision != 0 && p->gru_precision != 1) return fail(nullptr, PE_ERR_INVALID, "gru_precision must be 0 (f32) or 1 (bf16 operands)");
-    if (p->vectorizer != 0 && p->vectorizer != 2 && p->vectorizer != 3)
-        return fail(nullptr, PE_ERR_UNSUPPORTED, "vectorizer must be 2 (mfccs) or 3 (speechpy_mfccs); Vectorizer.mels (1) exists in the offline form only (pe_vectorize_mels), got %d", p->vectorizer);
+    if (p->vectorizer < 0 || p->vectorizer > 3)
+        return fail(nullptr, PE_ERR_UNSUPPORTED, "vectorizer must be 1 (mels), 2 (mfccs) or 3 (speechpy_mfccs), got %d", p->vectorizer);
     if (p->ring_precision != 0 && p->ring_precision != 1) return fail(nullptr, PE_ERR_INVALID, "ring_precision must be 0 (f32 rows) or 1 (bf16 rows)");
     if (p->ring_precision == 1 && p->gru_precision != 1) return fail(nullptr, PE_ERR_UNSUPPORTED, "bf16 feature rows (ring_precision = 1) feed the bf16-operand network only (gru_precision = 1)");
     if (w->n_layers < 1 || w->n_layers > 2 || !w->layers) return fail(nullptr, PE_ERR_UNSUPPORTED, "networks of 1 or 2 GRU layers have kernels (got %d layers)", w->n_layers);
@@ -1401,13 +1417,17 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
         if (p->use_delta && p->gru_precision == 1)
             return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta has no bf16-operand wide-GRU kernel (gru_precision = 1 networks of more than 32 units or two layers take plain feature rows)");
         if (p->use_delta && p->n_mfcc > kRowFloats)
-            return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta over more than 16 coefficients (n_mfcc = %d: %d inputs per frame) has no wide-GRU kernel: the first layer takes up to 32 inputs", p->n_mfcc, 2 * p->n_mfcc);
+            return fail(nullptr, PE_ERR_UNSUPPORTED, "use_delta over more than 16 %s (%s = %d: %d inputs per frame) has no wide-GRU kernel: the first layer takes up to 32 inputs",
+                        mels ? "mel values" : "coefficients", mels ? "n_filt" : "n_mfcc", p->n_mfcc, 2 * p->n_mfcc);
         if (p->n_mfcc > kRowFloats && p->gru_precision == 1)
-            return fail(nullptr, PE_ERR_UNSUPPORTED, "more than 16 coefficients per frame (n_mfcc = %d) have no bf16-operand wide-GRU kernel: gru_precision = 1 networks of more than 32 units or two layers take rows of <= 16 coefficients", p->n_mfcc);
+            return fail(nullptr, PE_ERR_UNSUPPORTED, "more than 16 %s per frame (%s = %d) have no bf16-operand wide-GRU kernel: gru_precision = 1 networks of more than 32 units or two layers take rows of <= 16 values",
+                        mels ? "mel values" : "coefficients", mels ? "n_filt" : "n_mfcc", p->n_mfcc);
         if (p->ring_precision == 1) return fail(nullptr, PE_ERR_UNSUPPORTED, "bf16 feature rows (ring_precision = 1) have no wide-GRU kernel: the bf16-operand wide network (gru_precision = 1) reads float32 rows");
         wide_units = (hmax + 63) / 64 * 64;
     }
     const int feature_size = p->use_delta ? 2 * p->n_mfcc : p->n_mfcc;          // params.py:99-109
+    if (L.n_in != feature_size && mels)
+        return fail(nullptr, PE_ERR_UNSUPPORTED, "Vectorizer.mels feeds %d inputs per frame, this network takes %d", feature_size, L.n_in);
     if (L.n_in != feature_size) return fail(nullptr, PE_ERR_INVALID, "layer n_in=%d does not match feature_size=%d", L.n_in, feature_size);
     if (!L.kernel || !L.recurrent_kernel || !L.bias || !w->dense_kernel) return fail(nullptr, PE_ERR_INVALID, "null weight pointer");
 
@@ -1437,7 +1457,7 @@ int create_engine(const pe_params* p, const double* mel_filters, const pe_weight
             return fail(nullptr, PE_ERR_UNSUPPORTED, "device %d is %s: libprecise_engine.so is built for gfx950 (MI355X) only", device, prop.gcnArchName);
     }
     if (p->n_mfcc > kRowFloats && !wide && (p->use_delta || p->gru_precision != 0))
-        return fail(nullptr, PE_ERR_UNSUPPORTED, "more than 16 coefficients per frame feed a float32 network without delta features only");
+        return fail(nullptr, PE_ERR_UNSUPPORTED, "more than 16 %s per frame feed a float32 network without delta features only", mels ? "mel values (n_filt)" : "coefficients");
     // (bf16 operands / bf16 rows behind the general front end: the same network kernels, fed from rows of <= 16 coefficients --
     //  more than 16 were refused above)
 
@@ -1962,19 +1982,19 @@ int vectorize_buffer(pe_engine* e, const double* audio_host, int64_t n_samples, 
     if (e->general) {
         if (e->prm.mfcc_precision == 0) {
             GeneralOfflineArgs<double> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f64(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_offline_f64(a, e->n_cus, nullptr, mel_rows(e)));
         } else {
             GeneralOfflineArgs<float> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f32(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_offline_f32(a, e->n_cus, nullptr, mel_rows(e)));
         }
     } else if (e->prm.mfcc_precision == 0) {
         MfccOfflineArgs<double> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames,
                                   mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr};
-        PE_HIP(e, launch_mfcc_offline_f64(a, tables<double>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_offline_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
     } else {
         MfccOfflineArgs<float> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames,
                                  mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr};
-        PE_HIP(e, launch_mfcc_offline_f32(a, tables<float>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_offline_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
     }
     PE_HIP(e, hipMemcpy(feats_out_host, e->st_mfcc.p, fb, hipMemcpyDeviceToHost));
     return PE_OK;
@@ -2014,17 +2034,17 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
     if (e->general) {
         if (e->prm.mfcc_precision == 0) {
             GeneralOfflineArgs<double> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f64(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_offline_f64(a, e->n_cus, nullptr, mel_rows(e)));
         } else {
             GeneralOfflineArgs<float> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f32(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_offline_f32(a, e->n_cus, nullptr, mel_rows(e)));
         }
     } else if (e->prm.mfcc_precision == 0) {
         MfccOfflineArgs<double> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr};
-        PE_HIP(e, launch_mfcc_offline_f64(a, tables<double>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_offline_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
     } else {
         MfccOfflineArgs<float> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr};
-        PE_HIP(e, launch_mfcc_offline_f32(a, tables<float>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_offline_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
     }
     GruArgs g = gru_args(e);
     g.n_streams = (int)n_windows;
@@ -2125,17 +2145,17 @@ int launch_clip_front_end(pe_engine* e, const ClipTable& ct, double* dev_out, fl
     if (e->general) {
         if (e->prm.mfcc_precision == 0) {
             GeneralClipArgs<double> a{geom(e), e->gtab, ct, dev_out, dev_rows, dev_mels, e->row_floats};
-            PE_HIP(e, launch_general_clips_f64(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_clips_f64(a, e->n_cus, nullptr, mel_rows(e)));
         } else {
             GeneralClipArgs<float> a{geom(e), e->gtab, ct, dev_out, dev_rows, dev_mels, e->row_floats};
-            PE_HIP(e, launch_general_clips_f32(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_clips_f32(a, e->n_cus, nullptr, mel_rows(e)));
         }
     } else if (e->prm.mfcc_precision == 0) {
         MfccClipArgs<double> a{geom(e), ct, dev_out, dev_rows, dev_mels};
-        PE_HIP(e, launch_mfcc_clips_f64(a, tables<double>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_clips_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
     } else {
         MfccClipArgs<float> a{geom(e), ct, dev_out, dev_rows, dev_mels};
-        PE_HIP(e, launch_mfcc_clips_f32(a, tables<float>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_clips_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
     }
     return PE_OK;
 }
@@ -2144,17 +2164,17 @@ int launch_rec_front_end(pe_engine* e, const RecTable& rt, float* dev_rows) {
     if (e->general) {
         if (e->prm.mfcc_precision == 0) {
             GeneralRecArgs<double> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
-            PE_HIP(e, launch_general_recs_f64(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_recs_f64(a, e->n_cus, nullptr, mel_rows(e)));
         } else {
             GeneralRecArgs<float> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
-            PE_HIP(e, launch_general_recs_f32(a, e->n_cus, nullptr));
+            PE_HIP(e, launch_general_recs_f32(a, e->n_cus, nullptr, mel_rows(e)));
         }
     } else if (e->prm.mfcc_precision == 0) {
         MfccRecArgs<double> a{geom(e), rt, dev_rows};
-        PE_HIP(e, launch_mfcc_recs_f64(a, tables<double>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_recs_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
     } else {
         MfccRecArgs<float> a{geom(e), rt, dev_rows};
-        PE_HIP(e, launch_mfcc_recs_f32(a, tables<float>(e), e->n_cus, nullptr));
+        PE_HIP(e, launch_mfcc_recs_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
     }
     return PE_OK;
 }
@@ -2761,11 +2781,11 @@ int pe_update_many_device(pe_engine* e, const int16_t* pcm_dev, int32_t chunk, i
         if (e->prm.mfcc_precision == 0) {
             GeneralStreamArgs<double> a = general_args<double>(e, pcm_dev, chunk, call);
             a.n_updates = n_updates; a.ke_hist = e->ke_hist;
-            PE_HIP(e, launch_general_stream_f64(a, s));
+            PE_HIP(e, launch_general_stream_f64(a, s, mel_rows(e)));
         } else {
             GeneralStreamArgs<float> a = general_args<float>(e, pcm_dev, chunk, call);
             a.n_updates = n_updates; a.ke_hist = e->ke_hist;
-            PE_HIP(e, launch_general_stream_f32(a, s));
+            PE_HIP(e, launch_general_stream_f32(a, s, mel_rows(e)));
         }
         GruArgs g = gru_args(e);
         g.ke_plain = e->ke_hist;
@@ -2790,11 +2810,11 @@ int pe_update_many_device(pe_engine* e, const int16_t* pcm_dev, int32_t chunk, i
     if (e->prm.mfcc_precision == 0) {
         MfccStreamArgs<double> a = mfcc_args<double>(e, pcm_dev, chunk, call);
         a.n_updates = n_updates; a.ke_hist = e->ke_hist; a.n_frame_rows = rows;
-        PE_HIP(e, launch_mfcc_f64(a, tables<double>(e), e->n_cus, s));
+        PE_HIP(e, launch_mfcc_f64(a, tables<double>(e), e->n_cus, s, mel_rows(e)));
     } else {
         MfccStreamArgs<float> a = mfcc_args<float>(e, pcm_dev, chunk, call);
         a.n_updates = n_updates; a.ke_hist = e->ke_hist; a.n_frame_rows = rows;
-        PE_HIP(e, launch_mfcc_f32(a, tables<float>(e), e->n_cus, s));
+        PE_HIP(e, launch_mfcc_f32(a, tables<float>(e), e->n_cus, s, mel_rows(e)));
     }
     GruArgs g = gru_args(e);
     g.ke_plain = e->ke_hist;
@@ -4053,6 +4073,7 @@ int pe_miner_create(pe_engine* e, const void* audio_host, int32_t sample_format,
     if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
     if (!out) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
     *out = nullptr;
+    if (e && mel_rows(e)) return fail(e, PE_ERR_UNSUPPORTED, "%s: this session has no Vectorizer.mels form (its windows are MFCC rows); create it over an mfccs engine", who);
     if (n_rec < 0) return fail(e, PE_ERR_INVALID, "%s: n_rec=%d", who, n_rec);
     if (n_rec > 0 && !offsets_host) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
     if (sample_format != 0 && sample_format != 1) return fail(e, PE_ERR_INVALID, "%s: sample_format must be 0 (float64) or 1 (float32), got %d", who, sample_format);
@@ -4309,6 +4330,7 @@ int pe_generator_create(pe_engine* e, const float* bg_audio, const int64_t* bg_o
     if (!e) return fail(e, PE_ERR_INVALID, "null engine handed to %s", who);
     if (!out) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
     *out = nullptr;
+    if (e && mel_rows(e)) return fail(e, PE_ERR_UNSUPPORTED, "%s: this session has no Vectorizer.mels form (its windows are MFCC rows); create it over an mfccs engine", who);
     if (chunk_size < 1) return fail(e, PE_ERR_INVALID, "%s: chunk_size must be >= 1, got %d", who, chunk_size);
     int rc;
     if ((rc = generator_check_offsets(e, who, "background", bg_offsets, n_bg))) return rc;
@@ -4671,6 +4693,7 @@ int pe_augmenter_create(pe_engine* e, const float* clip_audio, const int64_t* cl
     const char* who = "pe_augmenter_create";
     if (!out) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
     *out = nullptr;
+    if (e && mel_rows(e)) return fail(e, PE_ERR_UNSUPPORTED, "%s: this session has no Vectorizer.mels form (its windows are MFCC rows); create it over an mfccs engine", who);
     int rc;
     if ((rc = augmenter_check_pool(e, who, "clip", clip_offsets, n_clips))) return rc;
     if ((rc = augmenter_check_pool(e, who, "noise recording", noise_offsets, n_noise))) return rc;

@@ -67,11 +67,13 @@ __host__ __device__ inline size_t general_lds_bytes(int real_size, int n_fft, in
 __device__ __forceinline__ int bit_reverse(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
 
 // The part of a frame behind the power spectrum: P[0 .. n_fft / 2] in LDS, psum = this lane's share of the total power.
-template <class R>
+// MELS (Vectorizer.mels: the row is the log-mel energies themselves, n_mfcc = n_filt <= 32 of them): lane f returns LM[f];
+// neither the total power (coefficient 0 stays filter 0) nor the DCT is compiled.
+template <class R, bool MELS>
 __device__ __forceinline__ void general_frame_tail(const GeneralTables& t, const R* P, R* LM, R* PART, const int lane, R psum, R (&coeff)[1]) {
     using K = RealK<R>;
     group_sync();
-    psum = wave_sum(psum);
+    if constexpr (!MELS) psum = wave_sum(psum);
     auto vlog = [&](R x) -> R {
         // sonopy clips at eps (safe_log); speechpy replaces exact zeros only (zero_handling): 0 < x < eps stays x
         return real_log(t.log_mode == 0 ? (x > K::EPS ? x : K::EPS) : (x == R(0) ? K::EPS : x));
@@ -103,6 +105,12 @@ __device__ __forceinline__ void general_frame_tail(const GeneralTables& t, const
             LM[f] = vlog(acc);
         }
     }
+    if constexpr (MELS) {
+        group_sync();
+        coeff[0] = lane < t.n_mfcc ? LM[lane] : R(0);
+        group_sync();
+        return;
+    }
     if (lane == 0) LM[t.n_filt] = vlog(psum);
     group_sync();
     // DCT-II (ortho): lane c + 32 h adds the filters of half h for coefficient c (transposed table: a row per filter, the
@@ -132,7 +140,7 @@ __device__ __forceinline__ void general_frame_tail(const GeneralTables& t, const
 // zero beyond the frame length) for 0 <= n < M; it is called for all of a lane's points BEFORE any of them is used, so a
 // point() made of plain loads keeps them all in flight.
 // After the call: coefficient c (c < n_mfcc) sits in lane c of `coeff`; LM[f] holds the log-mel energy of filter f.
-template <class R, int BITS, class Point>
+template <class R, int BITS, bool MELS, class Point>
 __device__ __forceinline__ void general_frame_t(const GeneralTables& t, R* S, const int lane, Point point, R (&coeff)[1]) {
     constexpr int M = 1 << BITS, NP = (M + 63) / 64, NB = (M / 2 + 63) / 64, NS = (M / 2 + 1 + 63) / 64;
     constexpr bool OVERLAY = BITS <= 9;              // (general_overlay: n_fft <= 1024)
@@ -277,7 +285,7 @@ __device__ __forceinline__ void general_frame_t(const GeneralTables& t, R* S, co
             if (k != M - k) { P[M - k] = pb; psum += pb; }
         }
     }
-    general_frame_tail<R>(t, P, LM, PART, lane, psum, coeff);
+    general_frame_tail<R, MELS>(t, P, LM, PART, lane, psum, coeff);
 }
 
 // ---- n_fft that is not a power of two: Bluestein -------------------------------------------------------------------------
@@ -288,7 +296,7 @@ __device__ __forceinline__ void general_frame_t(const GeneralTables& t, R* S, co
 //   ->  decimation in TIME with conjugate twiddles (input bit-reversed, output natural) = the inverse transform
 // -- no permutation pass.  |w[k]| = 1, so the power spectrum is |c[k]|^2 / N directly.  sample(n): sample n of the frame as R
 // (already scaled; zero beyond the frame length), 0 <= n < N.
-template <class R, int BITS, class Sample>
+template <class R, int BITS, bool MELS, class Sample>
 __device__ __forceinline__ void general_frame_blue(const GeneralTables& t, R* S, const int lane, Sample sample, R (&coeff)[1]) {
     constexpr int L = 1 << BITS, NB = L / 2 / 64;
     const int N = t.n_fft, bins = N / 2 + 1;
@@ -374,14 +382,14 @@ __device__ __forceinline__ void general_frame_blue(const GeneralTables& t, R* S,
             psum += pk;
         }
     }
-    general_frame_tail<R>(t, P, LM, PART, lane, psum, coeff);
+    general_frame_tail<R, MELS>(t, P, LM, PART, lane, psum, coeff);
 }
 
 // (the transform length is a template parameter of the frame -- unrolled per-lane loops -- and of the kernels around it:
 //  the launchers dispatch on log2(n_fft / 2), kernels.hip)
-template <class R, int BITS, class Point>
+template <class R, int BITS, bool MELS, class Point>
 __device__ __forceinline__ void general_frame(const GeneralTables& t, R* S, const int lane, Point point, R (&coeff)[1]) {
-    general_frame_t<R, BITS>(t, S, lane, point, coeff);
+    general_frame_t<R, BITS, MELS>(t, S, lane, point, coeff);
 }
 
 // ---- streaming: one wave per stream, every frame the update completes ---------------------------------------------------
@@ -410,7 +418,7 @@ struct GeneralStreamArgs {
 // samples and the counters.  Both read the state before the update; only wave 0 writes the state after it.
 // n_updates > 1 (pe_update_many): the frames of the virtual stream carry ++ chunk 0 ++ ... ++ chunk n-1 in ONE launch, the
 // emitted-frame counter after every update recorded for the network launch that follows (round 5; it was one launch per update).
-template <class R, int BITS, bool BLUE = false>
+template <class R, int BITS, bool BLUE = false, bool MELS = false>
 __device__ __forceinline__ void general_stream(const GeneralStreamArgs<R>& a, R* S, const int s, const int par, const int lane, const int n_par = 2) {
     const StreamGeom& geo = a.geo;
     const int C = a.chunk, hop = geo.hop, flen = geo.frame_len, slots = geo.ring_slots;
@@ -448,9 +456,9 @@ __device__ __forceinline__ void general_stream(const GeneralStreamArgs<R>& a, R*
         int lane_k = lane;
         asm volatile("" : "+v"(lane_k));
         if constexpr (BLUE) {
-            general_frame_blue<R, BITS>(a.tab, S, lane_k, [&](int n) -> R { return n < flen ? (R)vsample(vb + n) * RealK<R>::INV_I16 : R(0); }, coeff);
+            general_frame_blue<R, BITS, MELS>(a.tab, S, lane_k, [&](int n) -> R { return n < flen ? (R)vsample(vb + n) * RealK<R>::INV_I16 : R(0); }, coeff);
         } else if (pairs) {
-            general_frame<R, BITS>(a.tab, S, lane_k, [&](int n) -> cplx<R> {
+            general_frame<R, BITS, MELS>(a.tab, S, lane_k, [&](int n) -> cplx<R> {
                 const int m = 2 * n < flen ? 2 * n : 0, v = vb + m;           // (beyond the frame: a valid pair, zeroed below)
                 const int16_t* p = v < q ? car + v : row(v - q);
                 const int w2 = *reinterpret_cast<const int*>(p);
@@ -458,7 +466,7 @@ __device__ __forceinline__ void general_stream(const GeneralStreamArgs<R>& a, R*
                 return cplx<R>{in ? (R)(int)(short)(w2 & 0xffff) * RealK<R>::INV_I16 : R(0), in ? (R)(w2 >> 16) * RealK<R>::INV_I16 : R(0)};
             }, coeff);
         } else {
-            general_frame<R, BITS>(a.tab, S, lane_k, [&](int n) -> cplx<R> {
+            general_frame<R, BITS, MELS>(a.tab, S, lane_k, [&](int n) -> cplx<R> {
                 return cplx<R>{2 * n < flen ? (R)vsample(vb + 2 * n) * RealK<R>::INV_I16 : R(0),
                                2 * n + 1 < flen ? (R)vsample(vb + 2 * n + 1) * RealK<R>::INV_I16 : R(0)};
             }, coeff);
@@ -526,7 +534,7 @@ struct GeneralOfflineArgs {
 
 // one frame of both whole-buffer forms: samples x[0 .. frame_len) (float64, or float32 widened here: exact) -> row `row` of
 // whichever outputs are given.  The arithmetic of a frame is this one function, whichever entry point asked for it.
-template <class R, int BITS, bool BLUE, class X>
+template <class R, int BITS, bool BLUE, bool MELS, class X>
 __device__ __forceinline__ void general_offline_frame(const StreamGeom& geo, const GeneralTables& tab, R* S, const int lane, const X* x, const long long row,
                                                       double* out, float* out_rows, double* out_mels, const int row_floats) {
     const int M = BLUE ? (1 << BITS) : (tab.n_fft >> 1);          // (BLUE: reals before LM = 2 L)
@@ -534,8 +542,8 @@ __device__ __forceinline__ void general_offline_frame(const StreamGeom& geo, con
     const int flen = geo.frame_len;
     int lane_k = lane;                                  // (per-frame recomputation of the lane invariants: general_stream)
     asm volatile("" : "+v"(lane_k));
-    if constexpr (BLUE) general_frame_blue<R, BITS>(tab, S, lane_k, [&](int n) -> R { return n < flen ? (R)(double)x[n] : R(0); }, coeff);
-    else general_frame<R, BITS>(tab, S, lane_k, [&](int n) -> cplx<R> {
+    if constexpr (BLUE) general_frame_blue<R, BITS, MELS>(tab, S, lane_k, [&](int n) -> R { return n < flen ? (R)(double)x[n] : R(0); }, coeff);
+    else general_frame<R, BITS, MELS>(tab, S, lane_k, [&](int n) -> cplx<R> {
         const int m0 = 2 * n, m1 = 2 * n + 1;                             // (clamped indices: plain loads, selected afterwards)
         const double x0 = (double)x[m0 < flen ? m0 : 0], x1 = (double)x[m1 < flen ? m1 : 0];
         return cplx<R>{m0 < flen ? (R)x0 : R(0), m1 < flen ? (R)x1 : R(0)};
@@ -549,10 +557,10 @@ __device__ __forceinline__ void general_offline_frame(const StreamGeom& geo, con
     group_sync();
 }
 
-template <class R, int BITS, bool BLUE = false>
+template <class R, int BITS, bool BLUE = false, bool MELS = false>
 __device__ __forceinline__ void general_offline(const GeneralOfflineArgs<R>& a, R* S, const long long first, const long long stride, const int lane) {
     for (long long fr = first; fr < a.n_frames; fr += stride)
-        general_offline_frame<R, BITS, BLUE>(a.geo, a.tab, S, lane, a.audio + fr * a.geo.hop, fr, a.out, a.out_rows, a.out_mels, a.row_floats);
+        general_offline_frame<R, BITS, BLUE, MELS>(a.geo, a.tab, S, lane, a.audio + fr * a.geo.hop, fr, a.out, a.out_rows, a.out_mels, a.row_floats);
 }
 
 // ---- the same, for many clips of different lengths (pe_vectorize_clips / pe_score_clips; pe_common.h: ClipTable) -------
@@ -569,7 +577,7 @@ struct GeneralClipArgs {
 
 // one wave per workgroup: wave `first` of `stride` takes the frame tasks first, first + stride, ... and the pad rows of the
 // clips first, first + stride, ...
-template <class R, int BITS, bool BLUE = false>
+template <class R, int BITS, bool BLUE = false, bool MELS = false>
 __device__ __forceinline__ void general_clips(const GeneralClipArgs<R>& a, R* S, const int first, const int stride, const int lane) {
     const StreamGeom& geo = a.geo;
     const int T = geo.n_features;
@@ -581,8 +589,8 @@ __device__ __forceinline__ void general_clips(const GeneralClipArgs<R>& a, R* S,
         c = clip_of_task(a.clips, g, c);
         const ClipTask task = clip_task(a.clips, g, c, geo.hop, T);
         // (the sample format is chosen once per frame, outside the loads)
-        if (a.clips.audio_f32) general_offline_frame<R, BITS, BLUE>(geo, a.tab, S, lane, static_cast<const float*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels, a.row_floats);
-        else general_offline_frame<R, BITS, BLUE>(geo, a.tab, S, lane, static_cast<const double*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels, a.row_floats);
+        if (a.clips.audio_f32) general_offline_frame<R, BITS, BLUE, MELS>(geo, a.tab, S, lane, static_cast<const float*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels, a.row_floats);
+        else general_offline_frame<R, BITS, BLUE, MELS>(geo, a.tab, S, lane, static_cast<const double*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels, a.row_floats);
     }
 }
 
@@ -595,25 +603,25 @@ struct GeneralRecArgs {
     float* out_rows;            // [rows of the pass][row_floats] float32 rows
     int row_floats;
 };
-template <class R, int BITS, bool BLUE = false>
+template <class R, int BITS, bool BLUE = false, bool MELS = false>
 __device__ __forceinline__ void general_recs(const GeneralRecArgs<R>& a, R* S, const int first, const int stride, const int lane) {
     int r = 0;
     for (uint32_t g = (uint32_t)first; g < a.recs.n_tasks; g += (uint32_t)stride) {
         r = slot_of_task(a.recs.prefix, a.recs.n_rec, g, r);
         const ClipTask task = rec_task(a.recs, g, r, a.geo.hop);
-        if (a.recs.audio_f32) general_offline_frame<R, BITS, BLUE>(a.geo, a.tab, S, lane, static_cast<const float*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr, a.row_floats);
-        else general_offline_frame<R, BITS, BLUE>(a.geo, a.tab, S, lane, static_cast<const double*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr, a.row_floats);
+        if (a.recs.audio_f32) general_offline_frame<R, BITS, BLUE, MELS>(a.geo, a.tab, S, lane, static_cast<const float*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr, a.row_floats);
+        else general_offline_frame<R, BITS, BLUE, MELS>(a.geo, a.tab, S, lane, static_cast<const double*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr, a.row_floats);
     }
 }
 
-// launchers (kernels.hip)
-hipError_t launch_general_recs_f64(const GeneralRecArgs<double>& a, int n_cus, hipStream_t s);
-hipError_t launch_general_recs_f32(const GeneralRecArgs<float>& a, int n_cus, hipStream_t s);
-hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s);
-hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s);
-hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s);
-hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s);
-hipError_t launch_general_offline_f64(const GeneralOfflineArgs<double>& a, int n_cus, hipStream_t s);
-hipError_t launch_general_offline_f32(const GeneralOfflineArgs<float>& a, int n_cus, hipStream_t s);
+// launchers (kernels.hip); mels: the MELS instantiation (rows = log-mel energies, the engine's n_mfcc = n_filt)
+hipError_t launch_general_recs_f64(const GeneralRecArgs<double>& a, int n_cus, hipStream_t s, bool mels = false);
+hipError_t launch_general_recs_f32(const GeneralRecArgs<float>& a, int n_cus, hipStream_t s, bool mels = false);
+hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s, bool mels = false);
+hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s, bool mels = false);
+hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s, bool mels = false);
+hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s, bool mels = false);
+hipError_t launch_general_offline_f64(const GeneralOfflineArgs<double>& a, int n_cus, hipStream_t s, bool mels = false);
+hipError_t launch_general_offline_f32(const GeneralOfflineArgs<float>& a, int n_cus, hipStream_t s, bool mels = false);
 
 }  // namespace pe

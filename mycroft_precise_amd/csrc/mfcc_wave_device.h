@@ -224,6 +224,8 @@ __device__ __forceinline__ void wave_scratch_init(R* S, int lane) {
 // Returns coefficient c in the four lanes 4c..4c+3 (c < n_mfcc).  S: this wave's scratch; after the call
 // S[kLogMelOff + f] holds the log-mel energy of filter f.
 // SH: compile-time bounds of the three table-driven loops (the tables are zero-padded up to them on the host)
+// MELS (Vectorizer.mels: the row is the log-mel energies themselves): lane f returns LM[f] (f < n_filt), and the DCT
+// stage -- its table reads, products and quad reduction -- is not compiled; coefficient 0 stays filter 0
 struct ShapeStock { static constexpr int MEL = 10, DCT = 5, NP = 8, WPE = 4; };      // 20 filters (sonopy 9 / 5 / 8, speechpy 4 / 5 / 7)
 struct ShapeAny { static constexpr int MEL = 16, DCT = 16, NP = 16, WPE = 3; };       // (its longer table loops want more than 128 registers)
 
@@ -241,7 +243,7 @@ __device__ __forceinline__ LaneRuns lane_runs(const pe_wave::Tab<R>& t, int lane
     return r;
 }
 
-template <class R, class SH>
+template <class R, class SH, bool MELS = false>
 __device__ __forceinline__ R mfcc_wave_frame(const pe_wave::Tab<R>& t, const pe_wave::LaneConsts<R>& lc, const LaneRuns& lr, R* S, const int lane,
                                              const int n_filt, const int n_mfcc, pe_wave::Regs<R>& v, const R pscale, const int log_mode) {
     using K = RealK<R>;
@@ -351,6 +353,11 @@ __device__ __forceinline__ R mfcc_wave_frame(const pe_wave::Tab<R>& t, const pe_
         }
     }
     group_sync();
+    if constexpr (MELS) {
+        const R m = lds_read(&LM[lane < n_filt ? lane : 0]);
+        group_sync();                       // the scratch may be rewritten by the next frame
+        return lane < n_filt ? m : R(0);
+    }
     // DCT-II (ortho): lane 4c + q adds its dct_len terms of coefficient c; quad reduction; c0 := log total power
     R part = R(0);
     {
@@ -428,7 +435,7 @@ __device__ __forceinline__ int wave_simd_id() { return (int)(__builtin_amdgcn_s_
 // SINGLE: the call is one update (n_updates == 1: every fused launch) and, NOPROJ, stores no projection rows: both known at
 // compile time there, which removes the several-updates arithmetic (chunk index of a frame, a frame's tail in the next
 // update's row) and the projection block from the frame loop.
-template <class R, class SH, bool SINGLE = false, bool NOPROJ = false>
+template <class R, class SH, bool SINGLE = false, bool NOPROJ = false, bool MELS = false>
 __device__ __forceinline__ void mfcc_frame_tasks(const MfccStreamArgs<R>& a, const WaveTables<R>& wt, unsigned char* smem,
                                                  const int first_task, const int task_stride, const bool by_simd = false) {
     using K = RealK<R>;
@@ -646,11 +653,16 @@ __device__ __forceinline__ void mfcc_frame_tasks(const MfccStreamArgs<R>& a, con
             FrameTask<R> nxt;
             const bool have_next = next_frame(nxt);
             if (have_next) pcm = request_pcm(nxt);                      // lands while the current frame is transformed
-            const R coeff = mfcc_wave_frame<R, SH>(tab, lc, lr, S, lane, geo.n_filt, geo.n_mfcc, v, K::PSCALE_I16, geo.log_mode);
+            const R coeff = mfcc_wave_frame<R, SH, MELS>(tab, lc, lr, S, lane, geo.n_filt, geo.n_mfcc, v, K::PSCALE_I16, geo.log_mode);
             // coefficient c sits in lanes 4c .. 4c+3: lane c fetches it, and the first 16 lanes store the row as ONE
             // contiguous 64-byte (bf16: 32-byte) write -- 13 coefficients + zero padding, as the clear kernel left it
-            const float mine = (lane >> 2) < geo.n_mfcc ? (float)coeff : 0.0f;
-            const float xf = __shfl(mine, (lane & 15) * 4, 64);
+            // (MELS: filter f already sits in lane f; the row is n_mfcc = n_filt <= 16 wide on this kernel)
+            float xf;
+            if constexpr (MELS) xf = lane < geo.n_mfcc ? (float)coeff : 0.0f;
+            else {
+                const float mine = (lane >> 2) < geo.n_mfcc ? (float)coeff : 0.0f;
+                xf = __shfl(mine, (lane & 15) * 4, 64);
+            }
             xf_prev = xf; row_prev = cur.ring_row;
             if (!NOPROJ && cur.proj_row) {
                 // input projection of this frame, once, for every window it will appear in: row[o] = b[o] + sum_c x[c] W[c][o]
@@ -680,7 +692,7 @@ __device__ __forceinline__ void mfcc_frame_tasks(const MfccStreamArgs<R>& a, con
 
 // one frame of both whole-buffer forms: samples x[0 .. frame_len) (float64, or float32 widened here: exact) -> row `row` of
 // whichever outputs are given.  The arithmetic of a frame is this one function, whichever entry point asked for it.
-template <class R, class SH, class X>
+template <class R, class SH, bool MELS, class X>
 __device__ __forceinline__ void mfcc_offline_frame(const StreamGeom& geo, const pe_wave::Tab<R>& tab, const pe_wave::LaneConsts<R>& lc, const LaneRuns& lr,
                                                    R* S, const int lane, const X* x, const long long row, double* out, float* out_rows, double* out_mels) {
     const int flen = geo.frame_len;
@@ -691,11 +703,16 @@ __device__ __forceinline__ void mfcc_offline_frame(const StreamGeom& geo, const 
         v.re[a4] = n < flen ? (R)(double)x[n] : R(0);
         v.im[a4] = n + 1 < flen ? (R)(double)x[n + 1] : R(0);
     }
-    const R coeff = mfcc_wave_frame<R, SH>(tab, lc, lr, S, lane, geo.n_filt, geo.n_mfcc, v, RealK<R>::INV_FFT, geo.log_mode);
-    const int c = lane >> 2;
-    if ((lane & 3) == 0) {
-        if (out && c < geo.n_mfcc) out[row * geo.n_mfcc + c] = (double)coeff;
-        if (out_rows) out_rows[row * kRowFloats + c] = c < geo.n_mfcc ? (float)coeff : 0.0f;
+    const R coeff = mfcc_wave_frame<R, SH, MELS>(tab, lc, lr, S, lane, geo.n_filt, geo.n_mfcc, v, RealK<R>::INV_FFT, geo.log_mode);
+    if constexpr (MELS) {       // value f in lane f, n_mfcc = n_filt <= 16 of them
+        if (out && lane < geo.n_mfcc) out[row * geo.n_mfcc + lane] = (double)coeff;
+        if (out_rows && lane < kRowFloats) out_rows[row * kRowFloats + lane] = lane < geo.n_mfcc ? (float)coeff : 0.0f;
+    } else {
+        const int c = lane >> 2;
+        if ((lane & 3) == 0) {
+            if (out && c < geo.n_mfcc) out[row * geo.n_mfcc + c] = (double)coeff;
+            if (out_rows) out_rows[row * kRowFloats + c] = c < geo.n_mfcc ? (float)coeff : 0.0f;
+        }
     }
     if (out_mels)             // the log-mel energies are still in this wave's scratch
         for (int f = lane; f < geo.n_filt; f += 64) out_mels[row * geo.n_filt + f] = (double)S[pe_wave::kLogMelOff + f];
@@ -703,7 +720,7 @@ __device__ __forceinline__ void mfcc_offline_frame(const StreamGeom& geo, const 
 }
 
 // ---- stateless whole-buffer form (vectorize_raw): one frame per wave, float64 samples in -------------------------
-template <class R, class SH>
+template <class R, class SH, bool MELS = false>
 __device__ __forceinline__ void mfcc_offline_frames(const MfccOfflineArgs<R>& a, const WaveTables<R>& wt, unsigned char* smem) {
     const StreamGeom& geo = a.geo;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
@@ -719,13 +736,13 @@ __device__ __forceinline__ void mfcc_offline_frames(const MfccOfflineArgs<R>& a,
     const LaneRuns lr = lane_runs(tab, lane, geo.n_filt);
     wave_scratch_init(S, lane);
     for (long long fr = (long long)blockIdx.x * waves + wave; fr < a.n_frames; fr += (long long)gridDim.x * waves)
-        mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, a.audio + fr * geo.hop, fr, a.out, a.out_rows, a.out_mels);
+        mfcc_offline_frame<R, SH, MELS>(geo, tab, lc, lr, S, lane, a.audio + fr * geo.hop, fr, a.out, a.out_rows, a.out_mels);
 }
 
 // ---- the same, for many clips of different lengths (pe_vectorize_clips / pe_score_clips) --------------------------
 // One frame per wave as above, the frame arithmetic the same call; what differs is where a task's samples come from and
 // where its row goes (pe_common.h: ClipTable).  Task, clip and addresses are wave-uniform.
-template <class R, class SH>
+template <class R, class SH, bool MELS = false>
 __device__ __forceinline__ void mfcc_clip_frames(const MfccClipArgs<R>& a, const WaveTables<R>& wt, unsigned char* smem) {
     const StreamGeom& geo = a.geo;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
@@ -750,14 +767,14 @@ __device__ __forceinline__ void mfcc_clip_frames(const MfccClipArgs<R>& a, const
         c = clip_of_task(a.clips, g, c);
         const ClipTask task = clip_task(a.clips, g, c, geo.hop, T);
         // (the sample format is chosen once per frame, outside the loads; the loads themselves are the offline form's)
-        if (a.clips.audio_f32) mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const float*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels);
-        else mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const double*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels);
+        if (a.clips.audio_f32) mfcc_offline_frame<R, SH, MELS>(geo, tab, lc, lr, S, lane, static_cast<const float*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels);
+        else mfcc_offline_frame<R, SH, MELS>(geo, tab, lc, lr, S, lane, static_cast<const double*>(a.clips.audio) + task.x, task.row, a.out, a.out_rows, a.out_mels);
     }
 }
 
 // ---- the same, for many whole recordings (pe_evaluate_clips / pe_simulate_clips; pe_common.h: RecTable) ------------
 // No crop and no pad rows: a task is frame j of its recording, its row is the recording's row base + j.
-template <class R, class SH>
+template <class R, class SH, bool MELS = false>
 __device__ __forceinline__ void mfcc_rec_frames(const MfccRecArgs<R>& a, const WaveTables<R>& wt, unsigned char* smem) {
     const StreamGeom& geo = a.geo;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
@@ -777,8 +794,8 @@ __device__ __forceinline__ void mfcc_rec_frames(const MfccRecArgs<R>& a, const W
     for (uint32_t g = (uint32_t)wave_id; g < a.recs.n_tasks; g += (uint32_t)n_waves) {
         r = slot_of_task(a.recs.prefix, a.recs.n_rec, g, r);
         const ClipTask task = rec_task(a.recs, g, r, geo.hop);
-        if (a.recs.audio_f32) mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const float*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr);
-        else mfcc_offline_frame<R, SH>(geo, tab, lc, lr, S, lane, static_cast<const double*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr);
+        if (a.recs.audio_f32) mfcc_offline_frame<R, SH, MELS>(geo, tab, lc, lr, S, lane, static_cast<const float*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr);
+        else mfcc_offline_frame<R, SH, MELS>(geo, tab, lc, lr, S, lane, static_cast<const double*>(a.recs.audio) + task.x, task.row, nullptr, a.out_rows, nullptr);
     }
 }
 

@@ -40,13 +40,18 @@ class Runner(metaclass=ABCMeta):
 
 
 def _require_streamable(params):
-    """The streaming kernels carry MFCC rows (<= 32 coefficients per frame) of the sonopy (``mfccs``) or the
-    legacy speechpy (``speechpy_mfccs``) front end; mel rows (n_filt = 20 wide, Vectorizer.mels) exist in the
-    offline form only -- the reference's own Listener cannot stream them either (network_runner.py:104,144)."""
-    if params.vectorizer not in (Vectorizer.mfccs, Vectorizer.speechpy_mfccs):
-        raise NotImplementedError('Vectorizer.%s cannot be streamed on the device: Vectorizer.mfccs and '
-                                  'Vectorizer.speechpy_mfccs have streaming kernels (mels: vectorization.vectorize '
-                                  '/ vectorize_raw)' % {Vectorizer.mels: 'mels'}.get(params.vectorizer, str(params.vectorizer)))
+    """The streaming kernels carry rows of up to 32 values per frame: MFCC rows of the sonopy (``mfccs``) or the legacy
+    speechpy (``speechpy_mfccs``) front end, or the ``n_filt`` log-mel energies of ``mels`` (window ``pr.feature_size`` wide,
+    params.py:99-109).  The limits of mel rows -- and a network whose first layer does not take them -- are refused by
+    ``HipEngine`` before the library is touched."""
+    if params.vectorizer not in (Vectorizer.mels, Vectorizer.mfccs, Vectorizer.speechpy_mfccs):
+        raise NotImplementedError('vectorizer %r cannot be streamed on the device: Vectorizer.mels, Vectorizer.mfccs and '
+                                  'Vectorizer.speechpy_mfccs have streaming kernels' % (params.vectorizer,))
+
+
+def _row_width(params):
+    """values per frame in the feature window: ``feature_size`` without the deltas"""
+    return params.n_filt if params.vectorizer == Vectorizer.mels else params.n_mfcc
 
 
 def _engine_params(use_delta=None):
@@ -179,7 +184,7 @@ class Listener:
             engine = runner.engine
         else:       # a foreign Runner plugged into the reference's seam: the GPU still does the MFCC
             if self._front is None:
-                self._front = HipEngine(_engine_params(use_delta=False), _placeholder_weights(self.pr.n_mfcc))
+                self._front = HipEngine(_engine_params(use_delta=False), _placeholder_weights(_row_width(self.pr)))
             engine = self._front
         old = self._engine
         self._fused, self._engine = fused, engine
@@ -201,12 +206,13 @@ class Listener:
     def clear(self):
         self.window_audio = np.array([])
         self._engine.clear()
-        self._mfccs = np.zeros((self.pr.n_features, self.pr.n_mfcc))
+        self._mfccs = np.zeros((self.pr.n_features, _row_width(self.pr)))
         self._float_mode = False
 
     @property
     def mfccs(self) -> np.ndarray:
-        """The [n_features, n_mfcc] feature window (float64 view of the device's float32 ring)."""
+        """The [n_features, n_mfcc] feature window (float64 view of the device's float32 ring); under Vectorizer.mels it is
+        [n_features, n_filt] wide."""
         if self._mfccs is None:
             self._mfccs = self._engine.get_vectors()[0].astype(np.float64)
         return self._mfccs
@@ -216,7 +222,7 @@ class Listener:
         """``listener.mfccs = window`` works on the reference's plain attribute (network_runner.py:104) and leaves
         ``window_audio`` alone: here the window is installed on the device too (``pe_set_vectors``) and the leftover
         samples are handed back to it, exactly as when the runner is replaced after construction."""
-        window = np.asarray(value, dtype=np.float64).reshape(self.pr.n_features, self.pr.n_mfcc)
+        window = np.asarray(value, dtype=np.float64).reshape(self.pr.n_features, _row_width(self.pr))
         self._mfccs = window.copy()
         if self._float_mode:
             return                                     # float samples: the window lives on the host (see _update_vectors_float)
@@ -364,7 +370,7 @@ class BatchedListener:
         self.engine.clear(mask)
 
     def update_vectors(self, chunks) -> np.ndarray:
-        """-> [n_streams, n_features, n_mfcc] float32"""
+        """-> [n_streams, n_features, n_mfcc] float32 (Vectorizer.mels: n_filt wide)"""
         return self.engine.update_vectors(self._pcm(chunks))
 
     def update_raw(self, chunks, streams=None) -> np.ndarray:
