@@ -356,7 +356,7 @@ class HipEngine:
         from .params import Vectorizer
         self._h = C.c_void_p()
         self._async_keep = []
-        self._miners = weakref.WeakSet()   # HipMiner / HipGenerator / HipAugmenter sessions over this engine: closed before the engine is destroyed
+        self._sessions = weakref.WeakSet()   # HipMiner / HipGenerator / HipAugmenter sessions over this engine: closed before the engine is destroyed
         self._views = 0                # host_array() buffers still referenced by numpy arrays (their memory dies with the engine)
         self._close_pending = False
         self.n_streams = int(n_streams)
@@ -951,8 +951,8 @@ class HipEngine:
                 except Exception:
                     pass
                 return
-            for miner in list(getattr(self, '_miners', ())):
-                miner.close()
+            for session in list(getattr(self, '_sessions', ())):
+                session.close()
             self._lib.pe_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1302,33 +1302,76 @@ class HipTrainer:
             pass
 
 
-class HipMiner:
+class _Session:
+    """
+    What the device sessions over one ``HipEngine`` share: the handle and its release, the engine's set of open sessions, and
+    the checks of ids and targets.  A subclass names its destroy function and the word of its "closed" message.
+    """
+    _destroy = None     # 'pe_miner_destroy'
+    _doing = None       # 'mining'
+
+    def _open(self, engine):
+        self._lib = load()
+        self._h = C.c_void_p()
+        self.engine = engine
+
+    def _opened(self):
+        """after the create call: the engine closes every session it still has before it is destroyed itself"""
+        if self.engine is not None:
+            self.engine._sessions.add(self)
+
+    @staticmethod
+    def _ids(ids, n, word):
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            raise ValueError('%s ids must be in 0..%d' % (word, n - 1))
+        return ids.astype(np.int32)
+
+    @staticmethod
+    def _targets(targets, ids):
+        targets = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
+        if targets.size != ids.size:
+            raise ValueError('%d targets for %d ids' % (targets.size, ids.size))
+        return targets
+
+    def _handle(self):
+        if not self._h.value:
+            raise ValueError('the %s session is closed (close(), or its engine was closed)' % self._doing)
+        return self._h
+
+    def close(self):
+        """the session's destroy call; the engine calls it for every session it still has when it is closed itself"""
+        if getattr(self, '_h', None) and self._h.value:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipMiner(_Session):
     """
     One C-ABI mining session (pe_miner) over one ``HipEngine``: the recordings resident on the device, every frame computed once;
     ``mining.Miner`` is the reference-shaped class.  Chunks carry GLOBAL ids: recording r's chunk i is ``chunk_offsets[r] + i``.
     The session keeps its engine alive; close it before the engine.
     """
+    _destroy, _doing = 'pe_miner_destroy', 'mining'
 
     def __init__(self, engine: HipEngine, audios, chunk_size: int, buffer_samples: int, carry_audio: bool = True):
-        self._lib = load()
-        self._h = C.c_void_p()
-        self.engine = engine
+        self._open(engine)
         audio, offsets, fmt = HipEngine._clips(audios)
         self.n_recordings = offsets.size - 1
         self.chunk_size, self.buffer_samples = int(chunk_size), int(buffer_samples)
         engine._check(self._lib.pe_miner_create(engine._h, audio.ctypes.data if audio.size else None, fmt, offsets.ctypes.data,
                                                 self.n_recordings, self.chunk_size, self.buffer_samples, int(bool(carry_audio)),
                                                 C.byref(self._h)))
-        engine._miners.add(self)
+        self._opened()
         self.chunk_offsets = np.zeros(self.n_recordings + 1, dtype=np.int64)
         engine._check(self._lib.pe_miner_layout(self._h, self.chunk_offsets.ctypes.data))
         self.n_chunks = int(self.chunk_offsets[-1])
-
-    def _hits(self, hits):
-        hits = np.ascontiguousarray(hits, dtype=np.int64).reshape(-1)
-        if hits.size and (hits.min() < 0 or hits.max() >= self.n_chunks):
-            raise ValueError('chunk ids must be in 0..%d' % (self.n_chunks - 1))
-        return hits.astype(np.int32)
 
     def scan(self, first=0, threshold=0.5, capacity=None, return_scores=False, model=0):
         """-> (hits int32 [<= capacity] ascending global ids, n_above, scores float32 [n_chunks - first] or None)"""
@@ -1344,47 +1387,29 @@ class HipMiner:
         return hits[:n_hits.value], int(n_above.value), scores
 
     def vectorize(self, hits) -> np.ndarray:
-        hits = self._hits(hits)
+        hits = self._ids(hits, self.n_chunks, 'chunk')
         out = np.empty((hits.size, self.engine.n_features, self.engine.n_mfcc), dtype=np.float64)
         if hits.size:
             self.engine._check(self._lib.pe_miner_vectorize(self._handle(), hits.ctypes.data, hits.size, out.ctypes.data))
         return out
 
     def append(self, trainer: HipTrainer, hits, validation=False, target=0.0):
-        hits = self._hits(hits)
+        hits = self._ids(hits, self.n_chunks, 'chunk')
         if hits.size:
             self.engine._check(self._lib.pe_miner_append(self._handle(), trainer._h, HipTrainer._source(validation), hits.ctypes.data,
                                                          hits.size, float(target)))
 
-    def _handle(self):
-        if not self._h.value:
-            raise ValueError('the mining session is closed (close(), or its engine was closed)')
-        return self._h
 
-    def close(self):
-        """pe_miner_destroy; the engine calls it for every session it still has when it is closed itself"""
-        if getattr(self, '_h', None) and self._h.value:
-            self._lib.pe_miner_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipGenerator:
+class HipGenerator(_Session):
     """
     One C-ABI generating session (pe_generator) over one ``HipEngine``: the background and clip pools resident on the device, one
     plan at a time mixed and vectorized there; ``generated.Generator`` is the reference-shaped class and the planner.  Chunks
     carry GLOBAL ids over the files of the resident plan.  The session keeps its engine alive; close it before the engine.
     """
+    _destroy, _doing = 'pe_generator_destroy', 'generating'
 
     def __init__(self, engine: HipEngine, backgrounds, clips, chunk_size: int):
-        self._lib = load()
-        self._h = C.c_void_p()
-        self.engine = engine
+        self._open(engine)
         self.chunk_size = int(chunk_size)
         bg, bg_off = self._pool(backgrounds)
         cl, cl_off = self._pool(clips)
@@ -1392,7 +1417,7 @@ class HipGenerator:
         engine._check(self._lib.pe_generator_create(engine._h, bg.ctypes.data if bg.size else None, bg_off.ctypes.data, bg_off.size - 1,
                                                     cl.ctypes.data if cl.size else None, cl_off.ctypes.data, cl_off.size - 1,
                                                     self.chunk_size, C.byref(self._h)))
-        engine._miners.add(self)
+        self._opened()
         self.chunk_offsets = np.zeros(1, dtype=np.int64)
 
     @staticmethod
@@ -1429,58 +1454,32 @@ class HipGenerator:
         self.engine._check(self._lib.pe_generator_audio(self._handle(), file, int(first), n, out.ctypes.data if out.size else None))
         return out
 
-    def _ids(self, ids):
-        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
-        if ids.size and (ids.min() < 0 or ids.max() >= self.n_chunks):
-            raise ValueError('chunk ids must be in 0..%d' % (self.n_chunks - 1))
-        return ids.astype(np.int32)
-
     def vectorize(self, ids) -> np.ndarray:
-        ids = self._ids(ids)
+        ids = self._ids(ids, self.n_chunks, 'chunk')
         out = np.empty((ids.size, self.engine.n_features, self.engine.feature_size), dtype=np.float32)
         if ids.size:
             self.engine._check(self._lib.pe_generator_vectorize(self._handle(), ids.ctypes.data, ids.size, out.ctypes.data))
         return out
 
     def append(self, trainer: HipTrainer, ids, targets, validation=False):
-        ids = self._ids(ids)
-        targets = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
-        if targets.size != ids.size:
-            raise ValueError('%d targets for %d ids' % (targets.size, ids.size))
+        ids = self._ids(ids, self.n_chunks, 'chunk')
+        targets = self._targets(targets, ids)
         if ids.size:
             self.engine._check(self._lib.pe_generator_append(self._handle(), trainer._h, HipTrainer._source(validation), ids.ctypes.data,
                                                              targets.ctypes.data, ids.size))
 
-    def _handle(self):
-        if not self._h.value:
-            raise ValueError('the generating session is closed (close(), or its engine was closed)')
-        return self._h
 
-    def close(self):
-        """pe_generator_destroy; the engine calls it for every session it still has when it is closed itself"""
-        if getattr(self, '_h', None) and self._h.value:
-            self._lib.pe_generator_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipAugmenter:
+class HipAugmenter(_Session):
     """
     One C-ABI augmenting session (pe_augmenter) over one ``HipEngine``: the clip and noise pools resident on the device, one plan
     at a time mixed and vectorized there; ``augment.NoiseAugmenter`` is the reference-shaped class and the planner.  The session
     keeps its engine alive; close it before the engine.  ``engine=None`` makes a session without a device that only checks the
     plans handed to ``set_plan``.
     """
+    _destroy, _doing = 'pe_augmenter_destroy', 'augmenting'
 
     def __init__(self, engine, clips, noises):
-        self._lib = load()
-        self._h = C.c_void_p()
-        self.engine = engine
+        self._open(engine)
         cl, cl_off = HipGenerator._pool(clips)
         no, no_off = HipGenerator._pool(noises)
         self.clip_lengths = np.diff(cl_off)
@@ -1489,8 +1488,7 @@ class HipAugmenter:
         self._check(self._lib.pe_augmenter_create(engine._h if engine is not None else None, cl.ctypes.data if cl.size else None,
                                                   cl_off.ctypes.data, cl_off.size - 1, no.ctypes.data if no.size else None,
                                                   no_off.ctypes.data, no_off.size - 1, C.byref(self._h)))
-        if engine is not None:
-            engine._miners.add(self)
+        self._opened()
 
     def _check(self, rc):
         if self.engine is not None:
@@ -1536,42 +1534,19 @@ class HipAugmenter:
         self._check(self._lib.pe_augmenter_audio(self._handle(), copy, None, out.ctypes.data))
         return out
 
-    def _ids(self, ids):
-        ids = np.arange(self.n_copies) if ids is None else ids
-        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
-        if ids.size and (ids.min() < 0 or ids.max() >= self.n_copies):
-            raise ValueError('copy ids must be in 0..%d' % (self.n_copies - 1))
-        return ids.astype(np.int32)
+    def _copies(self, ids):
+        return self._ids(np.arange(self.n_copies) if ids is None else ids, self.n_copies, 'copy')
 
     def vectorize(self, ids=None, max_samples: int = 0) -> np.ndarray:
-        ids = self._ids(ids)
+        ids = self._copies(ids)
         out = np.empty((ids.size, self.engine.n_features, self.engine.feature_size), dtype=np.float32)
         if ids.size:
             self._check(self._lib.pe_augmenter_vectorize(self._handle(), ids.ctypes.data, ids.size, int(max_samples), out.ctypes.data))
         return out
 
     def append(self, trainer: HipTrainer, ids, targets, validation=False, max_samples: int = 0):
-        ids = self._ids(ids)
-        targets = np.ascontiguousarray(targets, dtype=np.float32).reshape(-1)
-        if targets.size != ids.size:
-            raise ValueError('%d targets for %d ids' % (targets.size, ids.size))
+        ids = self._copies(ids)
+        targets = self._targets(targets, ids)
         if ids.size:
             self._check(self._lib.pe_augmenter_append(self._handle(), trainer._h, HipTrainer._source(validation), ids.ctypes.data,
                                                       targets.ctypes.data, ids.size, int(max_samples)))
-
-    def _handle(self):
-        if not self._h.value:
-            raise ValueError('the augmenting session is closed (close(), or its engine was closed)')
-        return self._h
-
-    def close(self):
-        """pe_augmenter_destroy; the engine calls it for every session it still has when it is closed itself"""
-        if getattr(self, '_h', None) and self._h.value:
-            self._lib.pe_augmenter_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

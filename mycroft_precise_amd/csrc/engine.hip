@@ -802,6 +802,30 @@ int64_t frames_of_buffer(const pe_params& p, int64_t n) {
 
 // Vectorizer.mels: the front-end launchers run their MELS instantiation (rows = log-mel energies; prm.n_mfcc == prm.n_filt)
 bool mel_rows(const pe_engine* e) { return e->prm.vectorizer == 1; }
+// floats of one row of a network input window [T][..] (pe_predict, the trainer, mine_gather): with use_delta x_t, x_t - x_(t-1)
+int window_floats(const pe_engine* e) { return e->prm.use_delta ? 2 * e->n_in : e->n_in; }
+
+// A pass's task table into one buffer, grown as needed: desc[n], then the uint32 prefix [n + 1] of their tasks.  Fills `t`
+// (ClipTable / RecTable) over it; n_tasks is the prefix's last entry.  rc: what ensure said; returns what the two copies said.
+template <class Desc, class Table>
+hipError_t upload_task_table(pe_engine* e, DeviceBuf& b, const std::vector<Desc>& desc, const std::vector<uint32_t>& prefix, const void* audio,
+                             int audio_f32, Table& t, int& rc) {
+    const size_t db = desc.size() * sizeof(Desc), pb = prefix.size() * sizeof(uint32_t);
+    if ((rc = ensure(e, b, db + pb))) return hipSuccess;
+    char* const p = static_cast<char*>(b.p);
+    t = Table{reinterpret_cast<const Desc*>(p), reinterpret_cast<const uint32_t*>(p + db), (int)desc.size(), prefix.back(), audio, audio_f32};
+    const hipError_t err = hipMemcpy(p, desc.data(), db, hipMemcpyHostToDevice);
+    return err != hipSuccess ? err : hipMemcpy(p + db, prefix.data(), pb, hipMemcpyHostToDevice);
+}
+// vectorize() of a clip of `len` samples that ends at sample `end` of a pass's audio: audio[-max_samples:] (max_samples 0: all
+// of it), then feats[-n_features:].  tasks: the kept frames of the pass so far -- the clip's prefix entry -- plus this clip's.
+ClipDesc clip_desc(const pe_params& prm, int T, int64_t end, int64_t len, int64_t max_samples, uint32_t& tasks) {
+    const int64_t cut = max_samples > 0 && len > max_samples ? max_samples : len;
+    const int64_t frames = frames_of_buffer(prm, cut);
+    const int64_t kept = frames < T ? frames : T;
+    tasks += (uint32_t)kept;
+    return ClipDesc{end - cut, (int)(frames - kept), (int)kept, (int)(T - kept), 0};
+}
 
 StreamGeom geom(const pe_engine* e) {
     StreamGeom g;
@@ -1953,7 +1977,7 @@ int pe_predict(pe_engine* e, const float* feats_host, int32_t n, float* out_host
     if (n == 0) return PE_OK;
     PE_HIP(e, hipSetDevice(e->device));
     int rc;
-    const size_t fb = (size_t)n * e->prm.n_features * (e->prm.use_delta ? 2 * e->n_in : e->n_in) * sizeof(float);
+    const size_t fb = (size_t)n * e->prm.n_features * window_floats(e) * sizeof(float);
     if ((rc = ensure(e, e->st_feats, fb))) return rc;
     if ((rc = ensure(e, e->st_out, (size_t)e->n_models * n * sizeof(float)))) return rc;
     PE_HIP(e, hipMemcpy(e->st_feats.p, feats_host, fb, hipMemcpyHostToDevice));
@@ -2220,23 +2244,15 @@ int run_clips(pe_engine* e, const char* who, const void* audio_host, int32_t sam
         desc.resize((size_t)n); prefix.resize((size_t)n + 1);
         uint32_t tasks = 0;
         for (int i = 0; i < n; ++i) {
-            const int64_t len = offsets_host[c0 + i + 1] - offsets_host[c0 + i];
-            const int64_t cut = max_samples > 0 && len > max_samples ? max_samples : len;        // vectorize: audio[-max_samples:]
-            const int64_t frames = frames_of_buffer(e->prm, cut);
-            const int64_t kept = frames < T ? frames : T;                                          // ... feats[-n_features:]
-            desc[(size_t)i] = ClipDesc{offsets_host[c0 + i + 1] - cut - base, (int)(frames - kept), (int)kept, (int)(T - kept), 0};
             prefix[(size_t)i] = tasks;
-            tasks += (uint32_t)kept;
+            desc[(size_t)i] = clip_desc(e->prm, T, offsets_host[c0 + i + 1] - base, offsets_host[c0 + i + 1] - offsets_host[c0 + i], max_samples, tasks);
         }
         prefix[(size_t)n] = tasks;
-        const size_t db = (size_t)n * sizeof(ClipDesc), pb = ((size_t)n + 1) * sizeof(uint32_t);
         if ((rc = ensure(e, e->st_audio, (size_t)n_samples * elem))) return rc;
-        if ((rc = ensure(e, e->st_clips, db + pb))) return rc;
         PE_HIP(e, hipMemcpy(e->st_audio.p, static_cast<const char*>(audio_host) + (size_t)base * elem, (size_t)n_samples * elem, hipMemcpyHostToDevice));
-        PE_HIP(e, hipMemcpy(e->st_clips.p, desc.data(), db, hipMemcpyHostToDevice));
-        PE_HIP(e, hipMemcpy(static_cast<char*>(e->st_clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
-        const ClipTable ct{static_cast<const ClipDesc*>(e->st_clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->st_clips.p) + db),
-                           n, tasks, e->st_audio.p, sample_format == 1 ? 1 : 0};
+        ClipTable ct;
+        PE_HIP(e, upload_task_table(e, e->st_clips, desc, prefix, e->st_audio.p, sample_format == 1 ? 1 : 0, ct, rc));
+        if (rc) return rc;
         double* dev_out = nullptr;
         float* dev_rows = nullptr;
         const size_t fb = (size_t)n * T * width * sizeof(double), rb = (size_t)n * T * e->row_floats * sizeof(float);
@@ -2450,17 +2466,15 @@ int run_recordings(pe_engine* e, const char* who, const void* audio_host, int32_
         if (padded > 0) {
             const int64_t base = offsets_host[c0], n_samples = offsets_host[c1] - base;
             const int64_t n_rows = (padded - 1) * hop + T;
-            const size_t db = (size_t)n * sizeof(RecDesc), pb = ((size_t)n + 1) * sizeof(uint32_t), rb = (size_t)n_rows * e->row_floats * sizeof(float);
+            const size_t rb = (size_t)n_rows * e->row_floats * sizeof(float);
             if ((rc = ensure(e, e->st_audio, (size_t)n_samples * elem))) return rc;
-            if ((rc = ensure(e, e->st_clips, db + pb))) return rc;
             if ((rc = ensure(e, e->st_feats, rb))) return rc;
             if ((rc = ensure(e, e->st_pred, (size_t)e->n_models * (size_t)padded * sizeof(float)))) return rc;
             PE_HIP(e, hipMemcpy(e->st_audio.p, static_cast<const char*>(audio_host) + (size_t)base * elem, (size_t)n_samples * elem, hipMemcpyHostToDevice));
-            PE_HIP(e, hipMemcpy(e->st_clips.p, desc.data(), db, hipMemcpyHostToDevice));
-            PE_HIP(e, hipMemcpy(static_cast<char*>(e->st_clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
+            RecTable rt;
+            PE_HIP(e, upload_task_table(e, e->st_clips, desc, prefix, e->st_audio.p, sample_format == 1 ? 1 : 0, rt, rc));
+            if (rc) return rc;
             PE_HIP(e, hipMemsetAsync(e->st_feats.p, 0, rb, nullptr));      // the rows between two recordings: read by the windows that are dropped
-            const RecTable rt{static_cast<const RecDesc*>(e->st_clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->st_clips.p) + db),
-                              n, (uint32_t)tasks, e->st_audio.p, sample_format == 1 ? 1 : 0};
             float* dev_rows = static_cast<float*>(e->st_feats.p);
             if (t) PE_HIP(e, hipEventRecord(e->ev[0], nullptr));
             if ((rc = launch_rec_front_end(e, rt, dev_rows))) return rc;
@@ -3957,39 +3971,97 @@ int pe_trainer_n_selected(const pe_trainer* t) { return t ? t->n_selected : -1; 
 
 }  // extern "C"
 
+// ---- what the data sessions below share: each step of a session's host side that is not its own, stated once ------------------
+namespace {
+
+// A session keeps its device buffers in one array indexed by its enum, as pe_trainer does: the enum declares a buffer, ensure
+// grows it, and this gives back all of them when the session goes -- with their bytes, which pe_info.device_bytes counts
+void release_buffers(pe_engine* e, DeviceBuf* first, int count) {
+    (void)hipSetDevice(e->device);
+    (void)hipDeviceSynchronize();
+    for (DeviceBuf* b = first; b != first + count; ++b)
+        if (b->p) { (void)hipFree(b->p); e->device_bytes -= (int64_t)b->bytes; }
+}
+
+// offsets[n + 1] of a pool of recordings (`what`); need_samples: a pool that must hold an entry, and samples in every entry
+int check_offsets(pe_engine* e, const char* who, const char* what, const int64_t* offsets, int32_t n, bool need_samples) {
+    if (need_samples && n < 1) return fail(e, PE_ERR_INVALID, "%s: %d %ss (at least one is needed)", who, n, what);
+    if (n < 0) return fail(e, PE_ERR_INVALID, "%s: %d %ss", who, n, what);
+    if (n > 0 && !offsets) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    if (n > 0 && offsets[0] != 0) return fail(e, PE_ERR_INVALID, "%s: %s offsets[0] must be 0, got %lld", who, what, (long long)offsets[0]);
+    for (int32_t r = 0; r < n; ++r) {
+        if (offsets[r + 1] < offsets[r])
+            return fail(e, PE_ERR_INVALID, "%s: offsets decrease at %s %d (%lld after %lld)", who, what, r, (long long)offsets[r + 1], (long long)offsets[r]);
+        if (need_samples && offsets[r + 1] == offsets[r]) return fail(e, PE_ERR_INVALID, "%s: %s %d is empty", who, what, r);
+    }
+    return PE_OK;
+}
+
+// the geometry of a mine_gather launch over the engine's rows; where the windows lie is the caller's
+MineGatherArgs gather_geometry(const pe_engine* e) {
+    MineGatherArgs g{};
+    g.T = e->prm.n_features; g.F = e->n_in; g.use_delta = e->prm.use_delta ? 1 : 0; g.row_floats = e->row_floats;
+    return g;
+}
+
+// may a session of `e` append its windows behind the resident set `source` of `trainer`?
+int check_append(pe_engine* e, const char* who, const pe_trainer* trainer, int source) {
+    if (!trainer) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    const int width = window_floats(e);
+    if (trainer->device != e->device) return fail(e, PE_ERR_INVALID, "%s: the trainer lives on device %d, the engine on %d", who, trainer->device, e->device);
+    if (trainer->F != width || trainer->T != e->prm.n_features)
+        return fail(e, PE_ERR_INVALID, "%s: the trainer takes [%d][%d] inputs, the engine's windows are [%d][%d]", who, trainer->T, trainer->F, e->prm.n_features, width);
+    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
+    return PE_OK;
+}
+int check_targets(pe_engine* e, const char* who, const float* targets, int32_t n) {
+    for (int32_t i = 0; i < n; ++i)
+        if (!(targets[i] >= 0.0f && targets[i] <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: targets[%d] = %g is outside [0, 1]", who, i, (double)targets[i]);
+    return PE_OK;
+}
+
+// what a train_append_* call said, as the engine's own error
+int trainer_said(pe_engine* e, const pe_trainer* trainer, int trc) { return trc ? fail(e, trc, "%s", trainer->err.c_str()) : PE_OK; }
+
+// the end of a pass that appends: the targets of its k windows go up, the null stream finishes rows_dev, the trainer copies both
+int rows_to_trainer(pe_engine* e, const char* who, pe_trainer* trainer, int source, const float* rows_dev, const float* targets_host, int k,
+                    DeviceBuf& targets_buf) {
+    int rc = ensure(e, targets_buf, (size_t)k * sizeof(float));
+    if (rc) return rc;
+    PE_HIP(e, hipMemcpy(targets_buf.p, targets_host, (size_t)k * sizeof(float), hipMemcpyHostToDevice));
+    PE_HIP(e, hipStreamSynchronize(nullptr));
+    return trainer_said(e, trainer, train_append_device_targets(trainer, who, source, rows_dev, static_cast<const float*>(targets_buf.p), k));
+}
+
 // ---- mining false activations (pe_miner; kernels: mine_device.h) ----------------------------------------------
+enum MinerBuf {
+    // resident: the samples as given, the three prefix sums [n_rec + 1] each (chunks, frames, samples), every frame's float32 row
+    kMineAudio, kMineTables, kMineRows,
+    // grown on demand: a pass's network input and its predictions [n_models][pass]; a scan's predictions, decoded values, block
+    // counts and hit ids; a pass's hit ids, saved clips, clip table, float64 rows / float32 rows and packed trainer rows
+    kMineBatch, kMinePred, kMineScores, kMineConf, kMineCounts, kMineHits, kMineIds, kMineRing, kMineClips, kMineFeats64, kMineClipRows, kMinePacked, kMineBufCount
+};
+
+}  // namespace
+
 struct pe_miner {
     pe_engine* e = nullptr;
     int n_rec = 0, chunk = 0, buffer_samples = 0, carry_audio = 1, audio_f32 = 0;
     int64_t total_chunks = 0, total_frames = 0;
     std::vector<int64_t> chunk_prefix;                  // [n_rec + 1]
-    // resident: the samples as given, the three prefix sums [n_rec + 1] each (chunks, frames, samples), every frame's float32 row
-    DeviceBuf audio, tables, rows;
-    // grown on demand: a pass's network input and its predictions [n_models][pass]; a scan's predictions, decoded values, block
-    // counts and hit ids; a pass's hit ids, saved clips, clip table, float64 rows / float32 rows and packed trainer rows
-    DeviceBuf batch, pred, scores, conf, counts, hits, ids, ring, clips, feats64, clip_rows, packed;
-    const long long* d_chunk_prefix() const { return static_cast<const long long*>(tables.p); }
+    DeviceBuf buf[kMineBufCount];                       // MinerBuf
+    const long long* d_chunk_prefix() const { return static_cast<const long long*>(buf[kMineTables].p); }
     const long long* d_frame_base() const { return d_chunk_prefix() + n_rec + 1; }
     const long long* d_rec_start() const { return d_chunk_prefix() + 2 * (n_rec + 1); }
 };
 
 namespace {
 
-void miner_free(pe_miner* m) {
-    pe_engine* e = m->e;
-    (void)hipSetDevice(e->device);
-    (void)hipDeviceSynchronize();
-    for (DeviceBuf* b : {&m->audio, &m->tables, &m->rows, &m->batch, &m->pred, &m->scores, &m->conf, &m->counts, &m->hits, &m->ids, &m->ring,
-                         &m->clips, &m->feats64, &m->clip_rows, &m->packed})
-        if (b->p) { (void)hipFree(b->p); e->device_bytes -= (int64_t)b->bytes; }
-    delete m;
-}
+void miner_free(pe_miner* m) { release_buffers(m->e, m->buf, kMineBufCount); delete m; }
 
 MineGatherArgs miner_gather_args(const pe_miner* m) {
-    const pe_engine* e = m->e;
-    MineGatherArgs g{};
-    g.chunk = m->chunk; g.emit_window = emit_window(e->prm); g.hop = e->prm.hop_samples;
-    g.T = e->prm.n_features; g.F = e->n_in; g.use_delta = e->prm.use_delta ? 1 : 0; g.row_floats = e->row_floats;
+    MineGatherArgs g = gather_geometry(m->e);
+    g.chunk = m->chunk; g.emit_window = emit_window(m->e->prm); g.hop = m->e->prm.hop_samples;
     return g;
 }
 
@@ -4013,10 +4085,7 @@ int miner_rows(pe_miner* m, const char* who, const int32_t* hits, int32_t n, dou
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
     const int T = e->prm.n_features, B = m->buffer_samples;
-    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
-    // vectorize() of a clip of B samples (no crop: buffer_samples <= max_samples, params.py:74,95): the same for every hit
-    const int64_t frames = frames_of_buffer(e->prm, B);
-    const int kept = (int)(frames < T ? frames : T);
+    const int width = window_floats(e);
     int64_t per_pass = e->clip_pass_bytes / ((int64_t)B * (int64_t)sizeof(float));
     per_pass = std::max<int64_t>(1, std::min<int64_t>(per_pass, 32768));
     std::vector<ClipDesc> desc;
@@ -4024,40 +4093,35 @@ int miner_rows(pe_miner* m, const char* who, const int32_t* hits, int32_t n, dou
     for (int32_t h0 = 0; h0 < n; h0 += (int32_t)per_pass) {
         const int k = (int)std::min<int64_t>(per_pass, n - h0);
         desc.resize((size_t)k); prefix.resize((size_t)k + 1);
-        for (int i = 0; i < k; ++i) {
-            desc[(size_t)i] = ClipDesc{(long long)i * B, (int)(frames - kept), kept, T - kept, 0};
-            prefix[(size_t)i] = (uint32_t)i * (uint32_t)kept;
-        }
-        prefix[(size_t)k] = (uint32_t)k * (uint32_t)kept;
-        const size_t db = (size_t)k * sizeof(ClipDesc), pb = ((size_t)k + 1) * sizeof(uint32_t);
-        if ((rc = ensure(e, m->ids, (size_t)k * sizeof(int32_t)))) return rc;
-        if ((rc = ensure(e, m->ring, (size_t)k * B * sizeof(float)))) return rc;
-        if ((rc = ensure(e, m->clips, db + pb))) return rc;
-        PE_HIP(e, hipMemcpy(m->ids.p, hits + h0, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice));
-        PE_HIP(e, hipMemcpy(m->clips.p, desc.data(), db, hipMemcpyHostToDevice));
-        PE_HIP(e, hipMemcpy(static_cast<char*>(m->clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
-        MineRingArgs r{static_cast<const int32_t*>(m->ids.p), k, m->d_chunk_prefix(), m->d_rec_start(), m->n_rec, m->chunk, B, m->carry_audio,
-                       m->audio.p, m->audio_f32, static_cast<float*>(m->ring.p)};
+        uint32_t tasks = 0;
+        // vectorize() of a clip of B samples (no crop: buffer_samples <= max_samples, params.py:74,95): the same for every hit
+        for (int i = 0; i < k; ++i) { prefix[(size_t)i] = tasks; desc[(size_t)i] = clip_desc(e->prm, T, (int64_t)(i + 1) * B, B, 0, tasks); }
+        prefix[(size_t)k] = tasks;
+        if ((rc = ensure(e, m->buf[kMineIds], (size_t)k * sizeof(int32_t)))) return rc;
+        if ((rc = ensure(e, m->buf[kMineRing], (size_t)k * B * sizeof(float)))) return rc;
+        PE_HIP(e, hipMemcpy(m->buf[kMineIds].p, hits + h0, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice));
+        ClipTable ct;
+        PE_HIP(e, upload_task_table(e, m->buf[kMineClips], desc, prefix, m->buf[kMineRing].p, 1, ct, rc));
+        if (rc) return rc;
+        MineRingArgs r{static_cast<const int32_t*>(m->buf[kMineIds].p), k, m->d_chunk_prefix(), m->d_rec_start(), m->n_rec, m->chunk, B, m->carry_audio,
+                       m->buf[kMineAudio].p, m->audio_f32, static_cast<float*>(m->buf[kMineRing].p)};
         PE_HIP(e, launch_mine_ring(r, nullptr));
-        const ClipTable ct{static_cast<const ClipDesc*>(m->clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(m->clips.p) + db),
-                           k, (uint32_t)k * (uint32_t)kept, m->ring.p, 1};
         if (feats_out_host) {
             const size_t fb = (size_t)k * T * e->prm.n_mfcc * sizeof(double);
-            if ((rc = ensure(e, m->feats64, fb))) return rc;
-            if ((rc = launch_clip_front_end(e, ct, static_cast<double*>(m->feats64.p), nullptr, nullptr))) return rc;
-            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)h0 * T * e->prm.n_mfcc, m->feats64.p, fb, hipMemcpyDeviceToHost));
+            if ((rc = ensure(e, m->buf[kMineFeats64], fb))) return rc;
+            if ((rc = launch_clip_front_end(e, ct, static_cast<double*>(m->buf[kMineFeats64].p), nullptr, nullptr))) return rc;
+            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)h0 * T * e->prm.n_mfcc, m->buf[kMineFeats64].p, fb, hipMemcpyDeviceToHost));
         } else {
-            if ((rc = ensure(e, m->clip_rows, (size_t)k * T * e->row_floats * sizeof(float)))) return rc;
-            if ((rc = ensure(e, m->packed, (size_t)k * T * width * sizeof(float)))) return rc;
-            if ((rc = launch_clip_front_end(e, ct, nullptr, static_cast<float*>(m->clip_rows.p), nullptr))) return rc;
+            if ((rc = ensure(e, m->buf[kMineClipRows], (size_t)k * T * e->row_floats * sizeof(float)))) return rc;
+            if ((rc = ensure(e, m->buf[kMinePacked], (size_t)k * T * width * sizeof(float)))) return rc;
+            if ((rc = launch_clip_front_end(e, ct, nullptr, static_cast<float*>(m->buf[kMineClipRows].p), nullptr))) return rc;
             MineGatherArgs g = miner_gather_args(m);
-            g.rows = static_cast<const float*>(m->clip_rows.p);
+            g.rows = static_cast<const float*>(m->buf[kMineClipRows].p);
             g.n = k;
-            g.out = static_cast<float*>(m->packed.p);
+            g.out = static_cast<float*>(m->buf[kMinePacked].p);
             PE_HIP(e, launch_mine_gather(g, nullptr));
             PE_HIP(e, hipStreamSynchronize(nullptr));
-            const int trc = train_append_device(trainer, who, source, static_cast<const float*>(m->packed.p), k, target);
-            if (trc) return fail(e, trc, "%s", trainer->err.c_str());
+            if ((rc = trainer_said(e, trainer, train_append_device(trainer, who, source, g.out, k, target)))) return rc;
         }
     }
     return PE_OK;
@@ -4105,24 +4169,21 @@ int pe_miner_create(pe_engine* e, const void* audio_host, int32_t sample_format,
     int rc = PE_OK;
     hipError_t herr = hipSuccess;
     do {
-        if ((rc = ensure(e, m->audio, (size_t)std::max<int64_t>(n_samples, 1) * elem))) break;
-        if ((rc = ensure(e, m->tables, tab.size() * sizeof(int64_t)))) break;
-        if ((rc = ensure(e, m->rows, (size_t)std::max<int64_t>(m->total_frames, 1) * e->row_floats * sizeof(float)))) break;
-        if (n_samples > 0 && (herr = hipMemcpy(m->audio.p, audio_host, (size_t)n_samples * elem, hipMemcpyHostToDevice)) != hipSuccess) break;
-        if ((herr = hipMemcpy(m->tables.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((rc = ensure(e, m->buf[kMineAudio], (size_t)std::max<int64_t>(n_samples, 1) * elem))) break;
+        if ((rc = ensure(e, m->buf[kMineTables], tab.size() * sizeof(int64_t)))) break;
+        if ((rc = ensure(e, m->buf[kMineRows], (size_t)std::max<int64_t>(m->total_frames, 1) * e->row_floats * sizeof(float)))) break;
+        if (n_samples > 0 && (herr = hipMemcpy(m->buf[kMineAudio].p, audio_host, (size_t)n_samples * elem, hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((herr = hipMemcpy(m->buf[kMineTables].p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
         if (m->total_frames > 0) {
             // every frame of every recording, once: pe_evaluate_clips' front-end launch with the rows back to back
             std::vector<RecDesc> desc((size_t)n_rec);
             std::vector<uint32_t> prefix((size_t)n_rec + 1);
             for (int32_t r = 0; r < n_rec; ++r) { desc[(size_t)r] = RecDesc{rs[r], fb[r]}; prefix[(size_t)r] = (uint32_t)fb[r]; }
             prefix[(size_t)n_rec] = (uint32_t)fb[n_rec];
-            const size_t db = (size_t)n_rec * sizeof(RecDesc), pb = ((size_t)n_rec + 1) * sizeof(uint32_t);
-            if ((rc = ensure(e, m->clips, db + pb))) break;
-            if ((herr = hipMemcpy(m->clips.p, desc.data(), db, hipMemcpyHostToDevice)) != hipSuccess) break;
-            if ((herr = hipMemcpy(static_cast<char*>(m->clips.p) + db, prefix.data(), pb, hipMemcpyHostToDevice)) != hipSuccess) break;
-            const RecTable rt{static_cast<const RecDesc*>(m->clips.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(m->clips.p) + db),
-                              n_rec, (uint32_t)m->total_frames, m->audio.p, m->audio_f32};
-            if ((rc = launch_rec_front_end(e, rt, static_cast<float*>(m->rows.p)))) break;
+            RecTable rt;
+            herr = upload_task_table(e, m->buf[kMineClips], desc, prefix, m->buf[kMineAudio].p, m->audio_f32, rt, rc);
+            if (rc || herr != hipSuccess) break;
+            if ((rc = launch_rec_front_end(e, rt, static_cast<float*>(m->buf[kMineRows].p)))) break;
         }
         herr = hipStreamSynchronize(nullptr);
     } while (false);
@@ -4158,49 +4219,49 @@ int pe_miner_scan(pe_miner* m, int32_t model, int64_t first_chunk, double thresh
     if (n == 0) return PE_OK;
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
-    const int T = e->prm.n_features, width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    const int T = e->prm.n_features, width = window_floats(e);
     const int64_t window_bytes = (int64_t)T * width * (int64_t)sizeof(float);
     const int64_t per_pass = std::max<int64_t>(1, std::min<int64_t>(e->clip_pass_bytes / window_bytes, 1 << 24));
     int rc;
-    if ((rc = ensure(e, m->scores, (size_t)n * sizeof(float)))) return rc;
-    float* const scores = static_cast<float*>(m->scores.p);
+    if ((rc = ensure(e, m->buf[kMineScores], (size_t)n * sizeof(float)))) return rc;
+    float* const scores = static_cast<float*>(m->buf[kMineScores].p);
     MineGatherArgs g = miner_gather_args(m);
-    g.rows = static_cast<const float*>(m->rows.p);
+    g.rows = static_cast<const float*>(m->buf[kMineRows].p);
     g.chunk_prefix = m->d_chunk_prefix(); g.frame_base = m->d_frame_base(); g.n_rec = m->n_rec;
     for (int64_t c0 = 0; c0 < n; c0 += per_pass) {
         const int k = (int)std::min<int64_t>(per_pass, n - c0);
-        if ((rc = ensure(e, m->batch, (size_t)k * (size_t)window_bytes))) return rc;
-        g.first = first_chunk + c0; g.n = k; g.out = static_cast<float*>(m->batch.p);
+        if ((rc = ensure(e, m->buf[kMineBatch], (size_t)k * (size_t)window_bytes))) return rc;
+        g.first = first_chunk + c0; g.n = k; g.out = static_cast<float*>(m->buf[kMineBatch].p);
         PE_HIP(e, launch_mine_gather(g, nullptr));
         if (e->n_models == 1) {
             if ((rc = pe_predict_device(e, g.out, k, scores + c0, nullptr))) return rc;
         } else {                // a K-model engine predicts all of its models: [K][k]; the scan keeps block `model`
-            if ((rc = ensure(e, m->pred, (size_t)e->n_models * k * sizeof(float)))) return rc;
-            if ((rc = pe_predict_device(e, g.out, k, static_cast<float*>(m->pred.p), nullptr))) return rc;
-            PE_HIP(e, hipMemcpyAsync(scores + c0, static_cast<const float*>(m->pred.p) + (size_t)model * k, (size_t)k * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+            if ((rc = ensure(e, m->buf[kMinePred], (size_t)e->n_models * k * sizeof(float)))) return rc;
+            if ((rc = pe_predict_device(e, g.out, k, static_cast<float*>(m->buf[kMinePred].p), nullptr))) return rc;
+            PE_HIP(e, hipMemcpyAsync(scores + c0, static_cast<const float*>(m->buf[kMinePred].p) + (size_t)model * k, (size_t)k * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
         }
     }
     // decode (pe_decode's kernel, when model has a table), then the ordered compaction over the whole range
     const DecState& d = e->dec[(size_t)model];
     const double* conf = nullptr;
     if (d.cd) {
-        if ((rc = ensure(e, m->conf, (size_t)n * sizeof(double)))) return rc;
+        if ((rc = ensure(e, m->buf[kMineConf], (size_t)n * sizeof(double)))) return rc;
         DecodeArgs a{};
         a.n_streams = (int)n; a.raw = scores; a.cd = d.cd; a.cd_len = d.cd_len; a.min_out = d.min_out; a.out_range = d.out_range; a.center = d.center;
-        a.conf_out = static_cast<double*>(m->conf.p);
+        a.conf_out = static_cast<double*>(m->buf[kMineConf].p);
         PE_HIP(e, launch_decode(a, nullptr));
         conf = a.conf_out;
     }
     const int n_blocks = mine_blocks(n);
-    if ((rc = ensure(e, m->counts, ((size_t)n_blocks + 1) * sizeof(uint32_t)))) return rc;
-    if (capacity > 0 && (rc = ensure(e, m->hits, (size_t)capacity * sizeof(int32_t)))) return rc;
-    MineCompactArgs c{scores, conf, n, threshold, first_chunk, static_cast<uint32_t*>(m->counts.p), n_blocks,
-                      capacity > 0 ? static_cast<int32_t*>(m->hits.p) : nullptr, capacity};
+    if ((rc = ensure(e, m->buf[kMineCounts], ((size_t)n_blocks + 1) * sizeof(uint32_t)))) return rc;
+    if (capacity > 0 && (rc = ensure(e, m->buf[kMineHits], (size_t)capacity * sizeof(int32_t)))) return rc;
+    MineCompactArgs c{scores, conf, n, threshold, first_chunk, static_cast<uint32_t*>(m->buf[kMineCounts].p), n_blocks,
+                      capacity > 0 ? static_cast<int32_t*>(m->buf[kMineHits].p) : nullptr, capacity};
     PE_HIP(e, launch_mine_compact(c, nullptr));
     uint32_t total = 0;
     PE_HIP(e, hipMemcpy(&total, c.block_counts + n_blocks, sizeof total, hipMemcpyDeviceToHost));
     const int32_t got = (int32_t)std::min<int64_t>(total, capacity);
-    if (got > 0) PE_HIP(e, hipMemcpy(hits_out, m->hits.p, (size_t)got * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (got > 0) PE_HIP(e, hipMemcpy(hits_out, m->buf[kMineHits].p, (size_t)got * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (scores_out) PE_HIP(e, hipMemcpy(scores_out, scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     *n_hits = got; *n_above = (int64_t)total;
     return PE_OK;
@@ -4216,12 +4277,8 @@ int pe_miner_append(pe_miner* m, pe_trainer* trainer, int32_t source, const int3
     const char* who = "pe_miner_append";
     if (!m) return PE_ERR_INVALID;
     pe_engine* e = m->e;
-    if (!trainer) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
-    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
-    if (trainer->device != e->device) return fail(e, PE_ERR_INVALID, "%s: the trainer lives on device %d, the engine on %d", who, trainer->device, e->device);
-    if (trainer->F != width || trainer->T != e->prm.n_features)
-        return fail(e, PE_ERR_INVALID, "%s: the trainer takes [%d][%d] inputs, the engine's windows are [%d][%d]", who, trainer->T, trainer->F, e->prm.n_features, width);
-    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
+    int rc = check_append(e, who, trainer, source);
+    if (rc) return rc;
     if (!(target >= 0.0f && target <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: target %g is outside [0, 1]", who, (double)target);
     return miner_rows(m, who, hits, n, nullptr, trainer, source, target);
 }
@@ -4229,6 +4286,15 @@ int pe_miner_append(pe_miner* m, pe_trainer* trainer, int32_t source, const int3
 }  // extern "C"
 
 // ---- generating training audio (pe_generator; kernel: generate_device.h) --------------------------------------
+namespace {
+enum GeneratorBuf {
+    // resident: the two pools as given; of the plan: chunk prefix | frame base, the segments, their prefix sum, every frame's row
+    kGenBg, kGenClips, kGenTables, kGenSegs, kGenSegPrefix, kGenRows,
+    // grown on demand: a pass's mixed samples and recording table; a pass's ids, targets and network input; pe_generator_audio's samples
+    kGenMixed, kGenRecs, kGenIds, kGenTargets, kGenBatch, kGenAudioOut, kGenBufCount
+};
+}  // namespace
+
 struct pe_generator {
     pe_engine* e = nullptr;
     int n_bg = 0, n_clips = 0, chunk = 0;
@@ -4237,39 +4303,19 @@ struct pe_generator {
     int n_files = 0;
     int64_t n_segments = 0, total_chunks = 0, total_frames = 0;
     std::vector<int64_t> chunk_prefix, frame_base, sample_base, seg_first;
-    // resident: the two pools as given; of the plan: chunk prefix | frame base, the segments, their prefix sum, every frame's row
-    DeviceBuf bg, clips, tables, segs, seg_prefix, rows;
-    // grown on demand: a pass's mixed samples and recording table; a pass's ids, targets and network input; pe_generator_audio's samples
-    DeviceBuf mixed, recs, ids, targets, batch, audio_out;
-    const long long* d_chunk_prefix() const { return static_cast<const long long*>(tables.p); }
+    DeviceBuf buf[kGenBufCount];                        // GeneratorBuf
+    const long long* d_chunk_prefix() const { return static_cast<const long long*>(buf[kGenTables].p); }
     const long long* d_frame_base() const { return d_chunk_prefix() + n_files + 1; }
 };
 
 namespace {
 
-void generator_free(pe_generator* g) {
-    pe_engine* e = g->e;
-    (void)hipSetDevice(e->device);
-    (void)hipDeviceSynchronize();
-    for (DeviceBuf* b : {&g->bg, &g->clips, &g->tables, &g->segs, &g->seg_prefix, &g->rows, &g->mixed, &g->recs, &g->ids, &g->targets, &g->batch, &g->audio_out})
-        if (b->p) { (void)hipFree(b->p); e->device_bytes -= (int64_t)b->bytes; }
-    delete g;
-}
-
-int generator_check_offsets(pe_engine* e, const char* who, const char* what, const int64_t* offsets, int32_t n) {
-    if (n < 0) return fail(e, PE_ERR_INVALID, "%s: %d %ss", who, n, what);
-    if (n > 0 && !offsets) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
-    if (n > 0 && offsets[0] != 0) return fail(e, PE_ERR_INVALID, "%s: %s offsets[0] must be 0, got %lld", who, what, (long long)offsets[0]);
-    for (int32_t r = 0; r < n; ++r)
-        if (offsets[r + 1] < offsets[r])
-            return fail(e, PE_ERR_INVALID, "%s: offsets decrease at %s %d (%lld after %lld)", who, what, r, (long long)offsets[r + 1], (long long)offsets[r]);
-    return PE_OK;
-}
+void generator_free(pe_generator* g) { release_buffers(g->e, g->buf, kGenBufCount); delete g; }
 
 GenMixArgs generator_mix_args(const pe_generator* g) {
     GenMixArgs a{};
-    a.bg = static_cast<const float*>(g->bg.p); a.clips = static_cast<const float*>(g->clips.p);
-    a.segs = static_cast<const GenSeg*>(g->segs.p); a.seg_prefix = static_cast<const long long*>(g->seg_prefix.p);
+    a.bg = static_cast<const float*>(g->buf[kGenBg].p); a.clips = static_cast<const float*>(g->buf[kGenClips].p);
+    a.segs = static_cast<const GenSeg*>(g->buf[kGenSegs].p); a.seg_prefix = static_cast<const long long*>(g->buf[kGenSegPrefix].p);
     a.keep = (float)(1.0 - 0.6);                                // train_generated.py:155,185
     return a;
 }
@@ -4291,31 +4337,24 @@ int generator_rows(pe_generator* g, const char* who, const int32_t* ids, const f
     if (n == 0) return PE_OK;
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
-    const int T = e->prm.n_features, width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    const int T = e->prm.n_features, width = window_floats(e);
     const int64_t window_bytes = (int64_t)T * width * (int64_t)sizeof(float);
     const int64_t per_pass = std::max<int64_t>(1, std::min<int64_t>(e->clip_pass_bytes / window_bytes, 1 << 24));
-    MineGatherArgs a{};
+    MineGatherArgs a = gather_geometry(e);
     a.chunk = g->chunk; a.emit_window = emit_window(e->prm); a.hop = e->prm.hop_samples;
-    a.T = T; a.F = e->n_in; a.use_delta = e->prm.use_delta ? 1 : 0; a.row_floats = e->row_floats;
-    a.rows = static_cast<const float*>(g->rows.p);
+    a.rows = static_cast<const float*>(g->buf[kGenRows].p);
     a.chunk_prefix = g->d_chunk_prefix(); a.frame_base = g->d_frame_base(); a.n_rec = g->n_files;
     int rc;
     for (int32_t i0 = 0; i0 < n; i0 += (int32_t)per_pass) {
         const int k = (int)std::min<int64_t>(per_pass, n - i0);
-        if ((rc = ensure(e, g->ids, (size_t)k * sizeof(int32_t)))) return rc;
-        if ((rc = ensure(e, g->batch, (size_t)k * (size_t)window_bytes))) return rc;
-        PE_HIP(e, hipMemcpy(g->ids.p, ids + i0, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice));
-        a.ids = static_cast<const int32_t*>(g->ids.p); a.n = k; a.out = static_cast<float*>(g->batch.p);
+        if ((rc = ensure(e, g->buf[kGenIds], (size_t)k * sizeof(int32_t)))) return rc;
+        if ((rc = ensure(e, g->buf[kGenBatch], (size_t)k * (size_t)window_bytes))) return rc;
+        PE_HIP(e, hipMemcpy(g->buf[kGenIds].p, ids + i0, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice));
+        a.ids = static_cast<const int32_t*>(g->buf[kGenIds].p); a.n = k; a.out = static_cast<float*>(g->buf[kGenBatch].p);
         PE_HIP(e, launch_mine_gather(a, nullptr));
         if (feats_out_host) {
-            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)i0 * T * width, g->batch.p, (size_t)k * (size_t)window_bytes, hipMemcpyDeviceToHost));
-        } else {
-            if ((rc = ensure(e, g->targets, (size_t)k * sizeof(float)))) return rc;
-            PE_HIP(e, hipMemcpy(g->targets.p, targets + i0, (size_t)k * sizeof(float), hipMemcpyHostToDevice));
-            PE_HIP(e, hipStreamSynchronize(nullptr));
-            const int trc = train_append_device_targets(trainer, who, source, a.out, static_cast<const float*>(g->targets.p), k);
-            if (trc) return fail(e, trc, "%s", trainer->err.c_str());
-        }
+            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)i0 * T * width, g->buf[kGenBatch].p, (size_t)k * (size_t)window_bytes, hipMemcpyDeviceToHost));
+        } else if ((rc = rows_to_trainer(e, who, trainer, source, a.out, targets + i0, k, g->buf[kGenTargets]))) return rc;
     }
     return PE_OK;
 }
@@ -4333,8 +4372,8 @@ int pe_generator_create(pe_engine* e, const float* bg_audio, const int64_t* bg_o
     if (e && mel_rows(e)) return fail(e, PE_ERR_UNSUPPORTED, "%s: this session has no Vectorizer.mels form (its windows are MFCC rows); create it over an mfccs engine", who);
     if (chunk_size < 1) return fail(e, PE_ERR_INVALID, "%s: chunk_size must be >= 1, got %d", who, chunk_size);
     int rc;
-    if ((rc = generator_check_offsets(e, who, "background", bg_offsets, n_bg))) return rc;
-    if ((rc = generator_check_offsets(e, who, "clip", clip_offsets, n_clips))) return rc;
+    if ((rc = check_offsets(e, who, "background", bg_offsets, n_bg, false))) return rc;
+    if ((rc = check_offsets(e, who, "clip", clip_offsets, n_clips, false))) return rc;
     const int64_t bg_samples = n_bg > 0 ? bg_offsets[n_bg] : 0, clip_samples = n_clips > 0 ? clip_offsets[n_clips] : 0;
     if ((bg_samples > 0 && !bg_audio) || (clip_samples > 0 && !clip_audio)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
     PE_HIP(e, hipSetDevice(e->device));
@@ -4347,10 +4386,10 @@ int pe_generator_create(pe_engine* e, const float* bg_audio, const int64_t* bg_o
     generator_drop_plan(g);
     hipError_t herr = hipSuccess;
     do {
-        if ((rc = ensure(e, g->bg, (size_t)std::max<int64_t>(bg_samples, 1) * sizeof(float)))) break;
-        if ((rc = ensure(e, g->clips, (size_t)std::max<int64_t>(clip_samples, 1) * sizeof(float)))) break;
-        if (bg_samples > 0 && (herr = hipMemcpy(g->bg.p, bg_audio, (size_t)bg_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
-        if (clip_samples > 0 && (herr = hipMemcpy(g->clips.p, clip_audio, (size_t)clip_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((rc = ensure(e, g->buf[kGenBg], (size_t)std::max<int64_t>(bg_samples, 1) * sizeof(float)))) break;
+        if ((rc = ensure(e, g->buf[kGenClips], (size_t)std::max<int64_t>(clip_samples, 1) * sizeof(float)))) break;
+        if (bg_samples > 0 && (herr = hipMemcpy(g->buf[kGenBg].p, bg_audio, (size_t)bg_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if (clip_samples > 0 && (herr = hipMemcpy(g->buf[kGenClips].p, clip_audio, (size_t)clip_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
     } while (false);
     if (!rc && herr != hipSuccess) rc = fail(e, PE_ERR_HIP, "%s: %s", who, hipGetErrorString(herr));
     if (rc) { generator_free(g); return rc; }
@@ -4424,13 +4463,13 @@ int pe_generator_set_plan(pe_generator* g, const pe_gen_file* files, int32_t n_f
     int rc;
     std::vector<int64_t> tab(cp);
     tab.insert(tab.end(), fb.begin(), fb.end());
-    if ((rc = ensure(e, g->tables, tab.size() * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(e, g->segs, std::max<size_t>(segs.size(), 1) * sizeof(GenSeg)))) return rc;
-    if ((rc = ensure(e, g->seg_prefix, prefix.size() * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(e, g->rows, (size_t)std::max<int64_t>(fb[(size_t)n_files], 1) * e->row_floats * sizeof(float)))) return rc;
-    PE_HIP(e, hipMemcpy(g->tables.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (!segs.empty()) PE_HIP(e, hipMemcpy(g->segs.p, segs.data(), segs.size() * sizeof(GenSeg), hipMemcpyHostToDevice));
-    PE_HIP(e, hipMemcpy(g->seg_prefix.p, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if ((rc = ensure(e, g->buf[kGenTables], tab.size() * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(e, g->buf[kGenSegs], std::max<size_t>(segs.size(), 1) * sizeof(GenSeg)))) return rc;
+    if ((rc = ensure(e, g->buf[kGenSegPrefix], prefix.size() * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(e, g->buf[kGenRows], (size_t)std::max<int64_t>(fb[(size_t)n_files], 1) * e->row_floats * sizeof(float)))) return rc;
+    PE_HIP(e, hipMemcpy(g->buf[kGenTables].p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!segs.empty()) PE_HIP(e, hipMemcpy(g->buf[kGenSegs].p, segs.data(), segs.size() * sizeof(GenSeg), hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(g->buf[kGenSegPrefix].p, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     // passes over whole files: mix, then every frame of the pass's files once (pe_evaluate_clips' front-end launch, rows back to back)
     std::vector<RecDesc> desc;
     std::vector<uint32_t> rprefix;
@@ -4439,10 +4478,10 @@ int pe_generator_set_plan(pe_generator* g, const pe_gen_file* files, int32_t n_f
         while (f1 < n_files && (sb[(size_t)f1 + 1] - sb[(size_t)f0]) * (int64_t)sizeof(double) <= e->clip_pass_bytes) ++f1;
         const int64_t n_samples = sb[(size_t)f1] - sb[(size_t)f0], n_frames = fb[(size_t)f1] - fb[(size_t)f0];
         if (n_samples > 0) {
-            if ((rc = ensure(e, g->mixed, (size_t)n_samples * sizeof(double)))) return rc;
+            if ((rc = ensure(e, g->buf[kGenMixed], (size_t)n_samples * sizeof(double)))) return rc;
             GenMixArgs a = generator_mix_args(g);
             a.seg_lo = (int)sf[(size_t)f0]; a.seg_hi = (int)sf[(size_t)f1];
-            a.first = sb[(size_t)f0]; a.n = n_samples; a.out = static_cast<double*>(g->mixed.p);
+            a.first = sb[(size_t)f0]; a.n = n_samples; a.out = static_cast<double*>(g->buf[kGenMixed].p);
             PE_HIP(e, launch_gen_mix(a, nullptr));
         }
         if (n_frames > 0) {
@@ -4453,13 +4492,10 @@ int pe_generator_set_plan(pe_generator* g, const pe_gen_file* files, int32_t n_f
                 rprefix[(size_t)i] = (uint32_t)(fb[(size_t)f0 + i] - fb[(size_t)f0]);
             }
             rprefix[(size_t)n] = (uint32_t)n_frames;
-            const size_t db = (size_t)n * sizeof(RecDesc), pb = ((size_t)n + 1) * sizeof(uint32_t);
-            if ((rc = ensure(e, g->recs, db + pb))) return rc;
-            PE_HIP(e, hipMemcpy(g->recs.p, desc.data(), db, hipMemcpyHostToDevice));
-            PE_HIP(e, hipMemcpy(static_cast<char*>(g->recs.p) + db, rprefix.data(), pb, hipMemcpyHostToDevice));
-            const RecTable rt{static_cast<const RecDesc*>(g->recs.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(g->recs.p) + db),
-                              n, (uint32_t)n_frames, g->mixed.p, 0};
-            if ((rc = launch_rec_front_end(e, rt, static_cast<float*>(g->rows.p)))) return rc;
+            RecTable rt;
+            PE_HIP(e, upload_task_table(e, g->buf[kGenRecs], desc, rprefix, g->buf[kGenMixed].p, 0, rt, rc));
+            if (rc) return rc;
+            if ((rc = launch_rec_front_end(e, rt, static_cast<float*>(g->buf[kGenRows].p)))) return rc;
         }
         PE_HIP(e, hipStreamSynchronize(nullptr));               // the next pass reuses the mixed samples and the table
         f0 = f1;
@@ -4483,12 +4519,12 @@ int pe_generator_audio(pe_generator* g, int32_t file, int64_t first, int64_t n, 
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
     int rc;
-    if ((rc = ensure(e, g->audio_out, (size_t)n * sizeof(double)))) return rc;
+    if ((rc = ensure(e, g->buf[kGenAudioOut], (size_t)n * sizeof(double)))) return rc;
     GenMixArgs a = generator_mix_args(g);
     a.seg_lo = (int)g->seg_first[(size_t)file]; a.seg_hi = (int)g->seg_first[(size_t)file + 1];
-    a.first = g->sample_base[(size_t)file] + first; a.n = n; a.out = static_cast<double*>(g->audio_out.p);
+    a.first = g->sample_base[(size_t)file] + first; a.n = n; a.out = static_cast<double*>(g->buf[kGenAudioOut].p);
     PE_HIP(e, launch_gen_mix(a, nullptr));
-    PE_HIP(e, hipMemcpy(out_host, g->audio_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    PE_HIP(e, hipMemcpy(out_host, g->buf[kGenAudioOut].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return PE_OK;
 }
 
@@ -4502,20 +4538,25 @@ int pe_generator_append(pe_generator* g, pe_trainer* trainer, int32_t source, co
     const char* who = "pe_generator_append";
     if (!g) return PE_ERR_INVALID;
     pe_engine* e = g->e;
-    if (!trainer || (n > 0 && !targets)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
-    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
-    if (trainer->device != e->device) return fail(e, PE_ERR_INVALID, "%s: the trainer lives on device %d, the engine on %d", who, trainer->device, e->device);
-    if (trainer->F != width || trainer->T != e->prm.n_features)
-        return fail(e, PE_ERR_INVALID, "%s: the trainer takes [%d][%d] inputs, the engine's windows are [%d][%d]", who, trainer->T, trainer->F, e->prm.n_features, width);
-    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
-    for (int32_t i = 0; i < n; ++i)
-        if (!(targets[i] >= 0.0f && targets[i] <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: targets[%d] = %g is outside [0, 1]", who, i, (double)targets[i]);
+    if (n > 0 && !targets) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    int rc;
+    if ((rc = check_append(e, who, trainer, source)) || (rc = check_targets(e, who, targets, n))) return rc;
     return generator_rows(g, who, ids, targets, n, nullptr, trainer, source);
 }
 
 }  // extern "C"
 
 // ---- noise augmentation (pe_augmenter; kernels: augment_device.h) ---------------------------------------------
+namespace {
+enum AugmenterBuf {
+    // resident: the two pools as given
+    kAugClips, kAugNoise,
+    // grown on demand: the chains' tables and sums; of a pass: its copies, pieces and piece prefix, the reloaded samples, the clip
+    // table, the front end's rows, the trainer's rows and targets; pe_augmenter_audio's samples; the plan's overflow counts
+    kAugTables, kAugSums, kAugSlots, kAugPassPieces, kAugReloaded, kAugDesc, kAugRows, kAugPacked, kAugTargets, kAugMixed, kAugPcm, kAugOverflow, kAugBufCount
+};
+}  // namespace
+
 struct pe_augmenter {
     pe_engine* e = nullptr;                             // null: a session that checks plans only
     int n_clips = 0, n_noise = 0;
@@ -4525,39 +4566,13 @@ struct pe_augmenter {
     std::vector<pe_aug_copy> copies;
     std::vector<pe_aug_piece> pieces;
     std::vector<double> noise_volume;
-    // resident: the two pools as given
-    DeviceBuf clips, noise;
-    // grown on demand: the chains' tables and sums; of a pass: its copies, pieces and piece prefix, the reloaded samples, the clip
-    // table, the front end's rows, the trainer's rows and targets; pe_augmenter_audio's samples; the plan's overflow counts
-    DeviceBuf tables, sums, slots, pass_pieces, reloaded, desc, rows, packed, targets, mixed, pcm, overflow;
+    DeviceBuf buf[kAugBufCount];                        // AugmenterBuf
     int64_t copy_length(int32_t o) const { const int32_t c = copies[(size_t)o].clip; return clip_offsets[(size_t)c + 1] - clip_offsets[(size_t)c]; }
 };
 
 namespace {
 
-void augmenter_free(pe_augmenter* g) {
-    if (pe_engine* e = g->e) {
-        (void)hipSetDevice(e->device);
-        (void)hipDeviceSynchronize();
-        for (DeviceBuf* b : {&g->clips, &g->noise, &g->tables, &g->sums, &g->slots, &g->pass_pieces, &g->reloaded, &g->desc, &g->rows, &g->packed,
-                             &g->targets, &g->mixed, &g->pcm, &g->overflow})
-            if (b->p) { (void)hipFree(b->p); e->device_bytes -= (int64_t)b->bytes; }
-    }
-    delete g;
-}
-
-// offsets[n + 1] of a pool whose entries must all hold samples
-int augmenter_check_pool(pe_engine* e, const char* who, const char* what, const int64_t* offsets, int32_t n) {
-    if (n < 1) return fail(e, PE_ERR_INVALID, "%s: %d %ss (at least one is needed)", who, n, what);
-    if (!offsets) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
-    if (offsets[0] != 0) return fail(e, PE_ERR_INVALID, "%s: %s offsets[0] must be 0, got %lld", who, what, (long long)offsets[0]);
-    for (int32_t r = 0; r < n; ++r) {
-        if (offsets[r + 1] < offsets[r])
-            return fail(e, PE_ERR_INVALID, "%s: offsets decrease at %s %d (%lld after %lld)", who, what, r, (long long)offsets[r + 1], (long long)offsets[r]);
-        if (offsets[r + 1] == offsets[r]) return fail(e, PE_ERR_INVALID, "%s: %s %d is empty", who, what, r);
-    }
-    return PE_OK;
-}
+void augmenter_free(pe_augmenter* g) { if (g->e) release_buffers(g->e, g->buf, kAugBufCount); delete g; }
 
 // Copies ids[0 .. k) as one pass: their slots, pieces and piece prefix go up, aug_mix writes what the caller asks for.
 // slot_begin[k + 1]: where every copy starts among the pass's samples.
@@ -4583,15 +4598,15 @@ int augmenter_mix(pe_augmenter* g, const int32_t* ids, int k, std::vector<int64_
     if (pieces.size() > 0x7fffffffu) return fail(e, PE_ERR_INVALID, "pe_augmenter: a pass of %d copies holds more than 2^31 - 1 pieces", k);
     int rc;
     const size_t pb = pieces.size() * sizeof(AugPiece), xb = prefix.size() * sizeof(int64_t);
-    if ((rc = ensure(e, g->slots, slots.size() * sizeof(AugSlot)))) return rc;
-    if ((rc = ensure(e, g->pass_pieces, pb + xb))) return rc;
-    PE_HIP(e, hipMemcpy(g->slots.p, slots.data(), slots.size() * sizeof(AugSlot), hipMemcpyHostToDevice));
-    PE_HIP(e, hipMemcpy(g->pass_pieces.p, pieces.data(), pb, hipMemcpyHostToDevice));
-    PE_HIP(e, hipMemcpy(static_cast<char*>(g->pass_pieces.p) + pb, prefix.data(), xb, hipMemcpyHostToDevice));
+    if ((rc = ensure(e, g->buf[kAugSlots], slots.size() * sizeof(AugSlot)))) return rc;
+    if ((rc = ensure(e, g->buf[kAugPassPieces], pb + xb))) return rc;
+    PE_HIP(e, hipMemcpy(g->buf[kAugSlots].p, slots.data(), slots.size() * sizeof(AugSlot), hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(g->buf[kAugPassPieces].p, pieces.data(), pb, hipMemcpyHostToDevice));
+    PE_HIP(e, hipMemcpy(static_cast<char*>(g->buf[kAugPassPieces].p) + pb, prefix.data(), xb, hipMemcpyHostToDevice));
     AugMixArgs a{};
-    a.clips = static_cast<const float*>(g->clips.p); a.noise = static_cast<const float*>(g->noise.p);
-    a.slots = static_cast<const AugSlot*>(g->slots.p); a.pieces = static_cast<const AugPiece*>(g->pass_pieces.p);
-    a.prefix = reinterpret_cast<const long long*>(static_cast<const char*>(g->pass_pieces.p) + pb);
+    a.clips = static_cast<const float*>(g->buf[kAugClips].p); a.noise = static_cast<const float*>(g->buf[kAugNoise].p);
+    a.slots = static_cast<const AugSlot*>(g->buf[kAugSlots].p); a.pieces = static_cast<const AugPiece*>(g->buf[kAugPassPieces].p);
+    a.prefix = reinterpret_cast<const long long*>(static_cast<const char*>(g->buf[kAugPassPieces].p) + pb);
     a.n_pieces = (int)pieces.size(); a.n = prefix.back();
     a.reloaded = reloaded; a.mixed = mixed; a.pcm = pcm; a.overflowed = overflowed;
     PE_HIP(e, launch_aug_mix(a, nullptr));
@@ -4633,7 +4648,7 @@ int augmenter_rows(pe_augmenter* g, const char* who, const int32_t* ids, const f
     if (n == 0) return PE_OK;
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
-    const int T = e->prm.n_features, width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
+    const int T = e->prm.n_features, width = window_floats(e);
     std::vector<int64_t> begin;
     std::vector<ClipDesc> desc;
     std::vector<uint32_t> prefix;
@@ -4642,42 +4657,27 @@ int augmenter_rows(pe_augmenter* g, const char* who, const int32_t* ids, const f
         const int k = i1 - i0;
         int64_t n_samples = 0;
         for (int32_t i = i0; i < i1; ++i) n_samples += g->copy_length(ids[i]);
-        if ((rc = ensure(e, g->reloaded, (size_t)n_samples * sizeof(float)))) return rc;
-        if ((rc = augmenter_mix(g, ids + i0, k, begin, static_cast<float*>(g->reloaded.p), nullptr, nullptr, nullptr))) return rc;
+        if ((rc = ensure(e, g->buf[kAugReloaded], (size_t)n_samples * sizeof(float)))) return rc;
+        if ((rc = augmenter_mix(g, ids + i0, k, begin, static_cast<float*>(g->buf[kAugReloaded].p), nullptr, nullptr, nullptr))) return rc;
         desc.resize((size_t)k); prefix.resize((size_t)k + 1);
         uint32_t tasks = 0;
         for (int i = 0; i < k; ++i) {
-            const int64_t len = begin[(size_t)i + 1] - begin[(size_t)i];
-            const int64_t cut = max_samples > 0 && len > max_samples ? max_samples : len;          // vectorize: audio[-max_samples:]
-            const int64_t frames = frames_of_buffer(e->prm, cut);
-            const int64_t kept = frames < T ? frames : T;                                          // ... feats[-n_features:]
-            desc[(size_t)i] = ClipDesc{begin[(size_t)i + 1] - cut, (int)(frames - kept), (int)kept, (int)(T - kept), 0};
             prefix[(size_t)i] = tasks;
-            tasks += (uint32_t)kept;
+            desc[(size_t)i] = clip_desc(e->prm, T, begin[(size_t)i + 1], begin[(size_t)i + 1] - begin[(size_t)i], max_samples, tasks);
         }
         prefix[(size_t)k] = tasks;
-        const size_t db = (size_t)k * sizeof(ClipDesc), pb = ((size_t)k + 1) * sizeof(uint32_t);
-        if ((rc = ensure(e, g->desc, db + pb))) return rc;
-        if ((rc = ensure(e, g->rows, (size_t)k * T * e->row_floats * sizeof(float)))) return rc;
-        if ((rc = ensure(e, g->packed, (size_t)k * T * width * sizeof(float)))) return rc;
-        PE_HIP(e, hipMemcpy(g->desc.p, desc.data(), db, hipMemcpyHostToDevice));
-        PE_HIP(e, hipMemcpy(static_cast<char*>(g->desc.p) + db, prefix.data(), pb, hipMemcpyHostToDevice));
-        const ClipTable ct{static_cast<const ClipDesc*>(g->desc.p), reinterpret_cast<const uint32_t*>(static_cast<const char*>(g->desc.p) + db),
-                           k, tasks, g->reloaded.p, 1};
-        if ((rc = launch_clip_front_end(e, ct, nullptr, static_cast<float*>(g->rows.p), nullptr))) return rc;
-        MineGatherArgs a{};
-        a.T = T; a.F = e->n_in; a.use_delta = e->prm.use_delta ? 1 : 0; a.row_floats = e->row_floats;
-        a.rows = static_cast<const float*>(g->rows.p); a.n = k; a.out = static_cast<float*>(g->packed.p);
+        if ((rc = ensure(e, g->buf[kAugRows], (size_t)k * T * e->row_floats * sizeof(float)))) return rc;
+        if ((rc = ensure(e, g->buf[kAugPacked], (size_t)k * T * width * sizeof(float)))) return rc;
+        ClipTable ct;
+        PE_HIP(e, upload_task_table(e, g->buf[kAugDesc], desc, prefix, g->buf[kAugReloaded].p, 1, ct, rc));
+        if (rc) return rc;
+        if ((rc = launch_clip_front_end(e, ct, nullptr, static_cast<float*>(g->buf[kAugRows].p), nullptr))) return rc;
+        MineGatherArgs a = gather_geometry(e);
+        a.rows = static_cast<const float*>(g->buf[kAugRows].p); a.n = k; a.out = static_cast<float*>(g->buf[kAugPacked].p);
         PE_HIP(e, launch_mine_gather(a, nullptr));
         if (feats_out_host) {
-            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)i0 * T * width, g->packed.p, (size_t)k * T * width * sizeof(float), hipMemcpyDeviceToHost));
-        } else {
-            if ((rc = ensure(e, g->targets, (size_t)k * sizeof(float)))) return rc;
-            PE_HIP(e, hipMemcpy(g->targets.p, targets + i0, (size_t)k * sizeof(float), hipMemcpyHostToDevice));
-            PE_HIP(e, hipStreamSynchronize(nullptr));
-            const int trc = train_append_device_targets(trainer, who, source, a.out, static_cast<const float*>(g->targets.p), k);
-            if (trc) return fail(e, trc, "%s", trainer->err.c_str());
-        }
+            PE_HIP(e, hipMemcpy(feats_out_host + (size_t)i0 * T * width, g->buf[kAugPacked].p, (size_t)k * T * width * sizeof(float), hipMemcpyDeviceToHost));
+        } else if ((rc = rows_to_trainer(e, who, trainer, source, a.out, targets + i0, k, g->buf[kAugTargets]))) return rc;
         PE_HIP(e, hipStreamSynchronize(nullptr));               // the next pass reuses the samples and the tables
         i0 = i1;
     }
@@ -4695,8 +4695,8 @@ int pe_augmenter_create(pe_engine* e, const float* clip_audio, const int64_t* cl
     *out = nullptr;
     if (e && mel_rows(e)) return fail(e, PE_ERR_UNSUPPORTED, "%s: this session has no Vectorizer.mels form (its windows are MFCC rows); create it over an mfccs engine", who);
     int rc;
-    if ((rc = augmenter_check_pool(e, who, "clip", clip_offsets, n_clips))) return rc;
-    if ((rc = augmenter_check_pool(e, who, "noise recording", noise_offsets, n_noise))) return rc;
+    if ((rc = check_offsets(e, who, "clip", clip_offsets, n_clips, true))) return rc;
+    if ((rc = check_offsets(e, who, "noise recording", noise_offsets, n_noise, true))) return rc;
     if (e && (!clip_audio || !noise_audio)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
     pe_augmenter* g = new pe_augmenter;
     g->e = e; g->n_clips = n_clips; g->n_noise = n_noise;
@@ -4710,18 +4710,18 @@ int pe_augmenter_create(pe_engine* e, const float* clip_audio, const int64_t* cl
     do {
         if ((herr = hipSetDevice(e->device)) != hipSuccess) break;
         if ((rc = drain_async(e))) break;
-        if ((rc = ensure(e, g->clips, (size_t)clip_samples * sizeof(float)))) break;
-        if ((rc = ensure(e, g->noise, (size_t)noise_samples * sizeof(float)))) break;
-        if ((rc = ensure(e, g->tables, ((size_t)n_clips + 1) * sizeof(int64_t)))) break;
-        if ((rc = ensure(e, g->sums, (size_t)n_clips * sizeof(float)))) break;
-        if ((herr = hipMemcpy(g->clips.p, clip_audio, (size_t)clip_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
-        if ((herr = hipMemcpy(g->noise.p, noise_audio, (size_t)noise_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
-        if ((herr = hipMemcpy(g->tables.p, clip_offsets, ((size_t)n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((rc = ensure(e, g->buf[kAugClips], (size_t)clip_samples * sizeof(float)))) break;
+        if ((rc = ensure(e, g->buf[kAugNoise], (size_t)noise_samples * sizeof(float)))) break;
+        if ((rc = ensure(e, g->buf[kAugTables], ((size_t)n_clips + 1) * sizeof(int64_t)))) break;
+        if ((rc = ensure(e, g->buf[kAugSums], (size_t)n_clips * sizeof(float)))) break;
+        if ((herr = hipMemcpy(g->buf[kAugClips].p, clip_audio, (size_t)clip_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((herr = hipMemcpy(g->buf[kAugNoise].p, noise_audio, (size_t)noise_samples * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((herr = hipMemcpy(g->buf[kAugTables].p, clip_offsets, ((size_t)n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
         AugEnergyArgs a{};                                      // S_a of every clip: it does not depend on the plan
-        a.pool = static_cast<const float*>(g->clips.p); a.offsets = static_cast<const long long*>(g->tables.p);
-        a.n = n_clips; a.sum_f32 = static_cast<float*>(g->sums.p);
+        a.pool = static_cast<const float*>(g->buf[kAugClips].p); a.offsets = static_cast<const long long*>(g->buf[kAugTables].p);
+        a.n = n_clips; a.sum_f32 = static_cast<float*>(g->buf[kAugSums].p);
         if ((herr = launch_aug_energy_clips(a, nullptr)) != hipSuccess) break;
-        herr = hipMemcpy(sums.data(), g->sums.p, (size_t)n_clips * sizeof(float), hipMemcpyDeviceToHost);
+        herr = hipMemcpy(sums.data(), g->buf[kAugSums].p, (size_t)n_clips * sizeof(float), hipMemcpyDeviceToHost);
     } while (false);
     if (!rc && herr != hipSuccess) rc = fail(e, PE_ERR_HIP, "%s: %s", who, hipGetErrorString(herr));
     if (rc) { augmenter_free(g); return rc; }
@@ -4782,14 +4782,14 @@ int pe_augmenter_set_plan(pe_augmenter* g, const pe_aug_copy* copies, int32_t n_
         PE_DRAIN(e);
         int rc;
         const size_t sb = (size_t)n_copies * sizeof(double), zb = (size_t)n_copies * sizeof(int32_t);
-        if ((rc = ensure(e, g->tables, tab.size() * sizeof(int64_t)))) return rc;
-        if ((rc = ensure(e, g->sums, sb + zb))) return rc;
-        PE_HIP(e, hipMemcpy(g->tables.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if ((rc = ensure(e, g->buf[kAugTables], tab.size() * sizeof(int64_t)))) return rc;
+        if ((rc = ensure(e, g->buf[kAugSums], sb + zb))) return rc;
+        PE_HIP(e, hipMemcpy(g->buf[kAugTables].p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
         AugEnergyArgs a{};
-        a.pool = static_cast<const float*>(g->noise.p);
-        a.first_piece = static_cast<const long long*>(g->tables.p); a.piece_prefix = a.first_piece + n_copies + 1; a.piece_src = a.piece_prefix + n_pieces + 1;
-        a.n = n_copies; a.sum_f64 = static_cast<double*>(g->sums.p);
-        a.zero = reinterpret_cast<int32_t*>(static_cast<char*>(g->sums.p) + sb);
+        a.pool = static_cast<const float*>(g->buf[kAugNoise].p);
+        a.first_piece = static_cast<const long long*>(g->buf[kAugTables].p); a.piece_prefix = a.first_piece + n_copies + 1; a.piece_src = a.piece_prefix + n_pieces + 1;
+        a.n = n_copies; a.sum_f64 = static_cast<double*>(g->buf[kAugSums].p);
+        a.zero = reinterpret_cast<int32_t*>(static_cast<char*>(g->buf[kAugSums].p) + sb);
         PE_HIP(e, launch_aug_energy_copies(a, nullptr));
         std::vector<int32_t> zero((size_t)n_copies);
         PE_HIP(e, hipMemcpy(vn.data(), a.sum_f64, sb, hipMemcpyDeviceToHost));
@@ -4818,19 +4818,19 @@ int pe_augmenter_volumes(pe_augmenter* g, double* clip_volume, double* noise_vol
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
     int rc;
-    if ((rc = ensure(e, g->overflow, (size_t)n * sizeof(unsigned long long)))) return rc;
-    PE_HIP(e, hipMemsetAsync(g->overflow.p, 0, (size_t)n * sizeof(unsigned long long), nullptr));
+    if ((rc = ensure(e, g->buf[kAugOverflow], (size_t)n * sizeof(unsigned long long)))) return rc;
+    PE_HIP(e, hipMemsetAsync(g->buf[kAugOverflow].p, 0, (size_t)n * sizeof(unsigned long long), nullptr));
     std::vector<int32_t> ids((size_t)n);
     for (int32_t o = 0; o < n; ++o) ids[(size_t)o] = o;
     std::vector<int64_t> begin;
     for (int32_t i0 = 0; i0 < n;) {             // the mix of every copy, nothing written but the counts
         const int32_t i1 = augmenter_pass_end(g, ids.data(), i0, n);
-        if ((rc = augmenter_mix(g, ids.data() + i0, i1 - i0, begin, nullptr, nullptr, nullptr, static_cast<unsigned long long*>(g->overflow.p)))) return rc;
+        if ((rc = augmenter_mix(g, ids.data() + i0, i1 - i0, begin, nullptr, nullptr, nullptr, static_cast<unsigned long long*>(g->buf[kAugOverflow].p)))) return rc;
         PE_HIP(e, hipStreamSynchronize(nullptr));
         i0 = i1;
     }
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied out as they are");
-    PE_HIP(e, hipMemcpy(overflowed, g->overflow.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    PE_HIP(e, hipMemcpy(overflowed, g->buf[kAugOverflow].p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
     return PE_OK;
 }
 
@@ -4844,13 +4844,13 @@ int pe_augmenter_audio(pe_augmenter* g, int32_t copy, double* mixed_out, int16_t
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
     const int64_t len = g->copy_length(copy);
-    if (mixed_out && (rc = ensure(e, g->mixed, (size_t)len * sizeof(double)))) return rc;
-    if (pcm_out && (rc = ensure(e, g->pcm, (size_t)len * sizeof(int16_t)))) return rc;
+    if (mixed_out && (rc = ensure(e, g->buf[kAugMixed], (size_t)len * sizeof(double)))) return rc;
+    if (pcm_out && (rc = ensure(e, g->buf[kAugPcm], (size_t)len * sizeof(int16_t)))) return rc;
     std::vector<int64_t> begin;
-    if ((rc = augmenter_mix(g, &copy, 1, begin, nullptr, mixed_out ? static_cast<double*>(g->mixed.p) : nullptr,
-                            pcm_out ? static_cast<int16_t*>(g->pcm.p) : nullptr, nullptr))) return rc;
-    if (mixed_out) PE_HIP(e, hipMemcpy(mixed_out, g->mixed.p, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
-    if (pcm_out) PE_HIP(e, hipMemcpy(pcm_out, g->pcm.p, (size_t)len * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if ((rc = augmenter_mix(g, &copy, 1, begin, nullptr, mixed_out ? static_cast<double*>(g->buf[kAugMixed].p) : nullptr,
+                            pcm_out ? static_cast<int16_t*>(g->buf[kAugPcm].p) : nullptr, nullptr))) return rc;
+    if (mixed_out) PE_HIP(e, hipMemcpy(mixed_out, g->buf[kAugMixed].p, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    if (pcm_out) PE_HIP(e, hipMemcpy(pcm_out, g->buf[kAugPcm].p, (size_t)len * sizeof(int16_t), hipMemcpyDeviceToHost));
     return PE_OK;
 }
 
@@ -4866,14 +4866,9 @@ int pe_augmenter_append(pe_augmenter* g, pe_trainer* trainer, int32_t source, co
     if (!g) return PE_ERR_INVALID;
     pe_engine* e = g->e;
     if (!e) return fail(e, PE_ERR_INVALID, "%s: the session was created without an engine: it checks plans only", who);
-    if (!trainer || (n > 0 && !targets)) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
-    const int width = e->prm.use_delta ? 2 * e->n_in : e->n_in;
-    if (trainer->device != e->device) return fail(e, PE_ERR_INVALID, "%s: the trainer lives on device %d, the engine on %d", who, trainer->device, e->device);
-    if (trainer->F != width || trainer->T != e->prm.n_features)
-        return fail(e, PE_ERR_INVALID, "%s: the trainer takes [%d][%d] inputs, the engine's windows are [%d][%d]", who, trainer->T, trainer->F, e->prm.n_features, width);
-    if (source != PE_TRAIN_SOURCE_DATA && source != PE_TRAIN_SOURCE_VALIDATION) return fail(e, PE_ERR_INVALID, "%s: source = %d", who, source);
-    for (int32_t i = 0; i < n; ++i)
-        if (!(targets[i] >= 0.0f && targets[i] <= 1.0f)) return fail(e, PE_ERR_INVALID, "%s: targets[%d] = %g is outside [0, 1]", who, i, (double)targets[i]);
+    if (n > 0 && !targets) return fail(e, PE_ERR_INVALID, "null argument to %s", who);
+    int rc;
+    if ((rc = check_append(e, who, trainer, source)) || (rc = check_targets(e, who, targets, n))) return rc;
     return augmenter_rows(g, who, ids, targets, n, max_samples, nullptr, trainer, source);
 }
 

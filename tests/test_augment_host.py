@@ -239,15 +239,19 @@ def test_create_refuses_empty_recordings_by_name():
     create = lambda co, no: lib.pe_augmenter_create(None, audio.ctypes.data, co.ctypes.data, co.size - 1, audio.ctypes.data, no.ctypes.data,
                                                     no.size - 1, ctypes.byref(h))
     err = lambda: lib.pe_last_global_error().decode()
-    assert create(off(0, 4, 4, 10), off(0, 10)) == INVALID and 'clip 1 is empty' in err() and not h.value
+    assert create(off(0, 4, 4, 10), off(0, 10)) == INVALID and err() == 'pe_augmenter_create: clip 1 is empty' and not h.value
     assert create(off(0, 4, 10), off(0, 0, 10)) == INVALID and 'noise recording 0 is empty' in err()
-    assert create(off(0, 4, 10), off(0)) == INVALID and '0 noise recordings' in err()
+    assert create(off(0, 4, 10), off(0)) == INVALID and err() == 'pe_augmenter_create: 0 noise recordings (at least one is needed)'
     assert create(off(0), off(0, 10)) == INVALID and '0 clips' in err()
-    assert create(off(1, 4), off(0, 10)) == INVALID and 'offsets[0]' in err()
-    assert create(off(0, 4, 2), off(0, 10)) == INVALID and 'decrease at clip 1' in err()
+    assert create(off(1, 4), off(0, 10)) == INVALID and err() == 'pe_augmenter_create: clip offsets[0] must be 0, got 1'
+    assert create(off(0, 4, 2), off(0, 10)) == INVALID and err() == 'pe_augmenter_create: offsets decrease at clip 1 (2 after 4)'
     assert lib.pe_augmenter_create(None, audio.ctypes.data, off(0, 4).ctypes.data, 1, audio.ctypes.data, off(0, 10).ctypes.data, 1, None) == INVALID
     assert create(off(0, 4, 10), off(0, 10)) == 0 and h.value
     assert lib.pe_augmenter_destroy(h) == 0
+    # a null session is refused before anything is read, whatever else is null
+    assert lib.pe_miner_vectorize(None, None, 0, None) == INVALID
+    assert lib.pe_generator_append(None, None, 0, None, None, 0) == INVALID
+    assert lib.pe_augmenter_append(None, None, 0, None, None, 0, 0) == INVALID
 
 
 def test_the_augmenter_symbols_are_declared_and_exported():
