@@ -1,6 +1,11 @@
 """What precise-train-generated does with its audio, restated with numpy and real generators (not a test; imported by
 test_generated*.py).  The slow, obviously-right version: the planner and the device are held to it.
 
+Held in turn to the script itself: tests/golden/train_generated.npz is what the reference's own
+``TrainGeneratedScript.vectors_from_fn`` gave over five background files on one script object (tools/make_script_fixtures.py),
+and test_generated_host.py asks this restatement for the same labels, draws per file, clips pulled, run summaries, merged audio
+bits and emitted windows -- and that ``mode='tail'`` and ``save_draw=False`` do NOT give them.
+
 Written from the script's contract (scripts/train_generated.py:118-202, util.py:30-32):
   * a file's volume is rms(audio) * (0.4 + 0.5 * random()); audio and every clip are scaled `volume * x / rms(x)`, which is
     float32 arithmetic on the float32 arrays load_audio returns;
@@ -169,3 +174,13 @@ def draws():
     int(16000 * 0.7) samples; then a fixed pseudo-random tail"""
     tail = random.Random(5)
     return [0.37, 0.9, 0.1] + [tail.random() for _ in range(4000)]
+
+
+# ---- the script's own stream: tests/golden/train_generated.npz ----------------------------------------------------------------
+def fixture_pools(g, C):
+    """the fixture's int16 pools as load_audio returns them -> (backgrounds, positives, negatives, draws)"""
+    k = '_%d' % C
+    cut = lambda pcm, off: [pcm[a:b].astype(np.float32) / float(np.iinfo(np.int16).max) for a, b in zip(off[:-1], off[1:])]
+    clips = cut(g['clip_pcm' + k], g['clip_offsets' + k])
+    n_pos = int(g['n_positives' + k])
+    return cut(g['background_pcm' + k], g['background_offsets' + k]), clips[:n_pos], clips[n_pos:], g['draws' + k].tolist()

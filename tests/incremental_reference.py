@@ -6,6 +6,11 @@ Written from the script's contract (scripts/train_incremental.py:113-137, util.p
   * a saved ring goes through int16: q = (x * 32767.0).astype(int16) (truncation toward zero), y = float32(q) / float32(32767);
   * per recording a flag says whether its hits go to the test set; after EVERY chunk `not test and count >= delay_samples and
     epochs > 0` retrains and resets the count; hits of test recordings count but never trigger.
+
+Held in turn to the script itself: tests/golden/train_incremental.npz is what the reference's own
+``TrainIncrementalScript.train_on_audio`` did over four recordings on one script object (tools/make_script_fixtures.py), and
+test_mining_host.py asks ``policy_loop``, ``rings`` and ``saved_pcm`` for the same hits, saved int16 rings and retrain points --
+and that ``rings(..., carry_audio=False)`` does NOT give them.
 """
 import numpy as np
 
@@ -25,10 +30,14 @@ def chunks(audio, chunk_size: int):
         yield audio[end - chunk_size:end]
 
 
+def saved_pcm(ring) -> np.ndarray:
+    """save_audio: the int16 samples a float64 ring is written as"""
+    return (np.asarray(ring, dtype=np.float64) * 32767.0).astype(np.int16)
+
+
 def round_trip(ring) -> np.ndarray:
     """save_audio then load_audio: float64 ring -> float32 samples"""
-    q = (np.asarray(ring, dtype=np.float64) * 32767.0).astype(np.int16)
-    return q.astype(np.float32) / np.float32(32767.0)
+    return saved_pcm(ring).astype(np.float32) / np.float32(32767.0)
 
 
 def rings(audios, chunk_size: int, buffer_samples: int, carry_audio: bool = True, only=None) -> list:
@@ -78,3 +87,9 @@ def policy_loop(audios, test_flags, chunk_size, buffer_samples, delay_samples, e
                 retrains.append((r, i))
                 retrain(saved)
     return hits, retrains, saved, count
+
+
+def fixture_recordings(g):
+    """the fixture's int16 recordings as load_audio returns them"""
+    off = g['offsets']
+    return [g['pcm'][a:b].astype(np.float32) / float(np.iinfo(np.int16).max) for a, b in zip(off[:-1], off[1:])]

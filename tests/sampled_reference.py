@@ -1,7 +1,12 @@
 """The loop of precise-train-sampled (scripts/train_sampled.py:54-90) restated in numpy over the PUBLIC API of a ``Trainer``:
 ``predict`` from host memory, the failed and remaining sets by hash, a pluggable order in front of the script's ``islice``,
 the metrics line, and ``fit`` on host copies of the selected rows.  ``test_sampled.py`` runs it on a second trainer with the
-same seed and initial weights and asks ``SampledTrainer`` for the same selection, lines, file and weights."""
+same seed and initial weights and asks ``SampledTrainer`` for the same selection, lines, file and weights.
+
+Held in turn to the script itself: tests/golden/train_sampled.npz is what the reference's own ``TrainScript.load_sample_data``,
+``TrainSampledScript.choose_new_samples`` and ``write_sampling_metrics`` gave in two cycles taken by hand
+(tools/make_script_fixtures.py); test_sampled_host.py asks for the same hash table (the LAST duplicate wins; the first does NOT
+reproduce it), remaining failed rows, counts and metrics lines."""
 import hashlib
 from itertools import islice
 

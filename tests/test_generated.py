@@ -289,3 +289,46 @@ def test_the_library_checks_its_arguments_itself():
     eng.close()
     with pytest.raises(ValueError):
         gen.vectorize([0])
+
+
+# ---- the script itself: tests/golden/train_generated.npz (tools/make_script_fixtures.py) --------------------------------------
+@pytest.mark.parametrize('C', [512, 2048])
+def test_generator_equals_the_scripts_own_stream(model_file, C):
+    """TrainGeneratedScript.vectors_from_fn's own output over five background files: the planner replays its draws, the mix
+    gives its merged chunks bit for bit, the ids and targets are its labels, and the rows are its windows within TOL_FEAT32 --
+    what tests/test_gpu_parity.py asks of float32 ring rows against the reference's Listener -- and, bit for bit as in
+    test_rows_equal_the_listener_per_chunk, the project's Listener fed the same chunks."""
+    from conftest import golden
+    from test_gpu_parity import TOL_FEAT32
+    g = golden('train_generated.npz')
+    k = '_%d' % C
+    backgrounds, positives, negatives, fixture_draws = ref.fixture_pools(g, C)
+    labels, offsets, audio_ids = g['label' + k], g['chunk_offsets' + k], g['audio_ids' + k]
+    runner = HipRunner(weights=weights())
+    gen = Generator(runner, backgrounds, positives, negatives, chunk_size=C, buffer_samples=int(g['buffer_samples']))
+    plan = gen.plan(ref.CountingRng(fixture_draws))
+    assert plan.n_draws == int(g['file_draws' + k].sum()) and plan.chunk_offsets.tolist() == offsets.tolist()
+    assert plan.ids.tolist() == np.flatnonzero(labels >= 0).tolist() and plan.targets.tolist() == labels[labels >= 0].tolist()
+    assert set(plan.targets.tolist()) == {0.0, 1.0} and plan.ids.size < plan.n_chunks
+    gen.load(plan)
+    mixed = [gen.audio(f) for f in range(len(backgrounds))]
+    file_of = np.searchsorted(offsets, audio_ids, side='right') - 1
+    assert set(file_of.tolist()) == set(range(len(backgrounds)))
+    for n, (f, chunk) in enumerate(zip(file_of.tolist(), audio_ids.tolist())):
+        i = chunk - int(offsets[f])
+        got = mixed[f][i * C:(i + 1) * C]
+        assert got.dtype == np.float64 and got.tobytes() == g['audio' + k][n * C:(n + 1) * C].tobytes(), (f, i)
+    rows = gen.vectorize(plan.ids)
+    want = g['windows' + k]
+    assert rows.dtype == np.float32 and rows.shape == want.shape
+    worst = float(np.abs(rows.astype(np.float64) - want).max())
+    print('C=%d: %d rows, worst |row - the script\'s window| %.3g (bound %.3g)' % (C, len(rows), worst, TOL_FEAT32))
+    assert worst <= TOL_FEAT32
+    lis = Listener(model_file, C)
+    windows = []
+    for audio in mixed:
+        lis.clear()
+        for i in range(audio.size // C):
+            windows.append(lis.update_vectors(audio[i * C:(i + 1) * C]).astype(np.float32))
+    assert rows.tobytes() == np.stack(windows)[plan.ids].tobytes()
+    gen.close()

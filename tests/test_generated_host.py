@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 
 import generated_reference as ref
-from conftest import REPO
+from conftest import REPO, golden
 from mycroft_precise_amd import _build, _lib
 from mycroft_precise_amd.generated import Generator, RunLabels
 
-from generated_reference import B, LONG_CLIP, draws, inputs, tone
+from generated_reference import B, LONG_CLIP, draws, fixture_pools, inputs, tone
 
 
 class Provenance(ref.Script):
@@ -202,3 +202,78 @@ def test_the_generator_symbols_are_declared_and_exported():
     for n in names:
         assert hasattr(raw, n) and n in _lib.EXPORTS
     assert _lib.GEN_FILE.itemsize == 40 and _lib.GEN_SEGMENT.itemsize == 40
+
+
+# ---- the script itself: tests/golden/train_generated.npz (tools/make_script_fixtures.py) --------------------------------------
+def restated_stream(g, C, mode='reference', save_draw=True):
+    """the restatement over the fixture's pools and draws, in the fixture's own terms"""
+    from oracle import listener as ol
+    backgrounds, positives, negatives, draws = fixture_pools(g, C)
+    rng = ref.CountingRng(draws)
+    script = ref.Script(positives, negatives, rng, C, int(g['buffer_samples']), mode=mode, save_draw=save_draw)
+    lis = ol.OracleListener(None)
+    keep = set(g['audio_ids_%d' % C].tolist())
+    out = {name: [] for name in ('label', 'ones', 'last', 'max_run', 'vals_len', 'file_draws', 'file_taken', 'audio', 'windows')}
+    chunk_offsets = [0]
+    for audio in backgrounds:
+        draws_before, taken_before, n = rng.n, len(script.taken), 0
+        lis.clear()
+        for i, chunk, _, targets, label in script.vectors_from(audio):
+            window = lis.update_vectors(chunk)
+            out['label'].append(label)
+            out['ones'].append(int(np.count_nonzero(targets == 1)))
+            out['last'].append(int(script.vals_buffer[-1]))
+            out['max_run'].append(int(ref.max_run_length(script.vals_buffer, 1)))
+            out['vals_len'].append(len(script.vals_buffer))
+            if chunk_offsets[-1] + i in keep:
+                assert chunk.dtype == np.float64
+                out['audio'].append(chunk)
+            if label >= 0:
+                out['windows'].append(window)
+            n += 1
+        chunk_offsets.append(chunk_offsets[-1] + n)
+        out['file_draws'].append(rng.n - draws_before)
+        out['file_taken'].append(len(script.taken) - taken_before)
+    out['chunk_offsets'], out['taken'] = chunk_offsets, script.taken
+    return out
+
+
+def stream_differences(g, C, got):
+    """the names of the fixture's arrays the restated stream does not reproduce exactly"""
+    k = '_%d' % C
+    bad = [name for name in ('label', 'ones', 'last', 'max_run', 'vals_len', 'file_draws', 'file_taken', 'chunk_offsets', 'taken')
+           if g[name + k].tolist() != list(got[name])]
+    audio = np.concatenate(got['audio']) if got['audio'] else np.zeros(0)
+    if audio.tobytes() != g['audio' + k].tobytes():
+        bad.append('audio')
+    windows = np.array(got['windows']).reshape(-1, 29, 13)
+    if not np.array_equal(windows, g['windows' + k]):          # (equality: what test_oracle.py asks of the Listener's ring)
+        bad.append('windows')
+    return bad
+
+
+@pytest.mark.parametrize('C', [512, 2048])
+def test_restatement_and_planner_equal_the_scripts_own_stream(C):
+    """TrainGeneratedScript.vectors_from_fn itself, over five background files on one script object: labels, draws per file,
+    clips pulled, run summaries, merged audio bits and the emitted windows."""
+    g = golden('train_generated.npz')
+    k = '_%d' % C
+    labels = g['label' + k]
+    assert set(labels.tolist()) == {1, 0, -1} and g['audio_ids' + k].size >= 10 and g['windows' + k].shape[0] == np.count_nonzero(labels >= 0)
+    lengths = np.diff(g['background_offsets' + k]).tolist()
+    clip_lengths = np.diff(g['clip_offsets' + k]).tolist()
+    assert C + 1 in lengths and 2 * C + 1 in lengths and C in clip_lengths and C - 1 in clip_lengths and max(clip_lengths) > 0.8 * B
+    assert stream_differences(g, C, restated_stream(g, C)) == []
+    # the wrong readings: each must fail against the fixture
+    tail = stream_differences(g, C, restated_stream(g, C, mode='tail'))
+    assert 'audio' in tail and 'label' in tail, tail
+    no_save = stream_differences(g, C, restated_stream(g, C, save_draw=False))
+    assert 'file_draws' in no_save, no_save
+    # the planner over the same pools and draws
+    backgrounds, positives, negatives, draws = fixture_pools(g, C)
+    plan = Generator(None, backgrounds, positives, negatives, chunk_size=C).plan(ref.CountingRng(draws))
+    assert plan.n_draws == int(g['file_draws' + k].sum()) and plan.chunk_offsets.tolist() == g['chunk_offsets' + k].tolist()
+    assert plan.ids.tolist() == np.flatnonzero(labels >= 0).tolist() and plan.targets.tolist() == labels[labels >= 0].tolist()
+    for mode, save in (('tail', True), ('reference', False)):
+        other = Generator(None, backgrounds, positives, negatives, chunk_size=C).plan(ref.CountingRng(draws), replay=mode, count_save_draw=save)
+        assert other.n_draws != plan.n_draws or other.ids.tolist() != plan.ids.tolist() or other.targets.tolist() != plan.targets.tolist()

@@ -637,3 +637,50 @@ def test_the_library_checks_its_arguments_itself():
         miner.scan()
     with pytest.raises(ValueError):
         Miner(HipRunner(weights=weights()), recordings(2048), buffer_samples=P.pr.max_samples + 1)
+
+
+# ---- the script itself: tests/golden/train_incremental.npz (tools/make_script_fixtures.py) ------------------------------------
+def test_miner_and_trainer_equal_the_scripts_own_run(stock_weights):
+    """TrainIncrementalScript.train_on_audio's own run over four recordings: the scan gives its hits, the hits' rows are
+    pe_vectorize_clips of the int16 clips save_audio wrote (the session hands a saved ring out as rows only), and
+    IncrementalTrainer, with a recorder in place of the fit, retrains where the script called retrain()."""
+    from conftest import golden
+    from test_gpu_parity import TOL_DECODE, TOL_RAW
+    g = golden('train_incremental.npz')
+    audios = ref.fixture_recordings(g)
+    C, B, delay, epochs = (int(g[n]) for n in ('chunk_size', 'buffer_samples', 'delay_samples', 'epochs'))
+    threshold = float(g['threshold'])
+    flags = (g['flag_draws'] > 0.8).tolist()
+    hits = [tuple(h) for h in g['hits'].tolist()]
+    ids = [int(g['chunk_starts'][r] + i) for r, i, _ in hits]
+    assert np.abs(g['conf'] - threshold).min() > TOL_DECODE and len(hits) >= 6 and B == P.pr.buffer_samples
+
+    runner = HipRunner(weights=stock_weights)
+    runner.engine.set_decoder(ThresholdDecoder(P.pr.threshold_config, P.pr.threshold_center))
+    miner = Miner(runner, audios, chunk_size=C)
+    assert miner.chunk_offsets.tolist() == g['chunk_starts'].tolist()
+    got, n_above, scores = miner.scan(threshold=threshold, return_scores=True)
+    worst = float(np.abs(scores.astype(np.float64) - g['raw'].astype(np.float64)).max())
+    print('%d chunks, worst |score - the script\'s raw output| %.3g, %d hits' % (scores.size, worst, got.size))
+    assert worst <= TOL_RAW
+    assert got.tolist() == ids and n_above == len(ids)
+    rec, chunk = miner.locate(got)
+    assert list(zip(rec.tolist(), chunk.tolist())) == [(r, i) for r, i, _ in hits]
+    clips = [pcm.astype(np.float32) / np.float32(32767.0) for pcm in g['saved']]             # load_audio of what save_audio wrote
+    assert miner.vectorize(got).tobytes() == runner.engine.vectorize_clips(clips, P.pr.max_samples).tobytes()
+    miner.close()
+
+    T, F = P.pr.n_features, P.pr.n_mfcc
+    trainer = Trainer(stock_weights, ModelParams(recurrent_units=20), seed=5)
+    trainer.set_data(np.zeros((4, T, F), np.float32), np.zeros(4, np.float32))
+    record = []
+    trainer.fit_resident = lambda *args, **kw: record.append(trainer.n_samples() - 4 + trainer.n_samples(True))
+    inc = IncrementalTrainer(trainer, runner, delay_samples=delay, epochs=epochs, threshold=threshold, chunk_size=C)
+    got_hits, got_retrains = inc.run(audios, test_flags=flags)
+    assert [(r, i, int(t)) for r, i, t in got_hits] == hits
+    assert [(r, i, n) for (r, i), n in zip(got_retrains, record)] == [tuple(x) for x in g['retrains'].tolist()]
+    assert inc.samples_since_train == int(g['samples_since_train'])
+    assert trainer.n_samples() == 4 + sum(1 for h in hits if not h[2]) and trainer.n_samples(True) == sum(1 for h in hits if h[2])
+    feats, targets = trainer._t.get_data(first=4)
+    want = runner.engine.vectorize_clips([c for c, h in zip(clips, hits) if not h[2]], P.pr.max_samples).astype(np.float32)
+    assert feats.tobytes() == want.reshape(feats.shape).tobytes() and not targets.any()

@@ -168,3 +168,72 @@ def test_incremental_policy_equals_the_scripts_loop(case):
         assert retrains == [] and trainer.fits == 0
     if case.startswith('capacity'):
         assert len(retrains) >= 1
+
+
+# ---- the script itself: tests/golden/train_incremental.npz (tools/make_script_fixtures.py) ------------------------------------
+class TableMiner(FakeMiner):
+    """a miner that scores every chunk with the fixture's confidence, whatever was retrained"""
+    conf = None
+
+    def scan(self, first=0, threshold=0.5, capacity=None, return_scores=False):
+        hits = first + np.flatnonzero(self.conf[first:] > threshold)
+        return hits[:capacity].astype(np.int32), int(hits.size), None
+
+
+def test_restatement_and_policy_equal_the_scripts_own_run(stock_weights):
+    """TrainIncrementalScript.train_on_audio itself over four recordings on one script object (retrain replaced by a recorder, so
+    every chunk is judged by the stock network): confidences, hits, saved int16 rings, retrain points."""
+    from conftest import golden
+    from oracle import listener as ol
+    from test_gpu_parity import TOL_DECODE
+    g = golden('train_incremental.npz')
+    audios = ref.fixture_recordings(g)
+    C, B, delay, epochs = (int(g[n]) for n in ('chunk_size', 'buffer_samples', 'delay_samples', 'epochs'))
+    threshold = float(g['threshold'])
+    flags = (g['flag_draws'] > 0.8).tolist()
+    hits = [tuple(h) for h in g['hits'].tolist()]
+    # what the fixture must hold to pin anything
+    assert len(audios) >= 3 and sum(flags) == 1 and len(hits) >= 6 and g['saved'].shape == (len(hits), B) and g['saved'].dtype == np.int16
+    assert any(r == 1 and (i + 1) * C < B for r, i, _ in hits)                      # a ring that still holds the first recording's tail
+    assert np.abs(g['conf'] - threshold).min() > TOL_DECODE
+    assert len(g['retrains']) >= 1 and g['chunk_starts'].tolist() == ref.chunk_offsets([len(a) for a in audios], C).tolist()
+
+    lis = ol.OracleListener(stock_weights)
+    raws, confs = [], []
+
+    def predict(r, i, chunk):
+        raws.append(lis.update_raw32(chunk))
+        confs.append(lis.threshold_decoder.decode(raws[-1]))
+        return confs[-1]
+
+    record = []
+    got_hits, got_retrains, saved, count = ref.policy_loop(audios, flags, C, B, delay, epochs, threshold, lambda r: lis.clear(), predict,
+                                                           lambda saved: record.append(len(saved)))
+    assert np.array_equal(np.array(raws, dtype=np.float32), g['raw']) and np.array_equal(np.array(confs), g['conf'])      # (as test_oracle.py)
+    assert [(r, i, int(t)) for r, i, t in got_hits] == hits
+    assert [(r, i, n) for (r, i), n in zip(got_retrains, record)] == [tuple(x) for x in g['retrains'].tolist()]
+    assert count == int(g['samples_since_train'])
+    # a retrain withheld by the test flag: the count stood at delay_samples or above inside the test recording
+    r_test = flags.index(True)
+    in_test = [n for n, (r, i, t) in enumerate(hits) if r == r_test]
+    before = max([n for r, i, n in g['retrains'].tolist() if r < r_test], default=0)
+    assert in_test and in_test[-1] + 1 - before >= delay and not any(r == r_test for r, _, _ in g['retrains'].tolist())
+
+    offsets = g['chunk_starts']
+    ids = [int(offsets[r] + i) for r, i, _ in hits]
+    rings = ref.rings(audios, C, B, only=set(ids))
+    assert np.array_equal(np.array([ref.saved_pcm(rings[i]) for i in ids]), g['saved'])
+    for (ring, test), want in zip(saved, g['saved']):
+        assert np.array_equal(ring, want.astype(np.float32) / np.float32(32767.0))
+    # the wrong reading: a ring cleared per recording fails against the fixture, at the early hit of the second recording
+    cleared = ref.rings(audios, C, B, carry_audio=False, only=set(ids))
+    wrong = [n for n, i in enumerate(ids) if not np.array_equal(ref.saved_pcm(cleared[i]), g['saved'][n])]
+    assert wrong and all(hits[n][0] >= 1 and (hits[n][1] + 1) * C < B for n in wrong), wrong
+
+    # IncrementalTrainer over the fixture's confidences retrains where the script did
+    runner, trainer = FakeRunner(), FakeTrainer()
+    TableMiner.conf = g['conf']
+    inc = IncrementalTrainer(trainer, runner, delay_samples=delay, epochs=epochs, threshold=threshold, chunk_size=C, miner_cls=TableMiner)
+    inc_hits, inc_retrains = inc.run(audios, test_flags=flags)
+    assert [(r, i, int(t)) for r, i, t in inc_hits] == hits and inc_retrains == got_retrains and inc.samples_since_train == count
+    assert [len(a) + len(b) for a, b in trainer.snapshots] == record

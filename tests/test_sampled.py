@@ -387,3 +387,50 @@ def test_sampled_trainer_at_the_stock_shape(stock_weights, tmp_path):
     y = (rng.random((40, 1)) < 0.5).astype(np.float64)
     x, y = duplicated(x, y, [(1, 39), (5, 6)])
     run_both(lambda: Trainer(stock_weights, ModelParams(recurrent_units=20), seed=7), x, y, 'error', tmp_path, cycles=2, epochs=1)
+
+
+# ---- the script itself: tests/golden/train_sampled.npz (tools/make_script_fixtures.py) ----------------------------------------
+def test_sampled_trainer_equals_the_scripts_own_cycles(stock_weights, tmp_path):
+    """TrainSampledScript.choose_new_samples and write_sampling_metrics themselves, two cycles on the stock network: with
+    num_sample_chunk below the remaining failures the choice is that many of the script's set, above it the whole set; the
+    counts and the metrics lines are the script's."""
+    from conftest import golden
+    from test_gpu_parity import TOL_RAW
+    from mycroft_precise_amd.train import flatten_weights, write_samples_file
+    g = golden('train_sampled.npz')
+    inputs, targets = g['inputs'], g['targets']
+    n = len(inputs)
+    assert np.abs(g['predictions'].astype(np.float64) - 0.5).min() > TOL_RAW
+
+    def fresh(num_sample_chunk):
+        trainer = Trainer(stock_weights, ModelParams(recurrent_units=20), seed=3)
+        assert trainer._t.get_weights().tobytes() == flatten_weights(stock_weights).tobytes()
+        st = SampledTrainer(trainer, inputs, targets, num_sample_chunk=num_sample_chunk, order='index')
+        assert np.array_equal(np.array([st.hash_to_ind[h] for h in st.hashes]), g['hash_to_ind'])
+        return st
+
+    k0, remaining = int(g['num_sample_chunk_0']), g['remaining_0'].tolist()
+    assert k0 < len(remaining)
+    st = fresh(k0)
+    report, _, probs = st.trainer._t.sample_choose(0, 'index', want_probs=True)                  # (max_new = 0: predictions alone)
+    worst = float(np.abs(probs.astype(np.float64) - g['predictions'].reshape(-1).astype(np.float64)).max())
+    print('%d rows, worst |p - the restated network\'s| %.3g' % (n, worst))
+    assert worst <= TOL_RAW and report['n_added'] == 0
+    result = st.cycle(epochs=1, batch_size=64)
+    assert result['remaining'] == len(remaining) and len(result['added']) == k0 and set(result['added']) <= set(remaining)
+    assert result['added'] == remaining[:k0]                                                    # order 'index'
+    assert result['correct'] == float(g['correct_0']) and st.metrics == [str(g['line_0'])]
+    st.trainer.close()
+
+    # the second cycle from the script's own first choice (a samples file, as a continued run reads it)
+    k1, remaining = int(g['num_sample_chunk_1']), g['remaining_1'].tolist()
+    assert k1 > len(remaining)
+    st = fresh(k1)
+    path = str(tmp_path / 'model.samples.json')
+    write_samples_file(path, [st.hashes[i] for i in g['chosen_0'].tolist()])
+    st.load_samples(path)
+    assert sorted(st.selected) == g['chosen_0'].tolist()
+    result = st.cycle(epochs=1, batch_size=64)
+    assert result['remaining'] == len(remaining) and sorted(result['added']) == remaining == g['chosen_1'].tolist()
+    assert len(st.samples) == int(g['n_samples_1']) and result['correct'] == float(g['correct_1']) and st.metrics == [str(g['line_1'])]
+    st.trainer.close()

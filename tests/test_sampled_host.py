@@ -100,3 +100,68 @@ def test_metrics_line_is_formatted_as_the_script_formats_it():
     want = '{}\t{}'.format(n_selected / len(targets), correct)                                         # train_sampled.py:59
     assert train.metrics_line(n_selected, n, n_correct) == want == '0.08333333333333333\t0.6833333333333333'
     assert train.metrics_line(0, 3, 3) == '0.0\t1.0'
+
+
+# ---- the script itself: tests/golden/train_sampled.npz (tools/make_script_fixtures.py) ----------------------------------------
+def test_hash_table_choice_and_metrics_equal_the_scripts_own(stock_weights):
+    """TrainScript.load_sample_data, TrainSampledScript.choose_new_samples and write_sampling_metrics themselves, two cycles by
+    hand on one script object: the hash table, the remaining failed samples, the counts and the metrics lines."""
+    from conftest import golden
+    from oracle import keras_gru
+    from test_gpu_parity import TOL_RAW
+    g = golden('train_sampled.npz')
+    inputs, targets, predicted = g['inputs'], g['targets'], g['predictions']
+    n = len(inputs)
+    assert inputs.shape == (n, 29, 13) and targets.shape == predicted.shape == (n, 1) and predicted.dtype == np.float32 and n >= 150
+    assert np.abs(predicted.astype(np.float64) - 0.5).min() > TOL_RAW
+    assert np.array_equal(keras_gru.predict(inputs, stock_weights), predicted)                  # the float32 restated network's
+    assert np.array_equal(inputs.astype(np.float32).astype(np.float64), inputs)                 # a float32 upload loses nothing
+
+    hashes = train.sample_hashes(inputs, targets)
+    assert hashes == [ref.calc_sample_hash(i, t) for i, t in zip(inputs, targets)]
+    hash_to_ind = {h: i for i, h in enumerate(hashes)}
+    table = np.array([hash_to_ind[h] for h in hashes])
+    assert np.array_equal(table, g['hash_to_ind'])
+    assert np.array_equal(train.eligible_mask(hashes), g['hash_to_ind'] == np.arange(n))
+    # what the fixture must hold: three groups of duplicated rows with equal targets, one of them failing, and one
+    # duplicated input with two targets (two hashes)
+    failing = ((predicted > 0.5) != (targets > 0.5)).reshape(-1)
+    groups = [np.flatnonzero(table == i) for i in np.unique(table) if np.count_nonzero(table == i) > 1]
+    assert len(groups) >= 3 and any(failing[grp].all() for grp in groups)
+    flat = inputs.reshape(n, -1)
+    split = [(a, b) for a in range(n) for b in np.flatnonzero((flat[a + 1:] == flat[a]).all(axis=1)) + a + 1 if hashes[a] != hashes[b]]
+    assert split and all(targets[a, 0] != targets[b, 0] for a, b in split)
+    # the wrong reading: first duplicate wins
+    first = {}
+    for i, h in enumerate(hashes):
+        first.setdefault(h, i)
+    assert not np.array_equal(np.array([first[h] for h in hashes]), g['hash_to_ind'])
+
+    def remaining_rows(table_of, samples):
+        failed = {calc_sample_hash(inp, target) for inp, pred, target in zip(inputs, predicted, targets) if (pred > 0.5) != (target > 0.5)}
+        return sorted(table_of[h] for h in failed - samples)
+
+    samples, mutant_fails = set(), []
+    n_correct = int(np.count_nonzero(~failing))
+    for c in (0, 1):
+        k, want = int(g['num_sample_chunk_%d' % c]), g['remaining_%d' % c].tolist()
+        assert remaining_rows(hash_to_ind, samples) == want
+        mutant_fails.append(remaining_rows(first, samples) != want)
+        chosen = g['chosen_%d' % c].tolist()
+        assert set(chosen) <= set(want) and len(chosen) == min(k, len(want)) and (k < len(want)) == (c == 0)
+        samples |= {hashes[i] for i in chosen}
+        assert len(samples) == int(g['n_samples_%d' % c])
+        assert float(g['correct_%d' % c]) == float(n_correct / n)
+        assert train.metrics_line(len(samples), n, n_correct) == str(g['line_%d' % c])
+    assert not remaining_rows(hash_to_ind, samples)
+    assert mutant_fails[0]              # first-duplicate-wins names other rows while the failing group still remains
+
+    # the restated loop, one cycle: a legal outcome of the script's islice, and its line
+    class Stub:
+        def predict(self, x):
+            return predicted
+
+        def fit(self, *args, **kw):
+            pass
+    per_cycle, lines, _ = ref.run(Stub(), inputs, targets, 1, 1, 16, int(g['num_sample_chunk_0']), 'index')
+    assert per_cycle[0] == g['remaining_0'][:int(g['num_sample_chunk_0'])].tolist() and lines == [str(g['line_0'])]

@@ -2,7 +2,10 @@
 -- precise-simulate (scripts/simulate.py:106-129) and compute_nww_annoyances (annoyance_estimator.py:56-73) without the
 per-recording loop.  The predictions are gated by bit-identity to ``evaluate`` per recording; the metrics by an oracle that
 lives here: the project's own ``runner.TriggerDetector`` (pinned by tests/golden/precise_runner.npz) fed ``float(p)``,
-``math.fsum``, and ``(p.astype(float64)[:, None] > thr).sum(0)``."""
+``math.fsum``, and ``(p.astype(float64)[:, None] > thr).sum(0)``.  That oracle is held in turn to the script itself:
+tests/golden/simulate.npz is what the reference's own ``SimulateScript.run`` computed and printed (tools/make_script_fixtures.py);
+test_simulate_host.py asks ``host_metric`` for its counts and sums and ``simulate.Metric`` for its report, and that a window stride
+of ``hop_frames +- 1`` does NOT give its predictions; the last test here reads the same file on the device."""
 import math
 
 import numpy as np
@@ -477,3 +480,44 @@ def test_streams_are_untouched(stock_weights, recordings):
     assert np.array_equal(out, b.update(pcm[0]))
     assert np.array_equal(a.get_vectors(), b.get_vectors())
     a.close(); b.close()
+
+
+# ---- the script itself: tests/golden/simulate.npz (tools/make_script_fixtures.py) ---------------------------------------------
+@pytest.mark.parametrize('chunk_size', [1024, 2048, 4096])
+def test_simulation_equals_the_scripts_own_report(stock_weights, chunk_size):
+    """SimulateScript.run's own numbers and printed report over recordings with 0, 1, 63, 64 and 65 predictions: activated
+    chunks and activations are equal, the sums follow assert_metrics' rule over the device's predictions, which lie within
+    TOL_RAW of the script's, and the report is the script's wherever its last figure has room for that (string_safe)."""
+    from conftest import golden
+    from mycroft_precise_amd.network_runner import HipRunner
+    from mycroft_precise_amd import simulate as S
+    g = golden('simulate.npz')
+    k = '_%d' % chunk_size
+    off, woff, threshold = g['offsets'], g['window_offsets' + k], float(g['threshold'])
+    audios = [g['pcm'][a:b].astype(np.float32) / np.float32(32767.0) for a, b in zip(off[:-1], off[1:])]
+    want = [g['predictions' + k][a:b] for a, b in zip(woff[:-1], woff[1:])]
+    flat = g['predictions' + k].astype(np.float64)
+    assert min(np.abs(flat - threshold).min(), np.abs(flat - (1.0 - threshold)).min()) > TOL_RAW and threshold != 0.5
+    runner = HipRunner(weights=stock_weights)
+    scores = runner.evaluate_clips(audios, chunk_size)
+    assert [len(s) for s in scores] == np.diff(woff).tolist()
+    worst = float(np.abs(np.concatenate(scores).reshape(-1).astype(np.float64) - flat).max())
+    print('chunk_size %d: %d predictions, worst |p - the script\'s| %.3g' % (chunk_size, flat.size, worst))
+    assert worst <= TOL_RAW
+    rows, _, _ = runner.simulate(audios, chunk_size, threshold)
+    assert_metrics(rows, scores, threshold, threshold, 0, chunk_size)
+    assert rows['activated_chunks'].tolist() == g['activated_chunks' + k].tolist()
+    assert rows['activations'].tolist() == g['activations' + k].tolist() and max(rows['activations']) >= 2
+    metrics, total = S.simulate_recordings(runner, audios, chunk_size=chunk_size, threshold=threshold)
+    assert [m.seconds for m in metrics] == g['seconds' + k].tolist()
+    assert [(m.activated_chunks, m.activations) for m in metrics] == list(zip(rows['activated_chunks'].tolist(), rows['activations'].tolist()))
+    safe = g['string_safe' + k]
+    for r, m in enumerate(metrics):
+        lines, want_lines = m.info_string('rec%02d.wav' % r).splitlines(), str(g['file_strings' + k][r]).splitlines()
+        assert lines[:4] == want_lines[:4] and (not safe[r] or lines == want_lines), (r, lines, want_lines)
+    assert (total.seconds, total.activated_chunks, total.activations) == tuple(g['total' + k][:3])
+    assert bool(g['total_string_safe' + k]) and total.info_string('Total') == str(g['total_string' + k])
+    # the buckets at the script's two comparisons: `p > t` is its activated chunks
+    thr = sorted([threshold, 1.0 - threshold])
+    buckets = S.nww_buckets(runner, audios, thresholds=thr, chunk_size=chunk_size)
+    assert np.array_equal(buckets, host_buckets(want, thr)) and buckets[thr.index(threshold)] == g['total' + k][1]

@@ -19,9 +19,10 @@ import argparse
 import os
 import random
 import sys
-import types
 
 import numpy as np
+
+from reference_stubs import install_stubs, install_wavio
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), 'tests', 'golden', 'add_noise.npz')
@@ -31,31 +32,6 @@ CLIP_LENGTHS = (2, 65, 300, 700, 1300)
 NOISE_LENGTHS = (2, 300, 700, 1000)
 INFLATION = 2
 AMPLITUDE = 8000
-
-
-class _Stub(types.ModuleType):
-    """a module any name can be imported from"""
-
-    def __getattr__(self, name):
-        if name.startswith('__'):
-            raise AttributeError(name)
-        return type(name, (), {'__init__': lambda self, *a, **k: None, '__call__': lambda self, *a, **k: self,
-                               '__getattr__': lambda self, n: self})
-
-
-class _Wavio(types.ModuleType):
-    """wavio's read / write over a dict of int16 arrays instead of files"""
-
-    def __init__(self, rate):
-        super().__init__('wavio')
-        self.files, self.rate = {}, rate
-
-    def read(self, name):
-        return types.SimpleNamespace(data=self.files[name].reshape(-1, 1), rate=self.rate, sampwidth=2)
-
-    def write(self, name, data, rate, sampwidth=None, scale=None):
-        assert data.dtype == np.int16 and rate == self.rate and sampwidth == 2 and scale == 'none'
-        self.files[name] = np.array(data)
 
 
 def pcm(rng, n):
@@ -71,16 +47,10 @@ def main():
     ap.add_argument('--out', default=OUT)
     args = ap.parse_args()
 
-    stubbed = []
-    for name in ('prettyparse', 'pyache', 'fitipy', 'sonopy', 'speechpy'):
-        try:
-            __import__(name)
-        except ImportError:
-            sys.modules[name] = _Stub(name)
-            stubbed.append(name)
+    stubbed = install_stubs(('prettyparse', 'pyache', 'fitipy', 'sonopy', 'speechpy'))
     sys.path.insert(0, os.path.abspath(args.reference))
     from precise.params import pr
-    wavio = sys.modules['wavio'] = _Wavio(pr.sample_rate)
+    wavio = install_wavio(pr.sample_rate)
     stubbed.append('wavio (in-memory int16 arrays)')
     from precise.scripts import add_noise
     from precise.util import load_audio, save_audio

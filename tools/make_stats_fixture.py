@@ -32,6 +32,8 @@ import types
 
 import numpy as np
 
+from reference_stubs import install_stubs
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), 'tests', 'golden', 'stats.npz')
 
@@ -40,16 +42,6 @@ NOISE_WINDOWS = (40, 300, 1)                # predictions per stood-in noise fil
 NOISE_SAMPLES = (170000, 1234567, 30000)    # ... and its length in samples
 INTERACTION_ESTIMATE, AMBIENT_ANNOYANCE = 100, 1.0
 SMOOTHING = 1.2
-
-
-class _Stub(types.ModuleType):
-    """a module any name can be imported from"""
-
-    def __getattr__(self, name):
-        if name.startswith('__'):
-            raise AttributeError(name)
-        return type(name, (), {'__init__': lambda self, *a, **k: None, '__call__': lambda self, *a, **k: self,
-                               '__getattr__': lambda self, n: self})
 
 
 def make_set(rng, n):
@@ -70,13 +62,7 @@ def main():
     ap.add_argument('--out', default=OUT)
     args = ap.parse_args()
 
-    stubbed = []
-    for name in ('prettyparse', 'pyache', 'fitipy', 'sonopy', 'speechpy', 'wavio'):
-        try:
-            __import__(name)
-        except ImportError:
-            sys.modules[name] = _Stub(name)
-            stubbed.append(name)
+    stubbed = install_stubs(('prettyparse', 'pyache', 'fitipy', 'sonopy', 'speechpy', 'wavio'))
     sys.path.insert(0, os.path.abspath(args.reference))
     from precise.params import pr
     from precise.stats import Stats
