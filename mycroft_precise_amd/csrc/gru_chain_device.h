@@ -40,10 +40,17 @@ __device__ __forceinline__ void chain_load(const float* chains, const size_t cel
 #pragma unroll
     for (int rho = 0; rho < 5; ++rho) h[rho] = chains[cell + (size_t)rho * 64];
 }
+// WT: the five stores are written through the L2 (relaxed agent-scope atomic stores: global_store_dword ... sc1) instead of left
+// dirty in it for the kernel boundary to write back.  A cell's next reader is a later launch, so no value changes; which
+// instantiations gain by it is measured (profiles/chain_store/README.md).
+template <bool WT>
 __device__ __forceinline__ void chain_store(float* chains, const size_t cell, const float (&h)[5], const bool on) {
     if (!on) return;
 #pragma unroll
-    for (int rho = 0; rho < 5; ++rho) chains[cell + (size_t)rho * 64] = h[rho];
+    for (int rho = 0; rho < 5; ++rho) {
+        if constexpr (WT) __hip_atomic_store(chains + cell + (size_t)rho * 64, h[rho], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else chains[cell + (size_t)rho * 64] = h[rho];
+    }
 }
 
 // the timestep's weights, which every wave of this form keeps
@@ -111,6 +118,9 @@ constexpr size_t kChainLdsBytes = (size_t)ChainLds::FLOATS * sizeof(float);
 // 48 bytes per lane, and callers whose chunks are at most a hop, or change, keep the stride loop this form always had.
 template <int NW, bool SKIP>
 __device__ __forceinline__ void gru_tile_chains_t(const GruArgs& a, const ChainArgs& ch, const int tile, const int wave, const int lane, float* const S) {
+    // chain_store's policy: the four-wave stride loop was slower with write-through stores, every other instantiation faster
+    // (profiles/chain_store/README.md)
+    constexpr bool kWriteThrough = SKIP || NW == 8;
     const int g = lane >> 4, j = lane & 15;
     const long long stream = (long long)tile * kTileStreams + j;
     const bool valid = stream < a.n_streams;
@@ -226,8 +236,8 @@ __device__ __forceinline__ void gru_tile_chains_t(const GruArgs& a, const ChainA
             }
             advance(h0, A0);
             if (two) advance(h1, A1);
-            chain_store(ch.chains, c0, h0, moved);
-            if (two) chain_store(ch.chains, c1, h1, moved);
+            chain_store<kWriteThrough>(ch.chains, c0, h0, moved);
+            if (two) chain_store<kWriteThrough>(ch.chains, c1, h1, moved);
             last_two = two;
         };
         // Flag clear: the stride of the ages is known.  Flag set: the wave walks the set bits of its part of the mask.
@@ -284,7 +294,7 @@ __device__ __forceinline__ void gru_tile_chains_rebuild(const GruArgs& a, const 
             N.project(*reinterpret_cast<const f32x4*>(xbase + (size_t)((start + (uint32_t)i) & smask) * kTileStreams * kRowFloats), p);
             N.S.step(h, p[kTZ], p[kTX], p[kTC], p[kTV]);
         }
-        chain_store(ch.chains, chain_cell(sid, start & smask, g), h, true);
+        chain_store<true>(ch.chains, chain_cell(sid, start & smask, g), h, true);
     }
     if (wave == 0 && g == 0) ch.chain_ke[sid] = ke;
 }
