@@ -258,7 +258,10 @@ size_t ring_floats(const pe_engine* e) {
     return e->prm.ring_precision == 1 ? rows * kRowFloats / 2 : rows * (size_t)e->row_floats;
 }
 
-
+// The front end's precision (pe_params::mfcc_precision: 0 float64, 1 float32) as a type: f(R{}) with R = double or float, and what
+// f returns.  The ONE place where the parameter becomes a type: table builders and front-end launches are written once, in R.
+template <class F>
+auto with_real(const pe_params& prm, F&& f) { return prm.mfcc_precision == 0 ? f(double{}) : f(float{}); }
 
 template <class R>
 int build_tables(pe_engine* e, const double* mel_filters) {
@@ -912,16 +915,27 @@ GeneralStreamArgs<R> general_args(const pe_engine* e, const int16_t* pcm_dev, in
 }
 
 // MFCC alone: every stream of the launch goes from its current side to the other one (records stamped `call`).
-int launch_mfcc(pe_engine* e, const int16_t* pcm_dev, int chunk, hipStream_t s, uint32_t call, const int32_t* ids = nullptr, int n_active = 0) {
+// The four kinds of front-end launch, each written once: the arguments built generically in the precision R (with_real), the
+// family -- general front end or stock wave kernels -- chosen by the one `if (e->general)`.
+// Streaming.  n_updates chunks per stream in one call (pe_update_many_device: ke_hist takes every update's emitted count).
+int launch_stream_front_end(pe_engine* e, const int16_t* pcm_dev, int chunk, hipStream_t s, uint32_t call, const int32_t* ids = nullptr, int n_active = 0,
+                            int n_updates = 1, uint32_t* ke_hist = nullptr) {
     // (no cap on the frames ONE update may complete: Listener.update takes a chunk of any length,
     //  network_runner.py:125-146; the frame tasks skip every row that the ring would overwrite again -- v_first in
     //  mfcc_frame_tasks -- so a long chunk costs its last ring_slots frames plus a scalar walk over the row indices)
-    if (e->general) {
-        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_general_stream_f64(general_args<double>(e, pcm_dev, chunk, call, ids, n_active), s, mel_rows(e)));
-        else PE_HIP(e, launch_general_stream_f32(general_args<float>(e, pcm_dev, chunk, call, ids, n_active), s, mel_rows(e)));
-    } else if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_mfcc_f64(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), e->n_cus, s, mel_rows(e)));
-    else PE_HIP(e, launch_mfcc_f32(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), e->n_cus, s, mel_rows(e)));
-    return PE_OK;
+    return with_real(e->prm, [&](auto real) -> int {
+        using R = decltype(real);
+        if (e->general) {
+            GeneralStreamArgs<R> a = general_args<R>(e, pcm_dev, chunk, call, ids, n_active);
+            a.n_updates = n_updates; a.ke_hist = ke_hist;
+            PE_HIP(e, launch_general_stream(a, s, mel_rows(e)));
+        } else {
+            MfccStreamArgs<R> a = mfcc_args<R>(e, pcm_dev, chunk, call, ids, n_active);
+            a.n_updates = n_updates; a.ke_hist = ke_hist; a.n_frame_rows = max_frames_per_call(e, (long long)n_updates * chunk);
+            PE_HIP(e, launch_mfcc(a, tables<R>(e), e->n_cus, s, mel_rows(e)));
+        }
+        return PE_OK;
+    });
 }
 
 // NetPack -> ModelNet: a model's weights as a launch of the form of `a` reads them.  The form -- which of the blobs b20 / x3 /
@@ -1302,8 +1316,10 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
         g.chunk = chunk;
         g.out = raw_out_dev;
         if (ids) { g.ids = ids; g.n_streams = n_active; }
-        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused_chains(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, ch, e->n_cus, s));
-        else PE_HIP(e, launch_fused_chains(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, ch, e->n_cus, s));
+        if ((rc = with_real(e->prm, [&](auto real) -> int {
+                using R = decltype(real);
+                PE_HIP(e, launch_fused_chains(mfcc_args<R>(e, pcm_dev, chunk, call, ids, n_active), tables<R>(e), g, ch, e->n_cus, s));
+                return PE_OK; }))) return rc;
         e->chains_built_epoch = e->chain_epoch;          // (only now: a launch that failed leaves the chains behind the streams)
         if (skip) e->chain_skip_chunk = chunk;
     } else if (raw_out_dev && can_fuse(e, chunk)) {
@@ -1315,11 +1331,13 @@ int do_update(pe_engine* e, const int16_t* pcm_dev, int chunk, float* raw_out_de
         if (ids) { g.ids = ids; g.n_streams = n_active; }
         const ModelSet ms = model_set(e, g);             // K > 1: K network roles beside the one frame role, outputs [K][windows]
         const ModelSet* const models = e->n_models > 1 ? &ms : nullptr;
-        if (e->prm.mfcc_precision == 0) PE_HIP(e, launch_fused(mfcc_args<double>(e, pcm_dev, chunk, call, ids, n_active), tables<double>(e), g, e->n_cus, s, models, e->n_models));
-        else PE_HIP(e, launch_fused(mfcc_args<float>(e, pcm_dev, chunk, call, ids, n_active), tables<float>(e), g, e->n_cus, s, models, e->n_models));
+        if ((rc = with_real(e->prm, [&](auto real) -> int {
+                using R = decltype(real);
+                PE_HIP(e, launch_fused(mfcc_args<R>(e, pcm_dev, chunk, call, ids, n_active), tables<R>(e), g, e->n_cus, s, models, e->n_models));
+                return PE_OK; }))) return rc;
         if (t) { PE_HIP(e, hipEventRecord(e->ev[1], s)); PE_HIP(e, hipEventRecord(e->ev[2], s)); e->ev_valid = true; e->ev_has_gru = false; }
     } else {
-        if ((rc = launch_mfcc(e, pcm_dev, chunk, s, call, ids, n_active))) return rc;
+        if ((rc = launch_stream_front_end(e, pcm_dev, chunk, s, call, ids, n_active))) return rc;
         if (t) { PE_HIP(e, hipEventRecord(e->ev[1], s)); }
         if (raw_out_dev) {
             if ((rc = launch_gru_ring(e, raw_out_dev, s, ids, n_active))) return rc;
@@ -1492,8 +1510,7 @@ int create_engine(const pe_params* p_given, const double* mel_filters, const pe_
         // a stock-shape filterbank whose runs need more than the 64 lanes of the wave kernel also takes the general path
         std::vector<unsigned char> probe;
         pe_wave::Layout lprobe{};
-        const std::string perr = p->mfcc_precision == 0 ? pe_wave::build<double>(mel_filters, p->n_filt, p->n_mfcc, probe, lprobe)
-                                                        : pe_wave::build<float>(mel_filters, p->n_filt, p->n_mfcc, probe, lprobe);
+        const std::string perr = with_real(*p, [&](auto real) { return pe_wave::build<decltype(real)>(mel_filters, p->n_filt, p->n_mfcc, probe, lprobe); });
         if (!perr.empty()) general = true;
     }
     e->general = general;
@@ -1533,15 +1550,15 @@ int create_engine(const pe_params* p_given, const double* mel_filters, const pe_
         // from the ring; they pay while the ring stays cache-resident (256 B per frame and stream)
         e->proj_ok = !wide && p->gru_precision == 0 && !p->use_delta && gru_small_regs(L.units) == 5 && !e->proj_w_host.empty();
         e->proj_on = false;          // opt-in (pe_set_input_projection): measured no gain for the MFMA kernels at <= 4096 streams
-        if (e->general) rc = (p->mfcc_precision == 0) ? build_general_tables<double>(e, mel_filters) : build_general_tables<float>(e, mel_filters);
-        else rc = (p->mfcc_precision == 0) ? build_tables<double>(e, mel_filters) : build_tables<float>(e, mel_filters);
+        rc = with_real(*p, [&](auto real) { return e->general ? build_general_tables<decltype(real)>(e, mel_filters) : build_tables<decltype(real)>(e, mel_filters); });
         if (rc) break;
         if (e->proj_on && (rc = dev_alloc(e, &e->proj_ring, (size_t)e->n_tiles * e->ring_slots * kTileStreams * kProjRow))) break;
         for (auto& ev : e->ev)
             if (hipEventCreate(&ev) != hipSuccess) { rc = fail(e, PE_ERR_HIP, "hipEventCreate failed"); break; }
         if (rc) break;
-        const size_t lds = e->general ? general_lds_bytes(p->mfcc_precision == 0 ? 8 : 4, p->n_fft, p->n_filt, e->gtab.n_rounds)
-                                      : (size_t)e->table_layout.total + (size_t)kFrameWaves * pe_wave::kScratchReals * (p->mfcc_precision == 0 ? 8 : 4);
+        const size_t real_bytes = with_real(*p, [](auto real) { return sizeof(real); });
+        const size_t lds = e->general ? general_lds_bytes(real_bytes, p->n_fft, p->n_filt, e->gtab.n_rounds)
+                                      : (size_t)e->table_layout.total + (size_t)kFrameWaves * pe_wave::kScratchReals * real_bytes;
         if (lds > 64 * 1024) { rc = fail(e, PE_ERR_UNSUPPORTED, "MFCC kernel would need %zu bytes of LDS per workgroup", lds); break; }
         if ((rc = pe_clear(e, nullptr))) break;
         hipError_t se = hipDeviceSynchronize();
@@ -1594,7 +1611,7 @@ int pe_set_weights(pe_engine* e, const pe_weights* w, int32_t model) {
         // the input-projection rows (pe_set_input_projection) live in the front end's table blob: built again from the new
         // network, written over the old blob; rows already in the feature ring get their projections again
         pack_projection_rows(e, w->layers[0]);
-        rc = e->prm.mfcc_precision == 0 ? build_tables<double>(e, e->mel_host.data()) : build_tables<float>(e, e->mel_host.data());
+        rc = with_real(e->prm, [&](auto real) { return build_tables<decltype(real)>(e, e->mel_host.data()); });
         if (rc) return rc;
         if (e->proj_on)
             PE_HIP(e, launch_project_rows(e->ring, e->proj_ring, reinterpret_cast<const float*>(e->table_blob + e->table_layout.proj_w),
@@ -1987,6 +2004,23 @@ int pe_predict(pe_engine* e, const float* feats_host, int32_t n, float* out_host
 }
 
 namespace {
+// Whole buffer: every frame of the n_samples float64 samples in st_audio, to whichever of the three outputs is not null
+// (float64 coefficients / float32 network rows / float64 log-mel energies)
+int launch_buffer_front_end(pe_engine* e, int64_t n_samples, int64_t n_frames, double* dev_out, float* dev_rows, double* dev_mels) {
+    return with_real(e->prm, [&](auto real) -> int {
+        using R = decltype(real);
+        const double* audio = static_cast<const double*>(e->st_audio.p);
+        if (e->general) {
+            GeneralOfflineArgs<R> a{geom(e), e->gtab, audio, n_frames, dev_out, dev_rows, dev_mels, e->row_floats};
+            PE_HIP(e, launch_general_offline(a, e->n_cus, nullptr, mel_rows(e)));
+        } else {
+            MfccOfflineArgs<R> a{geom(e), audio, n_samples, n_frames, dev_out, dev_rows, dev_mels};
+            PE_HIP(e, launch_mfcc_offline(a, tables<R>(e), e->n_cus, nullptr, mel_rows(e)));
+        }
+        return PE_OK;
+    });
+}
+
 int vectorize_buffer(pe_engine* e, const double* audio_host, int64_t n_samples, double* feats_out_host,
                      int64_t max_frames, int64_t* n_frames_out, bool mels) {
     if (!e || !n_frames_out) return fail(e, PE_ERR_INVALID, "null argument to pe_vectorize_*");
@@ -2003,23 +2037,7 @@ int vectorize_buffer(pe_engine* e, const double* audio_host, int64_t n_samples, 
     if ((rc = ensure(e, e->st_mfcc, fb))) return rc;
     PE_HIP(e, hipMemcpy(e->st_audio.p, audio_host, ab, hipMemcpyHostToDevice));
     double* dev_out = static_cast<double*>(e->st_mfcc.p);
-    if (e->general) {
-        if (e->prm.mfcc_precision == 0) {
-            GeneralOfflineArgs<double> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f64(a, e->n_cus, nullptr, mel_rows(e)));
-        } else {
-            GeneralOfflineArgs<float> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f32(a, e->n_cus, nullptr, mel_rows(e)));
-        }
-    } else if (e->prm.mfcc_precision == 0) {
-        MfccOfflineArgs<double> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames,
-                                  mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr};
-        PE_HIP(e, launch_mfcc_offline_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
-    } else {
-        MfccOfflineArgs<float> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames,
-                                 mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr};
-        PE_HIP(e, launch_mfcc_offline_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
-    }
+    if ((rc = launch_buffer_front_end(e, n_samples, n_frames, mels ? nullptr : dev_out, nullptr, mels ? dev_out : nullptr))) return rc;
     PE_HIP(e, hipMemcpy(feats_out_host, e->st_mfcc.p, fb, hipMemcpyDeviceToHost));
     return PE_OK;
 }
@@ -2055,21 +2073,7 @@ int pe_evaluate(pe_engine* e, const double* audio_host, int64_t n_samples, int32
     if ((rc = ensure(e, e->st_feats, rb))) return rc;
     if ((rc = ensure(e, e->st_out, (size_t)e->n_models * n_windows * sizeof(float)))) return rc;
     PE_HIP(e, hipMemcpy(e->st_audio.p, audio_host, ab, hipMemcpyHostToDevice));
-    if (e->general) {
-        if (e->prm.mfcc_precision == 0) {
-            GeneralOfflineArgs<double> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f64(a, e->n_cus, nullptr, mel_rows(e)));
-        } else {
-            GeneralOfflineArgs<float> a{geom(e), e->gtab, static_cast<const double*>(e->st_audio.p), n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr, e->row_floats};
-            PE_HIP(e, launch_general_offline_f32(a, e->n_cus, nullptr, mel_rows(e)));
-        }
-    } else if (e->prm.mfcc_precision == 0) {
-        MfccOfflineArgs<double> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr};
-        PE_HIP(e, launch_mfcc_offline_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
-    } else {
-        MfccOfflineArgs<float> a{geom(e), static_cast<const double*>(e->st_audio.p), n_samples, n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr};
-        PE_HIP(e, launch_mfcc_offline_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
-    }
+    if ((rc = launch_buffer_front_end(e, n_samples, n_frames, nullptr, static_cast<float*>(e->st_feats.p), nullptr))) return rc;
     GruArgs g = gru_args(e);
     g.n_streams = (int)n_windows;
     g.feats = static_cast<const float*>(e->st_feats.p);
@@ -2166,41 +2170,31 @@ hipError_t stats_run(char* scratch, const StatsScratch& s, const float* probs_de
 namespace {
 // the front-end launch over a clip table that is on the device (pe_vectorize_clips / pe_score_clips; pe_miner_vectorize / _append)
 int launch_clip_front_end(pe_engine* e, const ClipTable& ct, double* dev_out, float* dev_rows, double* dev_mels) {
-    if (e->general) {
-        if (e->prm.mfcc_precision == 0) {
-            GeneralClipArgs<double> a{geom(e), e->gtab, ct, dev_out, dev_rows, dev_mels, e->row_floats};
-            PE_HIP(e, launch_general_clips_f64(a, e->n_cus, nullptr, mel_rows(e)));
+    return with_real(e->prm, [&](auto real) -> int {
+        using R = decltype(real);
+        if (e->general) {
+            GeneralClipArgs<R> a{geom(e), e->gtab, ct, dev_out, dev_rows, dev_mels, e->row_floats};
+            PE_HIP(e, launch_general_clips(a, e->n_cus, nullptr, mel_rows(e)));
         } else {
-            GeneralClipArgs<float> a{geom(e), e->gtab, ct, dev_out, dev_rows, dev_mels, e->row_floats};
-            PE_HIP(e, launch_general_clips_f32(a, e->n_cus, nullptr, mel_rows(e)));
+            MfccClipArgs<R> a{geom(e), ct, dev_out, dev_rows, dev_mels};
+            PE_HIP(e, launch_mfcc_clips(a, tables<R>(e), e->n_cus, nullptr, mel_rows(e)));
         }
-    } else if (e->prm.mfcc_precision == 0) {
-        MfccClipArgs<double> a{geom(e), ct, dev_out, dev_rows, dev_mels};
-        PE_HIP(e, launch_mfcc_clips_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
-    } else {
-        MfccClipArgs<float> a{geom(e), ct, dev_out, dev_rows, dev_mels};
-        PE_HIP(e, launch_mfcc_clips_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
-    }
-    return PE_OK;
+        return PE_OK;
+    });
 }
 // ... and over a recording table (pe_evaluate_clips / pe_simulate_clips; pe_miner_create)
 int launch_rec_front_end(pe_engine* e, const RecTable& rt, float* dev_rows) {
-    if (e->general) {
-        if (e->prm.mfcc_precision == 0) {
-            GeneralRecArgs<double> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
-            PE_HIP(e, launch_general_recs_f64(a, e->n_cus, nullptr, mel_rows(e)));
+    return with_real(e->prm, [&](auto real) -> int {
+        using R = decltype(real);
+        if (e->general) {
+            GeneralRecArgs<R> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
+            PE_HIP(e, launch_general_recs(a, e->n_cus, nullptr, mel_rows(e)));
         } else {
-            GeneralRecArgs<float> a{geom(e), e->gtab, rt, dev_rows, e->row_floats};
-            PE_HIP(e, launch_general_recs_f32(a, e->n_cus, nullptr, mel_rows(e)));
+            MfccRecArgs<R> a{geom(e), rt, dev_rows};
+            PE_HIP(e, launch_mfcc_recs(a, tables<R>(e), e->n_cus, nullptr, mel_rows(e)));
         }
-    } else if (e->prm.mfcc_precision == 0) {
-        MfccRecArgs<double> a{geom(e), rt, dev_rows};
-        PE_HIP(e, launch_mfcc_recs_f64(a, tables<double>(e), e->n_cus, nullptr, mel_rows(e)));
-    } else {
-        MfccRecArgs<float> a{geom(e), rt, dev_rows};
-        PE_HIP(e, launch_mfcc_recs_f32(a, tables<float>(e), e->n_cus, nullptr, mel_rows(e)));
-    }
-    return PE_OK;
+        return PE_OK;
+    });
 }
 
 // pe_vectorize_clips (feats_out_host) / pe_score_clips (score_out_host) / pe_test_clips (stats; score_out_host may be null):
@@ -2779,7 +2773,6 @@ int pe_update_many_device(pe_engine* e, const int16_t* pcm_dev, int32_t chunk, i
     if (n_updates > e->max_updates || !e->ke_hist) return fail(e, PE_ERR_INVALID, "call pe_reserve_updates(e, >= %d, >= %d) first", n_updates, chunk);
     PE_HIP(e, hipSetDevice(e->device));
     PE_DRAIN(e);
-    const int flen = frame_len_of(e->prm);
     const int pending = pending_frames(e->prm);
     const long long frames = ((long long)n_updates * chunk + e->prm.hop_samples - 1) / e->prm.hop_samples + 1;
     if ((long long)n_updates * chunk >= (1ll << 30)) return fail(e, PE_ERR_INVALID, "n_updates * chunk_samples must stay below 2^30");
@@ -2789,53 +2782,19 @@ int pe_update_many_device(pe_engine* e, const int16_t* pcm_dev, int32_t chunk, i
     if ((rc = flush_kept(e, s))) return rc;
     uint32_t call = 0;
     if ((rc = begin_state_call(e, s, &call))) return rc;
-    if (e->general) {
-        // the general front end: every frame the call completes in ONE launch (mfcc_general_device.h: general_stream with n_updates),
-        // then the batched network launch over 16-float rows, or one network launch per update over 32-float rows
-        if (e->prm.mfcc_precision == 0) {
-            GeneralStreamArgs<double> a = general_args<double>(e, pcm_dev, chunk, call);
-            a.n_updates = n_updates; a.ke_hist = e->ke_hist;
-            PE_HIP(e, launch_general_stream_f64(a, s, mel_rows(e)));
-        } else {
-            GeneralStreamArgs<float> a = general_args<float>(e, pcm_dev, chunk, call);
-            a.n_updates = n_updates; a.ke_hist = e->ke_hist;
-            PE_HIP(e, launch_general_stream_f32(a, s, mel_rows(e)));
-        }
-        GruArgs g = gru_args(e);
-        g.ke_plain = e->ke_hist;
-        g.out = raw_out_dev;
-        if (e->wide || e->row_floats != kRowFloats) {
-            for (int u = 0; u < n_updates; ++u) {
-                GruArgs gu = g;
-                gu.ke_plain = e->ke_hist + (size_t)u * e->n_padded;
-                gu.out = raw_out_dev + (size_t)u * e->n_streams;
-                int nrc = launch_networks(e, gu, 1, s, (long long)n_updates * e->n_streams);
-                if (nrc) return nrc;
-            }
-            return PE_OK;
-        }
-        g.waves_per_tile = 1;
-        return launch_networks_many(e, g, n_updates, s);
+    if (!e->general) {
+        // the stock wave kernels: one task row per frame a stream can complete in this call, at most kMaxFrameRows rows
+        const int rows = max_frames_per_call(e, (long long)n_updates * chunk);
+        if (rows > kMaxFrameRows) return fail(e, PE_ERR_INVALID, "a call may complete at most %d frames per stream (%d updates of %d samples: %d)", kMaxFrameRows, n_updates, chunk, rows);
     }
-    // frames one stream can complete in this call: one task row per frame, at most kMaxFrameRows rows
-    const int rows = max_frames_per_call(e, (long long)n_updates * chunk);
-    if (rows > kMaxFrameRows) return fail(e, PE_ERR_INVALID, "a call may complete at most %d frames per stream (%d updates of %d samples: %d)", kMaxFrameRows, n_updates, chunk, rows);
-    (void)flen;
-    if (e->prm.mfcc_precision == 0) {
-        MfccStreamArgs<double> a = mfcc_args<double>(e, pcm_dev, chunk, call);
-        a.n_updates = n_updates; a.ke_hist = e->ke_hist; a.n_frame_rows = rows;
-        PE_HIP(e, launch_mfcc_f64(a, tables<double>(e), e->n_cus, s, mel_rows(e)));
-    } else {
-        MfccStreamArgs<float> a = mfcc_args<float>(e, pcm_dev, chunk, call);
-        a.n_updates = n_updates; a.ke_hist = e->ke_hist; a.n_frame_rows = rows;
-        PE_HIP(e, launch_mfcc_f32(a, tables<float>(e), e->n_cus, s, mel_rows(e)));
-    }
+    // every frame the call completes in ONE front-end launch (either family), then the batched network launch
+    if ((rc = launch_stream_front_end(e, pcm_dev, chunk, s, call, nullptr, 0, n_updates, e->ke_hist))) return rc;
     GruArgs g = gru_args(e);
     g.ke_plain = e->ke_hist;
     g.out = raw_out_dev;
-    if (e->wide) {
-        // the streamed-weight network: one launch per update of the call (each fills the machine on its own), the
-        // window of update u found through its row of the emitted-frame history
+    if (e->wide || e->row_floats != kRowFloats) {
+        // the streamed-weight network, and every network over 32-float rows (general front end only): one launch per update of the
+        // call (each fills the machine on its own), the window of update u found through its row of the emitted-frame history
         for (int u = 0; u < n_updates; ++u) {
             GruArgs gu = g;
             gu.ke_plain = e->ke_hist + (size_t)u * e->n_padded;

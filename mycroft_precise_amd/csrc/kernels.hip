@@ -2,8 +2,14 @@
 // in mfcc_wave_device.h / mfcc_device.h (MFCC front end: frames / bookkeeping) and gru_*_device.h (GRU + Dense
 // on the matrix cores).  What is said once here: a network shape (tile function, threads, LDS) is a Net* functor, run by
 // its one-model kernel, by gru_models_kernel and by the pe_update_many kernels (three kernels write the same call out: noted there); a fused update has one body per role layout
-// (float32 network, bf16 network) with a compile-time flag for "several models"; a `name` / `name_nopk` pair whose body is one call is one
+// (float32 network, bf16 network) with a compile-time flag for "several models"; every `name` / `name_nopk` pair is one
 // PE_KERNEL_PAIR; a runtime mode / flag becomes a template argument through with_const.
+// The front end has four kinds of launch (streaming, whole buffer, clip table, recording table) in two families (the stock-shape
+// wave kernels, the general front end) and two precisions.  Each kind of each family is ONE launcher here, a template over the
+// precision R instantiated for double and float (PE_FRONT_END_LAUNCHERS); the table shape and the mel-row flag of the stock family
+// become template arguments in with_frame_shape, the transform length and the mel-row flag of the general family in
+// with_general_bits.  Family and precision are chosen by the callers: engine.hip, one function per kind (launch_*_front_end),
+// the precision through with_real.
 #include <cstdlib>
 #include <type_traits>
 #include "mfcc_device.h"
@@ -90,18 +96,10 @@ __device__ __forceinline__ void mfcc_kernel_body(const MfccStreamArgs<R>& a, con
 PE_KERNEL_PAIR((template <class R, class SH, bool SINGLE = false, bool MELS = false>), PE_FRAME_KERNEL(64 * kFrameWaves, SH::WPE), mfcc_kernel,
                (const MfccStreamArgs<R> a, const WaveTables<R> t, const int n_frame_blocks),
                { mfcc_kernel_body<R, SH, SINGLE, MELS>(a, t, n_frame_blocks); })
-
-// (pairs whose body is more than a call are written out)
-template <class R, class SH, bool MELS = false>
-__global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_eu(SH::WPE))) void mfcc_offline_kernel(const MfccOfflineArgs<R> a, const WaveTables<R> t) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    mfcc_offline_frames<R, SH, MELS>(a, t, smem);
-}
-template <class R, class SH, bool MELS = false>
-__global__ __launch_bounds__(64 * kFrameWaves) __attribute__((amdgpu_waves_per_eu(SH::WPE))) PE_NO_PK_F32 void mfcc_offline_kernel_nopk(const MfccOfflineArgs<R> a, const WaveTables<R> t) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    mfcc_offline_frames<R, SH, MELS>(a, t, smem);
-}
+// a whole buffer's frames (pe_vectorize_raw / pe_vectorize_mels / pe_evaluate)
+PE_KERNEL_PAIR((template <class R, class SH, bool MELS = false>), PE_FRAME_KERNEL(64 * kFrameWaves, SH::WPE), mfcc_offline_kernel,
+               (const MfccOfflineArgs<R> a, const WaveTables<R> t),
+               { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; mfcc_offline_frames<R, SH, MELS>(a, t, smem); })
 // many clips in one launch (pe_vectorize_clips / pe_score_clips): frame tasks found in the clip table (pe_common.h: ClipTable)
 PE_KERNEL_PAIR((template <class R, class SH, bool MELS = false>), PE_FRAME_KERNEL(64 * kFrameWaves, SH::WPE), mfcc_clips_kernel,
                (const MfccClipArgs<R> a, const WaveTables<R> t),
@@ -565,80 +563,59 @@ static bool blob_matches_shape(const WaveTables<R>& t) {
     return t.L.mel_pad == ShapeStock::MEL ? shape_layout_matches<R, ShapeStock>(t.L) : shape_layout_matches<R, ShapeAny>(t.L);
 }
 
+// The table shape of a stock-family launch (ShapeStock / ShapeAny, by the blob's mel padding) and MELS (mel rows) as template
+// arguments: f(SH{}, MELS).  All four launchers of the family go through it: a (shape, rows) pair is spelled nowhere else.
+template <class R, class F>
+static void with_frame_shape(const WaveTables<R>& t, bool mels, F&& f) {
+    with_flag(t.L.mel_pad == ShapeStock::MEL, [&](auto ST) { with_flag(mels, [&](auto ME) {
+        f(std::conditional_t<PE_CONST(ST) != 0, ShapeStock, ShapeAny>{}, ME); }); });
+}
+
+// The four kinds of launch of the stock family: each ONE template over the precision R, declared in pe_common.h and instantiated
+// for double and float at the end of the front-end launchers (PE_FRONT_END_LAUNCHERS); engine.hip chooses R once (with_real).
 template <class R>
-static hipError_t launch_mfcc(const MfccStreamArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
+hipError_t launch_mfcc(const MfccStreamArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
     const int tiles = (a.geo.n_streams + kTileStreams - 1) / kTileStreams;
     const int fb = stream_frame_blocks(a.geo.n_streams, n_cus);
     if (!blob_matches_shape(t)) return hipErrorInvalidValue;
     const bool single = a.n_updates == 1 && !a.proj_ring;
-    if (mels) {
-        const dim3 grid(fb + tiles), block(64 * kFrameWaves);
-        with_flag(t.L.mel_pad == ShapeStock::MEL, [&](auto ST) { with_flag(single, [&](auto SI) {
-            using SH = std::conditional_t<PE_CONST(ST) != 0, ShapeStock, ShapeAny>;
-            PE_LAUNCH_R(R, mfcc_kernel, (SH, PE_CONST(SI) != 0, true), grid, block, frame_lds(t), s, a, t, fb); }); });
-        return hipGetLastError();
-    }
-    if (t.L.mel_pad == ShapeStock::MEL) {
-        if (single) PE_LAUNCH_R(R, mfcc_kernel, (ShapeStock, true), dim3(fb + tiles), dim3(64 * kFrameWaves), frame_lds(t), s, a, t, fb);
-        else PE_LAUNCH_R(R, mfcc_kernel, (ShapeStock), dim3(fb + tiles), dim3(64 * kFrameWaves), frame_lds(t), s, a, t, fb);
-    } else {
-        if (single) PE_LAUNCH_R(R, mfcc_kernel, (ShapeAny, true), dim3(fb + tiles), dim3(64 * kFrameWaves), frame_lds(t), s, a, t, fb);
-        else PE_LAUNCH_R(R, mfcc_kernel, (ShapeAny), dim3(fb + tiles), dim3(64 * kFrameWaves), frame_lds(t), s, a, t, fb);
-    }
+    const dim3 grid(fb + tiles), block(64 * kFrameWaves);
+    with_frame_shape(t, mels, [&](auto SH, auto ME) { with_flag(single, [&](auto SI) {
+        PE_LAUNCH_R(R, mfcc_kernel, (decltype(SH), PE_CONST(SI) != 0, PE_CONST(ME) != 0), grid, block, frame_lds(t), s, a, t, fb); }); });
     return hipGetLastError();
 }
-hipError_t launch_mfcc_f64(const MfccStreamArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels) { return launch_mfcc<double>(a, t, n_cus, s, mels); }
-hipError_t launch_mfcc_f32(const MfccStreamArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels) { return launch_mfcc<float>(a, t, n_cus, s, mels); }
 
 template <class R>
-static hipError_t launch_offline(const MfccOfflineArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
+hipError_t launch_mfcc_offline(const MfccOfflineArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
     if (a.n_frames <= 0) return hipSuccess;
     if (!blob_matches_shape(t)) return hipErrorInvalidValue;
-    if (mels) {
-        if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_offline_kernel, (ShapeStock, true), dim3(frame_blocks(a.n_frames, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-        else PE_LAUNCH_R(R, mfcc_offline_kernel, (ShapeAny, true), dim3(frame_blocks(a.n_frames, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-        return hipGetLastError();
-    }
-    if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_offline_kernel, (ShapeStock), dim3(frame_blocks(a.n_frames, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-    else PE_LAUNCH_R(R, mfcc_offline_kernel, (ShapeAny), dim3(frame_blocks(a.n_frames, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
+    const dim3 grid(frame_blocks(a.n_frames, n_cus)), block(64 * kFrameWaves);
+    with_frame_shape(t, mels, [&](auto SH, auto ME) {
+        PE_LAUNCH_R(R, mfcc_offline_kernel, (decltype(SH), PE_CONST(ME) != 0), grid, block, frame_lds(t), s, a, t); });
     return hipGetLastError();
 }
-hipError_t launch_mfcc_offline_f64(const MfccOfflineArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels) { return launch_offline<double>(a, t, n_cus, s, mels); }
-hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels) { return launch_offline<float>(a, t, n_cus, s, mels); }
 
 template <class R>
-static hipError_t launch_clips(const MfccClipArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
+hipError_t launch_mfcc_clips(const MfccClipArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
     if (a.clips.n_clips <= 0) return hipSuccess;
     if (!blob_matches_shape(t)) return hipErrorInvalidValue;
     // (a launch without frame tasks still stores the pad rows: one workgroup at least)
     const long long work = a.clips.n_tasks > (uint32_t)a.clips.n_clips ? (long long)a.clips.n_tasks : (long long)a.clips.n_clips;
-    if (mels) {
-        if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_clips_kernel, (ShapeStock, true), dim3(frame_blocks(work, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-        else PE_LAUNCH_R(R, mfcc_clips_kernel, (ShapeAny, true), dim3(frame_blocks(work, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-        return hipGetLastError();
-    }
-    if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_clips_kernel, (ShapeStock), dim3(frame_blocks(work, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-    else PE_LAUNCH_R(R, mfcc_clips_kernel, (ShapeAny), dim3(frame_blocks(work, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
+    const dim3 grid(frame_blocks(work, n_cus)), block(64 * kFrameWaves);
+    with_frame_shape(t, mels, [&](auto SH, auto ME) {
+        PE_LAUNCH_R(R, mfcc_clips_kernel, (decltype(SH), PE_CONST(ME) != 0), grid, block, frame_lds(t), s, a, t); });
     return hipGetLastError();
 }
-hipError_t launch_mfcc_clips_f64(const MfccClipArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels) { return launch_clips<double>(a, t, n_cus, s, mels); }
-hipError_t launch_mfcc_clips_f32(const MfccClipArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels) { return launch_clips<float>(a, t, n_cus, s, mels); }
 
 template <class R>
-static hipError_t launch_recs(const MfccRecArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
+hipError_t launch_mfcc_recs(const MfccRecArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels) {
     if (a.recs.n_tasks == 0) return hipSuccess;
     if (!blob_matches_shape(t)) return hipErrorInvalidValue;
-    if (mels) {
-        if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_recs_kernel, (ShapeStock, true), dim3(frame_blocks((long long)a.recs.n_tasks, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-        else PE_LAUNCH_R(R, mfcc_recs_kernel, (ShapeAny, true), dim3(frame_blocks((long long)a.recs.n_tasks, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-        return hipGetLastError();
-    }
-    if (t.L.mel_pad == ShapeStock::MEL) PE_LAUNCH_R(R, mfcc_recs_kernel, (ShapeStock), dim3(frame_blocks((long long)a.recs.n_tasks, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
-    else PE_LAUNCH_R(R, mfcc_recs_kernel, (ShapeAny), dim3(frame_blocks((long long)a.recs.n_tasks, n_cus)), dim3(64 * kFrameWaves), frame_lds(t), s, a, t);
+    const dim3 grid(frame_blocks((long long)a.recs.n_tasks, n_cus)), block(64 * kFrameWaves);
+    with_frame_shape(t, mels, [&](auto SH, auto ME) {
+        PE_LAUNCH_R(R, mfcc_recs_kernel, (decltype(SH), PE_CONST(ME) != 0), grid, block, frame_lds(t), s, a, t); });
     return hipGetLastError();
 }
-hipError_t launch_mfcc_recs_f64(const MfccRecArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels) { return launch_recs<double>(a, t, n_cus, s, mels); }
-hipError_t launch_mfcc_recs_f32(const MfccRecArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels) { return launch_recs<float>(a, t, n_cus, s, mels); }
 
 int gru_small_regs(int units) { return (units + 3) / 4; }
 int gru_small_tiles(int units) { return (3 * gru_small_regs(units) + 3) / 4; }
@@ -878,92 +855,87 @@ hipError_t launch_chains_rebuild(const GruArgs& a, const ChainArgs& ch, int n_pa
 #define PE_GEN_TWO_WAVES 0      // two waves per stream (one per frame-row parity): measured SLOWER (62.6 vs 47.7 us per update at 4096 streams:
                                 // the launch is bound by rounds of resident waves, and this doubles the waves)
 #endif
-template <class R, int BITS, bool BLUE = false, bool MELS = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) void mfcc_general_stream_kernel(const GeneralStreamArgs<R> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int s = PE_GEN_TWO_WAVES ? blockIdx.x >> 1 : blockIdx.x;
-    if (s < a.geo.n_streams) general_stream<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), s, PE_GEN_TWO_WAVES ? blockIdx.x & 1 : 0, threadIdx.x, PE_GEN_TWO_WAVES ? 2 : 1);
-}
-template <class R, int BITS, bool BLUE = false, bool MELS = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) PE_NO_PK_F32 void mfcc_general_stream_kernel_nopk(const GeneralStreamArgs<R> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int s = PE_GEN_TWO_WAVES ? blockIdx.x >> 1 : blockIdx.x;
-    if (s < a.geo.n_streams) general_stream<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), s, PE_GEN_TWO_WAVES ? blockIdx.x & 1 : 0, threadIdx.x, PE_GEN_TWO_WAVES ? 2 : 1);
-}
-template <class R, int BITS, bool BLUE = false, bool MELS = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) void mfcc_general_offline_kernel(const GeneralOfflineArgs<R> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    general_offline<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), blockIdx.x, gridDim.x, threadIdx.x);
-}
-template <class R, int BITS, bool BLUE = false, bool MELS = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))) PE_NO_PK_F32 void mfcc_general_offline_kernel_nopk(const GeneralOfflineArgs<R> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    general_offline<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), blockIdx.x, gridDim.x, threadIdx.x);
-}
-PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false, bool MELS = false>), (__launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4)))), mfcc_general_clips_kernel,
+#define PE_GENERAL_KERNEL (__launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4))))
+PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false, bool MELS = false>), PE_GENERAL_KERNEL, mfcc_general_stream_kernel,
+               (const GeneralStreamArgs<R> a),
+               { extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+                 const int s = PE_GEN_TWO_WAVES ? blockIdx.x >> 1 : blockIdx.x;
+                 if (s < a.geo.n_streams) general_stream<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), s, PE_GEN_TWO_WAVES ? blockIdx.x & 1 : 0, threadIdx.x, PE_GEN_TWO_WAVES ? 2 : 1); })
+PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false, bool MELS = false>), PE_GENERAL_KERNEL, mfcc_general_offline_kernel,
+               (const GeneralOfflineArgs<R> a),
+               { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; general_offline<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), blockIdx.x, gridDim.x, threadIdx.x); })
+PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false, bool MELS = false>), PE_GENERAL_KERNEL, mfcc_general_clips_kernel,
                (const GeneralClipArgs<R> a),
                { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; general_clips<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), (int)blockIdx.x, (int)gridDim.x, threadIdx.x); })
-PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false, bool MELS = false>), (__launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BITS >= 10 ? 2 : 4)))), mfcc_general_recs_kernel,
+PE_KERNEL_PAIR((template <class R, int BITS, bool BLUE = false, bool MELS = false>), PE_GENERAL_KERNEL, mfcc_general_recs_kernel,
                (const GeneralRecArgs<R> a),
                { extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; general_recs<R, BITS, BLUE, MELS>(a, reinterpret_cast<R*>(smem), (int)blockIdx.x, (int)gridDim.x, threadIdx.x); })
-// the transform length as a template argument: n_fft not a power of two (chirp) = Bluestein over L = 2^log2m points
-// ... and MELS (mel rows, Vectorizer.mels) beside it
+// the transform length as a template argument, f(BITS, BLUE, MELS): n_fft not a power of two (chirp) = Bluestein over
+// L = 2^log2m points (BLUE), each with its own list of lengths; MELS (mel rows, Vectorizer.mels) is one more constant beside them
 template <class F>
 static bool with_general_bits(const GeneralTables& tab, bool mels, F&& f) {
-    if (mels) {
-        if (tab.chirp) return with_const<7, 8, 9, 10, 11>(tab.log2m, [&](auto B) { f(B, std::true_type{}, std::true_type{}); });
-        return with_const<5, 6, 7, 8, 9, 10>(tab.log2m, [&](auto B) { f(B, std::false_type{}, std::true_type{}); });
-    }
-    if (tab.chirp) return with_const<7, 8, 9, 10, 11>(tab.log2m, [&](auto B) { f(B, std::true_type{}, std::false_type{}); });
-    return with_const<5, 6, 7, 8, 9, 10>(tab.log2m, [&](auto B) { f(B, std::false_type{}, std::false_type{}); });
+    bool ok = false;
+    with_flag(mels, [&](auto MELS) {
+        ok = tab.chirp ? with_const<7, 8, 9, 10, 11>(tab.log2m, [&](auto B) { f(B, std::true_type{}, MELS); })
+                       : with_const<5, 6, 7, 8, 9, 10>(tab.log2m, [&](auto B) { f(B, std::false_type{}, MELS); }); });
+    return ok;
 }
+// workgroups of a launch that walks `work` tasks (frames, clips, recordings): one wave each, sixteen per compute unit at most
+static unsigned general_blocks(long long work, int n_cus) {
+    const long long cap = (long long)n_cus * 16;
+    return (unsigned)(work < cap ? work : cap);
+}
+template <class ARGS>
+static size_t general_lds(const ARGS& a, size_t real_bytes) { return general_lds_bytes(real_bytes, a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds); }
+
+// The four kinds of launch of the general family, as the stock family's above: one template each over the precision R
+// (declared in mfcc_general_device.h)
 template <class R>
-static hipError_t launch_general_stream_t(const GeneralStreamArgs<R>& a, hipStream_t s, bool mels) {
+hipError_t launch_general_stream(const GeneralStreamArgs<R>& a, hipStream_t s, bool mels) {
     if (a.geo.n_streams == 0) return hipSuccess;
-    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const dim3 grid((PE_GEN_TWO_WAVES ? 2 : 1) * (unsigned)a.geo.n_streams);
     const bool ok = with_general_bits(a.tab, mels, [&](auto B, auto BLUE, auto MELS) {
-        PE_LAUNCH_R(R, mfcc_general_stream_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), dim3((PE_GEN_TWO_WAVES ? 2 : 1) * (unsigned)a.geo.n_streams), dim3(64), lds, s, a); });
+        PE_LAUNCH_R(R, mfcc_general_stream_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), grid, dim3(64), general_lds(a, sizeof(R)), s, a); });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 template <class R>
-static hipError_t launch_general_offline_t(const GeneralOfflineArgs<R>& a, int n_cus, hipStream_t s, bool mels) {
+hipError_t launch_general_offline(const GeneralOfflineArgs<R>& a, int n_cus, hipStream_t s, bool mels) {
     if (a.n_frames <= 0) return hipSuccess;
-    const long long cap = (long long)n_cus * 16;
-    const unsigned blocks = (unsigned)(a.n_frames < cap ? a.n_frames : cap);
-    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const dim3 grid(general_blocks(a.n_frames, n_cus));
     const bool ok = with_general_bits(a.tab, mels, [&](auto B, auto BLUE, auto MELS) {
-        PE_LAUNCH_R(R, mfcc_general_offline_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), dim3(blocks), dim3(64), lds, s, a); });
+        PE_LAUNCH_R(R, mfcc_general_offline_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), grid, dim3(64), general_lds(a, sizeof(R)), s, a); });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 template <class R>
-static hipError_t launch_general_clips_t(const GeneralClipArgs<R>& a, int n_cus, hipStream_t s, bool mels) {
+hipError_t launch_general_clips(const GeneralClipArgs<R>& a, int n_cus, hipStream_t s, bool mels) {
     if (a.clips.n_clips <= 0) return hipSuccess;
-    const long long cap = (long long)n_cus * 16;
     const long long work = a.clips.n_tasks > (uint32_t)a.clips.n_clips ? (long long)a.clips.n_tasks : (long long)a.clips.n_clips;
-    const unsigned blocks = (unsigned)(work < cap ? work : cap);
-    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const dim3 grid(general_blocks(work, n_cus));
     const bool ok = with_general_bits(a.tab, mels, [&](auto B, auto BLUE, auto MELS) {
-        PE_LAUNCH_R(R, mfcc_general_clips_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), dim3(blocks), dim3(64), lds, s, a); });
+        PE_LAUNCH_R(R, mfcc_general_clips_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), grid, dim3(64), general_lds(a, sizeof(R)), s, a); });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
-hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s, bool mels) { return launch_general_clips_t<double>(a, n_cus, s, mels); }
-hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s, bool mels) { return launch_general_clips_t<float>(a, n_cus, s, mels); }
 template <class R>
-static hipError_t launch_general_recs_t(const GeneralRecArgs<R>& a, int n_cus, hipStream_t s, bool mels) {
+hipError_t launch_general_recs(const GeneralRecArgs<R>& a, int n_cus, hipStream_t s, bool mels) {
     if (a.recs.n_tasks == 0) return hipSuccess;
-    const long long cap = (long long)n_cus * 16;
-    const unsigned blocks = (unsigned)((long long)a.recs.n_tasks < cap ? (long long)a.recs.n_tasks : cap);
-    const size_t lds = general_lds_bytes(sizeof(R), a.tab.n_fft, a.tab.n_filt, a.tab.n_rounds);
+    const dim3 grid(general_blocks((long long)a.recs.n_tasks, n_cus));
     const bool ok = with_general_bits(a.tab, mels, [&](auto B, auto BLUE, auto MELS) {
-        PE_LAUNCH_R(R, mfcc_general_recs_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), dim3(blocks), dim3(64), lds, s, a); });
+        PE_LAUNCH_R(R, mfcc_general_recs_kernel, (PE_CONST(B), PE_CONST(BLUE), PE_CONST(MELS)), grid, dim3(64), general_lds(a, sizeof(R)), s, a); });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
-hipError_t launch_general_recs_f64(const GeneralRecArgs<double>& a, int n_cus, hipStream_t s, bool mels) { return launch_general_recs_t<double>(a, n_cus, s, mels); }
-hipError_t launch_general_recs_f32(const GeneralRecArgs<float>& a, int n_cus, hipStream_t s, bool mels) { return launch_general_recs_t<float>(a, n_cus, s, mels); }
-hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s, bool mels) { return launch_general_stream_t<double>(a, s, mels); }
-hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s, bool mels) { return launch_general_stream_t<float>(a, s, mels); }
-hipError_t launch_general_offline_f64(const GeneralOfflineArgs<double>& a, int n_cus, hipStream_t s, bool mels) { return launch_general_offline_t<double>(a, n_cus, s, mels); }
-hipError_t launch_general_offline_f32(const GeneralOfflineArgs<float>& a, int n_cus, hipStream_t s, bool mels) { return launch_general_offline_t<float>(a, n_cus, s, mels); }
+
+// the eight front-end launchers for one precision: the only place where a launcher meets a concrete R
+#define PE_FRONT_END_LAUNCHERS(R)                                                                                            \
+    template hipError_t launch_mfcc(const MfccStreamArgs<R>&, const WaveTables<R>&, int, hipStream_t, bool);                 \
+    template hipError_t launch_mfcc_offline(const MfccOfflineArgs<R>&, const WaveTables<R>&, int, hipStream_t, bool);        \
+    template hipError_t launch_mfcc_clips(const MfccClipArgs<R>&, const WaveTables<R>&, int, hipStream_t, bool);             \
+    template hipError_t launch_mfcc_recs(const MfccRecArgs<R>&, const WaveTables<R>&, int, hipStream_t, bool);               \
+    template hipError_t launch_general_stream(const GeneralStreamArgs<R>&, hipStream_t, bool);                               \
+    template hipError_t launch_general_offline(const GeneralOfflineArgs<R>&, int, hipStream_t, bool);                        \
+    template hipError_t launch_general_clips(const GeneralClipArgs<R>&, int, hipStream_t, bool);                             \
+    template hipError_t launch_general_recs(const GeneralRecArgs<R>&, int, hipStream_t, bool);
+PE_FRONT_END_LAUNCHERS(double)
+PE_FRONT_END_LAUNCHERS(float)
 
 // ---- small utility kernels ---------------------------------------------------------------------
 __global__ void gather_kernel(const GatherArgs a) {

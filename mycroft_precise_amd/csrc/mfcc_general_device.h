@@ -615,13 +615,10 @@ __device__ __forceinline__ void general_recs(const GeneralRecArgs<R>& a, R* S, c
 }
 
 // launchers (kernels.hip); mels: the MELS instantiation (rows = log-mel energies, the engine's n_mfcc = n_filt)
-hipError_t launch_general_recs_f64(const GeneralRecArgs<double>& a, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_general_recs_f32(const GeneralRecArgs<float>& a, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_general_clips_f64(const GeneralClipArgs<double>& a, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_general_clips_f32(const GeneralClipArgs<float>& a, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_general_stream_f64(const GeneralStreamArgs<double>& a, hipStream_t s, bool mels = false);
-hipError_t launch_general_stream_f32(const GeneralStreamArgs<float>& a, hipStream_t s, bool mels = false);
-hipError_t launch_general_offline_f64(const GeneralOfflineArgs<double>& a, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_general_offline_f32(const GeneralOfflineArgs<float>& a, int n_cus, hipStream_t s, bool mels = false);
+// (templates over the precision R = double / float, instantiated in kernels.hip for both)
+template <class R> hipError_t launch_general_stream(const GeneralStreamArgs<R>& a, hipStream_t s, bool mels = false);
+template <class R> hipError_t launch_general_offline(const GeneralOfflineArgs<R>& a, int n_cus, hipStream_t s, bool mels = false);
+template <class R> hipError_t launch_general_clips(const GeneralClipArgs<R>& a, int n_cus, hipStream_t s, bool mels = false);
+template <class R> hipError_t launch_general_recs(const GeneralRecArgs<R>& a, int n_cus, hipStream_t s, bool mels = false);
 
 }  // namespace pe

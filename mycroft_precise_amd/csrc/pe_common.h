@@ -523,8 +523,8 @@ hipError_t launch_clear_activation(const uint8_t* mask, int32_t* activation, int
 // MFCC of one call (n_updates chunks per stream): every frame the call completes as a task of one wave, then the
 // per-stream bookkeeping (leftover samples to carry_next, counters to st_*_next, ke_hist)
 constexpr int kProjRow = pe_wave::kProjRow;
-hipError_t launch_mfcc_f64(const MfccStreamArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_mfcc_f32(const MfccStreamArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels = false);
+// (the front-end launchers are templates over the precision R = double / float, instantiated in kernels.hip for both)
+template <class R> hipError_t launch_mfcc(const MfccStreamArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels = false);
 // network for n_updates x n_streams windows, emitted counters from ke_hist, out[u][stream]
 hipError_t launch_gru_many(const GruArgs& a, int n_updates, int n_padded, hipStream_t s, const ModelSet* ms = nullptr, int n_models = 1);   // ms: out[K][n_updates][streams]
 // one launch, three roles: GRU waves read the feature windows as they will be after this update while MFCC waves
@@ -544,14 +544,12 @@ hipError_t launch_fused_chains(const MfccStreamArgs<double>& m, const WaveTables
 hipError_t launch_fused_chains(const MfccStreamArgs<float>& m, const WaveTables<float>& t, const GruArgs& g, const ChainArgs& ch, int n_cus, hipStream_t s);
 // all live chains of every stream from the ring and the records as they stand (entering chain mode)
 hipError_t launch_chains_rebuild(const GruArgs& a, const ChainArgs& ch, int n_padded, hipStream_t s);
-hipError_t launch_mfcc_offline_f64(const MfccOfflineArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_mfcc_offline_f32(const MfccOfflineArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels = false);
+// every frame of one whole buffer (MfccOfflineArgs)
+template <class R> hipError_t launch_mfcc_offline(const MfccOfflineArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels = false);
 // the same frames for many clips at once, every clip's window padded in place (ClipTable)
-hipError_t launch_mfcc_clips_f64(const MfccClipArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_mfcc_clips_f32(const MfccClipArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels = false);
+template <class R> hipError_t launch_mfcc_clips(const MfccClipArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels = false);
 // ... and for many whole recordings, each at a row base of its own (RecTable)
-hipError_t launch_mfcc_recs_f64(const MfccRecArgs<double>& a, const WaveTables<double>& t, int n_cus, hipStream_t s, bool mels = false);
-hipError_t launch_mfcc_recs_f32(const MfccRecArgs<float>& a, const WaveTables<float>& t, int n_cus, hipStream_t s, bool mels = false);
+template <class R> hipError_t launch_mfcc_recs(const MfccRecArgs<R>& a, const WaveTables<R>& t, int n_cus, hipStream_t s, bool mels = false);
 // sim_scan_kernel, then sim_fold_kernel (SimArgs); a.hist is added to, everything else is written
 hipError_t launch_simulate(const SimArgs& a, int n_models, int n_cus, hipStream_t s);
 // units <= 32; 0 feats, 1 ring, 2 rows.  ms != null: the n_models networks of a K-model engine in the same ONE launch, model m

@@ -306,6 +306,69 @@ def offline_case(kw, prec):
     eng.close()
 
 
+# ---- 3b. the same three offline launches on the stock wave kernel (n_filt <= 16), both precisions ----------------------------
+# (profiles/front_end_dispatch/README.md: the cells whole buffer / clip table / recording table x stock family x mel rows, which
+#  nothing above reaches -- 'default-512x20' is served by the general front end)
+STOCK_HOP_FRAMES = 3
+
+
+def stock_offline_reference():
+    def make():
+        pr = M.params(**SHAPES['stock-512x16'])
+        W, H, T = pr.window_samples, pr.hop_samples, pr.n_features
+        w = scaled_first_layer(synth.make_weights(n_in=pr.feature_size, units=(20,), seed=2))
+        # shorter than a window | a partly filled window | whole windows | longer than max_samples (cropped as a clip)
+        a, b, c, d = [synth.stream_pcm(700 + i, int(n), 'square' if i % 2 else 'tone_noise').astype(np.float64) / 32768.0
+                      for i, n in enumerate([W - 3, W + 5 * H + 3, W + (T + 2) * H + 3, W + (T + 6) * H + 1])]
+        clips, recs = [a, b, d], [a, c, d]
+        feats = np.stack([M.vectorize(x, pr) for x in clips])
+        rows = [M.vectorize_raw(x, pr) for x in recs]
+        windows = [M.predict(np.stack([r[i - T:i] for i in range(T, len(r), STOCK_HOP_FRAMES)]), w, pr) if len(r) > T else np.zeros(0, np.float32)
+                   for r in rows]
+        frames = np.concatenate([G.frames_of(x, W, H) for x in (b, c, d)])
+        r32 = err(G.float32_restatement(frames, pr.n_fft, pr.n_filt, min(13, pr.n_filt), pr.sample_rate, with_mels=True)[1],
+                  M.mels_from_frames(frames, pr))
+        return (w, [frozen(x) for x in clips], frozen(feats), frozen(M.predict(feats, w, pr)), [frozen(x) for x in recs],
+                frozen(rows[2]), [frozen(x) for x in windows], r32)
+    return shared(('offline', 'stock-512x16'), make)
+
+
+@pytest.mark.parametrize('prec', ['f64', 'f32'])
+def test_stock_kernel_offline_mel_rows(prec):
+    w, clips, want_feats, want_scores, recs, want_rows, want_windows, r32 = stock_offline_reference()
+    unsaturated(want_scores[1:])                    # (clip 0 is shorter than a window: every row a pad row)
+    unsaturated(np.concatenate(want_windows))
+    pr = M.params(**SHAPES['stock-512x16'])
+    eng = engine(SHAPES['stock-512x16'], w, 1, prec)
+    assert eng.row_width == 16
+
+    def hold_offline(label, got, want):             # float64: the bar of offline_case; float32: the bar of hold_rows
+        if prec == 'f64':
+            print('MELS | stock offline %s | f64 | rows | %.3g |' % (label, err(got, want)))
+            assert np.all(np.abs(got - want) <= 1e-9), (label, err(got, want))
+        else:
+            hold_rows('stock offline ' + label, prec, got, want, r32)
+    # whole buffer
+    off = eng.vectorize_mels(recs[2])
+    assert off.shape == want_rows.shape and np.array_equal(eng.vectorize_raw(recs[2]), off)
+    hold_offline('buffer', off, want_rows)
+    # clip table
+    feats = eng.vectorize_clips(clips, pr.max_samples)
+    assert feats.shape == want_feats.shape == (3, pr.n_features, 16)
+    assert np.all(feats[0] == 0) and np.all(feats[1][:-6] == 0) and np.all(feats[1][-6:] != 0)
+    hold_offline('clips', feats, want_feats)
+    scores = eng.score_clips(clips, pr.max_samples)
+    print('MELS | stock offline | %s | score_clips | %.3g |' % (prec, err(scores[:, 0], want_scores)))
+    assert scores.shape == (3, 1) and err(scores[:, 0], want_scores) <= TOL_RAW
+    # recording table
+    got = eng.evaluate_clips(recs, STOCK_HOP_FRAMES)
+    assert [g.shape[0] for g in got] == [0, 1, 3] == [len(x) for x in want_windows]
+    for g, x, r in zip(got, want_windows, recs):
+        assert np.array_equal(g, eng.evaluate(r, STOCK_HOP_FRAMES))
+        assert err(g[:, 0], x) <= TOL_RAW
+    eng.close()
+
+
 # ---- 4. networks -------------------------------------------------------------------------------------------------------------
 NETS = {    # name -> (shape, units, use_delta, (make_weights seed, first-layer scale): unsaturated on the CPU, as SEED)
     '20u': ('default-512x20', (20,), False, (3, 1.0)),
